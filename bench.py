@@ -15,6 +15,12 @@ softmax + full_cross_ent, T = 0.1, lr = 1e-3, wd = 1e-3 with the L2 norm-environ
 default), fixed-bond truncation (the only policy under which "bond 20" exists).  Synthetic pixels,
 81 % zeros.  --config c4 is the fixed global batch of 20000 split over the ranks (strong scaling).
 
+A plain run sets up, warms up, times --steps passes and prints the headline.  --full adds everything else the bench
+measures after the timed passes: the break-down (forward, batch hand-over, all-reduce), a validity pass, the roofline,
+per-kernel times and the critical path, the resident-batch and cold-start passes and the CPU baselines.
+--dump-outputs DIR writes what the last timed pass left a caller (the trained cores, their bonds and label position, the
+network output f of that pass) as DIR/<name>.npy; the inputs depend only on the arguments, so two builds can be compared.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -155,6 +161,19 @@ def cpu_baseline_reference_form(N, M, D, L, st, f, y1h, budget_s):
     return out
 
 
+def dump_outputs(ctx, dst):
+    """What the timed path hands a caller after its last pass, as float32 / float64 .npy files (15 MB at c5): the cores
+    (canonical (ml, D, mr[, L]) layout, concatenated site by site), the bond dimensions and label position that shape
+    them, and f (L, b) of the last sweep step on this rank's batch."""
+    cores, bond, l_pos = ctx.get_cores()
+    f = ctx.get_f()
+    os.makedirs(dst, exist_ok=True)
+    np.save(os.path.join(dst, 'cores.npy'), np.concatenate([c.ravel() for c in cores]))
+    np.save(os.path.join(dst, 'bond.npy'), bond.astype(np.float64))
+    np.save(os.path.join(dst, 'l_pos.npy'), np.array([l_pos], dtype=np.float64))
+    np.save(os.path.join(dst, 'f.npy'), f)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -164,12 +183,15 @@ def main():
     ap.add_argument('--policy', default='fixed', choices=['fixed', 'reference'])
     ap.add_argument('--no-l2', action='store_true', help='weight decay as wd*B instead of the L2 norm term')
     ap.add_argument('--batches', type=int, default=4, help='distinct staged batches the passes cycle through (1: one resident batch)')
-    ap.add_argument('--cpu-steps', type=int, default=40, help='oracle steps timed for cpu_baseline (0 = skip)')
-    ap.add_argument('--ref-form-budget', type=float, default=25.0, help='seconds for cpu_baseline_reference_form (0 = skip)')
-    ap.add_argument('--no-kernel-profile', action='store_true')
+    ap.add_argument('--full', action='store_true', help='after the timed passes also measure and check everything beyond the headline '
+                                                        '(break-down, validity, roofline, per-kernel, resident, cold start, CPU baselines)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the outputs of the last timed pass as DIR/<name>.npy')
+    ap.add_argument('--cpu-steps', type=int, default=40, help='--full: oracle steps timed for cpu_baseline (0 = skip)')
+    ap.add_argument('--ref-form-budget', type=float, default=25.0, help='--full: seconds for cpu_baseline_reference_form (0 = skip)')
+    ap.add_argument('--no-kernel-profile', action='store_true', help='--full: skip the per-kernel passes and the critical path')
     ap.add_argument('--svd-stop', type=float, default=None, help='Jacobi stopping threshold (tnml_set_svd_stop); default: the library default')
-    ap.add_argument('--no-cold', action='store_true', help='skip the re-initialised (cold start) passes')
-    ap.add_argument('--no-resident', action='store_true', help='skip the secondary single-resident-batch measurement')
+    ap.add_argument('--no-cold', action='store_true', help='--full: skip the re-initialised (cold start) passes')
+    ap.add_argument('--no-resident', action='store_true', help='--full: skip the secondary single-resident-batch measurement')
     ap.add_argument('--classic', action='store_true', help='classic launch sequence instead of the pipelined single-launch step')
     ap.add_argument('--per-step', action='store_true', help='one launch per sweep step (round 2) instead of the persistent per-sweep launch')
     ap.add_argument('--persist-mode', type=int, default=None, choices=[1, 2], help='persistent sweep as one kernel (1) or one kernel per role (2); default: the library default')
@@ -301,29 +323,8 @@ def main():
     main_run = timed(args.steps)
     ctx.marker(3)
     dt = main_run['dt']
-
-    # SURVEY.md 8.4 break-down: the environment build (forward) and the host -> device hand-over of one batch on their own
-    ctx.synchronize()
-    ctx.timer_start()
-    ctx.select_batch(0)
-    sel_ms = ctx.timer_stop()
-    ctx.timer_start()
-    ctx.forward(want_f=False)
-    fwd_ms = ctx.timer_stop()
-    left_dir = ctx.l_pos == N - 1
-    ctx.sweep(left_dir, N - 1, True, hp['lr'], hp['weight_dec'], hp['L2_flag'], hp['act_fn'], hp['loss_fn'], hp['T'],
-              hp['trunc'], want_metrics=False, want_f=False)
-    ctx.synchronize()
-    t0 = time.perf_counter()
-    ctx.set_input(*batches[0])
-    ctx.synchronize()
-    h2d_ms = 1e3 * (time.perf_counter() - t0)
-    # the exchange of a multi-GPU step on its own: one all-reduce of the pre-gradient message (collective: every rank calls it)
-    z_floats = min((M * D) * D * D * M * L, 2 * M * D * D * M * L) + 4
-    allreduce_us = ctx.comm_probe(z_floats) if (world > 1 or os.environ.get('TNML_FORCE_COMM') == '1') else None
-    # validity: one more pass handing back metrics and f; non-finite values raise inside the library
-    met, f = one_pass(want=True)
-    finite = bool(np.isfinite(f).all() and np.isfinite(met).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, args.dump_outputs)
 
     sweep_steps = args.steps * (N - 1)
     steps_per_s = sweep_steps / dt
@@ -356,15 +357,6 @@ def main():
                              'rate (= sweep steps per second on the global batch of %d): %.1f' % (b, b * world, steps_per_s)),
         'global_batch_steps_per_s': steps_per_s,
         'weak_scaling_aggregate': world * steps_per_s,
-        'finite': finite,
-        'breakdown': {'forward_ms': fwd_ms, 'select_batch_ms': sel_ms, 'h2d_batch_ms': h2d_ms,
-                      'sweep_only_steps_per_s': sweep_steps / max(1e-3 * main_run['sweep_ms'], 1e-9),
-                      'steps_per_s_incl_h2d': (N - 1) / (dt / args.steps + 1e-3 * h2d_ms),
-                      # multi-GPU: device time of ONE all-reduce of the step's message (%d floats) issued back to back on the
-                      # exchange stream; inside a sweep it runs beside the SVD of the step (tnml_set_comm_overlap)
-                      'allreduce_us': allreduce_us, 'allreduce_floats': z_floats if allreduce_us is not None else None,
-                      'comm_overlap': (not args.no_comm_overlap) if allreduce_us is not None else None},
-        'final_accuracy': float(met[-1, 0]),
         # the library's own account of the timed passes (tnml_get_counters: from the bond dimensions of every step that ran)
         'counters': main_run['counters'],
         # the SVD is iterative: how much work the timed passes actually contained
@@ -373,48 +365,83 @@ def main():
                    'svd_stop2': args.svd_stop if args.svd_stop is not None else 1e-6},
     }
 
-    # ---- roofline of the dominant kernel, measured live over the timed region ------------------------------------------------
-    # Pipelined step: one launch of step_pipe_kernel per sweep step carries the whole step (update + SVD of step k next to f /
-    # pre-gradient of step k+1), so it is the dominant kernel and its average duration is the device time of the timed
-    # sweeps (HIP events on the library's stream, first to last launch of each sweep) / launches.  Classic sequence and the
-    # large-tensor path (c5): several kernels per step; the figure is then the whole step per launch group.
-    # (c5: only the steps next to the chain ends fit the single-launch kernel; the figure there is per sweep step)
-    all_pipe = main_run['pipe_steps'] >= sweep_steps
-    step_launches = main_run['pipe_steps'] if all_pipe else sweep_steps
-    step_us = 1e3 * main_run['sweep_ms'] / max(step_launches, 1)
-    if args.config == 'c5':
-        fl = flops_per_step(b, M, D, L)
-        tf = fl / (step_us * 1e-6) / 1e12
-        out['roofline'] = {'bound': 'mfma', 'kernel': 'sweep step (wide_step_mfma_tiled_kernel + large-tensor chain; pipelined launches at the chain ends)',
-                           'achieved': tf, 'peak': MFMA_F32_PEAK_TF, 'unit': 'TFLOP/s', 'frac': tf / MFMA_F32_PEAK_TF, 'traffic': None,
-                           'algorithmic_flops_per_step': fl, 'algorithmic_bytes_per_step': bstep, 'step_avg_us_hip_events': step_us}
-    else:
-        ach = bstep / (step_us * 1e-6) / 1e9
-        persistent = all_pipe and main_run['launches'] <= 2 * args.steps
-        out['roofline'] = {'bound': 'hbm', 'kernel': ('sweep_persist_kernel (ONE launch per sweep of %d steps; the figures are per step)' % (N - 1)) if persistent
-                           else ('step_pipe_kernel' if all_pipe else 'wide_step_mfma_kernel + narrow_step_kernel'),
-                           'achieved': ach, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': ach / HBM_PEAK_GBS, 'traffic': None,
-                           'algorithmic_bytes_per_launch': bstep * ((N - 1) if persistent else 1), 'algorithmic_bytes_per_step': bstep,
-                           'kernel_avg_us_hip_events': step_us * ((N - 1) if persistent else 1), 'step_avg_us_hip_events': step_us,
-                           'launches_timed': main_run['launches'] if persistent else step_launches, 'steps_timed': step_launches,
-                           'note': 'one launch = one whole sweep (persistent kernel) or one whole sweep step; the step is bound by the sequential SVD of its merged tensor '
-                                   '(critical_path below), not by HBM'}
-        # HBM traffic from the committed counter passes (separate rocprofv3 --pmc runs of this command, cut to the timed passes by
-        # the phase markers; never collected inside a bench run).  gfx950: FETCH_SIZE counts half of a coalesced read stream
-        # (MI355X_MICROARCH.md, HBM section): x 2.
-        pmc = os.path.join(ROOT, 'profiles', 'r03_pmc_%s.json' % args.config)
-        if os.path.exists(pmc) and args.policy == 'fixed' and not args.no_l2 and not args.classic:
-            allk = json.load(open(pmc))
-            scope = 'timed' if 'timed' in allk else 'whole_process'
-            kname = 'sweep_persist_kernel' if persistent else 'step_pipe_kernel'
-            w = allk.get(scope, {}).get(kname, {})
-            if 'FETCH_SIZE' in w and 'WRITE_SIZE' in w:
-                per_launch = (2.0 * w['FETCH_SIZE']['mean_KB'] + w['WRITE_SIZE']['mean_KB']) * 1024.0
-                out['roofline']['traffic_from_profiles'] = {
-                    'bytes_per_launch': per_launch, 'bytes_per_step': per_launch / ((N - 1) if persistent else 1),
-                    'source': 'profiles/r03_pmc_%s.json [%s][%s] (separate rocprofv3 --pmc passes, not this run)' % (args.config, scope, kname)}
+    if args.full:
+        # SURVEY.md 8.4 break-down: the environment build (forward) and the host -> device hand-over of one batch on their own
+        ctx.synchronize()
+        ctx.timer_start()
+        ctx.select_batch(0)
+        sel_ms = ctx.timer_stop()
+        ctx.timer_start()
+        ctx.forward(want_f=False)
+        fwd_ms = ctx.timer_stop()
+        left_dir = ctx.l_pos == N - 1
+        ctx.sweep(left_dir, N - 1, True, hp['lr'], hp['weight_dec'], hp['L2_flag'], hp['act_fn'], hp['loss_fn'], hp['T'],
+                  hp['trunc'], want_metrics=False, want_f=False)
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        ctx.set_input(*batches[0])
+        ctx.synchronize()
+        h2d_ms = 1e3 * (time.perf_counter() - t0)
+        # the exchange of a multi-GPU step on its own: one all-reduce of the pre-gradient message (collective: every rank calls it)
+        z_floats = min((M * D) * D * D * M * L, 2 * M * D * D * M * L) + 4
+        allreduce_us = ctx.comm_probe(z_floats) if (world > 1 or os.environ.get('TNML_FORCE_COMM') == '1') else None
+        # validity: one more pass handing back metrics and f; non-finite values raise inside the library
+        met, f = one_pass(want=True)
+        finite = bool(np.isfinite(f).all() and np.isfinite(met).all())
+        out.update({
+            'finite': finite,
+            'breakdown': {'forward_ms': fwd_ms, 'select_batch_ms': sel_ms, 'h2d_batch_ms': h2d_ms,
+                          'sweep_only_steps_per_s': sweep_steps / max(1e-3 * main_run['sweep_ms'], 1e-9),
+                          'steps_per_s_incl_h2d': (N - 1) / (dt / args.steps + 1e-3 * h2d_ms),
+                          # multi-GPU: device time of ONE all-reduce of the step's message (%d floats) issued back to back on the
+                          # exchange stream; inside a sweep it runs beside the SVD of the step (tnml_set_comm_overlap)
+                          'allreduce_us': allreduce_us, 'allreduce_floats': z_floats if allreduce_us is not None else None,
+                          'comm_overlap': (not args.no_comm_overlap) if allreduce_us is not None else None},
+            'final_accuracy': float(met[-1, 0]),
+        })
 
-    if rank == 0 and not args.no_kernel_profile:
+        # ---- roofline of the dominant kernel, measured live over the timed region ------------------------------------------------
+        # Pipelined step: one launch of step_pipe_kernel per sweep step carries the whole step (update + SVD of step k next to f /
+        # pre-gradient of step k+1), so it is the dominant kernel and its average duration is the device time of the timed
+        # sweeps (HIP events on the library's stream, first to last launch of each sweep) / launches.  Classic sequence and the
+        # large-tensor path (c5): several kernels per step; the figure is then the whole step per launch group.
+        # (c5: only the steps next to the chain ends fit the single-launch kernel; the figure there is per sweep step)
+        all_pipe = main_run['pipe_steps'] >= sweep_steps
+        step_launches = main_run['pipe_steps'] if all_pipe else sweep_steps
+        step_us = 1e3 * main_run['sweep_ms'] / max(step_launches, 1)
+        if args.config == 'c5':
+            fl = flops_per_step(b, M, D, L)
+            tf = fl / (step_us * 1e-6) / 1e12
+            out['roofline'] = {'bound': 'mfma', 'kernel': 'sweep step (wide_step_mfma_tiled_kernel + large-tensor chain; pipelined launches at the chain ends)',
+                               'achieved': tf, 'peak': MFMA_F32_PEAK_TF, 'unit': 'TFLOP/s', 'frac': tf / MFMA_F32_PEAK_TF, 'traffic': None,
+                               'algorithmic_flops_per_step': fl, 'algorithmic_bytes_per_step': bstep, 'step_avg_us_hip_events': step_us}
+        else:
+            ach = bstep / (step_us * 1e-6) / 1e9
+            persistent = all_pipe and main_run['launches'] <= 2 * args.steps
+            out['roofline'] = {'bound': 'hbm', 'kernel': ('sweep_persist_kernel (ONE launch per sweep of %d steps; the figures are per step)' % (N - 1)) if persistent
+                               else ('step_pipe_kernel' if all_pipe else 'wide_step_mfma_kernel + narrow_step_kernel'),
+                               'achieved': ach, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': ach / HBM_PEAK_GBS, 'traffic': None,
+                               'algorithmic_bytes_per_launch': bstep * ((N - 1) if persistent else 1), 'algorithmic_bytes_per_step': bstep,
+                               'kernel_avg_us_hip_events': step_us * ((N - 1) if persistent else 1), 'step_avg_us_hip_events': step_us,
+                               'launches_timed': main_run['launches'] if persistent else step_launches, 'steps_timed': step_launches,
+                               'note': 'one launch = one whole sweep (persistent kernel) or one whole sweep step; the step is bound by the sequential SVD of its merged tensor '
+                                       '(critical_path below), not by HBM'}
+            # HBM traffic from the committed counter passes (separate rocprofv3 --pmc runs of this command, cut to the timed passes by
+            # the phase markers; never collected inside a bench run).  gfx950: FETCH_SIZE counts half of a coalesced read stream
+            # (see profiles/README.md): x 2.
+            pmc = os.path.join(ROOT, 'profiles', 'r03_pmc_%s.json' % args.config)
+            if os.path.exists(pmc) and args.policy == 'fixed' and not args.no_l2 and not args.classic:
+                allk = json.load(open(pmc))
+                scope = 'timed' if 'timed' in allk else 'whole_process'
+                kname = 'sweep_persist_kernel' if persistent else 'step_pipe_kernel'
+                w = allk.get(scope, {}).get(kname, {})
+                if 'FETCH_SIZE' in w and 'WRITE_SIZE' in w:
+                    per_launch = (2.0 * w['FETCH_SIZE']['mean_KB'] + w['WRITE_SIZE']['mean_KB']) * 1024.0
+                    out['roofline']['traffic_from_profiles'] = {
+                        'bytes_per_launch': per_launch, 'bytes_per_step': per_launch / ((N - 1) if persistent else 1),
+                        'source': 'profiles/r03_pmc_%s.json [%s][%s] (separate rocprofv3 --pmc passes, not this run)' % (args.config, scope, kname)}
+
+    if args.full and rank == 0 and not args.no_kernel_profile:
         # per-kernel device time with HIP events around every launch (two more passes; synchronises after each launch)
         drain_whole()
         ctx.profile_enable(1)
@@ -450,7 +477,7 @@ def main():
                                         'clock_GHz': (sc[5] + sc[6] + sc[7]) / max(sc[8] * 10.0, 1e-9)}
         except Exception as e:      # the stamps are diagnostics: never fail the bench on them
             out['critical_path'] = {'error': str(e)[:200]}
-    elif dist is not None and not args.no_kernel_profile:
+    elif args.full and dist is not None and not args.no_kernel_profile:
         # keep the collectives of the profiling passes matched on every rank
         one_pass()
         one_pass()
@@ -461,7 +488,7 @@ def main():
         ctx.sweep(left_dir, N - 1 - (N - 1) // 2, False, hp['lr'], hp['weight_dec'], hp['L2_flag'], hp['act_fn'], hp['loss_fn'], hp['T'],
                   hp['trunc'], want_metrics=False, want_f=False)
 
-    if not args.no_resident and nb > 1:
+    if args.full and not args.no_resident and nb > 1:
         # the round-1 regime for comparison: the same passes on ONE resident batch (the chain converges onto it and the
         # Jacobi iteration settles at ~2 sweeps per SVD)
         ctx.select_batch(0)
@@ -473,7 +500,7 @@ def main():
         out['resident_batch'] = {'value': (1 if strong else world) * sweep_steps / r['dt'], 'unit': 'sweep-steps/s',
                                  'jacobi_sweeps_per_svd': r['sweeps_per_svd'], 'cholesky_fraction': r['cholesky_fraction']}
 
-    if not args.no_cold:
+    if args.full and not args.no_cold:
         # "cold" passes: network re-initialised (random cores, calibrated) and swept twice -- the regime of the first
         # training batches, where the merged tensors are far from their SVD form
         ctx.select_batch(0)
@@ -484,7 +511,7 @@ def main():
         out['cold_start'] = {'value': (1 if strong else world) * 2 * (N - 1) / r['dt'], 'unit': 'sweep-steps/s', 'passes': 2,
                              'jacobi_sweeps_per_svd': r['sweeps_per_svd'], 'cholesky_fraction': r['cholesky_fraction']}
 
-    if rank == 0 and args.cpu_steps > 0:
+    if args.full and rank == 0 and args.cpu_steps > 0:
         rate, t_fwd, t_step, st, fcpu, Xc, y1h = cpu_baseline(N, M, D, L, b, args.cpu_steps, 1234)
         ncpu, blas_threads = host_threads()
         out['cpu_baseline'] = {'value': rate, 'unit': 'sweep-steps/s', 'cores': blas_threads or ncpu, 'host_cpus': ncpu,
@@ -502,10 +529,11 @@ def main():
                 'forms': rf,
                 'gpu_over_B3': steps_per_s / rf['B3_fixed_bond_L2']['steps_per_s'],
                 'gpu_over_B1_first_sweep': steps_per_s / rf['B1_reference_truncation_L2_first_sweep']['steps_per_s']}
-    drain_whole()
-    if 'roofline' in out and whole['launches'] and all_pipe:
-        out['roofline']['step_kernel_avg_us_hip_events_whole_run'] = 1e3 * whole['ms'] / whole['launches']
-        out['roofline']['step_kernel_launches_whole_run'] = whole['launches']
+    if args.full:
+        drain_whole()
+        if whole['launches'] and all_pipe:
+            out['roofline']['step_kernel_avg_us_hip_events_whole_run'] = 1e3 * whole['ms'] / whole['launches']
+            out['roofline']['step_kernel_launches_whole_run'] = whole['launches']
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

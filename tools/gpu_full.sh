@@ -11,7 +11,7 @@ timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/full
 tail -1 $OUT/full_smoke.log
 for cfg in c3 c2 c5; do
   if [ $cfg = c5 ]; then SW="--steps 6 --warmup 2"; else SW="--steps 20 --warmup 5"; fi
-  timeout -k 10 400 python3 bench.py --config $cfg $SW > $OUT/full_bench_$cfg.json 2> $OUT/full_bench_$cfg.err || { tail -5 $OUT/full_bench_$cfg.err; exit 1; }
+  timeout -k 10 400 python3 bench.py --full --config $cfg $SW > $OUT/full_bench_$cfg.json 2> $OUT/full_bench_$cfg.err || { tail -5 $OUT/full_bench_$cfg.err; exit 1; }
   python3 -c "
 import json
 d=json.load(open('gpurun_out/full_bench_$cfg.json')); r=d['roofline']
@@ -19,8 +19,8 @@ print('$cfg value %.0f'%d['value'], 'cold %.0f'%d['cold_start']['value'], 'resid
 "
 done
 # an early training window (passes 3-8) and the reference-policy case
-timeout -k 10 400 python3 bench.py --steps 6 --warmup 2 > $OUT/full_bench_c3_default.json 2> $OUT/full_bench_c3_default.err || { tail -5 $OUT/full_bench_c3_default.err; exit 1; }
-timeout -k 10 400 python3 bench.py --policy reference --steps 20 --warmup 5 > $OUT/full_bench_c3_refpolicy.json 2> $OUT/full_bench_c3_refpolicy.err || { tail -5 $OUT/full_bench_c3_refpolicy.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full --steps 6 --warmup 2 > $OUT/full_bench_c3_default.json 2> $OUT/full_bench_c3_default.err || { tail -5 $OUT/full_bench_c3_default.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full --policy reference --steps 20 --warmup 5 > $OUT/full_bench_c3_refpolicy.json 2> $OUT/full_bench_c3_refpolicy.err || { tail -5 $OUT/full_bench_c3_refpolicy.err; exit 1; }
 python3 -c "
 import json
 for f in ('c3_default','c3_refpolicy'):

@@ -11,7 +11,7 @@ if [ -f build_exp/libtnml_fs.so ]; then
   TNML_LIB=build_exp/libtnml_fs.so timeout -k 10 200 python3 tools/probe_step.py > $OUT/q_probe.txt 2>&1
   grep -A10 "back-to-back" $OUT/q_probe.txt | cut -c1-400 | grep -v "wide kernel WG0\|per wave\|per-wave"
 fi
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --cpu-steps 0 > $OUT/q_bench.json 2> $OUT/q_bench.err || { tail -5 $OUT/q_bench.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --cpu-steps 0 > $OUT/q_bench.json 2> $OUT/q_bench.err || { tail -5 $OUT/q_bench.err; exit 1; }
 python3 -c "
 import json
 d=json.load(open('gpurun_out/q_bench.json')); r=d['roofline']

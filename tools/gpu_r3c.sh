@@ -12,7 +12,7 @@ tail -3 $OUT/r3c_tests.log
 grep -E "^(FAILED|ERROR)" $OUT/r3c_tests.log | head -30
 for mode in persist perstep; do
   if [ $mode = perstep ]; then FL="--per-step"; else FL=""; fi
-  timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --cpu-steps 0 $FL > $OUT/r3c_bench_$mode.json 2> $OUT/r3c_bench_$mode.err || { tail -5 $OUT/r3c_bench_$mode.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --cpu-steps 0 $FL > $OUT/r3c_bench_$mode.json 2> $OUT/r3c_bench_$mode.err || { tail -5 $OUT/r3c_bench_$mode.err; exit 1; }
   python3 -c "
 import json
 d=json.load(open('gpurun_out/r3c_bench_$mode.json')); r=d['roofline']

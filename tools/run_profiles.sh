@@ -17,10 +17,10 @@ rm -rf $OUT/prof_kt_$CFG $OUT/prof_fetch_$CFG $OUT/prof_write_$CFG $OUT/prof_mfm
 # (--event-handoffs: under --pmc only one kernel runs at a time -- a kernel that polls for another stream's sequence number would wait
 #  for a producer that cannot start)
 SHORT="--config $CFG --steps 2 --warmup 1 --cpu-steps 0 --no-kernel-profile --no-cold --no-resident --sync-interval 4 --event-handoffs $EXTRA"
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_kt_$CFG -- python3 $ROOT/bench.py --config $CFG $KT --cpu-steps 0 $EXTRA > $OUT/prof_kt_$CFG.json 2> $OUT/prof_kt_$CFG.err && \
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/prof_fetch_$CFG -- python3 $ROOT/bench.py $SHORT > /dev/null 2> $OUT/prof_fetch_$CFG.err && \
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/prof_write_$CFG -- python3 $ROOT/bench.py $SHORT > /dev/null 2> $OUT/prof_write_$CFG.err && \
-timeout -k 10 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 --kernel-trace --output-format csv -d $OUT/prof_mfma_$CFG -- python3 $ROOT/bench.py $SHORT > /dev/null 2> $OUT/prof_mfma_$CFG.err
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_kt_$CFG -- python3 $ROOT/bench.py --full --config $CFG $KT --cpu-steps 0 $EXTRA > $OUT/prof_kt_$CFG.json 2> $OUT/prof_kt_$CFG.err && \
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/prof_fetch_$CFG -- python3 $ROOT/bench.py --full $SHORT > /dev/null 2> $OUT/prof_fetch_$CFG.err && \
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/prof_write_$CFG -- python3 $ROOT/bench.py --full $SHORT > /dev/null 2> $OUT/prof_write_$CFG.err && \
+timeout -k 10 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 --kernel-trace --output-format csv -d $OUT/prof_mfma_$CFG -- python3 $ROOT/bench.py --full $SHORT > /dev/null 2> $OUT/prof_mfma_$CFG.err
 echo "passes rc $?"
 cd $ROOT
 python3 tools/rocprof_summary.py $CFG > $OUT/prof_summary_$CFG.txt 2>&1
