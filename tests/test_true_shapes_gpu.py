@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 import golden_util as gu
+import sweep_invariants as si
 from oracle import mps_oracle as mo
 
 pytestmark = pytest.mark.gpu
@@ -153,14 +154,22 @@ def test_bench_config_true_shape(cfg, N, M, b, L):
     # ---- sweep 1: free-running
     f_o = mo.forward(st, X64)
     obs['fwd0'] = relerr(ctx.forward(), f_o)
-    vh = [[], []]
-    f_o = mo.sweep(st, X64, y, f_o, HP['lr'], HP['weight_dec'], left_dir=False, var_hist=vh, **okw)
+    o = si.oracle_sweep(st, X64, y, f_o, HP['lr'], HP['weight_dec'], left_dir=False, **okw)
+    f_o = o['f']
+    ctx.profile_reset()
     met, f_d = ctx.sweep(False, N - 1, True, *hp)
+    cnt = ctx.counters()
+    assert cnt['launches'] == 1 and cnt['sweep_steps'] == N - 1, cnt          # the persistent sweep ran: one launch
     obs['f0'] = relerr(f_d, f_o)
-    obs['acc0'] = float(np.abs(met[:, 0] - np.array(vh[0])).max())
-    obs['mae0'] = float(np.abs(met[:, 1] - np.array(vh[1])).max())
-    _, bond_d, lp = ctx.get_cores()
+    obs['acc0'] = float(np.abs(met[:, 0] - o['accuracy']).max())
+    obs['mae0'] = float(np.abs(met[:, 1] - o['MAE']).max())
+    cores_d, bond_d, lp = ctx.get_cores()
     assert list(bond_d) == list(st.bond) and lp == st.l_pos == N - 1
+    # every step's kept singular values and singular-vector orthogonality from the cores the launch left behind, and the
+    # behind environments its batch side wrote (tests/sweep_invariants.py)
+    diag, off = si.step_sigmas(cores_d, bond_d, False)
+    obs['sigma0'], obs['off0'] = float(si.sigma_errors(diag, o['S']).max()), float(off.max())
+    obs['env0'] = max(si.env_residual(ctx.get_env(hip().SIDE_LEFT, s), E) for s, E in o['env'].items())
     assert max(bond_d) == M and int(np.sum(np.asarray(bond_d) == M)) >= N - 1 - 2 * 6
     # ---- sweep 2: chunks, oracle re-based on the device between them
     resync(st, ctx, True)
@@ -195,6 +204,9 @@ def test_bench_config_true_shape(cfg, N, M, b, L):
     assert obs['fwd0'] < 5e-6 and obs['fwd1'] < 3e-5
     assert obs['f0'] < 2e-3
     assert obs['acc0'] <= 1.0 / b + 1e-6 and obs['mae0'] < 1e-6
+    # every step of the one-launch sweep (783 free-running steps), observed c2 / c3: sigma 3.5e-5 / 2.1e-5 of sigma_max, Gram
+    # off-diagonal 2.0e-5 / 3.9e-6, behind environments 1.5e-4 / 4.8e-4 (Procrustes-aligned)
+    assert obs['sigma0'] < 3e-4 and obs['off0'] < 1.5e-4 and obs['env0'] < 3e-3
     assert obs['f1_median_chunk'] < 5e-4 and obs['f1_worst_chunk'] < 2e-2
     assert obs['acc1'] <= 2.0 / b + 1e-6 and obs['mae1'] < 1e-6
     assert obs['fresh'] < 1e-3                               # same cores on both sides (float32 chain of 784 sites)
