@@ -74,7 +74,13 @@ int tnml_device_count(void);
 
 /* ---- life cycle ------------------------------------------------------------------------- */
 /* Network.__init__ (Network_class.py:84-191) minus the random init, which stays on the host.
- * b_capacity: largest batch a later tnml_set_input may bring (buffers grow if exceeded). */
+ * b_capacity: largest batch a later tnml_set_input may bring (buffers grow if exceeded).
+ * D: local feature dimension, 2 <= D <= 8 (TNML_ERR_ARG otherwise).  D = 2 runs every specialised path this header
+ * describes.  3 <= D <= 8 runs a generic path of per-step launches (batch kernel -> slab reduction -> update / SVD kernel)
+ * with the same layouts ([b][N][D] inputs, [ml][D][mr] cores, [ml][D][D][mr][L] merged tensors), the same capture block
+ * and the same limit (short side of the matricised merged tensor <= 128: bond <= 42 at D = 3, <= 32 at D = 4, <= 16 at
+ * D = 8).  On a D != 2 context tnml_set_persistent, tnml_set_step_pipeline, tnml_set_chain_path and tnml_set_narrow_path
+ * accept their arguments and have no effect, and tnml_comm_init returns TNML_ERR_STATE (multi-GPU is D = 2 only). */
 int tnml_create(tnml_ctx **out, int N, int D, int L, int Mmax, int b_capacity, int device);
 int tnml_destroy(tnml_ctx *ctx);
 int tnml_synchronize(tnml_ctx *ctx);
@@ -199,7 +205,7 @@ int tnml_set_sync_interval(tnml_ctx *ctx, int n_steps);
 /* The batch-independent part of a step (update_B's tail, compute_L2_reg, tensor_svd) runs in one
  * workgroup's LDS when the merged tensor fits (min(rows, cols) <= 64 and <= 160 KB of LDS: bond <= 32 at
  * two labels) and through HBM-resident kernels otherwise (min(rows, cols) <= 128: bond 50 with ten labels).
- * LIMIT: the Jacobi kernels take a short side of at most 128, i.e. bond dimension M <= 64 at D = 2; tnml_sweep
+ * LIMIT: the Jacobi kernels take a short side of at most 128, i.e. bond dimension M <= 64 at D = 2 (128 / D in general); tnml_sweep
  * returns TNML_ERR_ARG at the first step beyond it (the reference itself has no such limit; its largest published
  * bond is 50).
  * force_large = 1 sends every step down the second path (tests, diagnostics); 0 restores the automatic

@@ -161,6 +161,7 @@ struct tnml_ctx {
   unsigned long long *counters = nullptr;
   void *tables = nullptr;      // device scratch for ChainSite / NormChainSite tables
   size_t tables_bytes = 0;
+  double *anyd_W = nullptr, *anyd_T2 = nullptr;   // generic-D update kernel: Jacobi vectors beyond LDS, behind core + its norm product
   // multi-GPU
   ncclComm_t comm = nullptr;
   int rank = 0, nranks = 1;
@@ -224,7 +225,7 @@ extern "C" int tnml_create(tnml_ctx **out, int N, int D, int L, int Mmax, int b_
   if (!out) return fail(TNML_ERR_ARG, "out is NULL");
   *out = nullptr;
   if (N < 2 || L < 1 || Mmax < 1 || b_capacity < 1) return fail(TNML_ERR_ARG, "bad sizes N=%d L=%d M=%d b=%d", N, L, Mmax, b_capacity);
-  if (D != kD) return fail(TNML_ERR_ARG, "this build is specialised for D == %d (got %d)", kD, D);
+  if (D < 2 || D > kMaxD) return fail(TNML_ERR_ARG, "feature dimension D = %d outside the supported range [2, %d]", D, kMaxD);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(TNML_ERR_NOGPU, "no HIP device visible: the HIP path has no CPU fallback");
@@ -323,7 +324,8 @@ extern "C" int tnml_destroy(tnml_ctx *c) {
                   c->Ln, c->Rn, c->Bnew, c->slabs, c->red, c->metrics, c->scal, c->dbg, c->status, c->tables, c->counters, c->Bscr, c->Bscr2,
                   c->Xpred_stage, c->Xpred, c->fpred, c->prepB, c->prepG, c->sync, c->zslabs, c->gslabs, c->zred, c->pipe_cnt, c->big.Bf, c->big.T, c->big.part, c->big.gram, c->big.rotlog, c->big.lam, c->big.info, c->big.VW, c->big.Cb, c->big.T2, c->big.prog, c->bigflags, c->splitflags};
   for (void *p : ptrs) if (p) (void)hipFree(p);
-  void *pptrs[] = {c->zred2, c->Tbuf[0], c->Tbuf[1], c->TNbuf[0], c->TNbuf[1], c->prepRaw, c->Apub, c->pst_dev, c->pst_cnt, c->pst_flags};
+  void *pptrs[] = {c->zred2, c->Tbuf[0], c->Tbuf[1], c->TNbuf[0], c->TNbuf[1], c->prepRaw, c->Apub, c->pst_dev, c->pst_cnt, c->pst_flags,
+                   c->anyd_W, c->anyd_T2};
   for (void *p : pptrs) if (p) (void)hipFree(p);
   for (int i = 0; i < 2; ++i) {
     if (c->pst_host[i]) (void)hipHostFree(c->pst_host[i]);
@@ -396,6 +398,7 @@ extern "C" int tnml_comm_unique_id(void *uid128) {
 extern "C" int tnml_comm_init(tnml_ctx *c, int rank, int nranks, const void *uid128) {
   if (!c || !uid128) return fail(TNML_ERR_ARG, "NULL argument");
   if (nranks < 1 || rank < 0 || rank >= nranks) return fail(TNML_ERR_ARG, "bad rank %d / %d", rank, nranks);
+  if (c->D != kD) return fail(TNML_ERR_STATE, "multi-GPU runs are D == %d only (this context has D = %d)", kD, c->D);
   HIP_TRY(hipSetDevice(c->device));
   c->rank = rank;
   c->nranks = nranks;
@@ -520,7 +523,8 @@ extern "C" int tnml_set_input(tnml_ctx *c, const float *X, const int32_t *y, int
   // batch is [0, b); kernels mask samples >= b.
   c->b = b;
   HIP_TRY(hipMemcpyAsync(c->Xstage, X, (size_t)b * c->N * c->D * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  launch_transpose_input(c->Xstage, c->X, b, c->b_pad, c->N, c->stream);
+  if (c->D != kD) launch_transpose_input_anyd(c->Xstage, c->X, b, c->b_pad, c->N, c->D, c->stream);
+  else launch_transpose_input(c->Xstage, c->X, b, c->b_pad, c->N, c->stream);
   HIP_TRY(hipGetLastError());
   if (y) {
     HIP_TRY(hipMemsetAsync(c->y, 0, (size_t)c->b_pad * sizeof(int), c->stream));
@@ -579,7 +583,8 @@ extern "C" int tnml_select_batch(tnml_ctx *c, int slot) {
   }
   c->b = b;
   // what tnml_set_input does after its host -> device copy, entirely on the device and without waiting
-  launch_transpose_input(c->stageX[slot], c->X, b, c->b_pad, c->N, c->stream);
+  if (c->D != kD) launch_transpose_input_anyd(c->stageX[slot], c->X, b, c->b_pad, c->N, c->D, c->stream);
+  else launch_transpose_input(c->stageX[slot], c->X, b, c->b_pad, c->N, c->stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemsetAsync(c->y, 0, (size_t)c->b_pad * sizeof(int), c->stream));
   HIP_TRY(hipMemcpyAsync(c->y, c->stageY[slot], (size_t)b * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
@@ -658,6 +663,11 @@ static int run_chain(tnml_ctx *c, bool logmode) {
   int rc0 = upload_chain_table(c);
   if (rc0) return rc0;
   if (c->profile) HIP_TRY(hipEventRecord(c->pev0, c->stream));
+  if (D != kD) {
+    if (!launch_env_chain_anyd((const ChainSite *)c->tables, N, c->cores, c->lab[c->lab_cur], c->X, right_envs ? c->Renv : c->Lenv, c->f,
+                               c->b, c->b_pad, L, c->Mmax, D, logmode ? c->slabs : nullptr, c->stream))
+      return fail(TNML_ERR_ARG, "forward chain at D = %d, M = %d: %zu bytes of LDS exceed 160 KB", D, c->Mmax, anyd_chain_lds_bytes(c->Mmax, D, L));
+  } else
   launch_env_chain((const ChainSite *)c->tables, N, c->cores, c->lab[c->lab_cur], c->X,
                    right_envs ? c->Renv : c->Lenv, c->f, c->b, c->b_pad, L, c->Mmax,
                    logmode ? c->slabs : nullptr, c->stream, c->chain_plain);
@@ -714,9 +724,15 @@ extern "C" int tnml_predict(tnml_ctx *c, const float *X, int b, float *f_out) {
   }
   const int bpad = c->pred_cap;
   HIP_TRY(hipMemcpyAsync(c->Xpred_stage, X, (size_t)b * N * D * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  launch_transpose_input(c->Xpred_stage, c->Xpred, b, bpad, N, c->stream);
+  if (D != kD) launch_transpose_input_anyd(c->Xpred_stage, c->Xpred, b, bpad, N, D, c->stream);
+  else launch_transpose_input(c->Xpred_stage, c->Xpred, b, bpad, N, c->stream);
   int rc = upload_chain_table(c);
   if (rc) return rc;
+  if (D != kD) {
+    if (!launch_env_chain_anyd((const ChainSite *)c->tables, N, c->cores, c->lab[c->lab_cur], c->Xpred, nullptr, c->fpred, b, bpad, L,
+                               c->Mmax, D, nullptr, c->stream))
+      return fail(TNML_ERR_ARG, "forward chain at D = %d, M = %d: %zu bytes of LDS exceed 160 KB", D, c->Mmax, anyd_chain_lds_bytes(c->Mmax, D, L));
+  } else
   launch_env_chain((const ChainSite *)c->tables, N, c->cores, c->lab[c->lab_cur], c->Xpred, nullptr, c->fpred, b, bpad, L,
                    c->Mmax, nullptr, c->stream, c->chain_plain);
   HIP_TRY(hipGetLastError());
@@ -866,6 +882,11 @@ static int build_norm_chain(tnml_ctx *c, bool right_side) {
   if (tab.empty()) return TNML_OK;
   HIP_TRY(hipMemcpyAsync(c->tables, tab.data(), tab.size() * sizeof(NormChainSite), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  if (D != kD) {
+    if (!launch_norm_chain_anyd((const NormChainSite *)c->tables, (int)tab.size(), c->cores, right_side ? c->Rn : c->Ln, c->prepG, c->Mmax, D,
+                                c->stream))
+      return fail(TNML_ERR_ARG, "norm environments at M = %d: %zu bytes of LDS exceed 160 KB", c->Mmax, (size_t)c->Mmax * c->Mmax * sizeof(double));
+  } else
   launch_norm_chain((const NormChainSite *)c->tables, (int)tab.size(), c->cores, right_side ? c->Rn : c->Ln, c->Mmax,
                     c->stream);
   HIP_TRY(hipGetLastError());
@@ -1157,6 +1178,10 @@ static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float
 // the merged tensor -- the behind environment is extended and B_new lands in the debug block, but no
 // SVD runs and cores, bonds and l_pos stay as they are.  Bdirect_dev: merged tensor to use instead of
 // the product of the two cores (relative layout), or nullptr.
+static int sweep_anyd(tnml_ctx *c, int left_dir, int n_steps, float lr, float weight_dec, int l2_flag, int act_fn, int loss_fn, float T,
+                      int trunc_policy, float *metrics_out, float *f_out, int mode, const float *Bdirect_dev, hipEvent_t sw_ev1);
+static int standalone_anyd(tnml_ctx *c, NarrowParams &n);
+
 static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep, float lr, float weight_dec,
                       int l2_flag, int act_fn, int loss_fn, float T, int trunc_policy, float *metrics_out,
                       float *f_out, int mode, const float *Bdirect_dev) {
@@ -1206,6 +1231,9 @@ static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep
     sw_ev1 = c->sweep_ev[c->sweep_ev_used + 1];
     c->sweep_ev_used += 2;
   }
+  if (D != kD)
+    return sweep_anyd(c, left_dir, n_steps, lr, weight_dec, l2_flag, act_fn, loss_fn, T, trunc_policy, metrics_out, f_out, mode, Bdirect_dev,
+                      sw_ev1);
 
   int done_persist = 0;
   if (mode == 0 && !Bdirect_dev && first_of_sweep) {
@@ -1720,7 +1748,7 @@ extern "C" int tnml_l2_term(tnml_ctx *c, const float *B_canon, int left_dir, flo
   const size_t bsize = (size_t)ml * D * D * mr * L;
   if (capacity < bsize) return fail(TNML_ERR_ARG, "capacity too small");
   if (bsize > c->bmax) return fail(TNML_ERR_ARG, "merged tensor exceeds the buffers sized for M = %d", c->Mmax);
-  const int npath = narrow_path(c, h, g, 1, L, 1);
+  const int npath = D != kD ? 0 : narrow_path(c, h, g, 1, L, 1);
   if (npath < 0) return npath;
   int rc = norm_envs_for_label_site(c);
   if (rc) return rc;
@@ -1740,7 +1768,7 @@ extern "C" int tnml_l2_term(tnml_ctx *c, const float *B_canon, int left_dir, flo
   n.dbg = c->dbg; n.status = c->status; n.counters = nullptr;
   n.Bdirect = c->Bscr; n.stop_after_update = 1;
   n.svd_stop2 = c->svd_stop2;
-  rc = run_narrow(c, n, npath);
+  rc = D != kD ? standalone_anyd(c, n) : run_narrow(c, n, npath);
   if (rc) return rc;
   HIP_TRY(hipGetLastError());
   c->last_bsize = (int)bsize; c->last_n = 1; c->last_h = h; c->last_g = g; c->last_left_dir = left_dir;
@@ -1766,7 +1794,7 @@ extern "C" int tnml_svd_split(tnml_ctx *c, const float *mat, int rows, int cols,
   const size_t bsize = (size_t)rows * cols;
   if (bsize > c->bmax || (size_t)rows * m > c->bmax || (size_t)m * cols > c->bmax)
     return fail(TNML_ERR_ARG, "matrix exceeds the buffers sized for M = %d", c->Mmax);
-  const int npath = narrow_path(c, h, g, 1, 1, m);
+  const int npath = D != kD ? 0 : narrow_path(c, h, g, 1, 1, m);
   if (npath < 0) return npath;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipMemcpyAsync(c->Bscr, mat, bsize * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -1785,7 +1813,7 @@ extern "C" int tnml_svd_split(tnml_ctx *c, const float *mat, int rows, int cols,
   n.Bdirect = c->Bscr;
   n.svd_stop2 = c->svd_stop2;
   n.chol_thr = c->chol_thr;
-  { int rc = run_narrow(c, n, npath); if (rc) return rc; }
+  { int rc = D != kD ? standalone_anyd(c, n) : run_narrow(c, n, npath); if (rc) return rc; }
   HIP_TRY(hipGetLastError());
   c->last_bsize = (int)bsize; c->last_n = nn; c->last_h = h; c->last_g = g; c->last_left_dir = 0;
   HIP_TRY(hipMemcpyAsync(US, us_dev, (size_t)rows * m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -1797,6 +1825,212 @@ extern "C" int tnml_svd_split(tnml_ctx *c, const float *mat, int rows, int cols,
     for (int i = 0; i < nn; ++i) sigma[i] = sg[i];
   }
   return check_status(c);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Generic feature dimension (3 <= D <= 8, kernels_anyd.hip): the classic per-step sequence only -- batch kernel -> slab reduction
+// -> update kernel -- with no persistent sweep, pipelined step, large-tensor pipeline or communicator.  Planning, bookkeeping and
+// the capture block follow the D == 2 path statement for statement; the update kernel takes any short side up to kBigMaxN
+// (odd sides padded to even inside it).
+// ---------------------------------------------------------------------------------------------
+static int anyd_scratch(tnml_ctx *c) {
+  if (c->anyd_W) return TNML_OK;
+  HIP_TRY(hipMalloc(&c->anyd_W, (size_t)kBigMaxN * kBigMaxN * sizeof(double)));
+  HIP_TRY(hipMalloc(&c->anyd_T2, 2 * (size_t)c->D * c->Mmax * c->Mmax * sizeof(double)));
+  return TNML_OK;
+}
+
+// update kernel in "stop after the update" / "given matrix" mode (tnml_l2_term, tnml_svd_split)
+static int standalone_anyd(tnml_ctx *c, NarrowParams &n) {
+  const int r = c->D * n.h, cc = c->D * n.g * n.L, nn = std::min(r, cc);
+  if (nn > kBigMaxN) return fail(TNML_ERR_ARG, "min(rows, cols) = %d > %d: the Jacobi kernels handle n <= %d", nn, kBigMaxN, kBigMaxN);
+  int rc = anyd_scratch(c);
+  if (rc) return rc;
+  n.D = c->D;
+  if (!launch_update_anyd(n, c->anyd_W, nullptr, c->stream))
+    return fail(TNML_ERR_ARG, "update kernel at D = %d refused a %d x %d matrix (kept rank %d)", c->D, r, cc, n.m);
+  return TNML_OK;
+}
+
+static int sweep_anyd(tnml_ctx *c, int left_dir, int n_steps, float lr, float weight_dec, int l2_flag, int act_fn, int loss_fn, float T,
+                      int trunc_policy, float *metrics_out, float *f_out, int mode, const float *Bdirect_dev, hipEvent_t sw_ev1) {
+  const int N = c->N, D = c->D, L = c->L;
+  const int nblk = c->b_pad / kTS / 2;                       // 64 samples per batch-side workgroup
+  float *beh = left_dir ? c->Renv : c->Lenv;
+  float *ahe = left_dir ? c->Lenv : c->Renv;
+  double *nbeh = left_dir ? c->Rn : c->Ln;
+  double *nahe = left_dir ? c->Ln : c->Rn;
+  { int rc = anyd_scratch(c); if (rc) return rc; }
+  for (int step = 0; step < n_steps; ++step) {
+    const int l = c->l_pos;
+    const int p = left_dir ? l - 1 : l;
+    const int k = left_dir ? (N - 2 - p) : p;
+    const int sb = left_dir ? p + 1 : p, sa = left_dir ? p : p + 1;
+    const int h = left_dir ? c->mr(p + 1) : c->ml(p);
+    const int g = left_dir ? c->ml(p) : c->mr(p + 1);
+    const int s = c->bond[p];
+    const int m = tnml_trunc_rank(trunc_policy, left_dir, p, N, c->ml(p), D, c->mr(p + 1), L, c->Mpol);
+    if (m < 0) return fail(TNML_ERR_SHAPE, "shapes not aligned: the reference's un-truncated SVD factor does not fit "
+                                           "at sites (%d, %d) (Network_class.py:914 / :949)", p, p + 1);
+    const int r = D * h, cc = D * g * L, nn = std::min(r, cc);
+    const size_t bsize = (size_t)h * D * D * g * L;
+    if (bsize > c->bmax || m > c->Mmax)
+      return fail(TNML_ERR_ARG, "step at sites (%d,%d) exceeds the buffers sized for M = %d", p, p + 1, c->Mmax);
+    if ((size_t)h * D * m > c->core_stride || (size_t)m * D * g * L > c->lab_elems)
+      return fail(TNML_ERR_ARG, "new cores at sites (%d,%d) exceed the buffers sized for M = %d", p, p + 1, c->Mmax);
+    if (nn > kBigMaxN)
+      return fail(TNML_ERR_ARG, "step at sites (%d,%d): min(rows, cols) = %d > %d: the Jacobi kernels handle n <= %d", p, p + 1, nn,
+                  kBigMaxN, kBigMaxN);
+    // ---- batch side: f of the previous step, activation / metrics, behind environment, gradient slabs ----
+    WideParams w{};
+    w.b = c->b; w.b_pad = c->b_pad; w.L = L;
+    w.h = h; w.g = g;
+    w.act_fn = act_fn; w.loss_fn = loss_fn; w.T = T;
+    w.y = c->y; w.f = c->f;
+    w.slabs = c->slabs; w.slab_stride = c->slab_stride; w.bsize = (int)bsize;
+    w.x_k = c->X + (size_t)sb * c->b_pad * D;
+    w.x_kp1 = c->X + (size_t)sa * c->b_pad * D;
+    w.hp = 1; w.gp = 1;
+    w.do_ext = (k >= 1);
+    w.first_ext = (k == 1);
+    if (k >= 1) {
+      const int e_site = left_dir ? p + 2 : p - 1;
+      const int hp = left_dir ? c->mr(e_site) : c->ml(e_site);
+      w.hp = hp;
+      w.x_km1 = c->X + (size_t)e_site * c->b_pad * D;
+      w.ext_core.base = c->core_slot(e_site);
+      w.ext_core.n_in = hp; w.ext_core.n_out = h;
+      if (!left_dir) { w.ext_core.s_in = D * h; w.ext_core.s_d = h; w.ext_core.s_out = 1; }
+      else { w.ext_core.s_in = 1; w.ext_core.s_d = hp; w.ext_core.s_out = D * hp; }
+      w.Hprev = (k >= 2) ? c->env_slot(beh, left_dir ? p + 3 : p - 2) : nullptr;
+      w.Hcur = c->env_slot(beh, left_dir ? p + 2 : p - 1);
+    }
+    if (c->Bnew_valid && !c->f_current) {
+      if (k < 1 || c->prev_h != w.hp || c->prev_g != s)
+        return fail(TNML_ERR_STATE, "internal: previous-step dims (%d,%d) do not match (%d,%d)", c->prev_h, c->prev_g, w.hp, s);
+      w.do_f = 1;
+      w.gp = s;
+      w.Gprev = c->env_slot(ahe, left_dir ? p : p + 1);
+      w.Bprev = c->Bnew;
+    }
+    {
+      const int gs = left_dir ? p - 1 : p + 2;
+      w.Gcur = (gs >= 0 && gs <= N - 1) ? c->env_slot(ahe, gs) : nullptr;
+    }
+    prof_begin(c);
+    if (!launch_batch_anyd(w, D, nblk, true, c->stream))
+      return fail(TNML_ERR_ARG, "step at sites (%d,%d): the batch kernel at D = %d needs %zu bytes of LDS", p, p + 1, D,
+                  anyd_batch_lds_bytes(D, w.hp, w.gp, h, g, L));
+    prof_end(c, 1);
+    prof_begin(c);
+    launch_reduce(c->slabs, nblk, c->slab_stride, (int)bsize + kMetricSlots, c->red, c->stream);
+    prof_end(c, 2);
+    // ---- update side ----
+    NarrowParams n{};
+    n.L = L; n.D = D; n.h = h; n.g = g; n.s = s; n.m = m; n.bsize = (int)bsize;
+    n.l2_flag = l2_flag ? 1 : 0; n.lr = lr; n.wd = weight_dec;
+    n.red = c->red;
+    n.lab.base = c->lab[c->lab_cur]; n.lab.n_in = h; n.lab.n_out = s;
+    n.pl.base = c->core_slot(sa); n.pl.n_in = s; n.pl.n_out = g;
+    if (!left_dir) {
+      n.lab.s_in = D * s * L; n.lab.s_d = s * L; n.lab.s_out = L;
+      n.pl.s_in = D * g; n.pl.s_d = g; n.pl.s_out = 1;
+      n.ob_s_h = D * m; n.ob_s_d = m; n.ob_s_m = 1;
+      n.oa_s_m = D * g * L; n.oa_s_d = g * L; n.oa_s_g = L;
+    } else {
+      n.lab.s_in = L; n.lab.s_d = h * L; n.lab.s_out = D * h * L;
+      n.pl.s_in = 1; n.pl.s_d = s; n.pl.s_out = D * s;
+      n.ob_s_h = 1; n.ob_s_d = h; n.ob_s_m = D * h;
+      n.oa_s_m = L; n.oa_s_d = m * L; n.oa_s_g = D * m * L;
+    }
+    {
+      const int bs_ = left_dir ? p + 2 : p - 1, as_ = left_dir ? p - 1 : p + 2;
+      n.Nh = (l2_flag && bs_ >= 0 && bs_ <= N - 1) ? c->norm_slot(nbeh, bs_) : nullptr;
+      n.Ng = (l2_flag && as_ >= 0 && as_ <= N - 1) ? c->norm_slot(nahe, as_) : nullptr;
+      n.Nh_new = l2_flag ? c->norm_slot(nbeh, sb) : nullptr;
+    }
+    n.Bnew = c->Bnew;
+    n.out_behind = c->core_slot(sb);
+    n.out_ahead = c->lab[c->lab_cur ^ 1];
+    n.metrics = c->metrics + 2 * (size_t)step;
+    n.dbg = c->dbg;                              // the capture block is the update kernel's workspace
+    n.stamps = (c->debug || c->stamps) ? c->dbg + 4 * c->bmax + kDbgSigma + 5 : nullptr;
+    n.Bdirect = Bdirect_dev;
+    n.svd_stop2 = c->svd_stop2;
+    n.stop_after_update = mode == 1;
+    if (trunc_policy == TNML_TRUNC_ADAPTIVE && mode == 0) { n.trunc_thr = c->trunc_thr; n.left_dir = left_dir; n.m_out = c->status + 1; }
+    if (mode == 1) { n.Bnew = c->Bscr2; n.Nh_new = nullptr; }
+    n.status = c->status;
+    n.counters = c->counters;
+    prof_begin(c);
+    if (!launch_update_anyd(n, c->anyd_W, c->anyd_T2, c->stream))
+      return fail(TNML_ERR_ARG, "step at sites (%d,%d): update kernel at D = %d refused a %d x %d matrix", p, p + 1, D, r, cc);
+    prof_end(c, 3);
+    c->sweep_launches += 3;
+    c->last_bsize = (int)bsize; c->last_n = nn; c->last_h = h; c->last_g = g; c->last_left_dir = left_dir;
+    if (mode == 1) {
+      HIP_TRY(hipGetLastError());
+      if (metrics_out) {
+        HIP_TRY(hipMemcpyAsync(metrics_out, c->metrics, 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+      }
+      return TNML_OK;
+    }
+    // ---- bookkeeping (as the D == 2 path) ----
+    int m_kept = m;
+    if (trunc_policy == TNML_TRUNC_ADAPTIVE) {
+      HIP_TRY(hipMemcpyAsync(&m_kept, c->status + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));
+      if (m_kept < 1 || m_kept > m) return fail(TNML_ERR_NONFINITE, "adaptive truncation returned rank %d (cap %d)", m_kept, m);
+    }
+    c->bond[p] = m_kept;
+    c->l_pos = sa;
+    c->lab_cur ^= 1;
+    c->prev_h = h; c->prev_g = g; c->prev_p = p; c->prev_left_dir = left_dir;
+    {
+      const double bb = (double)c->b;
+      c->cnt_steps += 1;
+      c->cnt_bytes += 4.0 * bb * (2.0 * h + g + 3.0 * D + 2.0 * L + 1.0);
+      c->cnt_flops += 4.0 * bb * D * D * h * g * L + 2.0 * bb * D * h * h;
+    }
+    c->Bnew_valid = true;
+    c->f_current = false;
+    c->Z_valid = false; c->Zbig_valid = false;
+    if (c->check_launches) HIP_TRY(hipGetLastError());
+    if (c->sync_interval > 0 && (step + 1) % c->sync_interval == 0) HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  HIP_TRY(hipGetLastError());
+  if (!l2_flag) {
+    c->Ln_valid = c->Rn_valid = false;
+  } else if (c->l_pos == (left_dir ? 0 : N - 1)) {
+    if (left_dir) { c->Rn_valid = true; c->Ln_valid = false; } else { c->Ln_valid = true; c->Rn_valid = false; }
+  } else {
+    if (left_dir) c->Rn_valid = false; else c->Ln_valid = false;
+  }
+  // f from the last updated B (the value sweep_step returns, Network_class.py:573)
+  if (!c->f_current) {
+    WideParams w{};
+    w.b = c->b; w.b_pad = c->b_pad; w.L = L;
+    fill_prev_operands(c, w, left_dir, c->prev_p);
+    w.f = c->f;
+    w.do_f = 1;
+    prof_begin(c);
+    if (!launch_batch_anyd(w, D, nblk, false, c->stream))
+      return fail(TNML_ERR_ARG, "f of the last step at D = %d needs %zu bytes of LDS", D, anyd_batch_lds_bytes(D, w.hp, w.gp, 1, 1, L));
+    prof_end(c, 1);
+    HIP_TRY(hipGetLastError());
+    c->sweep_launches += 1;
+    c->f_current = true;
+  }
+  if (sw_ev1) HIP_TRY(hipEventRecord(sw_ev1, c->stream));
+  if (metrics_out)
+    HIP_TRY(hipMemcpyAsync(metrics_out, c->metrics, (size_t)n_steps * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (f_out) { int rc = copy_f_out(c, c->f, f_out); if (rc) return rc; }
+  if (metrics_out || f_out) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return check_status(c);
+  }
+  return TNML_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

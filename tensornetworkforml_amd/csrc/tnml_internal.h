@@ -10,7 +10,8 @@
 
 namespace tnml {
 
-constexpr int kD = 2;           // feature dimension the kernels are specialised for
+constexpr int kD = 2;           // feature dimension the kernels are specialised for (kernels_anyd.hip: 3 <= D <= kMaxD)
+constexpr int kMaxD = 8;
 constexpr int kTS = 32;         // samples per workgroup in the wide step kernel (v1)
 constexpr int kWideThreads = 1024; // 4 waves per SIMD: the v1 formulation is latency-bound
 constexpr int kNarrowThreads = 1024;
@@ -227,5 +228,19 @@ void launch_scale(float *p, size_t n, float factor, hipStream_t st);
 void launch_absmax(const float *f, int L, int b, int b_pad, float *out, hipStream_t st);
 void launch_activation(const float *f, const int *y, int L, int b, int b_pad, int act_fn, int loss_fn,
                        float T, float *act_out, float *der_out, hipStream_t st);
+
+// Generic feature dimension (kernels_anyd.hip): per-step launches only.  false: the launch was refused (geometry / LDS).
+void launch_transpose_input_anyd(const float *X_bnd, float *X_nbd, int b, int b_pad, int N, int D, hipStream_t st);
+size_t anyd_chain_lds_bytes(int Mmax, int D, int L);
+bool launch_env_chain_anyd(const ChainSite *sites_dev, int n_sites, const float *cores, const float *labcore, const float *X,
+                           float *env_base, float *f, int b, int b_pad, int L, int Mmax, int D, float *logmax_out, hipStream_t st);
+bool launch_norm_chain_anyd(const NormChainSite *sites_dev, int n_sites, const float *cores, double *env_base, double *T_scratch,
+                            int Mmax, int D, hipStream_t st);
+size_t anyd_batch_lds_bytes(int D, int hp, int gp, int h, int g, int L);
+// batch side of a step (WideParams as for the classic wide kernel; do_grad = false: f of the previous step only, f_only_kernel's role)
+bool launch_batch_anyd(const WideParams &p, int D, int nblk, bool do_grad, hipStream_t st);
+size_t anyd_update_lds_bytes(int n_pad, bool w_in_lds);
+// update side: p.dbg is required (the capture block is the workspace); W_scratch [128 x 128], T2_scratch [2 * D * Mmax * Mmax] doubles
+bool launch_update_anyd(const NarrowParams &p, double *W_scratch, double *T2_scratch, hipStream_t st);
 
 }  // namespace tnml

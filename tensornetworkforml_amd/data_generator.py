@@ -9,6 +9,7 @@ carries the stacked arrays as `.X` / `.y` so that the hot path skips the per-sam
 MNIST is read from local IDX files (there is no download path in this package).
 """
 import gzip
+import math
 import os
 import struct
 
@@ -111,16 +112,27 @@ class DataLoader:
             yield out
 
 
-def psi(x):
-    """Feature map [sin(pi x / 2), cos(pi x / 2)] on the last axis (data_generator.py:165-167)."""
-    x = np.array((np.sin(np.pi * x / 2), np.cos(np.pi * x / 2)))
-    return np.transpose(x, [1, 2, 0])
+def psi(x, D=2):
+    """Feature map on a new last axis.  D = 2: [sin(pi x / 2), cos(pi x / 2)] (data_generator.py:165-167).
+    General D (Stoudenmire & Schwab's d-component map):
+        phi_s(x) = sqrt(C(D-1, s)) sin^(D-1-s)(pi x / 2) cos^s(pi x / 2),   s = 0 .. D-1,
+    whose squared components sum to 1; at D = 2 it is the map above, computed by the same expressions."""
+    D = int(D)
+    if D < 1:
+        raise ValueError('feature dimension D = %d < 1' % D)
+    if D == 2:
+        x = np.array((np.sin(np.pi * x / 2), np.cos(np.pi * x / 2)))
+        return np.transpose(x, [1, 2, 0])
+    x = np.asarray(x)
+    sn, cs = np.sin(np.pi * x / 2), np.cos(np.pi * x / 2)
+    comps = [np.sqrt(float(math.comb(D - 1, s))) * sn ** (D - 1 - s) * cs ** s for s in range(D)]
+    return np.stack(comps, axis=-1)
 
 
-def prepare_dataset(data, label, train_perc, val_perc, train_batch_size, val_batch_size, test_batch_size):
+def prepare_dataset(data, label, train_perc, val_perc, train_batch_size, val_batch_size, test_batch_size, D=2):
     """Embed, split and wrap in loaders (data_generator.py:125-192).  As in the reference the
-    pixels go through psi un-normalised: pass data in [0, 1]."""
-    x = psi(data.reshape(len(data), -1))
+    pixels go through psi un-normalised: pass data in [0, 1].  D: components of the feature map (psi)."""
+    x = psi(data.reshape(len(data), -1), D)
     m = int(len(x) * train_perc)
     train_set = NumpyDataset(x[:m], label[:m])
     test_set = NumpyDataset(x[m:], label[m:])

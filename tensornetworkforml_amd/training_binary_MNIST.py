@@ -37,6 +37,7 @@ def main(argv=None):
     ap.add_argument('--loss_fn', type=str, default='full_cross_ent')
     ap.add_argument('--trunc', type=str, default='reference', choices=['reference', 'fixed'])
     ap.add_argument('--normalise', action='store_true', help='scale pixels to [0, 1] before the feature map')
+    ap.add_argument('--D', type=int, default=2, help='Local feature dimension (components of the feature map)')
     ap.add_argument('--out', type=str, default='trained_MNIST_model.dat')
     args = ap.parse_args(argv)
 
@@ -48,9 +49,9 @@ def main(argv=None):
     if args.normalise:
         data01 = data01 / 255.0
     train_batch = int(len(data01) * 0.8 / args.n_train_batch)
-    train_loader, val_loader, _ = gen.prepare_dataset(data01, labels01, 1, 0.2, train_batch, 128, 128)
+    train_loader, val_loader, _ = gen.prepare_dataset(data01, labels01, 1, 0.2, train_batch, 128, 128, D=args.D)
     x_cal = next(iter(train_loader)).X
-    net = tn.Network(N=data[0].size, M=args.M, L=2, calibration_X=x_cal, normalize=True, act_fn=args.act_fn,
+    net = tn.Network(N=data[0].size, M=args.M, D=args.D, L=2, calibration_X=x_cal, normalize=True, act_fn=args.act_fn,
                      loss_fn=args.loss_fn, trunc=args.trunc)
     val_acc, var_hist = net.train(train_loader, val_loader, lr=args.lr, n_epochs=args.n_epochs,
                                   weight_dec=args.L2_decay)

@@ -32,14 +32,15 @@ def main(argv=None):
     ap.add_argument('--loss_fn', type=str, default='full_cross_ent')
     ap.add_argument('--trunc', type=str, default='reference', choices=['reference', 'fixed'],
                     help="truncation policy of the SVD split ('reference' = the original's rule)")
+    ap.add_argument('--D', type=int, default=2, help='Local feature dimension (components of the feature map)')
     ap.add_argument('--out', type=str, default='trained_diag_model.dat')
     args = ap.parse_args(argv)
 
     train_batch = int(args.n_samples * 0.8 / args.n_train_batch)
     data, label = gen.create_dataset(args.n_samples, args.linear_dim, args.sigma)
-    train_loader, val_loader, _ = gen.prepare_dataset(data, label, 1, 0.2, train_batch, 128, 128)
+    train_loader, val_loader, _ = gen.prepare_dataset(data, label, 1, 0.2, train_batch, 128, 128, D=args.D)
     x_cal = next(iter(train_loader)).X
-    net = tn.Network(N=args.linear_dim ** 2, M=args.M, L=2, calibration_X=x_cal, normalize=True,
+    net = tn.Network(N=args.linear_dim ** 2, M=args.M, D=args.D, L=2, calibration_X=x_cal, normalize=True,
                      act_fn=args.act_fn, loss_fn=args.loss_fn, trunc=args.trunc)
     val_acc, var_hist = net.train(train_loader, val_loader, lr=args.lr, n_epochs=args.n_epochs,
                                   weight_dec=args.L2_decay)
