@@ -168,6 +168,42 @@ int tnml_svd_split(tnml_ctx *ctx, const float *mat, int rows, int cols, int m, f
  * l_pos restriction as tnml_forward. */
 int tnml_predict(tnml_ctx *ctx, const float *X, int b, float *f_out);
 
+/* ---- device-resident dataset --------------------------------------------------------------- */
+/* A context can hold ONE dataset of n samples with labels in HBM; batches and evaluations are then formed on the device from
+ * index lists, and only the lists and a few scalars cross the bus.  No reference analogue: the reference's
+ * loaders hand NumPy arrays to forward (Network_class.py:324-327), its evaluation scripts loop over such batches.
+ *   form TNML_DATASET_FEATURES  data [n][N][D] float32, already embedded: what tnml_set_input takes
+ *   form TNML_DATASET_PIXELS    data [n][N] float32 in [0, 1]; the feature map of data_generator.psi (D = 2: [sin(pi x / 2),
+ *                               cos(pi x / 2)]; D > 2: sqrt(C(D-1, s)) sin^(D-1-s) cos^s) is applied on the device whenever a
+ *                               batch is formed, in float64 with one rounding to float32: 1 / D of the memory and of the upload
+ * With a communicator attached every call of this block returns TNML_ERR_STATE (a resident dataset is not sharded over ranks). */
+enum { TNML_DATASET_FEATURES = 0, TNML_DATASET_PIXELS = 1 };
+/* Uploads data and labels [n] int32 (synchronous) and replaces an earlier dataset.  N and D describe `data` and must be the
+ * context's (TNML_ERR_ARG otherwise, as for labels outside [0, L)); a refused call leaves an earlier dataset in place.
+ * tnml_dataset_detach frees the dataset (tnml_destroy does too); tnml_dataset_size returns n, 0 without a dataset. */
+int tnml_dataset_attach(tnml_ctx *ctx, const float *data, const int32_t *labels, int n, int N, int D, int form);
+int tnml_dataset_detach(tnml_ctx *ctx);
+int tnml_dataset_size(tnml_ctx *ctx);
+/* The samples idx[0..b) become the resident batch, labels included: the counterpart of tnml_set_input / tnml_select_batch (same
+ * state resets, same growth of the batch buffers).  The list is copied to a buffer of the context and the call returns after
+ * enqueueing.  Indices outside [0, n) are refused (TNML_ERR_ARG) before anything is launched and with the resident batch left as it
+ * was; repeated indices are allowed. */
+int tnml_select_indices(tnml_ctx *ctx, const int32_t *idx, int b);
+/* tnml_predict for dataset samples: f_out [L][b]; the resident batch, its environments and f stay as they are. */
+int tnml_predict_indices(tnml_ctx *ctx, const int32_t *idx, int b, float *f_out);
+/* The evaluation loop of Network.train (Network_class.py:339-346) and of the reference's evaluation scripts, reduced on the device:
+ * forward chain over the listed samples in chunks that fit the prediction buffers (b may exceed every batch capacity), then
+ *   out3 = {samples whose argmax over labels equals their label (first maximum, taken on f itself: csrc/act_device.h),
+ *           sum over samples and labels of |onehot(y) - act(f)| (per sample in float32 as the sweep's metrics, across samples in float64),
+ *           samples with a non-finite activated output}
+ * Accuracy = out3[0] / b, mean absolute error = out3[1] / (b L).  Same l_pos restriction as tnml_forward. */
+int tnml_eval_indices(tnml_ctx *ctx, const int32_t *idx, int b, int act_fn, float T, double *out3);
+/* The same three numbers for the resident batch, from the f that tnml_forward or tnml_sweep left on the device (the per-batch
+ * training accuracy of Network.train, Network_class.py:327, without copying f back).  Needs no dataset. */
+int tnml_resident_metrics(tnml_ctx *ctx, int act_fn, float T, double *out3);
+/* The embedded samples idx[0..b) as the device forms them, X_out [b][N][D]: for tests and inspection, not a hot path. */
+int tnml_dataset_read(tnml_ctx *ctx, const int32_t *idx, int b, float *X_out);
+
 /* Accuracy / speed of the in-kernel Jacobi SVD (no reference analogue: the reference calls LAPACK,
  * Network_class.py:887).  The iteration ends after a sweep in which every rotation had
  * g^2 <= stop2 * scale^2; the off-diagonals left behind are of relative size ~stop2.  Default 1e-6

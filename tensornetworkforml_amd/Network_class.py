@@ -202,6 +202,8 @@ class Network():
         self._l_entries = None
         self._r_user = None
         self._l_user = None
+        self._dataset = None          # DeviceDataset attached to self._ctx (attach_dataset); lives and dies with the context
+        self._X_idx = None            # dataset indices of the resident batch when it was formed on the device
 
     def _context(self, b):
         if self._ctx is None:
@@ -287,6 +289,8 @@ class Network():
 
     @property
     def TX(self):
+        if self._X_host is None and getattr(self, '_X_idx', None) is not None and self._dataset is not None:
+            self._X_host = self._ctx.dataset_read(self._X_idx).astype(np.float64)      # a batch formed on the device, read on demand
         if self._X_host is None:
             return None
         return [Tensor(elem=self._X_host[:, i, :], axes_names=['b', 'd' + str(i)]) for i in range(self.N)]
@@ -381,6 +385,130 @@ class Network():
             print('\r' + "Epoch %d/%d - train accuracy : %.4f - val accuracy: %.4f"
                   % (epoch, n_epochs, epoch_train_acc.mean(), val_acc[-1]))
         return val_acc, np.array(var_hist)
+
+    # ------------------------------------------------------------------------------------------
+    # training and evaluation from a dataset that stays on the device
+    # ------------------------------------------------------------------------------------------
+    def attach_dataset(self, data, label, pixels=False):
+        """Upload a dataset to the device once.  pixels=False: `data` (n, N, D) are embedded features (what `forward`
+        takes); pixels=True: `data` (n, N) or (n, h, w) are pixels in [0, 1] and the feature map `data_generator.psi(., D)`
+        runs on the device whenever a batch is formed (1 / D of the memory and of the upload).  Replaces an earlier
+        dataset.  The dataset belongs to the device context: it is not pickled, and an unpickled network needs it attached
+        again.  Returns a `DeviceDataset` description."""
+        data = np.asarray(data)
+        if pixels:
+            data = data.reshape(len(data), -1)
+        assert data.ndim == (2 if pixels else 3) and data.shape[1] == self.N, \
+            "The 1 dimension of the input data must be the flattened number of pixels"
+        label = np.asarray(label)
+        assert label.shape == (len(data),), "one label per sample"
+        ctx = self._sync_to_device()
+        self._dataset = None
+        ctx.dataset_attach(data, label, 'pixels' if pixels else 'features')
+        self._dataset = DeviceDataset(len(data), self.N, self.D, bool(pixels))
+        return self._dataset
+
+    def detach_dataset(self):
+        if self._ctx is not None:
+            self._ctx.dataset_detach()
+        self._dataset = None
+
+    def _require_dataset(self):
+        if self._ctx is None or self._dataset is None:
+            raise RuntimeError("no dataset is attached to this network's device context (a dataset is not pickled and does "
+                               "not survive a new context): call attach_dataset(data, label) first")
+        return self._sync_to_device()
+
+    def _forward_indices(self, idx):
+        """forward() for the dataset samples idx, without any copy of X or f: the batch is formed on the device, the chain
+        builds the environment stack, and (correct, sum |onehot - act(f)|, non-finite) of f come back."""
+        lp = self.l_pos
+        if lp != 0 and lp != self.N - 1:
+            raise Exception('### Error ###\n l =', lp, ' -> forward should not be called if l has an intermediate position')
+        ctx = self._sync_to_device(len(idx))
+        ctx.select_indices(idx)
+        self._X_host, self._X_idx = None, np.array(idx, dtype=np.int64)
+        self._b = len(idx)
+        self._y_dev = None
+        ctx.forward(want_f=False)
+        self._invalidate_envs()
+        S_R, S_L = _hip.SIDE_RIGHT, _hip.SIDE_LEFT
+        if lp == 0:
+            self._r_entries = [('f',)] + [('env', S_R, i) for i in range(1, self.N)]
+            self._l_entries = None
+        else:
+            self._l_entries = [('env', S_L, i) for i in range(self.N - 1)] + [('f',)]
+            self._r_entries = None
+        return ctx.resident_metrics(self.act_fn, self.T)
+
+    def _sweep_resident(self, lr, weight_dec, L2_flag, left_dir, var_hist):
+        """sweep() on the batch `_forward_indices` left resident: labels and f are already on the device."""
+        ctx = self._ctx
+        if left_dir:
+            self._r_entries, self._r_user = [], None
+        else:
+            self._l_entries, self._l_user = [], None
+        met, _ = ctx.sweep(left_dir, self.N - 1, True, lr, weight_dec, L2_flag, self.act_fn, self.loss_fn, self.T, self.trunc,
+                           want_metrics=True, want_f=False)
+        var_hist[0].extend(float(v) for v in met[:, 0])
+        var_hist[1].extend(float(v) for v in met[:, 1])
+        self._device_newer = True
+        self._As = None
+        self._env_epoch += 1
+        lp = ctx.l_pos
+        S_R, S_L = _hip.SIDE_RIGHT, _hip.SIDE_LEFT
+        if left_dir:
+            self._r_entries = [('env', S_R, i) for i in range(self.N - 1, lp + 1, -1)]
+        else:
+            self._l_entries = [('env', S_L, i) for i in range(0, lp - 1)]
+
+    def train_resident(self, train_index_loader, val_index_loader, lr, n_epochs=10, weight_dec=0.001, L2_flag=True):
+        """`train` from the attached dataset: the loaders yield index arrays (data_generator.IndexLoader), and per batch
+        only the index list goes to the device and the per-step metrics and three scalars come back -- X and f never
+        cross the bus.  Same sweeps, same printed lines and same return value (val_acc, var_hist of shape
+        (n_epochs, 2, n_batches * (N-1))) as `train` on loaders that yield the same samples in the same order."""
+        self._require_dataset()
+        val_acc, var_hist = [], []
+        print("\n --- TRAINING PROCEDURE ---")
+        for epoch in range(n_epochs):
+            epoch_train_acc = np.zeros(len(train_index_loader))
+            var_hist.append([[], []])
+            for i, idx in enumerate(train_index_loader, 0):
+                correct, _, _ = self._forward_indices(idx)
+                epoch_train_acc[i] = correct / len(idx)
+                left_dir = (self.l_pos == self.N - 1)
+                self._sweep_resident(lr, weight_dec, L2_flag, left_dir, var_hist[epoch])
+                print('\r' + "Epoch %d/%d - train accuracy : %.4f - completed : %.2f "
+                      % (epoch, n_epochs, epoch_train_acc[i], (i + 1) * 100 / len(train_index_loader)) + '%', end=' ')
+            epoch_val_acc = np.zeros(len(val_index_loader))
+            for i, idx in enumerate(val_index_loader, 0):
+                correct, _, _ = self._ctx.eval_indices(idx, self.act_fn, self.T)
+                epoch_val_acc[i] = correct / len(idx)
+            val_acc.append(epoch_val_acc.mean())
+            print('\r' + "Epoch %d/%d - train accuracy : %.4f - val accuracy: %.4f"
+                  % (epoch, n_epochs, epoch_train_acc.mean(), val_acc[-1]))
+        return val_acc, np.array(var_hist)
+
+    def evaluate(self, indices, activated=True):
+        """(accuracy, mean absolute error) of the network over samples of the attached dataset, reduced on the device.
+        `indices` is an index loader -- the result is then the mean over its batches of the per-batch accuracy and error,
+        which is what the reference's evaluation scripts print (test_diagonals.py:67-81) and differs from the overall mean
+        when the last batch is ragged -- or an index array, for the overall figures.  The error is the mean over samples
+        and labels of |onehot(y) - act(f)| (the MAE of `var_hist`); activated=False takes f itself."""
+        ctx = self._require_dataset()
+        lp = self.l_pos
+        if lp != 0 and lp != self.N - 1:
+            raise Exception('### Error ###\n l =', lp, ' -> forward should not be called if l has an intermediate position')
+        act = self.act_fn if activated else 'linear'
+
+        def one(idx):
+            correct, abs_sum, nonfinite = ctx.eval_indices(idx, act, self.T)
+            n = len(idx)
+            return correct / n, (float('nan') if nonfinite else abs_sum / (n * self.L))
+        if isinstance(indices, np.ndarray) or (isinstance(indices, (list, tuple)) and (len(indices) == 0 or np.isscalar(indices[0]))):
+            return one(np.asarray(indices))
+        res = np.array([one(idx) for idx in indices], dtype=np.float64).reshape(-1, 2)
+        return float(res[:, 0].mean()), float(res[:, 1].mean())
 
     def accuracy(self, X, y, f=None):
         """Fraction of samples whose argmax over labels equals y (Network_class.py:354-380)."""
@@ -481,6 +609,7 @@ class Network():
             self._b = arr.shape[1]
             ctx.set_input(np.zeros((self._b, self.N, self.D), dtype=np.float32), None)
             self._X_host = None
+            self._X_idx = None
             self._y_dev = None
             self._invalidate_envs()
         ctx.set_f(arr)
@@ -649,6 +778,20 @@ class Network():
             cores.append(np.array(c, dtype=np.float64))
         self._host_cores = cores
         self._host_newer = True
+
+
+class DeviceDataset:
+    """Description of the dataset `Network.attach_dataset` uploaded: n samples of N sites, stored as pixels or as
+    D-component features.  The data itself lives in the network's device context."""
+
+    def __init__(self, n, N, D, pixels):
+        self.n, self.N, self.D, self.pixels = int(n), int(N), int(D), bool(pixels)
+
+    def __len__(self):
+        return self.n
+
+    def __repr__(self):
+        return 'DeviceDataset(n=%d, N=%d, D=%d, %s)' % (self.n, self.N, self.D, 'pixels' if self.pixels else 'features')
 
 
 def _unpack_batch(data):

@@ -16,6 +16,7 @@ ACT = {'linear': 0, 'sigmoid': 1, 'softmax': 2}
 LOSS = {'MSE': 0, 'cross_entropy': 1, 'full_cross_ent': 2}
 TRUNC = {'reference': 0, 'fixed': 1, 'adaptive': 2}
 SIDE_LEFT, SIDE_RIGHT = 0, 1
+DATASET_FORM = {'features': 0, 'pixels': 1}
 DBG = {'B': 0, 'dB_raw': 1, 'B_new': 2, 'sigma': 3, 'scalars': 4, 'L2_grad': 5}
 
 # every symbol include/tnml.h declares (tests check the library exports all of them)
@@ -29,6 +30,8 @@ SYMBOLS = [
     'tnml_update_B', 'tnml_l2_term', 'tnml_svd_split', 'tnml_set_svd_stop', 'tnml_set_narrow_path', 'tnml_predict', 'tnml_set_trunc_threshold',
     'tnml_set_sync_interval', 'tnml_set_step_pipeline', 'tnml_stage_batch', 'tnml_select_batch', 'tnml_get_counters',
     'tnml_svd_stats_ex', 'tnml_set_persistent', 'tnml_set_chain_path', 'tnml_marker', 'tnml_set_comm_overlap', 'tnml_comm_probe', 'tnml_set_flag_handoffs',
+    'tnml_dataset_attach', 'tnml_dataset_detach', 'tnml_dataset_size', 'tnml_select_indices', 'tnml_predict_indices', 'tnml_eval_indices',
+    'tnml_resident_metrics', 'tnml_dataset_read',
 ]
 
 
@@ -105,6 +108,14 @@ def lib():
         L.tnml_select_batch.argtypes = [vp, C.c_int]
         L.tnml_get_counters.argtypes = [vp, f64p]
         L.tnml_svd_split.argtypes = [vp, f32p, C.c_int, C.c_int, C.c_int, f32p, f32p, f64p]
+        L.tnml_dataset_attach.argtypes = [vp, f32p, i32p, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.tnml_dataset_detach.argtypes = [vp]
+        L.tnml_dataset_size.argtypes = [vp]
+        L.tnml_select_indices.argtypes = [vp, i32p, C.c_int]
+        L.tnml_predict_indices.argtypes = [vp, i32p, C.c_int, f32p]
+        L.tnml_eval_indices.argtypes = [vp, i32p, C.c_int, C.c_int, C.c_float, f64p]
+        L.tnml_resident_metrics.argtypes = [vp, C.c_int, C.c_float, f64p]
+        L.tnml_dataset_read.argtypes = [vp, i32p, C.c_int, f32p]
         _lib = L
     return _lib
 
@@ -223,6 +234,71 @@ class Context:
     def set_labels(self, y):
         y = np.ascontiguousarray(y, dtype=np.int32)
         _chk(lib().tnml_set_labels(self._h, _ptr(y, C.c_int32), y.shape[0]))
+
+    # ---- device-resident dataset
+    def dataset_attach(self, data, labels, form='features'):
+        """Upload a dataset once: data (n, N, D) embedded features, or (n, N) pixels in [0, 1] with form='pixels' (the feature
+        map then runs on the device when a batch is formed); labels (n,).  Replaces an earlier dataset."""
+        data = _f32(data)
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        if form == 'pixels':
+            assert data.ndim == 2, "the pixels form takes data of shape (n, N)"
+            N, D = data.shape[1], self.D
+        else:
+            assert data.ndim == 3, "the features form takes data of shape (n, N, D)"
+            N, D = data.shape[1], data.shape[2]
+        assert labels.shape == (data.shape[0],)
+        _chk(lib().tnml_dataset_attach(self._h, _ptr(data, C.c_float), _ptr(labels, C.c_int32), data.shape[0], N, D,
+                                       DATASET_FORM[form]))
+
+    def dataset_detach(self):
+        _chk(lib().tnml_dataset_detach(self._h))
+
+    @property
+    def dataset_size(self):
+        return int(lib().tnml_dataset_size(self._h))
+
+    @staticmethod
+    def _idx(idx):
+        idx = np.asarray(idx)
+        if idx.dtype.kind not in 'iu':
+            raise TypeError('sample indices must be integers, got %s' % idx.dtype)
+        if idx.size and (idx.min() < -2 ** 31 or idx.max() >= 2 ** 31):
+            raise TnmlError(-1, 'sample index beyond the int32 range')
+        return np.ascontiguousarray(idx.ravel(), dtype=np.int32)
+
+    def select_indices(self, idx):
+        """The dataset samples idx become the resident batch, labels included; only the index list crosses the bus."""
+        idx = self._idx(idx)
+        _chk(lib().tnml_select_indices(self._h, _ptr(idx, C.c_int32), idx.size))
+        self.b = idx.size
+
+    def predict_indices(self, idx):
+        """f (L, b) of the dataset samples idx; the resident batch stays as it is."""
+        idx = self._idx(idx)
+        f = np.empty((self.L, idx.size), dtype=np.float32)
+        _chk(lib().tnml_predict_indices(self._h, _ptr(idx, C.c_int32), idx.size, _ptr(f, C.c_float)))
+        return f
+
+    def eval_indices(self, idx, act_fn, T):
+        """(correct samples, sum |onehot - act(f)|, non-finite samples) over the dataset samples idx, reduced on the device."""
+        idx = self._idx(idx)
+        out = (C.c_double * 3)()
+        _chk(lib().tnml_eval_indices(self._h, _ptr(idx, C.c_int32), idx.size, ACT[act_fn], float(T), out))
+        return int(out[0]), float(out[1]), int(out[2])
+
+    def resident_metrics(self, act_fn, T):
+        """The same three numbers for the resident batch, from the f the last forward / sweep left on the device."""
+        out = (C.c_double * 3)()
+        _chk(lib().tnml_resident_metrics(self._h, ACT[act_fn], float(T), out))
+        return int(out[0]), float(out[1]), int(out[2])
+
+    def dataset_read(self, idx):
+        """The embedded samples (b, N, D) as the device forms them (tests, inspection)."""
+        idx = self._idx(idx)
+        X = np.empty((idx.size, self.N, self.D), dtype=np.float32)
+        _chk(lib().tnml_dataset_read(self._h, _ptr(idx, C.c_int32), idx.size, _ptr(X, C.c_float)))
+        return X
 
     # ---- hot path
     def forward(self, want_f=True):

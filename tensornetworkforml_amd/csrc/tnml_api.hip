@@ -162,6 +162,20 @@ struct tnml_ctx {
   void *tables = nullptr;      // device scratch for ChainSite / NormChainSite tables
   size_t tables_bytes = 0;
   double *anyd_W = nullptr, *anyd_T2 = nullptr;   // generic-D update kernel: Jacobi vectors beyond LDS, behind core + its norm product
+  // device-resident dataset (tnml_dataset_attach): features [n][N][D] or pixels [n][N], labels [n]; the index list of the call in
+  // flight lives in ds_idx (device), filled through one of two pinned host buffers so that the caller's list is free on return
+  float *ds_data = nullptr;
+  int *ds_labels = nullptr;
+  int ds_n = 0, ds_form = 0;
+  double ds_coef[kMaxD] = {0};
+  int *ds_idx = nullptr, *ds_idx_host[2] = {nullptr, nullptr};
+  hipEvent_t ds_idx_ev[2] = {nullptr, nullptr};
+  bool ds_idx_busy[2] = {false, false};
+  int ds_idx_cap = 0, ds_idx_cur = 0;
+  int *ds_ypred = nullptr;                   // labels of the chunk tnml_eval_indices is evaluating, beside Xpred / fpred
+  int ds_ypred_cap = 0;
+  double *ds_part = nullptr, *ds_acc = nullptr;   // block partials and the four accumulators of the metrics kernels
+  int ds_part_cap = 0;
   // multi-GPU
   ncclComm_t comm = nullptr;
   int rank = 0, nranks = 1;
@@ -332,6 +346,14 @@ extern "C" int tnml_destroy(tnml_ctx *c) {
     if (c->pst_ev[i]) (void)hipEventDestroy(c->pst_ev[i]);
   }
   for (int i = 0; i < tnml_ctx::kStageSlots; ++i) { if (c->stageX[i]) (void)hipFree(c->stageX[i]); if (c->stageY[i]) (void)hipFree(c->stageY[i]); }
+  {
+    void *dptrs[] = {c->ds_data, c->ds_labels, c->ds_idx, c->ds_ypred, c->ds_part, c->ds_acc};
+    for (void *p : dptrs) if (p) (void)hipFree(p);
+    for (int i = 0; i < 2; ++i) {
+      if (c->ds_idx_host[i]) (void)hipHostFree(c->ds_idx_host[i]);
+      if (c->ds_idx_ev[i]) (void)hipEventDestroy(c->ds_idx_ev[i]);
+    }
+  }
   for (hipEvent_t e : c->sweep_ev) (void)hipEventDestroy(e);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -699,6 +721,38 @@ extern "C" int tnml_forward(tnml_ctx *c, float *f_out) {
   return TNML_OK;
 }
 
+// tnml_predict's own batch: Xpred_stage [b][N][D] as uploaded, Xpred [N][pred_cap][D], fpred [L][pred_cap]; grown to bp samples
+static int pred_ensure_buffers(tnml_ctx *c, int bp) {
+  if (bp <= c->pred_cap) return TNML_OK;
+  const int N = c->N, D = c->D, L = c->L;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (c->Xpred_stage) { (void)hipFree(c->Xpred_stage); (void)hipFree(c->Xpred); (void)hipFree(c->fpred); }
+  c->Xpred_stage = c->Xpred = c->fpred = nullptr;
+  c->pred_cap = 0;
+  HIP_TRY(hipMalloc(&c->Xpred_stage, (size_t)bp * N * D * sizeof(float)));
+  HIP_TRY(hipMalloc(&c->Xpred, (size_t)bp * N * D * sizeof(float)));
+  HIP_TRY(hipMalloc(&c->fpred, (size_t)bp * L * sizeof(float)));
+  // on the context's stream: a memset on the null stream is not ordered against this (non-blocking) stream and could land behind
+  // the re-tiling kernel that follows
+  HIP_TRY(hipMemsetAsync(c->Xpred, 0, (size_t)bp * N * D * sizeof(float), c->stream));
+  c->pred_cap = bp;
+  return TNML_OK;
+}
+
+// one chain towards the label site over Xpred -> fpred, no environment stored (the chain table must be uploaded)
+static int pred_chain(tnml_ctx *c, int b) {
+  const int N = c->N, D = c->D, L = c->L, bpad = c->pred_cap;
+  if (D != kD) {
+    if (!launch_env_chain_anyd((const ChainSite *)c->tables, N, c->cores, c->lab[c->lab_cur], c->Xpred, nullptr, c->fpred, b, bpad, L,
+                               c->Mmax, D, nullptr, c->stream))
+      return fail(TNML_ERR_ARG, "forward chain at D = %d, M = %d: %zu bytes of LDS exceed 160 KB", D, c->Mmax, anyd_chain_lds_bytes(c->Mmax, D, L));
+  } else
+  launch_env_chain((const ChainSite *)c->tables, N, c->cores, c->lab[c->lab_cur], c->Xpred, nullptr, c->fpred, b, bpad, L,
+                   c->Mmax, nullptr, c->stream, c->chain_plain);
+  HIP_TRY(hipGetLastError());
+  return TNML_OK;
+}
+
 extern "C" int tnml_predict(tnml_ctx *c, const float *X, int b, float *f_out) {
   // Network.forward's output for a batch that is NOT made resident (validation, Network_class.py:339-346):
   // one chain towards the label site, no environment is stored, the training batch and its environments
@@ -710,32 +764,15 @@ extern "C" int tnml_predict(tnml_ctx *c, const float *X, int b, float *f_out) {
     return fail(TNML_ERR_STATE, "forward should not be called if l has an intermediate position (l_pos = %d)", c->l_pos);
   HIP_TRY(hipSetDevice(c->device));
   const int N = c->N, D = c->D, L = c->L;
-  const int bp = (b + 63) / 64 * 64;
-  if (bp > c->pred_cap) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->Xpred_stage) { (void)hipFree(c->Xpred_stage); (void)hipFree(c->Xpred); (void)hipFree(c->fpred); }
-    c->Xpred_stage = c->Xpred = c->fpred = nullptr;
-    c->pred_cap = 0;
-    HIP_TRY(hipMalloc(&c->Xpred_stage, (size_t)bp * N * D * sizeof(float)));
-    HIP_TRY(hipMalloc(&c->Xpred, (size_t)bp * N * D * sizeof(float)));
-    HIP_TRY(hipMalloc(&c->fpred, (size_t)bp * L * sizeof(float)));
-    HIP_TRY(hipMemset(c->Xpred, 0, (size_t)bp * N * D * sizeof(float)));
-    c->pred_cap = bp;
-  }
+  int rc = pred_ensure_buffers(c, (b + 63) / 64 * 64);
+  if (rc) return rc;
   const int bpad = c->pred_cap;
   HIP_TRY(hipMemcpyAsync(c->Xpred_stage, X, (size_t)b * N * D * sizeof(float), hipMemcpyHostToDevice, c->stream));
   if (D != kD) launch_transpose_input_anyd(c->Xpred_stage, c->Xpred, b, bpad, N, D, c->stream);
   else launch_transpose_input(c->Xpred_stage, c->Xpred, b, bpad, N, c->stream);
-  int rc = upload_chain_table(c);
+  rc = upload_chain_table(c);
   if (rc) return rc;
-  if (D != kD) {
-    if (!launch_env_chain_anyd((const ChainSite *)c->tables, N, c->cores, c->lab[c->lab_cur], c->Xpred, nullptr, c->fpred, b, bpad, L,
-                               c->Mmax, D, nullptr, c->stream))
-      return fail(TNML_ERR_ARG, "forward chain at D = %d, M = %d: %zu bytes of LDS exceed 160 KB", D, c->Mmax, anyd_chain_lds_bytes(c->Mmax, D, L));
-  } else
-  launch_env_chain((const ChainSite *)c->tables, N, c->cores, c->lab[c->lab_cur], c->Xpred, nullptr, c->fpred, b, bpad, L,
-                   c->Mmax, nullptr, c->stream, c->chain_plain);
-  HIP_TRY(hipGetLastError());
+  if ((rc = pred_chain(c, b))) return rc;
   HIP_TRY(hipMemcpy2DAsync(f_out, (size_t)b * sizeof(float), c->fpred, (size_t)bpad * sizeof(float), (size_t)b * sizeof(float),
                            L, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -805,6 +842,261 @@ extern "C" int tnml_activation(tnml_ctx *c, int act_fn, int loss_fn, float T, in
   HIP_TRY(hipGetLastError());
   if (act_out) { int rc = copy_f_out(c, c->ftmp, act_out); if (rc) return rc; }
   if (lossder_out) { int rc = copy_f_out(c, c->ftmp2, lossder_out); if (rc) return rc; }
+  return TNML_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// device-resident dataset: upload once, then batches and evaluations by index list
+// ---------------------------------------------------------------------------------------------
+static int ds_usable(tnml_ctx *c) {
+  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
+  if (c->comm) return fail(TNML_ERR_STATE, "a resident dataset is not sharded over ranks: the dataset calls are single-GPU only");
+  if (!c->ds_data) return fail(TNML_ERR_STATE, "no dataset attached: call tnml_dataset_attach first");
+  return TNML_OK;
+}
+
+static void ds_drop(tnml_ctx *c) {
+  if (c->ds_data) (void)hipFree(c->ds_data);
+  if (c->ds_labels) (void)hipFree(c->ds_labels);
+  c->ds_data = nullptr; c->ds_labels = nullptr; c->ds_n = 0;
+}
+
+extern "C" int tnml_dataset_attach(tnml_ctx *c, const float *data, const int32_t *labels, int n, int N, int D, int form) {
+  if (!c || !data || !labels) return fail(TNML_ERR_ARG, "NULL argument");
+  if (c->comm) return fail(TNML_ERR_STATE, "a resident dataset is not sharded over ranks: the dataset calls are single-GPU only");
+  if (n < 1) return fail(TNML_ERR_ARG, "empty dataset");
+  if (N != c->N || D != c->D) return fail(TNML_ERR_ARG, "dataset for N = %d, D = %d attached to a context with N = %d, D = %d", N, D, c->N, c->D);
+  if (form != TNML_DATASET_FEATURES && form != TNML_DATASET_PIXELS) return fail(TNML_ERR_ARG, "unknown dataset form %d", form);
+  for (int i = 0; i < n; ++i)
+    if (labels[i] < 0 || labels[i] >= c->L) return fail(TNML_ERR_ARG, "label %d of sample %d outside [0, %d)", labels[i], i, c->L);
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));          // an earlier dataset may still be read
+  ds_drop(c);
+  const size_t per = (size_t)c->N * (form == TNML_DATASET_PIXELS ? 1 : c->D);
+  float *dd = nullptr;
+  int *dl = nullptr;
+  hipError_t e = hipMalloc(&dd, (size_t)n * per * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&dl, (size_t)n * sizeof(int));
+  if (e == hipSuccess) e = hipMemcpy(dd, data, (size_t)n * per * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dl, labels, (size_t)n * sizeof(int), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (dd) (void)hipFree(dd);
+    if (dl) (void)hipFree(dl);
+    return fail(TNML_ERR_HIP, "uploading a dataset of %d samples failed: %s", n, hipGetErrorString(e));
+  }
+  c->ds_data = dd; c->ds_labels = dl; c->ds_n = n; c->ds_form = form;
+  double binom = 1.0;                                 // C(D-1, s), exact in float64 for D <= kMaxD
+  for (int s = 0; s < c->D; ++s) {
+    c->ds_coef[s] = std::sqrt(binom);
+    binom = binom * (double)(c->D - 1 - s) / (double)(s + 1);
+  }
+  return TNML_OK;
+}
+
+extern "C" int tnml_dataset_detach(tnml_ctx *c) {
+  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  ds_drop(c);
+  return TNML_OK;
+}
+
+extern "C" int tnml_dataset_size(tnml_ctx *c) { return c ? c->ds_n : TNML_ERR_ARG; }
+
+// idx[0..b) validated against [0, n) and copied to ds_idx; the caller's list is free when this returns and nothing waits for the
+// device except for a pinned buffer whose previous copy (two calls back) has not been consumed yet
+static int ds_upload_indices(tnml_ctx *c, const int32_t *idx, int b) {
+  for (int i = 0; i < b; ++i)
+    if (idx[i] < 0 || idx[i] >= c->ds_n) return fail(TNML_ERR_ARG, "index %d at position %d outside [0, %d)", idx[i], i, c->ds_n);
+  if (b > c->ds_idx_cap) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->ds_idx) (void)hipFree(c->ds_idx);
+    c->ds_idx = nullptr; c->ds_idx_cap = 0;
+    for (int i = 0; i < 2; ++i) {
+      if (c->ds_idx_host[i]) (void)hipHostFree(c->ds_idx_host[i]);
+      c->ds_idx_host[i] = nullptr; c->ds_idx_busy[i] = false;
+      if (!c->ds_idx_ev[i]) HIP_TRY(hipEventCreateWithFlags(&c->ds_idx_ev[i], hipEventDisableTiming));
+    }
+    const int cap = (b + 1023) / 1024 * 1024;
+    HIP_TRY(hipMalloc(&c->ds_idx, (size_t)cap * sizeof(int)));
+    for (int i = 0; i < 2; ++i) HIP_TRY(hipHostMalloc(&c->ds_idx_host[i], (size_t)cap * sizeof(int)));
+    c->ds_idx_cap = cap;
+  }
+  const int slot = (c->ds_idx_cur ^= 1);
+  if (c->ds_idx_busy[slot]) HIP_TRY(hipEventSynchronize(c->ds_idx_ev[slot]));
+  memcpy(c->ds_idx_host[slot], idx, (size_t)b * sizeof(int));
+  HIP_TRY(hipMemcpyAsync(c->ds_idx, c->ds_idx_host[slot], (size_t)b * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipEventRecord(c->ds_idx_ev[slot], c->stream));
+  c->ds_idx_busy[slot] = true;
+  return TNML_OK;
+}
+
+static int ds_gather(tnml_ctx *c, const int *idx_dev, int b, int b_pad, float *X_out, int *y_out) {
+  DatasetGather g{};
+  g.data = c->ds_data; g.labels = c->ds_labels; g.idx = idx_dev; g.out = X_out; g.y_out = y_out;
+  g.b = b; g.b_pad = b_pad; g.N = c->N; g.D = c->D; g.pixels = (c->ds_form == TNML_DATASET_PIXELS);
+  for (int s = 0; s < kMaxD; ++s) g.coef[s] = c->ds_coef[s];
+  if (!launch_dataset_gather(g, c->stream)) return fail(TNML_ERR_ARG, "internal: dataset gather refused (b %d, b_pad %d)", b, b_pad);
+  HIP_TRY(hipGetLastError());
+  return TNML_OK;
+}
+
+extern "C" int tnml_select_indices(tnml_ctx *c, const int32_t *idx, int b) {
+  int rc = ds_usable(c);
+  if (rc) return rc;
+  if (!idx) return fail(TNML_ERR_ARG, "NULL argument");
+  if (b < 1) return fail(TNML_ERR_ARG, "empty batch");
+  HIP_TRY(hipSetDevice(c->device));
+  rc = ds_upload_indices(c, idx, b);                  // refuses a bad index before anything of the resident batch is touched
+  if (rc) return rc;
+  if (b > c->b_cap) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    rc = alloc_batch_buffers(c, b);
+    if (rc != TNML_OK) return rc;
+  }
+  c->b = b;
+  // what tnml_set_input does after its host -> device copy, with the rows picked by index, on the device and without waiting
+  rc = ds_gather(c, c->ds_idx, b, c->b_pad, c->X, c->y);
+  if (rc) return rc;
+  c->have_input = true;
+  c->have_labels = true;
+  c->envs_valid_L = c->envs_valid_R = false;
+  c->f_current = false;
+  c->Bnew_valid = false;
+  c->Z_valid = false; c->Zbig_valid = false;
+  return TNML_OK;
+}
+
+// tnml_predict's buffers, at least bp samples wide, plus the labels tnml_eval_indices gathers beside them
+static int ds_ensure_pred(tnml_ctx *c, int bp) {
+  int rc = pred_ensure_buffers(c, bp);
+  if (rc) return rc;
+  if (c->ds_ypred_cap < c->pred_cap) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->ds_ypred) (void)hipFree(c->ds_ypred);
+    c->ds_ypred = nullptr; c->ds_ypred_cap = 0;
+    HIP_TRY(hipMalloc(&c->ds_ypred, (size_t)c->pred_cap * sizeof(int)));
+    c->ds_ypred_cap = c->pred_cap;
+  }
+  return TNML_OK;
+}
+
+static int ds_ensure_metrics(tnml_ctx *c, int b_pad) {
+  const int nblk = (b_pad + kDsMetricThreads - 1) / kDsMetricThreads;
+  if (!c->ds_acc) HIP_TRY(hipMalloc(&c->ds_acc, 4 * sizeof(double)));
+  if (nblk > c->ds_part_cap) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->ds_part) (void)hipFree(c->ds_part);
+    c->ds_part = nullptr; c->ds_part_cap = 0;
+    HIP_TRY(hipMalloc(&c->ds_part, (size_t)nblk * 4 * sizeof(double)));
+    c->ds_part_cap = nblk;
+  }
+  return TNML_OK;
+}
+
+static int ds_forward_allowed(tnml_ctx *c) {
+  if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
+  if (c->l_pos != 0 && c->l_pos != c->N - 1)
+    return fail(TNML_ERR_STATE, "forward should not be called if l has an intermediate position (l_pos = %d)", c->l_pos);
+  return TNML_OK;
+}
+
+extern "C" int tnml_predict_indices(tnml_ctx *c, const int32_t *idx, int b, float *f_out) {
+  int rc = ds_usable(c);
+  if (rc) return rc;
+  if (!idx || !f_out) return fail(TNML_ERR_ARG, "NULL argument");
+  if (b < 1) return fail(TNML_ERR_ARG, "empty batch");
+  if ((rc = ds_forward_allowed(c))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = ds_upload_indices(c, idx, b))) return rc;
+  if ((rc = ds_ensure_pred(c, (b + 63) / 64 * 64))) return rc;
+  const int bpad = c->pred_cap;
+  if ((rc = ds_gather(c, c->ds_idx, b, bpad, c->Xpred, nullptr))) return rc;
+  if ((rc = upload_chain_table(c))) return rc;
+  if ((rc = pred_chain(c, b))) return rc;
+  HIP_TRY(hipMemcpy2DAsync(f_out, (size_t)b * sizeof(float), c->fpred, (size_t)bpad * sizeof(float), (size_t)b * sizeof(float),
+                           c->L, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return TNML_OK;
+}
+
+static int ds_read_acc(tnml_ctx *c, double *out3) {
+  double acc[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(acc, c->ds_acc, sizeof acc, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  out3[0] = acc[0]; out3[1] = acc[1]; out3[2] = acc[2];
+  return TNML_OK;
+}
+
+extern "C" int tnml_eval_indices(tnml_ctx *c, const int32_t *idx, int b, int act_fn, float T, double *out3) {
+  int rc = ds_usable(c);
+  if (rc) return rc;
+  if (!idx || !out3) return fail(TNML_ERR_ARG, "NULL argument");
+  if (b < 1) return fail(TNML_ERR_ARG, "empty index list");
+  if (act_fn < 0 || act_fn > 2) return fail(TNML_ERR_ARG, "unknown activation");
+  if (dataset_metrics_lds_bytes(c->L) > 64 * 1024) return fail(TNML_ERR_ARG, "metrics kernel: %d labels exceed its LDS tile", c->L);
+  if ((rc = ds_forward_allowed(c))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = ds_upload_indices(c, idx, b))) return rc;
+  // chunks as wide as the prediction buffers (at least the resident batch's capacity); whole 256-sample blocks of the metrics
+  // kernel where they are wide enough, so that a sample's block does not depend on the chunking
+  if ((rc = ds_ensure_pred(c, std::max(c->pred_cap, c->b_pad)))) return rc;
+  const int bpad = c->pred_cap;
+  const int chunk = bpad >= kDsMetricThreads ? bpad / kDsMetricThreads * kDsMetricThreads : bpad;
+  if ((rc = ds_ensure_metrics(c, bpad))) return rc;
+  if ((rc = upload_chain_table(c))) return rc;
+  for (int off = 0; off < b; off += chunk) {
+    const int bc = std::min(chunk, b - off);
+    if ((rc = ds_gather(c, c->ds_idx + off, bc, bpad, c->Xpred, c->ds_ypred))) return rc;
+    if ((rc = pred_chain(c, bc))) return rc;
+    if (!launch_dataset_metrics(c->fpred, c->ds_ypred, c->L, bc, bpad, act_fn, T, c->ds_part, off == 0, c->ds_acc, c->stream))
+      return fail(TNML_ERR_ARG, "internal: metrics launch refused");
+    HIP_TRY(hipGetLastError());
+  }
+  return ds_read_acc(c, out3);
+}
+
+extern "C" int tnml_resident_metrics(tnml_ctx *c, int act_fn, float T, double *out3) {
+  if (!c || !out3) return fail(TNML_ERR_ARG, "NULL argument");
+  if (c->comm) return fail(TNML_ERR_STATE, "the metrics of a sharded batch are not reduced over ranks: single-GPU only");
+  if (act_fn < 0 || act_fn > 2) return fail(TNML_ERR_ARG, "unknown activation");
+  if (!c->have_input || !c->have_labels) return fail(TNML_ERR_STATE, "no resident batch with labels");
+  if (!c->f_current) return fail(TNML_ERR_STATE, "no f on the device: call tnml_forward or tnml_sweep first");
+  if (dataset_metrics_lds_bytes(c->L) > 64 * 1024) return fail(TNML_ERR_ARG, "metrics kernel: %d labels exceed its LDS tile", c->L);
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = ds_ensure_metrics(c, c->b_pad);
+  if (rc) return rc;
+  if (!launch_dataset_metrics(c->f, c->y, c->L, c->b, c->b_pad, act_fn, T, c->ds_part, 1, c->ds_acc, c->stream))
+    return fail(TNML_ERR_ARG, "internal: metrics launch refused");
+  HIP_TRY(hipGetLastError());
+  return ds_read_acc(c, out3);
+}
+
+extern "C" int tnml_dataset_read(tnml_ctx *c, const int32_t *idx, int b, float *X_out) {
+  int rc = ds_usable(c);
+  if (rc) return rc;
+  if (!idx || !X_out) return fail(TNML_ERR_ARG, "NULL argument");
+  if (b < 1) return fail(TNML_ERR_ARG, "empty index list");
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = ds_upload_indices(c, idx, b))) return rc;
+  const int N = c->N, D = c->D, bp = (b + 63) / 64 * 64;
+  float *tmp = nullptr;
+  HIP_TRY(hipMalloc(&tmp, (size_t)N * bp * D * sizeof(float)));
+  rc = ds_gather(c, c->ds_idx, b, bp, tmp, nullptr);
+  std::vector<float> host;
+  if (!rc) {
+    host.resize((size_t)N * bp * D);
+    hipError_t e = hipMemcpyAsync(host.data(), tmp, host.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) rc = fail(TNML_ERR_HIP, "reading the gathered samples back failed: %s", hipGetErrorString(e));
+  } else {
+    (void)hipStreamSynchronize(c->stream);
+  }
+  (void)hipFree(tmp);
+  if (rc) return rc;
+  for (int s = 0; s < b; ++s)              // [N][bp][D] as the device forms it -> [b][N][D]
+    for (int n = 0; n < N; ++n)
+      memcpy(X_out + ((size_t)s * N + n) * D, host.data() + ((size_t)n * bp + s) * D, (size_t)D * sizeof(float));
   return TNML_OK;
 }
 

@@ -243,4 +243,23 @@ size_t anyd_update_lds_bytes(int n_pad, bool w_in_lds);
 // update side: p.dbg is required (the capture block is the workspace); W_scratch [128 x 128], T2_scratch [2 * D * Mmax * Mmax] doubles
 bool launch_update_anyd(const NarrowParams &p, double *W_scratch, double *T2_scratch, hipStream_t st);
 
+// Device-resident dataset (kernels_dataset.hip): gather / embed / re-tile of the samples idx[0..b) and metrics over f.
+struct DatasetGather {
+  const float *data;       // features [n][N][D], or pixels [n][N] when `pixels`
+  const int *labels;       // [n]; read only when y_out is set
+  const int *idx;          // [b] sample rows, every one inside [0, n) (checked on the host before the launch)
+  float *out;              // [N][b_pad][D]; samples b .. b_pad-1 are zeroed
+  int *y_out;              // [b_pad] or nullptr
+  int b, b_pad, N, D, pixels;
+  double coef[kMaxD];      // pixels form: sqrt(C(D-1, s)), the constant factors of the feature map
+};
+constexpr int kDsMetricThreads = 256;
+// false: refused (geometry / LDS)
+bool launch_dataset_gather(const DatasetGather &p, hipStream_t st);
+size_t dataset_metrics_lds_bytes(int L);
+// part [ceil(b / kDsMetricThreads)][4] block partials; acc[4] = {correct, sum |onehot - act(f)|, non-finite samples, samples},
+// restarted from zero when reset != 0 and continued otherwise
+bool launch_dataset_metrics(const float *f, const int *y, int L, int b, int b_pad, int act_fn, float T, double *part, int reset, double *acc,
+                            hipStream_t st);
+
 }  // namespace tnml

@@ -141,3 +141,48 @@ def prepare_dataset(data, label, train_perc, val_perc, train_batch_size, val_bat
     val_loader = DataLoader(train_set, val_batch_size, sampler=SubsetRandomSampler(np.arange(train_len, m)), drop_last=True)
     test_loader = DataLoader(test_set, test_batch_size, drop_last=False)
     return train_loader, val_loader, test_loader
+
+
+class IndexLoader:
+    """Batches of sample INDICES into a device-resident dataset (`Network.attach_dataset`): iterating yields int arrays
+    instead of `Batch` lists, so that only the index list crosses the bus per batch.  With `shuffle` a pass draws one
+    `np.random.permutation(len(indices))` from the global generator, exactly as `DataLoader` does through
+    `SubsetRandomSampler`: the same subset, batch size, `drop_last` and generator state give the same sample order."""
+
+    def __init__(self, indices, batch_size=1, shuffle=True, drop_last=False):
+        self.indices = np.asarray(indices, dtype=np.int64).ravel()
+        self.batch_size, self.shuffle, self.drop_last = int(batch_size), bool(shuffle), bool(drop_last)
+        if self.batch_size < 1:
+            raise ValueError('batch_size = %d < 1' % self.batch_size)
+
+    def __len__(self):
+        n = len(self.indices)
+        return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        order = self.indices[np.random.permutation(len(self.indices))] if self.shuffle else self.indices
+        for k in range(len(self)):
+            yield order[k * self.batch_size:(k + 1) * self.batch_size]
+
+
+def split_indices(n, train_perc, val_perc):
+    """(train, validation, test) index arrays of the split `prepare_dataset` makes over n samples."""
+    m = int(n * train_perc)
+    train_len = int(m * (1 - val_perc))
+    return np.arange(train_len), np.arange(train_len, m), np.arange(m, n)
+
+
+def prepare_device_dataset(net, data, label, train_perc, val_perc, train_batch_size, val_batch_size, test_batch_size, D=2,
+                           pixels=True):
+    """`prepare_dataset` for a dataset that stays on the device: uploads all samples once through `net.attach_dataset`
+    (pixels=True: the raw pixels in [0, 1], embedded by the device's psi whenever a batch is formed; pixels=False: the
+    host's psi(data, D) as float32 features) and returns (dataset, train, validation, test index loaders) over the same
+    split, batch sizes, `drop_last` settings and shuffling as `prepare_dataset`'s three loaders."""
+    if int(D) != net.D:
+        raise ValueError('feature dimension D = %d, the network has D = %d' % (D, net.D))
+    flat = np.asarray(data).reshape(len(data), -1)
+    dataset = net.attach_dataset(flat if pixels else psi(flat, D), label, pixels=pixels)
+    tr, va, te = split_indices(len(flat), train_perc, val_perc)
+    return (dataset, IndexLoader(tr, train_batch_size, shuffle=True, drop_last=True),
+            IndexLoader(va, val_batch_size, shuffle=True, drop_last=True),
+            IndexLoader(te, test_batch_size, shuffle=False, drop_last=False))

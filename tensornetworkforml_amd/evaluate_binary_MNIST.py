@@ -1,0 +1,54 @@
+#!/usr/bin/env python3
+"""Evaluate a trained binary (0 vs 1) MNIST classifier on the MI355X backend: loads a pickled network
+(training_binary_MNIST.py --out), prepares the digits 0 / 1 of the MNIST test files the way the training script does (2x2
+max-pooling while the network has fewer sites than the images have pixels), uploads them once and reports accuracy and mean
+absolute error through `Network.evaluate`.  MNIST is read from local IDX files under --data_dir (nothing is downloaded).
+
+    python tensornetworkforml_amd/evaluate_binary_MNIST.py [--filename trained_MNIST_model.dat --data_dir datasets ...]
+"""
+import argparse
+import os
+import pickle
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import tensornetworkforml_amd  # noqa: E402,F401
+import data_generator as gen   # noqa: E402
+
+
+def pooling(X):
+    """2x2 max pooling of a stack of images, as training_binary_MNIST.py prepares them."""
+    n, h, w = X.shape
+    return X[:, :h - h % 2, :w - w % 2].reshape(n, h // 2, 2, w // 2, 2).max(axis=(2, 4))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description='Evaluate a trained Tensor Network on the binary MNIST test set')
+    ap.add_argument('--filename', type=str, default='trained_MNIST_model.dat', help='Pickled network to load')
+    ap.add_argument('--data_dir', type=str, default='datasets')
+    ap.add_argument('--batch_size', type=int, default=128, help='Samples per evaluation batch')
+    ap.add_argument('--normalise', action='store_true', help='scale pixels to [0, 1] before the feature map (as in training)')
+    ap.add_argument('--features', action='store_true', help='upload host-embedded features instead of pixels')
+    args = ap.parse_args(argv)
+
+    with open(args.filename, 'rb') as fh:
+        net = pickle.load(fh)
+    _, _, data, labels = gen.get_MNIST_dataset(args.data_dir)
+    while data[0].size > net.N and min(data.shape[1:]) >= 2:
+        data = pooling(data)
+    if data[0].size != net.N:
+        raise SystemExit('the network has N = %d sites, the (pooled) images have %d pixels' % (net.N, data[0].size))
+    mask = (labels == 0) | (labels == 1)
+    data01, labels01 = data[mask], labels[mask]
+    if args.normalise:
+        data01 = data01 / 255.0
+    _, _, _, test_loader = gen.prepare_device_dataset(net, data01, labels01, 0, 0, 1, 1, args.batch_size, D=net.D,
+                                                      pixels=not args.features)
+    acc, mae = net.evaluate(test_loader)
+    print('\tAccuracy:            ', acc)
+    print('\tMean Absolute Error: ', mae)
+    return acc, mae
+
+
+if __name__ == '__main__':
+    main()

@@ -1,0 +1,46 @@
+#!/usr/bin/env python3
+"""Evaluate a trained diagonals classifier on the MI355X backend: loads a pickled network (training_diagonals.py --out),
+draws a fresh data set of noisy diagonals of the network's size, uploads it once and reports accuracy and mean absolute
+error over it through `Network.evaluate` (forward chain, activation, argmax and error reduced on the device).
+
+    python tensornetworkforml_amd/evaluate_diagonals.py [--filename trained_diag_model.dat --n_samples 1000 ...]
+
+The two figures are means over the batches of --batch_size samples, the last one ragged when n_samples is not a multiple.
+"""
+import argparse
+import os
+import pickle
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import tensornetworkforml_amd  # noqa: E402,F401  (registers the bare module names)
+import data_generator as gen   # noqa: E402
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description='Evaluate a trained Tensor Network on a generated dataset of diagonals')
+    ap.add_argument('--filename', type=str, default='trained_diag_model.dat', help='Pickled network to load')
+    ap.add_argument('--n_samples', type=int, default=1000, help='Number of samples to generate')
+    ap.add_argument('--sigma', type=float, default=0.6, help='Sigma of the noise added to the dataset')
+    ap.add_argument('--batch_size', type=int, default=128, help='Samples per evaluation batch')
+    ap.add_argument('--features', action='store_true', help='upload host-embedded features instead of pixels')
+    args = ap.parse_args(argv)
+
+    with open(args.filename, 'rb') as fh:
+        net = pickle.load(fh)
+    linear_dim = int(round(np.sqrt(net.N)))
+    if linear_dim * linear_dim != net.N:
+        raise SystemExit('the network has N = %d sites, which is not a square image' % net.N)
+    data, label = gen.create_dataset(args.n_samples, linear_dim, args.sigma)
+    _, _, _, test_loader = gen.prepare_device_dataset(net, data, label, 0, 0, 1, 1, args.batch_size, D=net.D,
+                                                      pixels=not args.features)
+    acc, mae = net.evaluate(test_loader)
+    print('\tAccuracy:            ', acc)
+    print('\tMean Absolute Error: ', mae)
+    return acc, mae
+
+
+if __name__ == '__main__':
+    main()

@@ -38,6 +38,8 @@ def main(argv=None):
     ap.add_argument('--trunc', type=str, default='reference', choices=['reference', 'fixed'])
     ap.add_argument('--normalise', action='store_true', help='scale pixels to [0, 1] before the feature map')
     ap.add_argument('--D', type=int, default=2, help='Local feature dimension (components of the feature map)')
+    ap.add_argument('--resident', action='store_true',
+                    help='upload the data set once and train from index batches formed on the device (Network.train_resident)')
     ap.add_argument('--out', type=str, default='trained_MNIST_model.dat')
     args = ap.parse_args(argv)
 
@@ -49,12 +51,22 @@ def main(argv=None):
     if args.normalise:
         data01 = data01 / 255.0
     train_batch = int(len(data01) * 0.8 / args.n_train_batch)
-    train_loader, val_loader, _ = gen.prepare_dataset(data01, labels01, 1, 0.2, train_batch, 128, 128, D=args.D)
-    x_cal = next(iter(train_loader)).X
+    if args.resident:
+        # the calibration batch is the first batch a training pass would draw, embedded on the host; everything after it is
+        # formed on the device from the pixels uploaded once
+        tr_idx, _, _ = gen.split_indices(len(data01), 1, 0.2)
+        x_cal = gen.psi(data01.reshape(len(data01), -1)[next(iter(gen.IndexLoader(tr_idx, train_batch, drop_last=True)))], args.D)
+    else:
+        train_loader, val_loader, _ = gen.prepare_dataset(data01, labels01, 1, 0.2, train_batch, 128, 128, D=args.D)
+        x_cal = next(iter(train_loader)).X
     net = tn.Network(N=data[0].size, M=args.M, D=args.D, L=2, calibration_X=x_cal, normalize=True, act_fn=args.act_fn,
                      loss_fn=args.loss_fn, trunc=args.trunc)
-    val_acc, var_hist = net.train(train_loader, val_loader, lr=args.lr, n_epochs=args.n_epochs,
-                                  weight_dec=args.L2_decay)
+    if args.resident:
+        _, train_idx, val_idx, _ = gen.prepare_device_dataset(net, data01, labels01, 1, 0.2, train_batch, 128, 128, D=args.D)
+        val_acc, var_hist = net.train_resident(train_idx, val_idx, lr=args.lr, n_epochs=args.n_epochs, weight_dec=args.L2_decay)
+    else:
+        val_acc, var_hist = net.train(train_loader, val_loader, lr=args.lr, n_epochs=args.n_epochs,
+                                      weight_dec=args.L2_decay)
     with open(args.out, 'wb') as fh:
         pickle.dump(net, fh)
     print('validation accuracy per epoch:', ['%.4f' % v for v in val_acc])
