@@ -6,7 +6,10 @@
 //   * "device memory" comes from one reserved address range with unmapped gaps between allocations; every copy / memset the host
 //     code issues is checked against the allocation registry;
 //   * every launch is checked: grid, block and dynamic LDS against the gfx950 limits, and -- for the kernels that carry the sweep
-//     (typed decoders below) -- every pointer of their argument blocks together with the extent the kernel will touch.
+//     (typed decoders below) -- every pointer of their argument blocks together with the extent the kernel will touch;
+//   * with TNML_SAN_TRACE=<file>, every runtime call is written there as one line of text, in call order: launches with every argument
+//     (the planners' structs field by field, record arrays and site tables on continuation lines), copies, memsets, all-reduces, event
+//     and stream calls; device pointers as offsets from the arena base, streams and events by their order of creation.
 // A violation prints what and where and aborts.  Test infrastructure only; never linked into libtnml_hip.so.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -17,6 +20,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <vector>
 #include <cxxabi.h>
 #include "../tnml_internal.h"
 #include "../wide_pipe_device.h"
@@ -122,6 +126,7 @@ static void check_narrow(const NarrowParams &p) {
   }
   if (p.zpoll_flag) need(p.zpoll_flag, 4, "NarrowParams.zpoll_flag");
   if (p.done_flag) need(p.done_flag, 4, "NarrowParams.done_flag");
+  if (p.m_out) { need(p.m_out, 4, "NarrowParams.m_out"); memcpy(p.m_out, &p.m, 4); }     // the adaptive rank the kernel would decide: the cap
   opt(p.metrics, 2 * 4, "NarrowParams.metrics"); opt(p.counters, 4 * 8, "NarrowParams.counters") /* null in compute_L2_reg alone: the kernel tests it */; need(p.status, 4, "NarrowParams.status");
   if (p.pipe) {
     need(p.zred, (size_t)(p.zsize + kMetricSlots) * 4, "NarrowParams.zred");
@@ -182,6 +187,111 @@ static void check_chain(const ChainSite *sites, int n, const float *cores, const
     if (i + 1 < n && sites[i + 1].n_in != c.n_out) die("chain: site %d produces %d, site %d takes %d", i, c.n_out, i + 1, sites[i + 1].n_in);
   }
 }
+
+// ---- call trace ----------------------------------------------------------------------------------------------------------------
+static FILE *g_tr = nullptr;
+static long g_tr_lines = 0;
+static bool tracing() {
+  static const bool on = [] { const char *f = getenv("TNML_SAN_TRACE"); return f && *f && (g_tr = fopen(f, "w")); }();
+  return on;
+}
+static void tr(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+static void tr(const char *fmt, ...) {
+  if (!tracing()) return;
+  va_list ap;
+  va_start(ap, fmt);
+  vfprintf(g_tr, fmt, ap);
+  va_end(ap);
+  if (fmt[strlen(fmt) - 1] == '\n') ++g_tr_lines;
+}
+static std::string dp(const void *p) {
+  if (!p) return "0";
+  if (!in_arena(p)) return "host";
+  char b[24];
+  snprintf(b, sizeof b, "@%zx", (size_t)((const char *)p - g_base));
+  return b;
+}
+// streams (kind 0) and events (kind 1) are handles to their number in the order of creation; -1: the null stream
+static void *new_handle(int kind) { static long next[2]; long *h = (long *)malloc(sizeof(long)); *h = next[kind]++; return h; }
+static long id(const void *h) { return h ? *(const long *)h : -1; }
+#define I(f) tr(" " #f "=%lld", (long long)p.f);
+#define R(f) tr(" " #f "=%.17g", (double)p.f);
+#define P(f) tr(" " #f "=%s", dp(p.f).c_str());
+#define V(f) tr(" " #f "=[%s %d %d %d %d %d]", dp(p.f.base).c_str(), p.f.n_in, p.f.n_out, p.f.s_in, p.f.s_d, p.f.s_out);
+static void tr_struct(const NarrowParams &p) {
+  I(L) I(D) I(h) I(g) I(s) I(m) I(bsize) I(l2_flag) R(lr) R(wd) R(inv_b_global) P(red) V(lab) V(pl) P(Nh) P(Ng) P(Bnew)
+  P(out_behind) I(ob_s_h) I(ob_s_d) I(ob_s_m) P(out_ahead) I(oa_s_m) I(oa_s_d) I(oa_s_g) P(Nh_new) P(metrics) P(dbg) P(stamps)
+  P(counters) P(Bdirect) I(stop_after_update) I(fused) I(prep_ready) P(slabs) I(nslabs) I(slab_stride) I(nred) P(red_out) P(prepB)
+  P(prepG) P(sync) R(trunc_thr) I(left_dir) P(m_out) R(chol_thr) R(svd_stop2) P(status) I(wait_count) I(pipe) I(z_first) I(z_rows)
+  I(zsize) P(zred) V(zcore) P(flag) I(token) I(persist) I(write_ahead) I(persist_off) I(Mcap) P(prepRaw) P(pready) I(pwant) P(Apub)
+  P(coreflag) I(coretoken) P(zpoll_flag) I(zpoll_want) P(done_flag) I(done_val) P(abort_flag)
+}
+static void tr_struct(const WideParams &p) {
+  I(b) I(b_pad) I(L) I(h) I(g) I(hp) I(gp) I(do_f) I(do_ext) I(first_ext) I(act_fn) I(loss_fn) R(T) P(x_km1) P(x_k) P(x_kp1) P(Hprev)
+  P(Hcur) P(Gprev) P(Gcur) P(Bprev) V(ext_core) P(y) P(f) P(slabs) I(slab_stride) I(bsize) P(stamps)
+}
+static void tr_struct(const WidePipeParams &p) {
+  I(b) I(b_pad) I(L) I(hj) I(gj) I(gn) I(hprev) I(first) I(do_ext) I(first_ext) I(do_f) I(wait_flag) I(do_z) I(act_fn) I(loss_fn) R(T)
+  P(x_jm1) P(x_j) P(x_jp1) P(x_jp2) P(Eprev) P(Ecur) V(ext_core) P(Gj) P(Gn) P(Bnew) P(y) P(f) I(zsize) I(slab_stride) P(slabs) P(gslabs)
+  P(zred) P(gcnt) P(tcnt) I(nwide) I(gsz) I(ngroups) I(one_level) I(wg0) I(tiles_per_wg) I(ntiles) P(flag) I(token) P(status) I(persist)
+  P(coreflag) I(corewant) P(zready) I(zpublish) P(abort_flag) P(stamps)
+}
+static void tr_struct(const PersistHelperParams &p) {
+  I(zr) I(s) I(g) I(L) I(h) I(l2_flag) P(W) V(lab) V(pl) P(Ng) P(T) P(TN) P(Z) P(prepRaw) P(prepB) P(prepG) P(Apub) P(flag) I(want)
+  P(aflag) I(awant) P(zready) I(zwant) P(tcnt) P(pcnt) P(abort_flag) P(status) P(stamps)
+}
+static void tr_struct(const PersistStep &p) { tr(" n:"); tr_struct(p.n); tr(" w:"); tr_struct(p.w); tr(" t:"); tr_struct(p.t); }
+static void tr_struct(const PrepParams &p) { V(lab) V(pl) P(Nh) P(Ng) I(h) I(g) I(s) I(L) I(l2_flag) P(prepB) P(prepG) I(nparts) }
+static void tr_struct(const BigExtArgs &p) { P(Eprev) P(x_km1) P(x_k) V(A) I(b_pad) P(Ecur) P(Pk) }
+static void tr_struct(const ChainSite &p) { I(core_off) I(is_label) I(n_in) I(n_out) I(s_in) I(s_d) I(s_out) I(x_site) I(env_out_off) }
+static void tr_struct(const NormChainSite &p) { I(core_off) I(n_in) I(n_out) I(s_in) I(s_d) I(s_out) I(env_out_off) }
+#undef I
+#undef R
+#undef P
+#undef V
+template <class S> static void tr_rows(const char *what, const S *rows, int n) {
+  for (int i = 0; i < n; ++i) { tr("  %s %d:", what, i); tr_struct(rows[i]); tr("\n"); }
+}
+// every argument of a launch, by the parameter types of the kernel's demangled signature
+static void tr_launch(const std::string &name, dim3 g, dim3 b, size_t shm, hipStream_t st, void **args) {
+  const size_t lp = name.find('('), rp = name.rfind(')');
+  tr("launch %s grid=%u,%u,%u block=%u,%u,%u lds=%zu stream=s%ld", name.substr(0, lp).c_str(), g.x, g.y, g.z, b.x, b.y, b.z, shm, id(st));
+  std::vector<std::string> types;
+  for (size_t i = lp + 1, from = i, depth = 0; lp != std::string::npos && i <= rp; ++i) {
+    const char ch = name[i];
+    depth += (ch == '<') - (ch == '>');
+    if ((ch == ',' && !depth) || i == rp) { if (i > from) types.push_back(name.substr(from, i - from)); from = i + 1; }
+  }
+  for (size_t i = 0; i < types.size(); ++i) {
+    const std::string &t = types[i];
+    auto is = [&](const char *s) { return t.find(s) != std::string::npos; };
+    tr(" |");
+    if (is("*")) tr(" %s", dp(*(void **)args[i]).c_str());
+    else if (is("NarrowParams")) tr_struct(*(const NarrowParams *)args[i]);
+    else if (is("WidePipeParams")) tr_struct(*(const WidePipeParams *)args[i]);
+    else if (is("WideParams")) tr_struct(*(const WideParams *)args[i]);
+    else if (is("PrepParams")) tr_struct(*(const PrepParams *)args[i]);
+    else if (is("BigExtArgs")) tr_struct(*(const BigExtArgs *)args[i]);
+    else if (is("CoreView")) { const CoreView &v = *(const CoreView *)args[i]; tr(" [%s %d %d %d %d %d]", dp(v.base).c_str(), v.n_in, v.n_out, v.s_in, v.s_d, v.s_out); }
+    else if (is("BigFrontTiles")) tr(" %d %d", ((int *)args[i])[0], ((int *)args[i])[1]);
+    else if (is("float")) tr(" %.9g", *(float *)args[i]);
+    else if (is("long")) tr(" %lld", *(long long *)args[i]);
+    else if (is("int") || is("bool")) tr(" %d", *(int *)args[i]);
+    else tr(" ?");
+  }
+  tr("\n");
+  // tables and record arrays behind the first argument (their length is the second)
+  if (types.size() < 2 || types[0].find('*') == std::string::npos) return;
+  const void *tab = *(void **)args[0];
+  const int n = *(int *)args[1];
+  if (types[0].find("NormChainSite") != std::string::npos) tr_rows("site", (const NormChainSite *)tab, n);
+  else if (types[0].find("ChainSite") != std::string::npos) tr_rows("site", (const ChainSite *)tab, n);
+  else if (types[0].find("PersistStep") != std::string::npos) tr_rows("step", (const PersistStep *)tab, n + 1);      // (record n: the batch side's prologue)
+}
+static void tr_copy(const char *what, hipMemcpyKind k, const void *d, const void *s, size_t n, hipStream_t st) {
+  const char *kind = k == hipMemcpyHostToDevice ? "H2D" : k == hipMemcpyDeviceToHost ? "D2H" : k == hipMemcpyDeviceToDevice ? "D2D" : k == hipMemcpyHostToHost ? "H2H" : "default";
+  tr("%s %s dst=%s src=%s n=%zu stream=s%ld\n", what, kind, dp(d).c_str(), dp(s).c_str(), n, id(st));
+}
 }  // namespace san
 using namespace san;
 
@@ -202,7 +312,7 @@ static thread_local struct { dim3 g, b; size_t shm; hipStream_t st; } t_cfg;
 hipError_t __hipPushCallConfiguration(dim3 g, dim3 b, size_t shm, hipStream_t st) { t_cfg = {g, b, shm, st}; return hipSuccess; }
 hipError_t __hipPopCallConfiguration(dim3 *g, dim3 *b, size_t *shm, hipStream_t *st) { *g = t_cfg.g; *b = t_cfg.b; *shm = t_cfg.shm; *st = t_cfg.st; return hipSuccess; }
 
-hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t shm, hipStream_t) {
+hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t shm, hipStream_t st) {
   auto it = g_kernels.find(fn);
   const std::string name = it == g_kernels.end() ? "?" : it->second;
   g_ctx = name.c_str();
@@ -211,8 +321,7 @@ hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t s
     die("illegal launch: grid (%u,%u,%u) block (%u,%u,%u) dynamic LDS %zu", g.x, g.y, g.z, b.x, b.y, b.z, shm);
   const std::string key = name.substr(0, name.find('('));
   g_launches[key]++;
-  static const bool trace = getenv("SAN_TRACE") != nullptr;
-  if (trace) fprintf(stderr, "launch %s grid %u block %u lds %zu\n", key.c_str(), g.x, b.x, shm);
+  if (tracing()) tr_launch(name, g, b, shm, st, args);
   auto has = [&](const char *s) { return name.find(s) != std::string::npos; };
   if (has("sweep_persist") || has("persist_update_kernel") || has("persist_helper_kernel") || has("persist_batch_kernel")) {
     const PersistStep *st = *(const PersistStep **)args[0];
@@ -354,15 +463,23 @@ static void copy_checked(void *d, const void *s, size_t n, hipMemcpyKind k, cons
   memmove(d, s, n);                        // host sides are checked by AddressSanitizer
   g_ctx = "";
 }
-hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind k) { copy_checked(d, s, n, k, "hipMemcpy"); return hipSuccess; }
-hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind k, hipStream_t) { copy_checked(d, s, n, k, "hipMemcpyAsync"); return hipSuccess; }
-hipError_t hipMemcpy2DAsync(void *d, size_t dp, const void *s, size_t sp, size_t w, size_t h, hipMemcpyKind k, hipStream_t) {
-  if (w > dp || w > sp) die("hipMemcpy2DAsync: width %zu exceeds a pitch (%zu, %zu)", w, dp, sp);
-  for (size_t r = 0; r < h; ++r) copy_checked((char *)d + r * dp, (const char *)s + r * sp, w, k, "hipMemcpy2DAsync");
+hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind k) { tr_copy("memcpy", k, d, s, n, nullptr); copy_checked(d, s, n, k, "hipMemcpy"); return hipSuccess; }
+hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind k, hipStream_t st) { tr_copy("memcpy_async", k, d, s, n, st); copy_checked(d, s, n, k, "hipMemcpyAsync"); return hipSuccess; }
+hipError_t hipMemcpy2DAsync(void *d, size_t dpitch, const void *s, size_t spitch, size_t w, size_t h, hipMemcpyKind k, hipStream_t st) {
+  tr("memcpy2d_async rows=%zu dst_pitch=%zu src_pitch=%zu of ", h, dpitch, spitch);
+  tr_copy("row", k, d, s, w, st);
+  if (w > dpitch || w > spitch) die("hipMemcpy2DAsync: width %zu exceeds a pitch (%zu, %zu)", w, dpitch, spitch);
+  for (size_t r = 0; r < h; ++r) copy_checked((char *)d + r * dpitch, (const char *)s + r * spitch, w, k, "hipMemcpy2DAsync");
   return hipSuccess;
 }
-hipError_t hipMemset(void *d, int v, size_t n) { g_ctx = "hipMemset"; if (n) { need(d, n, "memset"); memset(d, v, n); } g_ctx = ""; return hipSuccess; }
-hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t) { return hipMemset(d, v, n); }
+hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t st) {
+  tr("memset dst=%s v=%d n=%zu stream=s%ld\n", dp(d).c_str(), v, n, id(st));
+  g_ctx = "hipMemset";
+  if (n) { need(d, n, "memset"); memset(d, v, n); }
+  g_ctx = "";
+  return hipSuccess;
+}
+hipError_t hipMemset(void *d, int v, size_t n) { return hipMemsetAsync(d, v, n, nullptr); }
 
 // ---- device, streams, events -----------------------------------------------------------------------------------------------------
 hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
@@ -381,15 +498,15 @@ hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_tR0600 *p, int) {
 }
 const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : "error (stub)"; }
 hipError_t hipGetLastError() { return hipSuccess; }
-hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = (hipStream_t)malloc(8); return hipSuccess; }
+hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = (hipStream_t)new_handle(0); return hipSuccess; }
 hipError_t hipStreamDestroy(hipStream_t s) { free(s); return hipSuccess; }
-hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
-hipError_t hipEventCreate(hipEvent_t *e) { *e = (hipEvent_t)malloc(8); return hipSuccess; }
+hipError_t hipStreamSynchronize(hipStream_t s) { tr("stream_sync s%ld\n", id(s)); return hipSuccess; }
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { tr("stream_wait s%ld e%ld\n", id(s), id(e)); return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t *e) { *e = (hipEvent_t)new_handle(1); return hipSuccess; }
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return hipEventCreate(e); }
 hipError_t hipEventDestroy(hipEvent_t e) { free(e); return hipSuccess; }
-hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
-hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { tr("event_record e%ld s%ld\n", id(e), id(s)); return hipSuccess; }
+hipError_t hipEventSynchronize(hipEvent_t e) { tr("event_sync e%ld\n", id(e)); return hipSuccess; }
 hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) { *ms = 0.01f; return hipSuccess; }
 
 // ---- RCCL: a one-rank world --------------------------------------------------------------------------------------------------------
@@ -397,7 +514,8 @@ ncclResult_t ncclGetUniqueId(ncclUniqueId *id) { memset(id, 7, sizeof *id); retu
 ncclResult_t ncclCommInitRank(ncclComm_t *c, int n, ncclUniqueId, int r) { if (n != 1 || r != 0) return ncclInvalidArgument; *c = (ncclComm_t)malloc(8); return ncclSuccess; }
 ncclResult_t ncclCommDestroy(ncclComm_t c) { free(c); return ncclSuccess; }
 const char *ncclGetErrorString(ncclResult_t) { return "rccl (stub)"; }
-ncclResult_t ncclAllReduce(const void *s, void *d, size_t count, ncclDataType_t t, ncclRedOp_t, ncclComm_t, hipStream_t) {
+ncclResult_t ncclAllReduce(const void *s, void *d, size_t count, ncclDataType_t t, ncclRedOp_t, ncclComm_t, hipStream_t st) {
+  tr("allreduce send=%s recv=%s count=%zu stream=s%ld\n", dp(s).c_str(), dp(d).c_str(), count, id(st));
   g_ctx = "ncclAllReduce";
   ++g_allreduces;
   const size_t el = t == ncclFloat ? 4 : (t == ncclDouble ? 8 : 4);
@@ -413,6 +531,7 @@ void san_stub_report(void) {
   for (auto &kv : g_launches) total += kv.second;
   printf("san-stub: %ld launches checked (%zu kernels), %ld pointer extents checked, %zu live allocations\n", total, g_launches.size(), g_checked_ptrs, g_alloc.size());
   for (auto &kv : g_launches) printf("    %-60s %ld\n", kv.first.c_str(), kv.second);
+  if (tracing()) { fflush(g_tr); printf("san-stub: call trace of %ld lines written\n", g_tr_lines); }
 }
 long san_stub_allreduces(void) { return g_allreduces; }
 long san_stub_launches(const char *substr) {

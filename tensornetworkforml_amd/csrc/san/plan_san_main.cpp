@@ -221,11 +221,16 @@ int main(int argc, char **argv) {
       {"c5 bond 50 L 10 b 5000", 784, 50, 5000, 10, TNML_TRUNC_FIXED, 2},
       {"c3 reference policy", 784, 20, 5000, 2, TNML_TRUNC_REFERENCE, 3},
       {"ragged N 25 bond 12 L 3", 25, 12, 77, 3, TNML_TRUNC_FIXED, 2},
+      {"ragged, adaptive rank", 25, 12, 77, 3, TNML_TRUNC_ADAPTIVE, 2},
       {"tiny N 3 bond 3", 3, 3, 9, 2, TNML_TRUNC_REFERENCE, 2},
       {"bond 64 L 3 (largest)", 18, 64, 200, 3, TNML_TRUNC_FIXED, 2},
   };
   for (size_t i = 0; i < cfgs.size(); ++i) {
     if (quick && cfgs[i].N == 784 && cfgs[i].M != 10) continue;
+    if (cfgs[i].policy == TNML_TRUNC_ADAPTIVE) {         // the kept rank comes back from the device after every step: per-step launches only
+      run(cfgs[i], 1); run(cfgs[i], 2); run(cfgs[i], 3);
+      continue;
+    }
     run(cfgs[i], 0);
     if (cfgs[i].M <= 20) { run(cfgs[i], 1); run(cfgs[i], 2); run(cfgs[i], 4); run(cfgs[i], 5); run(cfgs[i], 6); }
     else if (cfgs[i].M == 50) run(cfgs[i], 5);

@@ -89,7 +89,7 @@ struct tnml_ctx {
   bool f_current = false;     // ctx->f holds the f the next step must start from
   bool Bnew_valid = false;    // ctx->Bnew holds the updated B of the previous step
   int prev_h = 0, prev_g = 0; // dims of Bnew (relative frame)
-  int prev_left_dir = 0, prev_p = -1;
+  int prev_left_dir = 0;
   int last_bsize = 0, last_n = 0, last_h = 0, last_g = 0, last_left_dir = 0;
   bool debug = false, profile = false, stamps = false;
   bool check_launches = false;               // tnml_debug_enable bit 2: read the launch status back after every kernel launch
@@ -1201,38 +1201,62 @@ static void prof_end(tnml_ctx *c, int which) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// pipelined step (wide_pipe_device.h): operands of the batch-side workgroups for base step j (relative index; -1 = start of
-// a sweep), i.e. f from B_new(j) and the pre-gradient Z of step j+1.  Relative site t is absolute site t (right sweep)
-// or N-1-t (left sweep); E_t (behind environment of step t) lives in the behind stack's slot of relative site t-1, the
-// ahead environment of step t in the ahead stack's slot of relative site t+2.
+// The sweep-relative frame, in ONE place: sweep_impl (one launch per step at D = 2), sweep_persist (one launch
+// per sweep) and sweep_anyd (D = 3..8) all turn "the step at the label site, in direction d" into sites, bonds, strides and
+// environment / core slots through the functions of this section, and advance the host state through them.  Relative site t is
+// absolute site t (right sweep) or N-1-t (left sweep); the label core sits on relative site k, the step merges relative sites
+// (k, k+1); rel_site / rel_bond / x_rel / env_rel / norm_rel address the chain by the offset dt from the label site.
 // ---------------------------------------------------------------------------------------------
+static int rel_site(const tnml_ctx *c, int left_dir, int dt) { return left_dir ? c->l_pos - dt : c->l_pos + dt; }
+// bond between relative sites (k + dt, k + dt + 1); 1 beyond a chain end
+static int rel_bond(const tnml_ctx *c, int left_dir, int dt) {
+  const int i = left_dir ? c->l_pos - dt - 1 : c->l_pos + dt;
+  return (i < 0 || i > c->N - 2) ? 1 : c->bond[i];
+}
+// features of relative site k + dt; nullptr beyond a chain end
+static const float *x_rel(const tnml_ctx *c, int left_dir, int dt) {
+  const int i = rel_site(c, left_dir, dt);
+  return (i < 0 || i > c->N - 1) ? nullptr : c->X + (size_t)i * c->b_pad * c->D;
+}
+// environment over the sites behind (dt < 0: the stack the sweep grows) or ahead (dt > 0: the stack forward built) of relative
+// site k + dt, kept in that site's slot; nullptr beyond a chain end (== the scalar 1)
+static float *env_rel(const tnml_ctx *c, int left_dir, int dt) {
+  const int i = rel_site(c, left_dir, dt);
+  return (i < 0 || i > c->N - 1) ? nullptr : c->env_slot((dt > 0) != (left_dir != 0) ? c->Renv : c->Lenv, i);
+}
+// the same for the norm environments; dt == 0: the slot the step writes (behind norm environment of the next step)
+static double *norm_rel(const tnml_ctx *c, int left_dir, int dt) {
+  const int i = rel_site(c, left_dir, dt);
+  return (i < 0 || i > c->N - 1) ? nullptr : c->norm_slot((dt > 0) != (left_dir != 0) ? c->Rn : c->Ln, i);
+}
+
+// pipelined step (wide_pipe_device.h): operands of the batch-side workgroups for base step j (relative index; -1 = start of a sweep),
+// i.e. f from B_new(j) and the pre-gradient Z of step j+1; j is the step at the label site or the one before it.  E_t (behind
+// environment of step t) lives in the behind stack's slot of relative site t-1, the ahead environment of step t in the ahead stack's
+// slot of relative site t+2.
 static void fill_wide_pipe(tnml_ctx *c, WidePipeParams &w, int left_dir, int j, int act_fn, int loss_fn, float T) {
   const int N = c->N, D = c->D;
-  auto ab = [&](int t) { return left_dir ? N - 1 - t : t; };                       // relative -> absolute site
-  auto rb = [&](int t) { return left_dir ? c->bond[N - 2 - t] : c->bond[t]; };     // bond between relative sites t, t+1
-  float *beh = left_dir ? c->Renv : c->Lenv;
-  float *ahe = left_dir ? c->Lenv : c->Renv;
-  auto xs = [&](int t) -> const float * { return (t >= 0 && t <= N - 1) ? c->X + (size_t)ab(t) * c->b_pad * D : nullptr; };
+  const int o = j - (left_dir ? N - 1 - c->l_pos : c->l_pos);      // relative site j as an offset from the label site (0 or -1)
   w = WidePipeParams{};
   w.b = c->b; w.b_pad = c->b_pad; w.L = c->L;
   w.first = j < 0;
-  w.hj = j >= 1 ? rb(j - 1) : 1;
-  w.gj = (j >= 0 && j + 1 <= N - 2) ? rb(j + 1) : 1;
-  w.gn = (j + 2 <= N - 2) ? rb(j + 2) : 1;
-  w.hprev = j >= 2 ? rb(j - 2) : 1;
+  w.hj = rel_bond(c, left_dir, o - 1);
+  w.gj = j >= 0 ? rel_bond(c, left_dir, o + 1) : 1;
+  w.gn = rel_bond(c, left_dir, o + 2);
+  w.hprev = rel_bond(c, left_dir, o - 2);
   w.first_ext = (j == 1);
   w.act_fn = act_fn; w.loss_fn = loss_fn; w.T = T;
-  w.x_jm1 = xs(j - 1); w.x_j = xs(j); w.x_jp1 = xs(j + 1); w.x_jp2 = xs(j + 2);
-  w.Eprev = j >= 2 ? c->env_slot(beh, ab(j - 2)) : nullptr;
-  w.Ecur = j >= 1 ? c->env_slot(beh, ab(j - 1)) : nullptr;
+  w.x_jm1 = x_rel(c, left_dir, o - 1); w.x_j = x_rel(c, left_dir, o); w.x_jp1 = x_rel(c, left_dir, o + 1); w.x_jp2 = x_rel(c, left_dir, o + 2);
+  w.Eprev = env_rel(c, left_dir, o - 2);
+  w.Ecur = env_rel(c, left_dir, o - 1);
   if (j >= 1) {
-    w.ext_core.base = c->core_slot(ab(j - 1));
+    w.ext_core.base = c->core_slot(rel_site(c, left_dir, o - 1));
     w.ext_core.n_in = w.hprev; w.ext_core.n_out = w.hj;
     if (!left_dir) { w.ext_core.s_in = D * w.hj; w.ext_core.s_d = w.hj; w.ext_core.s_out = 1; }
     else { w.ext_core.s_in = 1; w.ext_core.s_d = w.hprev; w.ext_core.s_out = D * w.hprev; }
   }
-  w.Gj = (j >= 0 && j + 2 <= N - 1) ? c->env_slot(ahe, ab(j + 2)) : nullptr;
-  w.Gn = (j + 3 <= N - 1) ? c->env_slot(ahe, ab(j + 3)) : nullptr;
+  w.Gj = j >= 0 ? env_rel(c, left_dir, o + 2) : nullptr;
+  w.Gn = env_rel(c, left_dir, o + 3);
   w.Bnew = c->Bnew;
   w.y = c->y; w.f = c->f;
   w.zsize = (w.first ? 1 : w.hj * D) * D * D * w.gn * c->L;
@@ -1251,6 +1275,13 @@ static bool wide_pipe_fits(const tnml_ctx *c, const WidePipeParams &w) {
   return true;
 }
 
+// a small pre-gradient (bonds of a few): one reduction level, the sixteen chunk sums through the last arriver's LDS
+static void pipe_try_one_level(WidePipeParams &w) {
+  if (w.do_z && w.nwide <= 256 && (size_t)16 * (w.zsize + kMetricSlots) * sizeof(float) <= wide_pipe_lds_bytes(w) - 16) {
+    w.gsz = w.nwide; w.ngroups = 1; w.one_level = 1;
+  }
+}
+
 // Communicator path: whatever the batch-side stream still holds (f, environments, the exchanged pre-gradient) has to be complete
 // before the context's stream touches it outside a split step.
 static int split_join(tnml_ctx *c, bool leave_zbig = false) {
@@ -1266,31 +1297,221 @@ static int split_join(tnml_ctx *c, bool leave_zbig = false) {
   return TNML_OK;
 }
 
-// f-part operands for "the step that just ended" seen from relative step index k (k >= 1):
-// fills hp, gp, Hprev, Gprev, x_km1, x_k, Bprev of `w`.
-static void fill_prev_operands(tnml_ctx *c, WideParams &w, int left_dir, int p_prev) {
-  // previous step acted on sites (p_prev, p_prev+1)
-  const int N = c->N;
-  float *beh = left_dir ? c->Renv : c->Lenv;     // stack the sweep grows
-  float *ahe = left_dir ? c->Lenv : c->Renv;     // stack forward built
-  const int sbp = left_dir ? p_prev + 1 : p_prev, sap = left_dir ? p_prev : p_prev + 1;
-  w.hp = c->prev_h;
-  w.gp = c->prev_g;
-  const int beh_site = left_dir ? p_prev + 2 : p_prev - 1;   // env slot holding H of the previous step
-  const int ahe_site = left_dir ? p_prev - 1 : p_prev + 2;   // env slot holding G of the previous step
-  w.Hprev = (beh_site >= 0 && beh_site <= N - 1) ? c->env_slot(beh, beh_site) : nullptr;
-  w.Gprev = (ahe_site >= 0 && ahe_site <= N - 1) ? c->env_slot(ahe, ahe_site) : nullptr;
-  w.x_km1 = c->X + (size_t)sbp * c->b_pad * c->D;
-  w.x_k = c->X + (size_t)sap * c->b_pad * c->D;
-  w.Bprev = c->Bnew;
+// Two-stream communicator path of the pipelined step.  Hand-offs between the two streams: sequence numbers in memory where both
+// sides are kernels of this library (the update workgroup polls / stores them itself, the side stream runs a one-wave gate kernel and a
+// one-thread signal kernel) -- an event costs the stream that records or waits 6-7 us even when satisfied (tools/c5_gaps.py); events
+// stay for the first step of a run and for joining the side stream afterwards.
+// the side stream goes on once the last update launch has ended: gate kernel on its sequence number, or its event
+static int split_wait_update(tnml_ctx *c) {
+  if (c->split_flags_enabled && c->split_done_valid) {
+    if (!launch_big_gate(c->splitflags + 1, c->split_dseq, c->status, c->stream2)) return fail(TNML_ERR_HIP, "%s", big_launch_error());
+  } else HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_upd[c->split_upd], 0));
+  return TNML_OK;
+}
+// behind a batch-side launch: the pre-gradient summed over the ranks (zsize < 0: none), the sequence number and event the next update waits for
+static int split_exchange(tnml_ctx *c, int zsize) {
+  if (zsize >= 0) NCCL_TRY(ncclAllReduce(c->zred, c->zred, zsize + kMetricSlots, ncclFloat, ncclSum, c->comm, c->stream2));
+  if (c->split_flags_enabled) {
+    ++c->split_zseq;
+    if (!launch_big_signal(c->splitflags, c->split_zseq, c->stream2)) return fail(TNML_ERR_HIP, "%s", big_launch_error());
+    c->split_zsig_valid = true;
+  }
+  c->split_bat ^= 1;
+  HIP_TRY(hipEventRecord(c->ev_bat[c->split_bat], c->stream2));
+  c->split_pending = true;
+  return TNML_OK;
+}
+
+// Geometry of the step at the label site.  fail: 0, or 1 the reference's un-truncated factor does not fit, 2 merged tensor / 3 new cores over the buffers
+struct StepGeom {
+  int left_dir, p, k;      // the step merges absolute sites (p, p + 1); k: its index counted from the chain end the sweep left
+  int sb, sa;              // absolute site that keeps the behind (plain) core / that receives the label core
+  int h, g, s, m;          // behind, ahead, shared bond; kept rank (the cap under the adaptive policy)
+  int nn;                  // short side of the merged tensor as a matrix
+  size_t bsize;            // h D D g L
+  int fail;
+};
+static StepGeom step_geom(const tnml_ctx *c, int left_dir, int trunc_policy) {
+  const int N = c->N, D = c->D, L = c->L;
+  StepGeom q{};
+  q.left_dir = left_dir;
+  q.sb = c->l_pos; q.sa = rel_site(c, left_dir, 1);
+  q.p = std::min(q.sb, q.sa);
+  q.k = left_dir ? N - 1 - q.sb : q.sb;
+  q.h = rel_bond(c, left_dir, -1); q.s = rel_bond(c, left_dir, 0); q.g = rel_bond(c, left_dir, 1);
+  q.m = tnml_trunc_rank(trunc_policy, left_dir, q.p, N, c->ml(q.p), D, c->mr(q.p + 1), L, c->Mpol);
+  q.nn = std::min(D * q.h, D * q.g * L);
+  q.bsize = (size_t)q.h * D * D * q.g * L;
+  if (q.m < 0) q.fail = 1;
+  else if (q.bsize > c->bmax || q.m > c->Mmax) q.fail = 2;
+  else if ((size_t)q.h * D * q.m > c->core_stride || (size_t)q.m * D * q.g * L > c->lab_elems) q.fail = 3;
+  return q;
+}
+static int step_geom_error(const tnml_ctx *c, const StepGeom &q) {
+  if (q.fail == 1) return fail(TNML_ERR_SHAPE, "shapes not aligned: the reference's un-truncated SVD factor does not fit "
+                                               "at sites (%d, %d) (Network_class.py:914 / :949)", q.p, q.p + 1);
+  if (q.fail == 2) return fail(TNML_ERR_ARG, "step at sites (%d,%d) exceeds the buffers sized for M = %d", q.p, q.p + 1, c->Mmax);
+  return fail(TNML_ERR_ARG, "new cores at sites (%d,%d) exceed the buffers sized for M = %d", q.p, q.p + 1, c->Mmax);
+}
+
+// Update side of the step: what every planner passes the same way.  The caller adds what is its own: red, out_ahead, metrics; dbg,
+// stamps, Bdirect, stop_after_update, chol_thr; the fused / pipelined / persistent and the adaptive fields.
+static void fill_update(const tnml_ctx *c, NarrowParams &n, const StepGeom &q, int l2_flag, float lr, float wd) {
+  const int D = c->D, L = c->L, h = q.h, g = q.g, s = q.s, m = q.m;
+  n.L = L; n.D = D; n.h = h; n.g = g; n.s = s; n.m = m; n.bsize = (int)q.bsize;
+  n.l2_flag = l2_flag ? 1 : 0; n.lr = lr; n.wd = wd;
+  n.lab.base = c->lab[c->lab_cur]; n.lab.n_in = h; n.lab.n_out = s;
+  n.pl.base = c->core_slot(q.sa); n.pl.n_in = s; n.pl.n_out = g;
+  if (!q.left_dir) {
+    n.lab.s_in = D * s * L; n.lab.s_d = s * L; n.lab.s_out = L;
+    n.pl.s_in = D * g; n.pl.s_d = g; n.pl.s_out = 1;
+    n.ob_s_h = D * m; n.ob_s_d = m; n.ob_s_m = 1;
+    n.oa_s_m = D * g * L; n.oa_s_d = g * L; n.oa_s_g = L;
+  } else {
+    n.lab.s_in = L; n.lab.s_d = h * L; n.lab.s_out = D * h * L;
+    n.pl.s_in = 1; n.pl.s_d = s; n.pl.s_out = D * s;
+    n.ob_s_h = 1; n.ob_s_d = h; n.ob_s_m = D * h;
+    n.oa_s_m = L; n.oa_s_d = m * L; n.oa_s_g = D * m * L;
+  }
+  if (l2_flag) {
+    n.Nh = norm_rel(c, q.left_dir, -1);     // sites t < k
+    n.Ng = norm_rel(c, q.left_dir, 2);      // sites t > k + 1
+    n.Nh_new = norm_rel(c, q.left_dir, 0);
+  }
+  n.Bnew = c->Bnew;
+  n.out_behind = c->core_slot(q.sb);
+  n.svd_stop2 = c->svd_stop2;
+  n.status = c->status; n.counters = c->counters;
+}
+
+// Batch side of a classic step (wide kernel, generic-D batch kernel): gradient slabs of this step, the behind environment extended
+// by the core of relative site k - 1 and, where f is not current, f of the previous step from its updated B.  `stamps` is the caller's.
+static int fill_wide(const tnml_ctx *c, WideParams &w, const StepGeom &q, int act_fn, int loss_fn, float T) {
+  const int D = c->D, ld = q.left_dir;
+  w = WideParams{};
+  w.b = c->b; w.b_pad = c->b_pad; w.L = c->L;
+  w.h = q.h; w.g = q.g;
+  w.act_fn = act_fn; w.loss_fn = loss_fn; w.T = T;
+  w.y = c->y; w.f = c->f;
+  w.slabs = c->slabs; w.slab_stride = c->slab_stride; w.bsize = (int)q.bsize;
+  w.x_k = x_rel(c, ld, 0);
+  w.x_kp1 = x_rel(c, ld, 1);
+  w.hp = 1; w.gp = 1;
+  w.do_ext = (q.k >= 1);
+  w.first_ext = (q.k == 1);
+  if (q.k >= 1) {                                    // relative site k - 1, plain since the previous step
+    const int hp = w.hp = rel_bond(c, ld, -2);
+    w.x_km1 = x_rel(c, ld, -1);
+    w.ext_core.base = c->core_slot(rel_site(c, ld, -1));
+    w.ext_core.n_in = hp; w.ext_core.n_out = q.h;
+    if (!ld) { w.ext_core.s_in = D * q.h; w.ext_core.s_d = q.h; w.ext_core.s_out = 1; }
+    else { w.ext_core.s_in = 1; w.ext_core.s_d = hp; w.ext_core.s_out = D * hp; }
+    w.Hprev = env_rel(c, ld, -2);
+    w.Hcur = env_rel(c, ld, -1);
+  }
+  if (c->Bnew_valid && !c->f_current) {
+    // f of the previous step from its updated B: that step acted on relative sites k - 1, k
+    if (q.k < 1 || c->prev_h != w.hp || c->prev_g != q.s)
+      return fail(TNML_ERR_STATE, "internal: previous-step dims (%d,%d) do not match (%d,%d)", c->prev_h, c->prev_g, w.hp, q.s);
+    w.do_f = 1;
+    w.gp = q.s;
+    w.Gprev = env_rel(c, ld, 1);                     // sites t > k
+    w.Bprev = c->Bnew;
+  }
+  w.Gcur = env_rel(c, ld, 2);
+  return TNML_OK;
+}
+
+// algorithmic work of a step: environments, features of three sites, f, labels; gradient + f products and the extension
+static void add_step_work(const tnml_ctx *c, const StepGeom &q, double &bytes, double &flops) {
+  const double bb = (double)c->b, D = c->D, L = c->L, h = q.h, g = q.g;
+  bytes += 4.0 * bb * (2.0 * h + g + 3.0 * D + 2.0 * L + 1.0);
+  flops += 4.0 * bb * D * D * h * g * L + 2.0 * bb * D * h * h;
+}
+
+// the step is planned: the label moves on to site sa, the bond between the two sites is the kept rank, the other label buffer is current
+static void advance_frame(tnml_ctx *c, const StepGeom &q, int m_kept, bool note_last = true) {
+  c->bond[q.p] = m_kept;
+  c->l_pos = q.sa;
+  c->lab_cur ^= 1;
+  c->prev_h = q.h; c->prev_g = q.g; c->prev_left_dir = q.left_dir;
+  if (note_last) { c->last_bsize = (int)q.bsize; c->last_n = q.nn; c->last_h = q.h; c->last_g = q.g; c->last_left_dir = q.left_dir; }
+}
+
+// after the launches of a step of the per-step planners; f_stored: the batch-side work of the step stored its f already
+static int finish_step(tnml_ctx *c, const StepGeom &q, int trunc_policy, int step, bool f_stored) {
+  int m_kept = q.m;
+  if (trunc_policy == TNML_TRUNC_ADAPTIVE) {       // the kept rank is decided on the device: one sync per step
+    HIP_TRY(hipMemcpyAsync(&m_kept, c->status + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (m_kept < 1 || m_kept > q.m) return fail(TNML_ERR_NONFINITE, "adaptive truncation returned rank %d (cap %d)", m_kept, q.m);
+  }
+  advance_frame(c, q, m_kept);
+  c->cnt_steps += 1;
+  add_step_work(c, q, c->cnt_bytes, c->cnt_flops);
+  c->Bnew_valid = true;
+  c->f_current = f_stored;
+  if (c->check_launches) HIP_TRY(hipGetLastError());
+  if (c->sync_interval > 0 && (step + 1) % c->sync_interval == 0) HIP_TRY(hipStreamSynchronize(c->stream));
+  return TNML_OK;
+}
+
+// mode 1 (standalone update_B) ends here: the behind environment list grew (as update_B does, Network_class.py:637-652), nothing else changes
+static int finish_update_only(tnml_ctx *c, float *metrics_out) {
+  HIP_TRY(hipGetLastError());
+  if (metrics_out) {
+    HIP_TRY(hipMemcpyAsync(metrics_out, c->metrics, 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  return TNML_OK;
+}
+
+// after the last step of a call: valid norm stacks, f from the last updated B (what sweep_step returns, Network_class.py:573), copies out
+static int finish_sweep(tnml_ctx *c, int left_dir, int n_steps, int l2_flag, int nblk, hipEvent_t sw_ev1, float *metrics_out, float *f_out) {
+  // the behind norm stack is whole (the one valid for the opposite direction) once the sweep is complete; mid-sweep the ahead one stays usable
+  bool &behind = left_dir ? c->Rn_valid : c->Ln_valid, &ahead = left_dir ? c->Ln_valid : c->Rn_valid;
+  const bool complete = c->l_pos == (left_dir ? 0 : c->N - 1);
+  behind = l2_flag && complete;
+  if (!l2_flag || complete) ahead = false;
+  if (!c->f_current) {
+    // the step that just ended acted on relative sites (k - 1, k) seen from the label site
+    WideParams w{};
+    w.b = c->b; w.b_pad = c->b_pad; w.L = c->L;
+    w.hp = c->prev_h; w.gp = c->prev_g;
+    w.Hprev = env_rel(c, left_dir, -2);
+    w.Gprev = env_rel(c, left_dir, 1);
+    w.x_km1 = x_rel(c, left_dir, -1);
+    w.x_k = x_rel(c, left_dir, 0);
+    w.Bprev = c->Bnew;
+    w.f = c->f;
+    prof_begin(c);
+    if (c->D == kD) launch_f_only(w, nblk, c->stream);
+    else {
+      w.do_f = 1;
+      if (!launch_batch_anyd(w, c->D, nblk, false, c->stream))
+        return fail(TNML_ERR_ARG, "f of the last step at D = %d needs %zu bytes of LDS", c->D, anyd_batch_lds_bytes(c->D, w.hp, w.gp, 1, 1, c->L));
+      c->sweep_launches += 1;
+    }
+    prof_end(c, 1);
+    HIP_TRY(hipGetLastError());
+    c->f_current = true;
+  }
+  if (sw_ev1) HIP_TRY(hipEventRecord(sw_ev1, c->stream));
+  if (metrics_out) HIP_TRY(hipMemcpyAsync(metrics_out, c->metrics, (size_t)n_steps * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (f_out) { int rc = copy_f_out(c, c->f, f_out); if (rc) return rc; }
+  if (metrics_out || f_out) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return check_status(c);
+  }
+  return TNML_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
 // Persistent sweep: the whole sweep as ONE launch of sweep_persist_kernel (kernels_narrow.hip).  Applies to a full sweep that
 // starts right after tnml_forward on a single GPU, fixed or reference truncation (all bond dimensions are known before the
-// launch), every step in the in-LDS regime, no per-step capture.  Plans every step exactly as the per-step path does (the
-// records ARE its NarrowParams / WidePipeParams, plus the hand-off fields), so the host bookkeeping -- bonds, label position,
-// label-core buffer -- advances through the same statements.  Returns 1 if the sweep was enqueued, 0 if this sweep has to take
+// launch), every step in the in-LDS regime, no per-step capture.  Every step is planned through the shared frame functions above (the
+// records ARE the per-step path's NarrowParams / WidePipeParams, plus the hand-off fields), and the host bookkeeping -- bonds, label
+// position, label-core buffer -- advances through advance_frame.  Returns 1 if the sweep was enqueued, 0 if this sweep has to take
 // the per-step path (state untouched), < 0 on error.
 // ---------------------------------------------------------------------------------------------
 static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float weight_dec, int l2_flag, int act_fn, int loss_fn,
@@ -1309,7 +1530,6 @@ static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float
   PersistStep *st = c->pst_host[buf];
   st[n_steps] = PersistStep{};
   WidePipeParams &pro = st[n_steps].w;                       // the batch side's prologue rides in the record after the last step
-  double *nbeh = left_dir ? c->Rn : c->Ln, *nahe = left_dir ? c->Ln : c->Rn;
   const int ntiles = c->b_pad / kTS;
   // one sample tile per batch-side workgroup while the device has the CUs (the reduced pre-gradient of step k+1 has to be there
   // when step k ends: with two tiles per workgroup it arrived ~2 us late behind a 40-round SVD); fixed for the whole launch --
@@ -1331,59 +1551,27 @@ static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float
   pro.wg0 = 1 + nH; pro.persist = 1; pro.zred = zr2[0]; pro.zready = fl + 2; pro.zpublish = 1; pro.abort_flag = fl + 4;
   pro.gcnt = c->pst_cnt + (size_t)n_steps * 32; pro.tcnt = pro.gcnt + 16;
   if (!wide_pipe_fits(c, pro)) return give_up();
-  if (pro.nwide <= 256 && (size_t)16 * (pro.zsize + kMetricSlots) * sizeof(float) <= wide_pipe_lds_bytes(pro) - 16) { pro.gsz = pro.nwide; pro.ngroups = 1; pro.one_level = 1; }
+  pipe_try_one_level(pro);
   lds_wide = wide_pipe_lds_bytes(pro);
   double bytes = 0, flops = 0;
   for (int k = 0; k < n_steps; ++k) {
-    const int l = c->l_pos;
-    const int p = left_dir ? l - 1 : l;
-    const int sb = left_dir ? p + 1 : p, sa = left_dir ? p : p + 1;
-    const int h = left_dir ? c->mr(p + 1) : c->ml(p);
-    const int g = left_dir ? c->ml(p) : c->mr(p + 1);
-    const int s = c->bond[p];
-    const int m = tnml_trunc_rank(trunc_policy, left_dir, p, N, c->ml(p), D, c->mr(p + 1), L, c->Mpol);
-    if (m < 0) return give_up();                             // the per-step path reports the reference's ValueError
-    const size_t bsize = (size_t)h * D * D * g * L;
-    if (bsize > c->bmax || m > c->Mmax || (size_t)h * D * m > c->core_stride || (size_t)m * D * g * L > c->lab_elems) return give_up();
-    const int r = D * h, cc = D * g * L, nn = std::min(r, cc);
+    const StepGeom q = step_geom(c, left_dir, trunc_policy);
+    if (q.fail) return give_up();                            // the per-step path reports it (the reference's ValueError, the buffers)
+    const int h = q.h, g = q.g, s = q.s, m = q.m;
     const size_t nlds = narrow_lds_bytes(h, g, s, L, m);
-    if (nn > 64 || (nn & 1) || nlds + pbytes > 160 * 1024 || h > Mcap || m > Mcap || bsize > 8192) return give_up();
+    if (q.nn > 64 || (q.nn & 1) || nlds + pbytes > 160 * 1024 || h > Mcap || m > Mcap || q.bsize > 8192) return give_up();
     PersistStep &ps = st[k];
     ps = PersistStep{};
-    // ---- update + SVD workgroup
+    // ---- update + SVD workgroup (Nh / Ng: only "is there one", the values are in LDS)
     NarrowParams &n = ps.n;
-    n.L = L; n.D = D; n.h = h; n.g = g; n.s = s; n.m = m; n.bsize = (int)bsize;
-    n.l2_flag = l2_flag ? 1 : 0; n.lr = lr; n.wd = weight_dec;
-    n.pl.base = c->core_slot(sa); n.pl.n_in = s; n.pl.n_out = g;
-    n.lab.base = c->lab[c->lab_cur]; n.lab.n_in = h; n.lab.n_out = s;
-    if (!left_dir) {
-      n.lab.s_in = D * s * L; n.lab.s_d = s * L; n.lab.s_out = L;
-      n.pl.s_in = D * g; n.pl.s_d = g; n.pl.s_out = 1;
-      n.ob_s_h = D * m; n.ob_s_d = m; n.ob_s_m = 1;
-      n.oa_s_m = D * g * L; n.oa_s_d = g * L; n.oa_s_g = L;
-    } else {
-      n.lab.s_in = L; n.lab.s_d = h * L; n.lab.s_out = D * h * L;
-      n.pl.s_in = 1; n.pl.s_d = s; n.pl.s_out = D * s;
-      n.ob_s_h = 1; n.ob_s_d = h; n.ob_s_m = D * h;
-      n.oa_s_m = L; n.oa_s_d = m * L; n.oa_s_g = D * m * L;
-    }
-    {
-      const int bs_ = left_dir ? p + 2 : p - 1, as_ = left_dir ? p - 1 : p + 2;
-      n.Nh = (l2_flag && bs_ >= 0 && bs_ <= N - 1) ? c->norm_slot(nbeh, bs_) : nullptr;     // only "is there one": the values are in LDS
-      n.Ng = (l2_flag && as_ >= 0 && as_ <= N - 1) ? c->norm_slot(nahe, as_) : nullptr;
-      n.Nh_new = l2_flag ? c->norm_slot(nbeh, sb) : nullptr;
-    }
-    n.Bnew = c->Bnew;
-    n.out_behind = c->core_slot(sb);
+    fill_update(c, n, q, l2_flag, lr, weight_dec);
     // the label core is written once, by the last step: into the buffer the per-step sequence would have ended on
     n.out_ahead = c->lab[(c->lab_cur + (n_steps - k)) & 1];
     n.write_ahead = (k == n_steps - 1);
     n.metrics = c->metrics + 2 * (size_t)k;
-    n.svd_stop2 = c->svd_stop2; n.chol_thr = c->chol_thr;
-    n.status = c->status; n.counters = c->counters;
+    n.chol_thr = c->chol_thr;
     n.stamps = (c->stamps && k == n_steps / 2) ? c->dbg + 4 * c->bmax + kDbgSigma + 5 : nullptr;
     n.pipe = 1; n.persist = 1; n.z_first = (k == 0);
-    ps.w = WidePipeParams{};
     fill_wide_pipe(c, ps.w, left_dir, k, act_fn, loss_fn, T);
     WidePipeParams &wp = ps.w;
     const int zr = k == 0 ? 1 : wp.hprev * D;
@@ -1407,7 +1595,7 @@ static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float
     wp.gcnt = c->pst_cnt + (size_t)k * 32; wp.tcnt = wp.gcnt + 16;
     wp.stamps = n.stamps;
     if (!wide_pipe_fits(c, wp)) return give_up();
-    if (wp.do_z && wp.nwide <= 256 && (size_t)16 * (wp.zsize + kMetricSlots) * sizeof(float) <= wide_pipe_lds_bytes(wp) - 16) { wp.gsz = wp.nwide; wp.ngroups = 1; wp.one_level = 1; }
+    pipe_try_one_level(wp);
     lds_wide = std::max(lds_wide, wide_pipe_lds_bytes(wp));
     // ---- helper workgroups: T_k, T_k . Ng beside the SVD of step k-1; the three projections once its behind core is published
     PersistHelperParams &t = ps.t;
@@ -1421,14 +1609,9 @@ static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float
     t.abort_flag = fl + 4; t.status = c->status; t.stamps = n.stamps;
     lds_help = std::max(lds_help, persist_helper_lds_bytes(zr, s, g, L, h, nH));
     if ((size_t)zr * D * D * g * L + kMetricSlots > (size_t)c->zstride) return give_up();
-    // ---- the bookkeeping of the per-step path
-    c->bond[p] = m;
-    c->l_pos = sa;
-    c->lab_cur ^= 1;
-    c->prev_h = h; c->prev_g = g; c->prev_p = p;
-    bytes += 4.0 * c->b * (2.0 * h + g + 3.0 * D + 2.0 * L + 1.0);
-    flops += 4.0 * c->b * D * D * h * g * L + 2.0 * c->b * D * h * h;
-    if (!c->stamps || k <= n_steps / 2) { c->last_bsize = (int)bsize; c->last_n = nn; c->last_h = h; c->last_g = g; c->last_left_dir = left_dir; }
+    // ---- the bookkeeping of the per-step path (the capture block belongs to the stamped step, if there is one)
+    advance_frame(c, q, m, !c->stamps || k <= n_steps / 2);
+    add_step_work(c, q, bytes, flops);
   }
   const size_t lds = c->persist_mode >= 2 ? lds_narrow + pbytes : std::max(std::max(lds_narrow + pbytes, lds_wide), lds_help);
   if (lds > 160 * 1024 || lds_wide > 160 * 1024 || lds_help > 160 * 1024) return give_up();
@@ -1459,7 +1642,6 @@ static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float
     launch_sweep_persist(c->pst_dev, n_steps, nH, 1 + nH + nwide, lds, c->stream);
     HIP_TRY(hipGetLastError());
   }
-  c->prev_left_dir = left_dir;
   c->cnt_steps += n_steps; c->cnt_bytes += bytes; c->cnt_flops += flops;
   c->sweep_launches += 1; c->step_launches += n_steps; c->persist_sweeps += 1;
   c->Bnew_valid = true; c->f_current = true; c->Z_valid = false; c->Zbig_valid = false;
@@ -1508,10 +1690,6 @@ static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep
     if (left_dir && !c->Ln_valid) { int rc = build_norm_chain(c, false); if (rc) return rc; c->Ln_valid = true; }
   }
   const int nblk = c->b_pad / kTS;
-  float *beh = left_dir ? c->Renv : c->Lenv;
-  float *ahe = left_dir ? c->Lenv : c->Renv;
-  double *nbeh = left_dir ? c->Rn : c->Ln;
-  double *nahe = left_dir ? c->Ln : c->Rn;
   hipEvent_t sw_ev1 = nullptr;
   if (c->sweep_timing && mode == 0) {
     if (c->sweep_ev_used + 2 > c->sweep_ev.size()) {
@@ -1533,22 +1711,10 @@ static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep
     if (done_persist < 0) return done_persist;
   }
   for (int step = 0; step < (done_persist ? 0 : n_steps); ++step) {
-    const int l = c->l_pos;
-    const int p = left_dir ? l - 1 : l;
-    const int k = left_dir ? (N - 2 - p) : p;
-    const int sb = left_dir ? p + 1 : p, sa = left_dir ? p : p + 1;
-    const int h = left_dir ? c->mr(p + 1) : c->ml(p);
-    const int g = left_dir ? c->ml(p) : c->mr(p + 1);
-    const int s = c->bond[p];
-    const int m = tnml_trunc_rank(trunc_policy, left_dir, p, N, c->ml(p), D, c->mr(p + 1), L, c->Mpol);
-    if (m < 0) return fail(TNML_ERR_SHAPE, "shapes not aligned: the reference's un-truncated SVD factor does not fit "
-                                           "at sites (%d, %d) (Network_class.py:914 / :949)", p, p + 1);
-    const int r = D * h, cc = D * g * L, nn = std::min(r, cc);
-    const size_t bsize = (size_t)h * D * D * g * L;
-    if (bsize > c->bmax || m > c->Mmax)
-      return fail(TNML_ERR_ARG, "step at sites (%d,%d) exceeds the buffers sized for M = %d", p, p + 1, c->Mmax);
-    if ((size_t)h * D * m > c->core_stride || (size_t)m * D * g * L > c->lab_elems)
-      return fail(TNML_ERR_ARG, "new cores at sites (%d,%d) exceed the buffers sized for M = %d", p, p + 1, c->Mmax);
+    const StepGeom q = step_geom(c, left_dir, trunc_policy);
+    if (q.fail) return step_geom_error(c, q);
+    const int p = q.p, k = q.k, h = q.h, g = q.g, s = q.s, m = q.m, nn = q.nn;
+    const size_t bsize = q.bsize;
     const int npath = narrow_path(c, h, g, s, L, m);
     if (npath < 0) return npath;
     bool f_by_z = false;          // f of this step stored by the batch kernel of the next one (pipelined large-tensor step)
@@ -1556,41 +1722,16 @@ static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep
     // ---- parameters of the narrow kernel (built first: the wide launch carries its slice workgroups) ---------
     // single GPU + in-LDS path: the slab reduction rides in the narrow launch as helper workgroups (no separate
     // reduce kernel, no boundary) and the merge / L2 products ride in the wide launch (or, with the plain-FMA wide
-    // kernel, in the narrow launch as well); TNML_NARROW_FUSED=0 turns all of that off
-    const bool fuse_ok = true;
-    const bool prep_ok = fuse_ok && npath == 0 && mode == 0 && !Bdirect_dev;     // merge / L2 slices in the wide launch
-    const bool fused = prep_ok && !c->comm;                                       // + slab reduction in the narrow launch
+    // kernel, in the narrow launch as well)
+    const bool prep_ok = npath == 0 && mode == 0 && !Bdirect_dev;     // merge / L2 slices in the wide launch
+    const bool fused = prep_ok && !c->comm;                           // + slab reduction in the narrow launch
     NarrowParams n{};
-    n.L = L; n.D = D; n.h = h; n.g = g; n.s = s; n.m = m; n.bsize = (int)bsize;
-    n.l2_flag = l2_flag ? 1 : 0; n.lr = lr; n.wd = weight_dec;
+    fill_update(c, n, q, l2_flag, lr, weight_dec);
     n.red = c->red;
-    n.lab.base = c->lab[c->lab_cur]; n.lab.n_in = h; n.lab.n_out = s;
-    n.pl.base = c->core_slot(sa); n.pl.n_in = s; n.pl.n_out = g;
-    if (!left_dir) {
-      n.lab.s_in = D * s * L; n.lab.s_d = s * L; n.lab.s_out = L;
-      n.pl.s_in = D * g; n.pl.s_d = g; n.pl.s_out = 1;
-      n.ob_s_h = D * m; n.ob_s_d = m; n.ob_s_m = 1;
-      n.oa_s_m = D * g * L; n.oa_s_d = g * L; n.oa_s_g = L;
-    } else {
-      n.lab.s_in = L; n.lab.s_d = h * L; n.lab.s_out = D * h * L;
-      n.pl.s_in = 1; n.pl.s_d = s; n.pl.s_out = D * s;
-      n.ob_s_h = 1; n.ob_s_d = h; n.ob_s_m = D * h;
-      n.oa_s_m = L; n.oa_s_d = m * L; n.oa_s_g = D * m * L;
-    }
-    {
-      const int bs_ = left_dir ? p + 2 : p - 1;     // norm env behind: sites t < k
-      const int as_ = left_dir ? p - 1 : p + 2;     // norm env ahead:  sites t > k+1
-      n.Nh = (l2_flag && bs_ >= 0 && bs_ <= N - 1) ? c->norm_slot(nbeh, bs_) : nullptr;
-      n.Ng = (l2_flag && as_ >= 0 && as_ <= N - 1) ? c->norm_slot(nahe, as_) : nullptr;
-      n.Nh_new = l2_flag ? c->norm_slot(nbeh, sb) : nullptr;
-    }
-    n.Bnew = c->Bnew;
-    n.out_behind = c->core_slot(sb);
     n.out_ahead = c->lab[c->lab_cur ^ 1];
     n.metrics = c->metrics + 2 * (size_t)step;
     n.dbg = (c->debug || mode == 1) ? c->dbg : nullptr;
     n.Bdirect = Bdirect_dev;
-    n.svd_stop2 = c->svd_stop2;
     n.chol_thr = c->chol_thr;
     n.stop_after_update = mode == 1;
     if (fused) {
@@ -1601,10 +1742,8 @@ static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep
     if (trunc_policy == TNML_TRUNC_ADAPTIVE && mode == 0) { n.trunc_thr = c->trunc_thr; n.left_dir = left_dir; n.m_out = c->status + 1; }
     if (mode == 1) { n.Bnew = c->Bscr2; n.Nh_new = nullptr; }
     n.stamps = (c->debug || c->stamps) ? c->dbg + 4 * c->bmax + kDbgSigma + 5 : nullptr;
-    n.status = c->status;
-    n.counters = c->counters;
     // ---- pipelined step: ONE launch (update + SVD of step k next to the batch-side work of step k+1) ----------------
-    bool pipe = c->pipe_enabled && fuse_ok && npath == 0 && mode == 0 && !Bdirect_dev;
+    bool pipe = c->pipe_enabled && prep_ok;
     if (pipe && prep_slice_lds_bytes(h, g, s, L) > 160 * 1024) pipe = false;      // the slice workgroups of the launch must fit too
     WidePipeParams wp{}, wpro{};
     bool need_prologue = false;
@@ -1613,10 +1752,7 @@ static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep
       wp.do_ext = k >= 1; wp.do_f = 1; wp.wait_flag = 1;
       wp.do_z = (k + 1 <= N - 2);
       if (wp.do_z && !wide_pipe_fits(c, wp)) wp.do_z = 0;            // the next step will start from its own prologue
-      if (wp.do_z && wp.nwide <= 256 && (size_t)16 * (wp.zsize + kMetricSlots) * sizeof(float) <= wide_pipe_lds_bytes(wp) - 16) {
-        // a small pre-gradient (bonds of a few): one reduction level, the sixteen chunk sums through the last arriver's LDS
-        wp.gsz = wp.nwide; wp.ngroups = 1; wp.one_level = 1;
-      }
+      pipe_try_one_level(wp);
       if (wp.do_z && c->pipe_tiles > wp.tiles_per_wg && nn >= 32) {
         // the SVD of this step is long (short side >= 32): a batch-side workgroup accumulates several sample tiles in
         // registers before it writes its partial pre-gradient -- proportionally fewer partial tensors to write and re-read
@@ -1641,87 +1777,29 @@ static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep
     // batch side on stream2 followed by the all-reduce, which then travels beside the SVD; the next update launch waits
     // for its event.  Same kernels, same arithmetic as the fused launch (the B_new hand-off is a flag in memory either way).
     const bool split = pipe && c->comm && c->split_enabled && !c->profile;
-    if (pipe && !split) { int rc = split_join(c); if (rc) return rc; }
-    if (pipe && split) {
-      // Hand-offs between the two streams: sequence numbers in memory where both sides are kernels of this library (the update
-      // workgroup polls / stores them itself, the side stream runs a one-wave gate kernel and a one-thread signal kernel) -- an
-      // event costs the stream that records or waits 6-7 us even when satisfied (tools/c5_gaps.py); events stay for the first step of a
-      // run and for joining the side stream afterwards.
-      const bool sflags = c->split_flags_enabled;
-      if (sflags && !c->splitflags) {
-        HIP_TRY(hipMalloc(&c->splitflags, 4 * sizeof(unsigned)));
-        HIP_TRY(hipMemsetAsync(c->splitflags, 0, 4 * sizeof(unsigned), c->stream));
-      }
-      if (!c->split_pending) {                 // first split step after anything else: stream2 starts behind the context's stream
-        c->split_upd ^= 1;
-        HIP_TRY(hipEventRecord(c->ev_upd[c->split_upd], c->stream));
-        c->split_done_valid = false; c->split_zsig_valid = false;
-      }
-      if (need_prologue) {
-        NarrowParams none{};
-        wpro.wg0 = 0;
-        if (sflags && c->split_done_valid) { if (!launch_big_gate(c->splitflags + 1, c->split_dseq, c->status, c->stream2)) return fail(TNML_ERR_HIP, "%s", big_launch_error()); }
-        else HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_upd[c->split_upd], 0));
-        launch_step_pipe(none, wpro, wide_pipe_lds_bytes(wpro), c->stream2);
-        c->sweep_launches++; c->step_launches++;
-        NCCL_TRY(ncclAllReduce(c->zred, c->zred, wpro.zsize + kMetricSlots, ncclFloat, ncclSum, c->comm, c->stream2));
-        if (sflags) { ++c->split_zseq; if (!launch_big_signal(c->splitflags, c->split_zseq, c->stream2)) return fail(TNML_ERR_HIP, "%s", big_launch_error()); c->split_zsig_valid = true; }
-        c->split_bat ^= 1;
-        HIP_TRY(hipEventRecord(c->ev_bat[c->split_bat], c->stream2));
-        c->split_pending = true;
-        if (wpro.do_f) c->f_current = true;
-      }
-      n.fused = 1; n.nred = 0; n.sync = c->sync; n.red_out = nullptr;
-      n.prep_ready = 0;
-      n.wait_count = kD * kD * (h > 8 ? 2 : 1);
-      n.pipe = 1; n.z_first = (k == 0); n.z_rows = wp.hprev * D;
-      n.zsize = (k == 0 ? 1 : n.z_rows) * D * D * g * L;
-      n.zred = c->zred; n.red = c->zred; n.zcore = wp.ext_core;
-      n.flag = c->pipe_cnt + 17; n.token = ++c->token;
-      wp.token = n.token;
-      wp.wg0 = 1 + n.wait_count;
-      const size_t lds_u = std::max(narrow_lds_bytes(h, g, s, L, m), prep_slice_lds_bytes(h, g, s, L));
-      const size_t lds_b = wide_pipe_lds_bytes(wp);
-      if (lds_u > 160 * 1024 || lds_b > 160 * 1024) return fail(TNML_ERR_ARG, "internal: pipelined step needs %zu / %zu bytes of LDS", lds_u, lds_b);
-      // batch side of step k: needs the behind core the update launch of step k-1 left (event), then B_new(k) (flag in memory)
-      const int upd_prev = c->split_upd;
-      if (sflags && c->split_done_valid) { if (!launch_big_gate(c->splitflags + 1, c->split_dseq, c->status, c->stream2)) return fail(TNML_ERR_HIP, "%s", big_launch_error()); }
-      else HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_upd[upd_prev], 0));
-      {
-        NarrowParams none{};
-        WidePipeParams wb = wp;
-        wb.wg0 = 0;
-        launch_step_pipe(none, wb, lds_b, c->stream2);
-      }
-      // update side of step k: needs Z_k summed over the ranks (the exchange enqueued behind the previous batch-side launch)
-      if (c->split_pending) {
-        if (sflags && c->split_zsig_valid) { n.zpoll_flag = c->splitflags; n.zpoll_want = c->split_zseq; }
-        else HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_bat[c->split_bat], 0));
-      }
-      if (sflags) { n.done_flag = c->splitflags + 1; n.done_val = ++c->split_dseq; }
-      launch_step_pipe_update(n, wp, lds_u, c->stream);
-      if (sflags) c->split_done_valid = true;
+    if (pipe) {
+      if (!split) { int rc = split_join(c); if (rc) return rc; }
       else {
-        c->split_upd ^= 1;
-        HIP_TRY(hipEventRecord(c->ev_upd[c->split_upd], c->stream));
+        if (c->split_flags_enabled && !c->splitflags) {
+          HIP_TRY(hipMalloc(&c->splitflags, 4 * sizeof(unsigned)));
+          HIP_TRY(hipMemsetAsync(c->splitflags, 0, 4 * sizeof(unsigned), c->stream));
+        }
+        if (!c->split_pending) {                 // first split step after anything else: stream2 starts behind the context's stream
+          c->split_upd ^= 1;
+          HIP_TRY(hipEventRecord(c->ev_upd[c->split_upd], c->stream));
+          c->split_done_valid = false; c->split_zsig_valid = false;
+        }
       }
-      if (wp.do_z) NCCL_TRY(ncclAllReduce(c->zred, c->zred, wp.zsize + kMetricSlots, ncclFloat, ncclSum, c->comm, c->stream2));
-      if (sflags) { ++c->split_zseq; if (!launch_big_signal(c->splitflags, c->split_zseq, c->stream2)) return fail(TNML_ERR_HIP, "%s", big_launch_error()); c->split_zsig_valid = true; }
-      c->split_bat ^= 1;
-      HIP_TRY(hipEventRecord(c->ev_bat[c->split_bat], c->stream2));
-      c->split_pending = true;
-      c->sweep_launches += 2; c->step_launches++;
-      c->Zbig_valid = false;
-      c->Z_valid = wp.do_z != 0; c->Z_k = k + 1; c->Z_left = left_dir; c->Z_act = act_fn; c->Z_loss = loss_fn; c->Z_T = T;
-    } else if (pipe) {
       if (need_prologue) {
         NarrowParams none{};
         wpro.wg0 = 0;
+        if (split) { int rc = split_wait_update(c); if (rc) return rc; }
         prof_begin(c);
-        launch_step_pipe(none, wpro, wide_pipe_lds_bytes(wpro), c->stream);
+        launch_step_pipe(none, wpro, wide_pipe_lds_bytes(wpro), split ? c->stream2 : c->stream);
         prof_end(c, 1);
         c->sweep_launches++; c->step_launches++;
-        if (c->comm) NCCL_TRY(ncclAllReduce(c->zred, c->zred, wpro.zsize + kMetricSlots, ncclFloat, ncclSum, c->comm, c->stream));
+        if (split) { int rc = split_exchange(c, wpro.zsize); if (rc) return rc; }
+        else if (c->comm) NCCL_TRY(ncclAllReduce(c->zred, c->zred, wpro.zsize + kMetricSlots, ncclFloat, ncclSum, c->comm, c->stream));
         if (wpro.do_f) c->f_current = true;
       }
       // merged tensor / L2 term of this step: from the slice workgroups this launch carries (a slice of more than 8 rows is
@@ -1736,13 +1814,42 @@ static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep
       n.flag = c->pipe_cnt + 17; n.token = ++c->token;
       wp.token = n.token;
       wp.wg0 = 1 + n.wait_count;
-      const size_t lds = std::max(std::max(narrow_lds_bytes(h, g, s, L, m), wide_pipe_lds_bytes(wp)), prep_slice_lds_bytes(h, g, s, L));
-      if (lds > 160 * 1024) return fail(TNML_ERR_ARG, "internal: pipelined step needs %zu bytes of LDS", lds);
-      prof_begin(c);
-      launch_step_pipe(n, wp, lds, c->stream);
-      prof_end(c, 3);
-      c->sweep_launches++; c->step_launches++;
-      if (c->comm && wp.do_z) NCCL_TRY(ncclAllReduce(c->zred, c->zred, wp.zsize + kMetricSlots, ncclFloat, ncclSum, c->comm, c->stream));
+      const size_t lds_u = std::max(narrow_lds_bytes(h, g, s, L, m), prep_slice_lds_bytes(h, g, s, L));
+      const size_t lds_b = wide_pipe_lds_bytes(wp);
+      if (split) {
+        if (lds_u > 160 * 1024 || lds_b > 160 * 1024) return fail(TNML_ERR_ARG, "internal: pipelined step needs %zu / %zu bytes of LDS", lds_u, lds_b);
+        const bool sflags = c->split_flags_enabled;
+        // batch side of step k: needs the behind core the update launch of step k-1 left, then B_new(k) (flag in memory)
+        { int rc = split_wait_update(c); if (rc) return rc; }
+        {
+          NarrowParams none{};
+          WidePipeParams wb = wp;
+          wb.wg0 = 0;
+          launch_step_pipe(none, wb, lds_b, c->stream2);
+        }
+        // update side of step k: needs Z_k summed over the ranks (the exchange enqueued behind the previous batch-side launch)
+        if (c->split_pending) {
+          if (sflags && c->split_zsig_valid) { n.zpoll_flag = c->splitflags; n.zpoll_want = c->split_zseq; }
+          else HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_bat[c->split_bat], 0));
+        }
+        if (sflags) { n.done_flag = c->splitflags + 1; n.done_val = ++c->split_dseq; }
+        launch_step_pipe_update(n, wp, lds_u, c->stream);
+        if (sflags) c->split_done_valid = true;
+        else {
+          c->split_upd ^= 1;
+          HIP_TRY(hipEventRecord(c->ev_upd[c->split_upd], c->stream));
+        }
+        { int rc = split_exchange(c, wp.do_z ? wp.zsize : -1); if (rc) return rc; }
+        c->sweep_launches += 2; c->step_launches++;
+      } else {
+        const size_t lds = std::max(lds_u, lds_b);
+        if (lds > 160 * 1024) return fail(TNML_ERR_ARG, "internal: pipelined step needs %zu bytes of LDS", lds);
+        prof_begin(c);
+        launch_step_pipe(n, wp, lds, c->stream);
+        prof_end(c, 3);
+        c->sweep_launches++; c->step_launches++;
+        if (c->comm && wp.do_z) NCCL_TRY(ncclAllReduce(c->zred, c->zred, wp.zsize + kMetricSlots, ncclFloat, ncclSum, c->comm, c->stream));
+      }
       c->Zbig_valid = false;
       c->Z_valid = wp.do_z != 0; c->Z_k = k + 1; c->Z_left = left_dir; c->Z_act = act_fn; c->Z_loss = loss_fn; c->Z_T = T;
     } else {
@@ -1751,7 +1858,7 @@ static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep
       bool zbig = false;
       if (c->Zbig_valid && k >= 3 && c->Zbig_k == k && c->Zbig_left == left_dir && c->Zbig_act == act_fn && c->Zbig_loss == loss_fn && c->Zbig_T == T &&
           npath == 1 && mode == 0 && !Bdirect_dev)
-        zbig = c->Zbig_cols == D * D * g * L && c->Zbig_rows == D * (left_dir ? c->mr(p + 2) : c->ml(p - 1));
+        zbig = c->Zbig_cols == D * D * g * L && c->Zbig_rows == D * rel_bond(c, left_dir, -2);
       // (a step fed by Z does not wait for the side stream with an event: the workgroups of its first launch that need Z poll the
       //  sequence number the side stream leaves behind its chain -- see big_signal_kernel; everything else of that launch starts at once)
       const bool zpoll = zbig && c->bigflags_enabled && c->zbig_pending;
@@ -1759,41 +1866,7 @@ static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep
       c->Z_valid = false; c->Zbig_valid = false;
       // ---- wide kernel -----------------------------------------------------------------------
       WideParams w{};
-      w.b = c->b; w.b_pad = c->b_pad; w.L = L;
-      w.h = h; w.g = g;
-      w.act_fn = act_fn; w.loss_fn = loss_fn; w.T = T;
-      w.y = c->y; w.f = c->f;
-      w.slabs = c->slabs; w.slab_stride = c->slab_stride; w.bsize = (int)bsize;
-      w.x_k = c->X + (size_t)sb * c->b_pad * D;
-      w.x_kp1 = c->X + (size_t)sa * c->b_pad * D;
-      w.hp = 1; w.gp = 1;
-      w.do_ext = (k >= 1);
-      w.first_ext = (k == 1);
-      if (k >= 1) {
-        const int e_site = left_dir ? p + 2 : p - 1;          // site t = k-1, plain since the previous step
-        const int hp = left_dir ? c->mr(e_site) : c->ml(e_site);
-        w.hp = hp;
-        w.x_km1 = c->X + (size_t)e_site * c->b_pad * D;
-        w.ext_core.base = c->core_slot(e_site);
-        w.ext_core.n_in = hp; w.ext_core.n_out = h;
-        if (!left_dir) { w.ext_core.s_in = D * h; w.ext_core.s_d = h; w.ext_core.s_out = 1; }
-        else { w.ext_core.s_in = 1; w.ext_core.s_d = hp; w.ext_core.s_out = D * hp; }
-        w.Hprev = (k >= 2) ? c->env_slot(beh, left_dir ? p + 3 : p - 2) : nullptr;
-        w.Hcur = c->env_slot(beh, left_dir ? p + 2 : p - 1);
-      }
-      if (c->Bnew_valid && !c->f_current) {
-        // f of the previous step from its updated B: that step acted on sites t = k-1, k
-        if (k < 1 || c->prev_h != w.hp || c->prev_g != s)
-          return fail(TNML_ERR_STATE, "internal: previous-step dims (%d,%d) do not match (%d,%d)", c->prev_h, c->prev_g, w.hp, s);
-        w.do_f = 1;
-        w.gp = s;
-        w.Gprev = c->env_slot(ahe, left_dir ? p : p + 1);     // sites t > k
-        w.Bprev = c->Bnew;
-      }
-      {
-        const int gs = left_dir ? p - 1 : p + 2;
-        w.Gcur = (gs >= 0 && gs <= N - 1) ? c->env_slot(ahe, gs) : nullptr;
-      }
+      { int rc = fill_wide(c, w, q, act_fn, loss_fn, T); if (rc) return rc; }
       w.stamps = c->stamps ? c->dbg + 4 * c->bmax + kDbgSigma + 5 + 17 : nullptr;
       PrepParams prep{};
       prep.lab = n.lab; prep.pl = n.pl; prep.Nh = n.Nh; prep.Ng = n.Ng; prep.h = h; prep.g = g; prep.s = s; prep.L = L;
@@ -1847,13 +1920,12 @@ static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep
       size_t lds_z = 0;
       if (c->bigpipe_enabled && c->pipe_enabled && npath == 1 && mode == 0 && !Bdirect_dev && !c->debug && !c->profile && trunc_policy != TNML_TRUNC_ADAPTIVE &&
           k >= 2 && k + 1 <= N - 2 && nblk <= c->pipe_nwide) {
-        const int pn = left_dir ? p - 1 : p + 1;                   // sites (pn, pn + 1) of step k+1
-        gnext = left_dir ? c->ml(pn) : c->mr(pn + 1);
-        const int snext = left_dir ? c->ml(p) : c->mr(p + 1);      // == g: the bond the two steps share
-        const int mnext = tnml_trunc_rank(trunc_policy, left_dir, pn, N, left_dir ? c->ml(pn) : m, D, left_dir ? m : c->mr(pn + 1), L, c->Mpol);
+        const int pn = std::min(q.sa, rel_site(c, left_dir, 2));   // sites (pn, pn + 1) of step k+1; g is the bond the two steps share
+        gnext = rel_bond(c, left_dir, 2);
+        const int mnext = tnml_trunc_rank(trunc_policy, left_dir, pn, N, left_dir ? gnext : m, D, left_dir ? m : gnext, L, c->Mpol);
         const size_t zs = (size_t)D * h * D * D * gnext * L;
         lds_z = wide_tiled_lds_bytes(L, D * h, h, g, gnext, false);      // (its launch extends no environment and hands Hcur in)
-        next_z = mnext > 0 && narrow_path(c, m, gnext, snext, L, mnext) == 1 && zs + kMetricSlots <= (size_t)c->zstride &&
+        next_z = mnext > 0 && narrow_path(c, m, gnext, g, L, mnext) == 1 && zs + kMetricSlots <= (size_t)c->zstride &&
                  lds_z > 0 && lds_z <= 160 * 1024 && D * h <= 2 * c->Mmax && (size_t)D * h * c->b_pad <= (size_t)2 * c->Mmax * c->b_pad;
       }
       if (next_z) { int rc = ensure_big(c); if (rc) return rc; }          // (the flag words of the hand-offs live with its scratch)
@@ -1890,10 +1962,10 @@ static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep
         z.do_f = 1; z.do_ext = 0; z.first_ext = 0;
         z.act_fn = act_fn; z.loss_fn = loss_fn; z.T = T;
         z.x_km1 = w.x_k; z.x_k = w.x_kp1;
-        z.x_kp1 = c->X + (size_t)(left_dir ? p - 1 : p + 2) * c->b_pad * D;
+        z.x_kp1 = x_rel(c, left_dir, 2);
         z.Hprev = w.Hcur; z.Hcur = c->bigPk;
         z.Gprev = w.Gcur;
-        { const int gs2 = left_dir ? p - 2 : p + 3; z.Gcur = (gs2 >= 0 && gs2 <= N - 1) ? c->env_slot(ahe, gs2) : nullptr; }
+        z.Gcur = env_rel(c, left_dir, 3);
         z.Bprev = c->Bnew;
         z.y = c->y; z.f = c->f;
         z.slabs = c->zslabs; z.slab_stride = c->zstride; z.bsize = (int)((size_t)D * h * D * D * gnext * L);
@@ -1914,72 +1986,14 @@ static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep
       c->sweep_launches += (zbig ? 0 : ((fused_now && npath == 0) ? 1 : 2)) + (npath == 1 ? ((Bdirect_dev || prep_ahead) ? 8 : 7) : 1);
       if (zbig) c->step_launches++;           // (counted with the single-launch steps: a step that took its gradient from Z)
       c->last_bsize = (int)bsize; c->last_n = nn; c->last_h = h; c->last_g = g; c->last_left_dir = left_dir;
-      if (mode == 1) {
-        // the behind environment list grew (as update_B does, Network_class.py:637-652); nothing else changes
-        HIP_TRY(hipGetLastError());
-        if (metrics_out) {
-          HIP_TRY(hipMemcpyAsync(metrics_out, c->metrics, 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-          HIP_TRY(hipStreamSynchronize(c->stream));
-        }
-        return TNML_OK;
-      }
+      if (mode == 1) return finish_update_only(c, metrics_out);
     }
-    // ---- bookkeeping ---------------------------------------------------------------------------
-    int m_kept = m;
-    if (trunc_policy == TNML_TRUNC_ADAPTIVE) {       // the kept rank is decided on the device: one sync per step
-      HIP_TRY(hipMemcpyAsync(&m_kept, c->status + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      if (m_kept < 1 || m_kept > m) return fail(TNML_ERR_NONFINITE, "adaptive truncation returned rank %d (cap %d)", m_kept, m);
-    }
-    c->bond[p] = m_kept;
-    c->l_pos = sa;
-    c->lab_cur ^= 1;
-    c->prev_h = h; c->prev_g = g; c->prev_p = p; c->prev_left_dir = left_dir;
-    {   // algorithmic work of this step (SURVEY.md 8.4 with the step's own bond dimensions): environments read / written,
-      // features of three sites, f in and out, labels; gradient + f products and the environment extension
-      const double bb = (double)c->b;
-      c->cnt_steps += 1;
-      c->cnt_bytes += 4.0 * bb * (2.0 * h + g + 3.0 * D + 2.0 * L + 1.0);
-      c->cnt_flops += 4.0 * bb * D * D * h * g * L + 2.0 * bb * D * h * h;
-    }
-    c->Bnew_valid = true;
-    c->f_current = pipe || f_by_z;          // the batch-side work of a pipelined step stored f of this step already
-    c->last_bsize = (int)bsize; c->last_n = nn; c->last_h = h; c->last_g = g; c->last_left_dir = left_dir;
-    if (c->check_launches) HIP_TRY(hipGetLastError());
-    if (c->sync_interval > 0 && (step + 1) % c->sync_interval == 0) HIP_TRY(hipStreamSynchronize(c->stream));
+    // (the batch-side work of a pipelined step stored f of this step already)
+    { int rc = finish_step(c, q, trunc_policy, step, pipe || f_by_z); if (rc) return rc; }
   }
   HIP_TRY(hipGetLastError());
   { int rc = split_join(c); if (rc) return rc; }
-  // the sweep grew the behind stacks: they are the ones valid for the opposite direction now
-  if (!l2_flag) {
-    c->Ln_valid = c->Rn_valid = false;
-  } else if (c->l_pos == (left_dir ? 0 : N - 1)) {          // sweep complete
-    if (left_dir) { c->Rn_valid = true; c->Ln_valid = false; } else { c->Ln_valid = true; c->Rn_valid = false; }
-  } else {                                                   // mid-sweep: the ahead stack stays usable
-    if (left_dir) c->Rn_valid = false; else c->Ln_valid = false;
-  }
-  // f from the last updated B (the value sweep_step returns, Network_class.py:573)
-  if (!c->f_current) {
-    WideParams w{};
-    w.b = c->b; w.b_pad = c->b_pad; w.L = L;
-    fill_prev_operands(c, w, left_dir, c->prev_p);
-    w.f = c->f;
-    prof_begin(c);
-    launch_f_only(w, nblk, c->stream);
-    prof_end(c, 1);
-    HIP_TRY(hipGetLastError());
-    c->f_current = true;
-  }
-  if (sw_ev1) HIP_TRY(hipEventRecord(sw_ev1, c->stream));
-  if (metrics_out) {
-    HIP_TRY(hipMemcpyAsync(metrics_out, c->metrics, (size_t)n_steps * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  }
-  if (f_out) { int rc = copy_f_out(c, c->f, f_out); if (rc) return rc; }
-  if (metrics_out || f_out) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return check_status(c);
-  }
-  return TNML_OK;
+  return finish_sweep(c, left_dir, n_steps, l2_flag, nblk, sw_ev1, metrics_out, f_out);
 }
 
 extern "C" int tnml_sweep(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep, float lr, float weight_dec,
@@ -2034,7 +2048,7 @@ extern "C" int tnml_l2_term(tnml_ctx *c, const float *B_canon, int left_dir, flo
   if (p < 0 || p > c->N - 2) return fail(TNML_ERR_STATE, "no merged tensor at l_pos = %d for a %s step", l, left_dir ? "left" : "right");
   if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
   HIP_TRY(hipSetDevice(c->device));
-  const int N = c->N, D = c->D, L = c->L;
+  const int D = c->D, L = c->L;
   const int ml = c->ml(p), mr = c->mr(p + 1);
   const int h = left_dir ? mr : ml, g = left_dir ? ml : mr;
   const size_t bsize = (size_t)ml * D * D * mr * L;
@@ -2052,10 +2066,8 @@ extern "C" int tnml_l2_term(tnml_ctx *c, const float *B_canon, int left_dir, flo
   n.L = L; n.D = D; n.h = h; n.g = g; n.s = 1; n.m = 1; n.bsize = (int)bsize;
   n.l2_flag = 1; n.lr = 0.f; n.wd = weight_dec;
   n.red = c->red;
-  double *nbeh = left_dir ? c->Rn : c->Ln, *nahe = left_dir ? c->Ln : c->Rn;
-  const int bs_ = left_dir ? p + 2 : p - 1, as_ = left_dir ? p - 1 : p + 2;
-  n.Nh = (bs_ >= 0 && bs_ <= N - 1) ? c->norm_slot(nbeh, bs_) : nullptr;
-  n.Ng = (as_ >= 0 && as_ <= N - 1) ? c->norm_slot(nahe, as_) : nullptr;
+  n.Nh = norm_rel(c, left_dir, -1);
+  n.Ng = norm_rel(c, left_dir, 2);
   n.Bnew = c->Bscr2;
   n.dbg = c->dbg; n.status = c->status; n.counters = nullptr;
   n.Bdirect = c->Bscr; n.stop_after_update = 1;
@@ -2121,9 +2133,9 @@ extern "C" int tnml_svd_split(tnml_ctx *c, const float *mat, int rows, int cols,
 
 // ---------------------------------------------------------------------------------------------
 // Generic feature dimension (3 <= D <= 8, kernels_anyd.hip): the classic per-step sequence only -- batch kernel -> slab reduction
-// -> update kernel -- with no persistent sweep, pipelined step, large-tensor pipeline or communicator.  Planning, bookkeeping and
-// the capture block follow the D == 2 path statement for statement; the update kernel takes any short side up to kBigMaxN
-// (odd sides padded to even inside it).
+// -> update kernel -- with no persistent sweep, pipelined step, large-tensor pipeline or communicator.  Planning and bookkeeping
+// go through the shared frame functions (step_geom, fill_wide, fill_update, finish_step, finish_sweep), the capture block is laid
+// out as on the D == 2 path; the update kernel takes any short side up to kBigMaxN (odd sides padded to even inside it).
 // ---------------------------------------------------------------------------------------------
 static int anyd_scratch(tnml_ctx *c) {
   if (c->anyd_W) return TNML_OK;
@@ -2146,183 +2158,51 @@ static int standalone_anyd(tnml_ctx *c, NarrowParams &n) {
 
 static int sweep_anyd(tnml_ctx *c, int left_dir, int n_steps, float lr, float weight_dec, int l2_flag, int act_fn, int loss_fn, float T,
                       int trunc_policy, float *metrics_out, float *f_out, int mode, const float *Bdirect_dev, hipEvent_t sw_ev1) {
-  const int N = c->N, D = c->D, L = c->L;
+  const int D = c->D, L = c->L;
   const int nblk = c->b_pad / kTS / 2;                       // 64 samples per batch-side workgroup
-  float *beh = left_dir ? c->Renv : c->Lenv;
-  float *ahe = left_dir ? c->Lenv : c->Renv;
-  double *nbeh = left_dir ? c->Rn : c->Ln;
-  double *nahe = left_dir ? c->Ln : c->Rn;
   { int rc = anyd_scratch(c); if (rc) return rc; }
   for (int step = 0; step < n_steps; ++step) {
-    const int l = c->l_pos;
-    const int p = left_dir ? l - 1 : l;
-    const int k = left_dir ? (N - 2 - p) : p;
-    const int sb = left_dir ? p + 1 : p, sa = left_dir ? p : p + 1;
-    const int h = left_dir ? c->mr(p + 1) : c->ml(p);
-    const int g = left_dir ? c->ml(p) : c->mr(p + 1);
-    const int s = c->bond[p];
-    const int m = tnml_trunc_rank(trunc_policy, left_dir, p, N, c->ml(p), D, c->mr(p + 1), L, c->Mpol);
-    if (m < 0) return fail(TNML_ERR_SHAPE, "shapes not aligned: the reference's un-truncated SVD factor does not fit "
-                                           "at sites (%d, %d) (Network_class.py:914 / :949)", p, p + 1);
-    const int r = D * h, cc = D * g * L, nn = std::min(r, cc);
-    const size_t bsize = (size_t)h * D * D * g * L;
-    if (bsize > c->bmax || m > c->Mmax)
-      return fail(TNML_ERR_ARG, "step at sites (%d,%d) exceeds the buffers sized for M = %d", p, p + 1, c->Mmax);
-    if ((size_t)h * D * m > c->core_stride || (size_t)m * D * g * L > c->lab_elems)
-      return fail(TNML_ERR_ARG, "new cores at sites (%d,%d) exceed the buffers sized for M = %d", p, p + 1, c->Mmax);
-    if (nn > kBigMaxN)
-      return fail(TNML_ERR_ARG, "step at sites (%d,%d): min(rows, cols) = %d > %d: the Jacobi kernels handle n <= %d", p, p + 1, nn,
+    const StepGeom q = step_geom(c, left_dir, trunc_policy);
+    if (q.fail) return step_geom_error(c, q);
+    const int p = q.p, h = q.h, g = q.g;
+    if (q.nn > kBigMaxN)
+      return fail(TNML_ERR_ARG, "step at sites (%d,%d): min(rows, cols) = %d > %d: the Jacobi kernels handle n <= %d", p, p + 1, q.nn,
                   kBigMaxN, kBigMaxN);
     // ---- batch side: f of the previous step, activation / metrics, behind environment, gradient slabs ----
     WideParams w{};
-    w.b = c->b; w.b_pad = c->b_pad; w.L = L;
-    w.h = h; w.g = g;
-    w.act_fn = act_fn; w.loss_fn = loss_fn; w.T = T;
-    w.y = c->y; w.f = c->f;
-    w.slabs = c->slabs; w.slab_stride = c->slab_stride; w.bsize = (int)bsize;
-    w.x_k = c->X + (size_t)sb * c->b_pad * D;
-    w.x_kp1 = c->X + (size_t)sa * c->b_pad * D;
-    w.hp = 1; w.gp = 1;
-    w.do_ext = (k >= 1);
-    w.first_ext = (k == 1);
-    if (k >= 1) {
-      const int e_site = left_dir ? p + 2 : p - 1;
-      const int hp = left_dir ? c->mr(e_site) : c->ml(e_site);
-      w.hp = hp;
-      w.x_km1 = c->X + (size_t)e_site * c->b_pad * D;
-      w.ext_core.base = c->core_slot(e_site);
-      w.ext_core.n_in = hp; w.ext_core.n_out = h;
-      if (!left_dir) { w.ext_core.s_in = D * h; w.ext_core.s_d = h; w.ext_core.s_out = 1; }
-      else { w.ext_core.s_in = 1; w.ext_core.s_d = hp; w.ext_core.s_out = D * hp; }
-      w.Hprev = (k >= 2) ? c->env_slot(beh, left_dir ? p + 3 : p - 2) : nullptr;
-      w.Hcur = c->env_slot(beh, left_dir ? p + 2 : p - 1);
-    }
-    if (c->Bnew_valid && !c->f_current) {
-      if (k < 1 || c->prev_h != w.hp || c->prev_g != s)
-        return fail(TNML_ERR_STATE, "internal: previous-step dims (%d,%d) do not match (%d,%d)", c->prev_h, c->prev_g, w.hp, s);
-      w.do_f = 1;
-      w.gp = s;
-      w.Gprev = c->env_slot(ahe, left_dir ? p : p + 1);
-      w.Bprev = c->Bnew;
-    }
-    {
-      const int gs = left_dir ? p - 1 : p + 2;
-      w.Gcur = (gs >= 0 && gs <= N - 1) ? c->env_slot(ahe, gs) : nullptr;
-    }
+    { int rc = fill_wide(c, w, q, act_fn, loss_fn, T); if (rc) return rc; }
     prof_begin(c);
     if (!launch_batch_anyd(w, D, nblk, true, c->stream))
       return fail(TNML_ERR_ARG, "step at sites (%d,%d): the batch kernel at D = %d needs %zu bytes of LDS", p, p + 1, D,
                   anyd_batch_lds_bytes(D, w.hp, w.gp, h, g, L));
     prof_end(c, 1);
     prof_begin(c);
-    launch_reduce(c->slabs, nblk, c->slab_stride, (int)bsize + kMetricSlots, c->red, c->stream);
+    launch_reduce(c->slabs, nblk, c->slab_stride, (int)q.bsize + kMetricSlots, c->red, c->stream);
     prof_end(c, 2);
-    // ---- update side ----
+    // ---- update side (chol_thr stays 0: the generic-D update kernel has no Cholesky step) ----
     NarrowParams n{};
-    n.L = L; n.D = D; n.h = h; n.g = g; n.s = s; n.m = m; n.bsize = (int)bsize;
-    n.l2_flag = l2_flag ? 1 : 0; n.lr = lr; n.wd = weight_dec;
+    fill_update(c, n, q, l2_flag, lr, weight_dec);
     n.red = c->red;
-    n.lab.base = c->lab[c->lab_cur]; n.lab.n_in = h; n.lab.n_out = s;
-    n.pl.base = c->core_slot(sa); n.pl.n_in = s; n.pl.n_out = g;
-    if (!left_dir) {
-      n.lab.s_in = D * s * L; n.lab.s_d = s * L; n.lab.s_out = L;
-      n.pl.s_in = D * g; n.pl.s_d = g; n.pl.s_out = 1;
-      n.ob_s_h = D * m; n.ob_s_d = m; n.ob_s_m = 1;
-      n.oa_s_m = D * g * L; n.oa_s_d = g * L; n.oa_s_g = L;
-    } else {
-      n.lab.s_in = L; n.lab.s_d = h * L; n.lab.s_out = D * h * L;
-      n.pl.s_in = 1; n.pl.s_d = s; n.pl.s_out = D * s;
-      n.ob_s_h = 1; n.ob_s_d = h; n.ob_s_m = D * h;
-      n.oa_s_m = L; n.oa_s_d = m * L; n.oa_s_g = D * m * L;
-    }
-    {
-      const int bs_ = left_dir ? p + 2 : p - 1, as_ = left_dir ? p - 1 : p + 2;
-      n.Nh = (l2_flag && bs_ >= 0 && bs_ <= N - 1) ? c->norm_slot(nbeh, bs_) : nullptr;
-      n.Ng = (l2_flag && as_ >= 0 && as_ <= N - 1) ? c->norm_slot(nahe, as_) : nullptr;
-      n.Nh_new = l2_flag ? c->norm_slot(nbeh, sb) : nullptr;
-    }
-    n.Bnew = c->Bnew;
-    n.out_behind = c->core_slot(sb);
     n.out_ahead = c->lab[c->lab_cur ^ 1];
     n.metrics = c->metrics + 2 * (size_t)step;
     n.dbg = c->dbg;                              // the capture block is the update kernel's workspace
     n.stamps = (c->debug || c->stamps) ? c->dbg + 4 * c->bmax + kDbgSigma + 5 : nullptr;
     n.Bdirect = Bdirect_dev;
-    n.svd_stop2 = c->svd_stop2;
     n.stop_after_update = mode == 1;
     if (trunc_policy == TNML_TRUNC_ADAPTIVE && mode == 0) { n.trunc_thr = c->trunc_thr; n.left_dir = left_dir; n.m_out = c->status + 1; }
     if (mode == 1) { n.Bnew = c->Bscr2; n.Nh_new = nullptr; }
-    n.status = c->status;
-    n.counters = c->counters;
     prof_begin(c);
     if (!launch_update_anyd(n, c->anyd_W, c->anyd_T2, c->stream))
-      return fail(TNML_ERR_ARG, "step at sites (%d,%d): update kernel at D = %d refused a %d x %d matrix", p, p + 1, D, r, cc);
+      return fail(TNML_ERR_ARG, "step at sites (%d,%d): update kernel at D = %d refused a %d x %d matrix", p, p + 1, D, D * h, D * g * L);
     prof_end(c, 3);
     c->sweep_launches += 3;
-    c->last_bsize = (int)bsize; c->last_n = nn; c->last_h = h; c->last_g = g; c->last_left_dir = left_dir;
-    if (mode == 1) {
-      HIP_TRY(hipGetLastError());
-      if (metrics_out) {
-        HIP_TRY(hipMemcpyAsync(metrics_out, c->metrics, 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-      }
-      return TNML_OK;
-    }
-    // ---- bookkeeping (as the D == 2 path) ----
-    int m_kept = m;
-    if (trunc_policy == TNML_TRUNC_ADAPTIVE) {
-      HIP_TRY(hipMemcpyAsync(&m_kept, c->status + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-      if (m_kept < 1 || m_kept > m) return fail(TNML_ERR_NONFINITE, "adaptive truncation returned rank %d (cap %d)", m_kept, m);
-    }
-    c->bond[p] = m_kept;
-    c->l_pos = sa;
-    c->lab_cur ^= 1;
-    c->prev_h = h; c->prev_g = g; c->prev_p = p; c->prev_left_dir = left_dir;
-    {
-      const double bb = (double)c->b;
-      c->cnt_steps += 1;
-      c->cnt_bytes += 4.0 * bb * (2.0 * h + g + 3.0 * D + 2.0 * L + 1.0);
-      c->cnt_flops += 4.0 * bb * D * D * h * g * L + 2.0 * bb * D * h * h;
-    }
-    c->Bnew_valid = true;
-    c->f_current = false;
+    c->last_bsize = (int)q.bsize; c->last_n = q.nn; c->last_h = h; c->last_g = g; c->last_left_dir = left_dir;
+    if (mode == 1) return finish_update_only(c, metrics_out);
+    { int rc = finish_step(c, q, trunc_policy, step, false); if (rc) return rc; }
     c->Z_valid = false; c->Zbig_valid = false;
-    if (c->check_launches) HIP_TRY(hipGetLastError());
-    if (c->sync_interval > 0 && (step + 1) % c->sync_interval == 0) HIP_TRY(hipStreamSynchronize(c->stream));
   }
   HIP_TRY(hipGetLastError());
-  if (!l2_flag) {
-    c->Ln_valid = c->Rn_valid = false;
-  } else if (c->l_pos == (left_dir ? 0 : N - 1)) {
-    if (left_dir) { c->Rn_valid = true; c->Ln_valid = false; } else { c->Ln_valid = true; c->Rn_valid = false; }
-  } else {
-    if (left_dir) c->Rn_valid = false; else c->Ln_valid = false;
-  }
-  // f from the last updated B (the value sweep_step returns, Network_class.py:573)
-  if (!c->f_current) {
-    WideParams w{};
-    w.b = c->b; w.b_pad = c->b_pad; w.L = L;
-    fill_prev_operands(c, w, left_dir, c->prev_p);
-    w.f = c->f;
-    w.do_f = 1;
-    prof_begin(c);
-    if (!launch_batch_anyd(w, D, nblk, false, c->stream))
-      return fail(TNML_ERR_ARG, "f of the last step at D = %d needs %zu bytes of LDS", D, anyd_batch_lds_bytes(D, w.hp, w.gp, 1, 1, L));
-    prof_end(c, 1);
-    HIP_TRY(hipGetLastError());
-    c->sweep_launches += 1;
-    c->f_current = true;
-  }
-  if (sw_ev1) HIP_TRY(hipEventRecord(sw_ev1, c->stream));
-  if (metrics_out)
-    HIP_TRY(hipMemcpyAsync(metrics_out, c->metrics, (size_t)n_steps * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  if (f_out) { int rc = copy_f_out(c, c->f, f_out); if (rc) return rc; }
-  if (metrics_out || f_out) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return check_status(c);
-  }
-  return TNML_OK;
+  return finish_sweep(c, left_dir, n_steps, l2_flag, nblk, sw_ev1, metrics_out, f_out);
 }
 
 // ---------------------------------------------------------------------------------------------
