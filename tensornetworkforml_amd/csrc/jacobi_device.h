@@ -24,6 +24,8 @@ __device__ inline __amdgpu_buffer_rsrc_t sc1_rsrc(const void *base) {
 __device__ inline void st_sc1_b128(__amdgpu_buffer_rsrc_t r, unsigned byte_off, tn_uvec4 v) {
   __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)byte_off, 0, 16);
 }
+typedef double dvec2_t __attribute__((ext_vector_type(2)));
+__device__ inline tn_uvec4 pack_d2(double a, double b) { return __builtin_bit_cast(tn_uvec4, dvec2_t{a, b}); }
 __device__ inline tn_uvec4 ld_sc1_b128(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
   return __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 16);
 }

@@ -1066,11 +1066,22 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
     // The next step's projections are formed by the helper workgroups: they get the behind core before its rounding to float32
     // (the projection divides by sigma: rounding errors of A' would come back multiplied by sigma_max / sigma_j) and 1 / sigma, now,
     // so that the stores travel while the norm environment is formed; the batch-side workgroups extend their environments with
-    // the float32 core in its slot.  Agent-scope stores; the flag follows at the end of the step.
-    for (int e = tid; e < r * mk; e += NT) __hip_atomic_store(p.Apub + e, PL.Ad[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (int sp = tid; sp < mk; sp += NT) {
-      const double iq = k.dSq[ne + sp];
-      __hip_atomic_store(p.Apub + r * mk + sp, iq * iq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // the float32 core in its slot.  The two are all that the helpers' first product level needs, so they get a token of their own
+    // here and the projections start beside the norm environment below.  ONE wave stores them (agent scope), drains its own counter
+    // and raises the token: no meeting of the workgroup, the other waves are in phase 10 meanwhile (the last wave: the norm
+    // environment's few tiles are dealt from wave 0).
+    if (wave_u == (NT >> 6) - 1) {
+      // (layout of the block: persist_pub_off; r * mk is even, 1 / sigma ends in a padded double where mk is odd; two doubles per
+      // lane and store, from the LDS copies)
+      const int ln = tid & 63;
+      const __amdgpu_buffer_rsrc_t rP = sc1_rsrc(p.Apub);
+      for (int e = ln; e < (r * mk) >> 1; e += 64) st_sc1_b128(rP, (unsigned)e * 16u, pack_d2(PL.Ad[2 * e], PL.Ad[2 * e + 1]));
+      for (int e = ln; e < (mk + 1) >> 1; e += 64) {
+        const double i0 = k.dSq[ne + 2 * e], i1 = 2 * e + 1 < mk ? k.dSq[ne + 2 * e + 1] : 0.0;
+        st_sc1_b128(rP, (unsigned)(r * mk + 2 * e) * 8u, pack_d2(i0 * i0, i1 * i1));
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (ln == 0) __hip_atomic_store(p.aflag, p.coretoken, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
 
@@ -1085,8 +1096,15 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
     mm_lds(1, mk, mk, h * D, k.sCb, 0, 1, mk, k.dT2, 0, mk, 1,
            [&](int, int i, int j, double v) {
              p.Nh_new[i * mk + j] = v;
-             if (p.persist) { PL.Nh[i * mk + j] = v; __hip_atomic_store(p.Apub + r * mk + mk + i * mk + j, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+             if (p.persist) PL.Nh[i * mk + j] = v;
            });
+    if (p.persist) {                      // the helpers' copy: 16-byte stores from the LDS copy, the last double padded where mk is odd
+      lds_barrier();
+      const __amdgpu_buffer_rsrc_t rP = sc1_rsrc(p.Apub);
+      const int oN = persist_pub_off(r * mk, mk), nn2 = mk * mk;
+      for (int e = tid; e < (nn2 + 1) >> 1; e += NT)
+        st_sc1_b128(rP, (unsigned)(oN + 2 * e) * 8u, pack_d2(PL.Nh[2 * e], 2 * e + 1 < nn2 ? PL.Nh[2 * e + 1] : 0.0));
+    }
   }
 
   if (p.stamps && tid == 0) {
@@ -1110,8 +1128,8 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
     if (ldtail(2) != 0.f) atomicOr(p.status, 1);
   }
   if (p.persist) {
-    // (the behind core, 1 / sigma and the behind norm environment left for the helper workgroups as their products finished: see
-    // publish_core / the norm-environment product) every storing wave drains, the workgroup meets, one lane raises the flag
+    // (the behind norm environment left for the helper workgroups as its product finished, the float32 behind core for the batch side in
+    // phase 9) every storing wave drains, the workgroup meets, one lane raises the end-of-step token
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     lds_barrier();
     if (tid == 0) __hip_atomic_store(p.coreflag, p.coretoken, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1185,6 +1203,36 @@ void launch_step_pipe_update(const NarrowParams &p, const WidePipeParams &w, siz
 //         dB_raw = A'^T Z_k,   B_k = diag(1 / sigma) A'^T T_k,   (Ln.B.Rn)_k = Nh^T diag(1 / sigma) A'^T TN_k
 //       -> prepRaw / prepB / prepG, then its arrival.
 // (2) of step k is the only part on the critical path of the sweep: three 2 x 2-tile products and one more, on LDS operands.
+// Columns [c0, c0 + nc) of `rows` rows of a row-major [rows][RW] array, from an LDS tile with row stride `srs`, as agent-scope stores:
+// 16 bytes wherever a whole aligned group of the row lies inside the slice, single elements for the head and the tail of each row
+// (at most 16 / sizeof(T) - 1 each: neither the slice width nor a row's start need to sit on the 16-byte grid).
+__device__ inline void st_sc1_elem(float *p, float v) { st_sc1(p, v); }
+__device__ inline void st_sc1_elem(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <class T>
+__device__ inline void st_sc1_rows(T *dst, const T *stage, int rows, int srs, int RW, int c0, int nc) {
+  constexpr int V = 16 / (int)sizeof(T);
+  if (nc <= 0) return;
+  const __amdgpu_buffer_rsrc_t rD = sc1_rsrc(dst);
+  const int ns = (nc + 2 * V - 2) / V;                       // aligned groups a slice of nc elements can touch
+  for (int it = threadIdx.x; it < rows * ns; it += kNarrowThreads) {
+    const int i = it / ns, q = it - i * ns;
+    const int gs = i * RW + c0, ge = gs + nc, lo = (gs & ~(V - 1)) + q * V;
+    if (lo >= ge) continue;
+    const T *src = stage + i * srs + (lo - gs);
+    if (lo >= gs && lo + V <= ge) {
+      T v[V];
+#pragma unroll
+      for (int u = 0; u < V; ++u) v[u] = src[u];
+      tn_uvec4 w;
+      __builtin_memcpy(&w, v, 16);
+      st_sc1_b128(rD, (unsigned)lo * (unsigned)sizeof(T), w);
+    } else {
+#pragma unroll
+      for (int u = 0; u < V; ++u) if (lo + u >= gs && lo + u < ge) st_sc1_elem(dst + lo + u, src[u]);
+    }
+  }
+}
+
 template <class HP>
 __device__ __forceinline__ bool persist_helper_block(const HP &t, int hid, int nH, unsigned char *smem_raw, bool do_part2) {
   const int tid = threadIdx.x, NT = kNarrowThreads;
@@ -1243,18 +1291,23 @@ __device__ __forceinline__ bool persist_helper_block(const HP &t, int hid, int n
   }
   // ---------------- part 2: columns [c0, c0 + nc) of the RW columns ----------------
   // Order of the waits = order in which the operands become final: T_k / TN_k (beside the previous SVD), Z_k (shortly before or
-  // after the previous step ends), A' / 1 / sigma / Nh (the previous step's last act).  Only the last load and the two products
-  // are on the critical path of the sweep.
+  // after the previous step ends), A' / 1 / sigma (after the previous step's cores), Nh (the previous step's last act).  The first
+  // product level needs A' and 1 / sigma only and runs beside the update workgroup's norm environment; Nh is waited for in front of
+  // the third product, and only with the L2 term.
   const int cw = (RW + nH - 1) / nH, c0 = min(RW, hid * cw), nc = min(RW, c0 + cw) - c0;
-  const int cw3 = 3 * cw;
+  const int cw2 = 2 * cw;
+  // (sA | sIv | sNh mirror the published block, persist_pub_off: 16-byte loads land where they are used)
   double *sA = (double *)smem_raw;                           // [zr][h]  A' (float64)
-  double *sIv = sA + (size_t)zr * h;                         // [h]      1 / sigma
+  double *sIv = sA + (((size_t)zr * h + 1) & ~(size_t)1);    // [h]      1 / sigma
   double *sNh = sIv + ((h + 1) & ~1);                        // [h][h]
-  double *sS = sNh + (((size_t)h * h + 1) & ~(size_t)1);     // [zr][3 cw]  (Z | T | TN) columns of this slice
-  double *sP2 = sS + (size_t)zr * cw3;                       // [h][cw]  diag(1 / sigma) A'^T TN
+  double *sS = sNh + (((size_t)h * h + 1) & ~(size_t)1);     // [zr][2 cw]  (T | TN) columns of this slice; dead after the first product
+                                                             // level: then [h][cw] staging tile of prepG
+  float *sOut = (float *)(sS + persist_helper_ss_doubles(zr, h, cw));   // [2][h][cw] staging tiles of prepRaw and prepB
+  double *sP2 = (double *)sOut + (size_t)h * cw;             // [h][cw]  diag(1 / sigma) A'^T TN
   float *sZf = (float *)(sP2 + (size_t)h * cw);              // [zr][cw] Z columns of this slice
   float *sAff = sZf + (size_t)zr * cw;                       // [zr][h]  A' as stored (float32)
   double *hst = (t.stamps && hid == 0 && tid == 0) ? t.stamps : nullptr;
+  double *hst2 = (t.stamps && hid == 0) ? t.stamps : nullptr;   // (the last wave's stamps around the second wait)
   auto rt = []() { return (double)(__builtin_amdgcn_s_memrealtime() & ((1ull << 40) - 1)); };
   if (tid == 0) { if (hst) hst[22] = rt(); give_up(spin_wait_ge(t.tcnt, (unsigned)nH, t.abort_flag)); if (hst) hst[30] = rt(); }
   lds_barrier();
@@ -1262,8 +1315,8 @@ __device__ __forceinline__ bool persist_helper_block(const HP &t, int hid, int n
   for (int e = tid; e < zr * nc; e += NT) {
     const int i = e / nc, cc = e - i * nc;
     const size_t src = (size_t)i * RW + c0 + cc;
-    sS[i * cw3 + cw + cc] = __hip_atomic_load(t.T + src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    sS[i * cw3 + 2 * cw + cc] = t.l2_flag ? __hip_atomic_load(t.TN + src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+    sS[i * cw2 + cc] = __hip_atomic_load(t.T + src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    sS[i * cw2 + cw + cc] = t.l2_flag ? __hip_atomic_load(t.TN + src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
   }
   lds_barrier();                                             // (tid 0 rewrites sBad)
   if (tid == 0) { give_up(spin_wait_ge(t.zready, t.zwant, t.abort_flag)); if (hst) hst[24] = rt(); }
@@ -1278,10 +1331,14 @@ __device__ __forceinline__ bool persist_helper_block(const HP &t, int hid, int n
   lds_barrier();
   if (sBad) return true;
   if (t.awant) {
-    const double *pub = t.Apub;
-    for (int e = tid; e < zr * h; e += NT) { const double a = __hip_atomic_load(pub + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); sA[e] = a; sAff[e] = (float)a; }
-    for (int e = tid; e < h; e += NT) sIv[e] = __hip_atomic_load(pub + zr * h + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (t.l2_flag) for (int e = tid; e < h * h; e += NT) sNh[e] = __hip_atomic_load(pub + zr * h + h + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // A' and 1 / sigma: one run of 16-byte agent-scope loads (zr * h is even past k == 0; the padded double of 1 / sigma comes along)
+    const __amdgpu_buffer_rsrc_t rP = sc1_rsrc(t.Apub);
+    const int n1 = persist_pub_off(zr * h, h) >> 1, nA = (zr * h) >> 1;
+    for (int e = tid; e < n1; e += NT) {
+      const tn_uvec4 q = ld_sc1_b128(rP, (unsigned)e * 16u);
+      *reinterpret_cast<tn_uvec4 *>(sA + 2 * e) = q;
+      if (e < nA) { const dvec2_t a = __builtin_bit_cast(dvec2_t, q); sAff[2 * e] = (float)a[0]; sAff[2 * e + 1] = (float)a[1]; }
+    }
   } else if (tid == 0) {                                     // k == 0: zr == h == 1, the identity
     sA[0] = 1.0; sAff[0] = 1.f; sIv[0] = 1.0; sNh[0] = 1.0;
   }
@@ -1290,19 +1347,47 @@ __device__ __forceinline__ bool persist_helper_block(const HP &t, int hid, int n
   if (nc > 0) {
     // [h][cw] = Af^T Z with the core as stored, on the float32 matrix pipe (the per-step path's contraction, number for number), and
     // [h][2 cw] = A'^T (T | TN) with the unrounded core; independent, their tiles dealt as one list
-    mm_lds_f32(h, nc, zr, sAff, 1, h, sZf, cw, 1, [&](int i, int j, float v) { st_sc1(t.prepRaw + (size_t)i * RW + c0 + j, v); });
+    // (results into LDS staging tiles: they leave as 16-byte stores once the workgroup has met)
+    mm_lds_f32(h, nc, zr, sAff, 1, h, sZf, cw, 1, [&](int i, int j, float v) { sOut[i * cw + j] = v; });
     const int slot = (((h + 15) >> 4) * ((nc + 15) >> 4)) & ((NT >> 6) - 1);
-    mm_lds(1, h, t.l2_flag ? 2 * cw : cw, zr, sA, 0, 1, h, sS + cw, 0, cw3, 1,
+    mm_lds(1, h, t.l2_flag ? 2 * cw : cw, zr, sA, 0, 1, h, sS, 0, cw2, 1,
            [&](int, int i, int j, double v) {
-             if (j < cw) { if (j < nc) st_sc1(t.prepB + (size_t)i * RW + c0 + j, (float)(v * sIv[i])); }
+             if (j < cw) { if (j < nc) sOut[(h + i) * cw + j] = (float)(v * sIv[i]); }
              else sP2[i * cw + (j - cw)] = v * sIv[i];
            }, false, slot);
-    if (t.l2_flag) {
-      lds_barrier();
-      // (Ln.B.Rn)[e_, c] = sum_a Nh[a, e_] P2[a, c]
-      mm_lds(1, h, nc, h, sNh, 0, 1, h, sP2, 0, cw, 1,
-             [&](int, int i, int j, double v) { __hip_atomic_store(t.prepG + (size_t)i * RW + c0 + j, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); });
+  }
+  if (t.l2_flag) {
+    // The last wave, its tiles done, waits for the end of step k-1 and fetches Nh on its own; the others meet it at the barrier the
+    // third product needs anyway (every helper takes this path, also one without columns: the give-up is decided for the workgroup)
+    if (t.awant && (tid >> 6) == (NT >> 6) - 1) {
+      const int ln = tid & 63;
+      int bad = 0;
+      if (ln == 0) { if (hst2) hst2[31] = rt(); bad = spin_wait_ge(t.nflag, t.awant, t.abort_flag); give_up(bad); if (hst2) hst2[21] = rt(); }
+      if (!__builtin_amdgcn_readfirstlane(bad)) {
+        // 16-byte loads, four per lane in flight (h * h odd: the padded double comes along)
+        const __amdgpu_buffer_rsrc_t rP = sc1_rsrc(t.Apub);
+        const int oN = persist_pub_off(zr * h, h), nq = (h * h + 1) >> 1;
+        for (int e0 = ln; e0 < nq; e0 += 4 * 64) {
+          tn_uvec4 q[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) if (e0 + 64 * u < nq) q[u] = ld_sc1_b128(rP, (unsigned)(oN + 2 * (e0 + 64 * u)) * 8u);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) if (e0 + 64 * u < nq) *reinterpret_cast<tn_uvec4 *>(sNh + 2 * (e0 + 64 * u)) = q[u];
+        }
+      }
     }
+  }
+  lds_barrier();
+  if (t.l2_flag && sBad) return true;
+  st_sc1_rows(t.prepRaw, sOut, h, cw, RW, c0, nc);
+  st_sc1_rows(t.prepB, sOut + (size_t)h * cw, h, cw, RW, c0, nc);
+  if (t.l2_flag) {
+    if (nc > 0) {
+      // (Ln.B.Rn)[e_, c] = sum_a Nh[a, e_] P2[a, c]   (staged where T | TN were)
+      mm_lds(1, h, nc, h, sNh, 0, 1, h, sP2, 0, cw, 1, [&](int, int i, int j, double v) { sS[i * cw + j] = v; });
+    }
+    lds_barrier();
+    st_sc1_rows(t.prepG, sS, h, cw, RW, c0, nc);
   }
   if (hst) hst[26] = rt();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

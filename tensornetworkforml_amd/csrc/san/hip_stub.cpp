@@ -141,8 +141,8 @@ static void check_narrow(const NarrowParams &p) {
   }
   if (p.persist) {
     need(p.prepB, (size_t)p.bsize * 4, "NarrowParams.prepB (persistent)"); need(p.prepG, (size_t)p.bsize * 8, "NarrowParams.prepG (persistent)");
-    need(p.pready, 4, "NarrowParams.pready"); need(p.coreflag, 4, "NarrowParams.coreflag"); need(p.abort_flag, 4, "NarrowParams.abort_flag");
-    need(p.Apub, ((size_t)kD * p.h * p.m + p.m + (size_t)p.m * p.m) * 8, "NarrowParams.Apub");
+    need(p.pready, 4, "NarrowParams.pready"); need(p.aflag, 4, "NarrowParams.aflag"); need(p.coreflag, 4, "NarrowParams.coreflag"); need(p.abort_flag, 4, "NarrowParams.abort_flag");
+    need(p.Apub, persist_pub_doubles(kD * p.h * p.m, p.m) * 8, "NarrowParams.Apub");
   }
 }
 static void check_pipe(const WidePipeParams &w) {
@@ -224,7 +224,7 @@ static void tr_struct(const NarrowParams &p) {
   P(counters) P(Bdirect) I(stop_after_update) I(fused) I(prep_ready) P(slabs) I(nslabs) I(slab_stride) I(nred) P(red_out) P(prepB)
   P(prepG) P(sync) R(trunc_thr) I(left_dir) P(m_out) R(chol_thr) R(svd_stop2) P(status) I(wait_count) I(pipe) I(z_first) I(z_rows)
   I(zsize) P(zred) V(zcore) P(flag) I(token) I(persist) I(write_ahead) I(persist_off) I(Mcap) P(prepRaw) P(pready) I(pwant) P(Apub)
-  P(coreflag) I(coretoken) P(zpoll_flag) I(zpoll_want) P(done_flag) I(done_val) P(abort_flag)
+  P(aflag) P(coreflag) I(coretoken) P(zpoll_flag) I(zpoll_want) P(done_flag) I(done_val) P(abort_flag)
 }
 static void tr_struct(const WideParams &p) {
   I(b) I(b_pad) I(L) I(h) I(g) I(hp) I(gp) I(do_f) I(do_ext) I(first_ext) I(act_fn) I(loss_fn) R(T) P(x_km1) P(x_k) P(x_kp1) P(Hprev)
@@ -238,7 +238,7 @@ static void tr_struct(const WidePipeParams &p) {
 }
 static void tr_struct(const PersistHelperParams &p) {
   I(zr) I(s) I(g) I(L) I(h) I(l2_flag) P(W) V(lab) V(pl) P(Ng) P(T) P(TN) P(Z) P(prepRaw) P(prepB) P(prepG) P(Apub) P(flag) I(want)
-  P(aflag) I(awant) P(zready) I(zwant) P(tcnt) P(pcnt) P(abort_flag) P(status) P(stamps)
+  P(aflag) P(nflag) I(awant) P(zready) I(zwant) P(tcnt) P(pcnt) P(abort_flag) P(status) P(stamps)
 }
 static void tr_struct(const PersistStep &p) { tr(" n:"); tr_struct(p.n); tr(" w:"); tr_struct(p.w); tr(" t:"); tr_struct(p.t); }
 static void tr_struct(const PrepParams &p) { V(lab) V(pl) P(Nh) P(Ng) I(h) I(g) I(s) I(L) I(l2_flag) P(prepB) P(prepG) I(nparts) }

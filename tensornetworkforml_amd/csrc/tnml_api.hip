@@ -301,7 +301,7 @@ extern "C" int tnml_create(tnml_ctx **out, int N, int D, int L, int Mmax, int b_
   HIP_TRY(hipMalloc(&c->TNbuf[0], (size_t)c->zstride * sizeof(double)));
   HIP_TRY(hipMalloc(&c->TNbuf[1], (size_t)c->zstride * sizeof(double)));
   HIP_TRY(hipMalloc(&c->prepRaw, c->bmax * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->Apub, ((size_t)D * Mmax * Mmax + Mmax + (size_t)Mmax * Mmax + 8) * sizeof(double)));
+  HIP_TRY(hipMalloc(&c->Apub, persist_pub_doubles(D * Mmax * Mmax, Mmax) * sizeof(double)));
   HIP_TRY(hipMalloc(&c->pst_dev, (size_t)(N + 1) * sizeof(PersistStep)));
   for (int i = 0; i < 2; ++i) {
     HIP_TRY(hipHostMalloc(&c->pst_host[i], (size_t)(N + 1) * sizeof(PersistStep)));
@@ -1541,7 +1541,7 @@ static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float
   if (1 + nH + nwide > c->num_cus) return 0;                 // every workgroup of the launch must be resident
   const int Mcap = c->Mmax;
   const size_t pbytes = persist_lds_bytes(Mcap);
-  unsigned *fl = c->pst_flags;                               // [0] B_new token, [2] Z ready, [3] behind core / Apub stored, [4] abort
+  unsigned *fl = c->pst_flags;                               // [0] B_new token, [2] Z ready, [3] end of step: behind core / Nh stored, [4] abort, [5] A' / 1 / sigma stored
   float *zr2[2] = {c->zred, c->zred2};
   size_t lds_narrow = 0, lds_wide = 0, lds_help = 0;
   // prologue: Z_0 from forward's f
@@ -1582,7 +1582,7 @@ static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float
     n.pready = c->pst_cnt + (size_t)k * 32 + 21; n.pwant = (unsigned)nH;
     n.flag = fl + 0; n.token = (unsigned)k + 1;
     n.Apub = c->Apub;
-    n.coreflag = fl + 3; n.coretoken = (unsigned)k + 1; n.abort_flag = fl + 4;
+    n.aflag = fl + 5; n.coreflag = fl + 3; n.coretoken = (unsigned)k + 1; n.abort_flag = fl + 4;
     n.Mcap = Mcap;
     lds_narrow = std::max(lds_narrow, nlds);
     // ---- batch-side workgroups: f from B_new(k), pre-gradient of step k+1
@@ -1604,7 +1604,7 @@ static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float
     t.lab = n.lab; t.pl = n.pl; t.Ng = n.Ng;
     t.T = c->Tbuf[k & 1]; t.TN = c->TNbuf[k & 1]; t.Z = zr2[k & 1];
     t.prepRaw = c->prepRaw; t.prepB = c->prepB; t.prepG = c->prepG; t.Apub = c->Apub;
-    t.flag = fl + 0; t.want = (unsigned)k; t.aflag = fl + 3; t.awant = (unsigned)k; t.zready = fl + 2; t.zwant = (unsigned)k + 1;
+    t.flag = fl + 0; t.want = (unsigned)k; t.aflag = fl + 5; t.nflag = fl + 3; t.awant = (unsigned)k; t.zready = fl + 2; t.zwant = (unsigned)k + 1;
     t.tcnt = c->pst_cnt + (size_t)k * 32 + 20; t.pcnt = c->pst_cnt + (size_t)k * 32 + 21;
     t.abort_flag = fl + 4; t.status = c->status; t.stamps = n.stamps;
     lds_help = std::max(lds_help, persist_helper_lds_bytes(zr, s, g, L, h, nH));

@@ -127,7 +127,10 @@ struct NarrowParams {
   const unsigned *pready;  // >= pwant: every helper workgroup has stored its slice of the three
   unsigned pwant;
   double *Apub;            // out: behind core before rounding [D h][m], 1 / sigma [m], next behind norm environment [m][m]
-  unsigned *coreflag;      // set to coretoken once Apub and the float32 behind core are stored: helpers project, batch side extends
+  unsigned *aflag;         // set to coretoken once the behind core before rounding and 1 / sigma are stored (right after phase 9): the
+                           // helpers start the projections that do not need the norm environment
+  unsigned *coreflag;      // set to coretoken at the end of the step: the norm environment in Apub and the float32 behind core are stored
+                           // (helpers: the L2 projection; batch side: extends)
   unsigned coretoken;
   // two-stream communicator path without events (tnml_api.hip, split branch): the update workgroup waits for zpoll_flag to reach
   // zpoll_want before it touches zred (the side stream's all-reduce is followed by a one-thread kernel that stores it), and stores
