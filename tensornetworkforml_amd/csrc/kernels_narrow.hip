@@ -169,9 +169,88 @@ __device__ inline void narrow_helper_block(const NarrowParams &p, unsigned char 
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// The step record as narrow_body sees it, one type per launch mode.  A by-value NarrowParams is ~125 dwords that stay live
+// across the whole step against the 102 scalar registers of a wave: the overflow is parked in VGPR lanes and then in scratch,
+// on the dependent chain of the one workgroup the sweep waits for.  A mode type carries the fields of its mode only: what
+// another mode reads is a compile-time constant here (its branches fold away), what the front of the step or an inner loop
+// reads is held by value, and what only the end of the step reads is read from the record where it is used.
+// ------------------------------------------------------------------------------------------
+// per-step launches (kernel argument): the persistent branches fold away
+struct StepArgs : NarrowParams {
+  __device__ __forceinline__ StepArgs(const NarrowParams &q) : NarrowParams(q) {}
+  static constexpr int persist = 0;
+};
+
+// a field of a record the host wrote before the launch and nothing in the kernel writes (constant address space: a scalar load,
+// and the compiler knows that no store in between can change it), read where it is used
+template <class T>
+struct RecField {
+  const __attribute__((address_space(4))) T *a;
+  __device__ __forceinline__ operator T() const { return *a; }
+};
+template <class T>
+__device__ __forceinline__ RecField<T> rec_field(const T *field) { return RecField<T>{(const __attribute__((address_space(4))) T *)field}; }
+
+// persistent sweep (sweep_persist_kernel, persist_update_kernel): sweep_persist (tnml_api.hip) sets pipe = persist = 1 and a B_new
+// token and leaves debug capture, adaptive rank, standalone update, helper slabs and communicator polls unset -- it checks that
+// before the launch (persist_record_ok), since a field that is a constant here would be ignored silently.  z_first, z_rows, red,
+// lab, pl and Ng ARE planned (the helper and batch-side records are built from them), but under persist the update role never
+// reads them: its operands are the helpers' projections.
+struct PersistArgs {
+  // -- by value: geometry, the front of the step (one batch of scalar loads, one wait), what the Jacobi rounds read
+  int L, h, g, s, m, bsize, l2_flag;
+  float lr, wd;
+  const double *Nh;
+  int persist_off, Mcap;
+  const unsigned *pready; unsigned pwant;
+  unsigned *abort_flag;
+  const float *zred; int zsize;
+  const float *prepRaw; float *prepB; double *prepG;
+  float *Bnew;
+  unsigned *flag; unsigned token;
+  double chol_thr, svd_stop2;
+  double *stamps;
+  // -- read where they are used: the end of the step
+  RecField<float *> out_behind, out_ahead;
+  RecField<int> ob_s_h, ob_s_d, ob_s_m, oa_s_m, oa_s_d, oa_s_g, write_ahead;
+  RecField<double *> Nh_new, Apub;
+  RecField<float *> metrics;
+  RecField<unsigned long long *> counters;
+  RecField<int *> status;
+  RecField<unsigned *> aflag, coreflag;
+  RecField<unsigned> coretoken;
+  // -- the other modes' fields
+  static constexpr int D = kD, fused = 0, prep_ready = 0, pipe = 1, persist = 1, z_first = 0, z_rows = 0, stop_after_update = 0, left_dir = 0;
+  static constexpr int wait_count = 0;
+  static constexpr unsigned zpoll_want = 0, done_val = 0;
+  static constexpr double trunc_thr = 0.0;
+  static constexpr const float *red = nullptr, *Bdirect = nullptr;
+  static constexpr const double *Ng = nullptr;
+  static constexpr double *dbg = nullptr;
+  static constexpr int *m_out = nullptr;
+  unsigned *sync = nullptr, *done_flag = nullptr;       // (members: an atomic builtin refuses a literal null even in a dead branch)
+  const unsigned *zpoll_flag = nullptr;
+  CoreView lab{}, pl{}, zcore{};
+
+  __device__ __forceinline__ explicit PersistArgs(const NarrowParams *rec)
+      : out_behind(rec_field(&rec->out_behind)), out_ahead(rec_field(&rec->out_ahead)),
+        ob_s_h(rec_field(&rec->ob_s_h)), ob_s_d(rec_field(&rec->ob_s_d)), ob_s_m(rec_field(&rec->ob_s_m)),
+        oa_s_m(rec_field(&rec->oa_s_m)), oa_s_d(rec_field(&rec->oa_s_d)), oa_s_g(rec_field(&rec->oa_s_g)),
+        write_ahead(rec_field(&rec->write_ahead)), Nh_new(rec_field(&rec->Nh_new)), Apub(rec_field(&rec->Apub)),
+        metrics(rec_field(&rec->metrics)), counters(rec_field(&rec->counters)), status(rec_field(&rec->status)),
+        aflag(rec_field(&rec->aflag)), coreflag(rec_field(&rec->coreflag)), coretoken(rec_field(&rec->coretoken)) {
+    const auto *r = (const __attribute__((address_space(4))) NarrowParams *)rec;
+    L = r->L; h = r->h; g = r->g; s = r->s; m = r->m; bsize = r->bsize; l2_flag = r->l2_flag;
+    lr = r->lr; wd = r->wd; Nh = r->Nh; persist_off = r->persist_off; Mcap = r->Mcap;
+    pready = r->pready; pwant = r->pwant; abort_flag = r->abort_flag; zred = r->zred; zsize = r->zsize;
+    prepRaw = r->prepRaw; prepB = r->prepB; prepG = r->prepG; Bnew = r->Bnew; flag = r->flag; token = r->token;
+    chol_thr = r->chol_thr; svd_stop2 = r->svd_stop2; stamps = r->stamps;
+  }
+};
+
 // returns true when a wait of a persistent sweep timed out (the caller leaves its step loop)
-// NP: NarrowParams (kernel argument) or its constant-address-space twin (persistent sweep: the per-step records are read with scalar
-// loads only if the compiler knows nothing in the kernel writes them)
+// NP: StepArgs (per-step launches) or PersistArgs (persistent sweep), above
 template <class NP>
 __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw) {
   // value ranges the launcher guarantees (narrow_lds_bytes / narrow_path): with them the compiler turns the index products into
@@ -179,7 +258,15 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
   __builtin_assume(p.h >= 1 && p.h <= 64 && p.g >= 1 && p.g <= 64 && p.s >= 1 && p.s <= 128 && p.m >= 1 && p.m <= 64);
   __builtin_assume(p.L >= 1 && p.L <= 2048 && p.bsize >= 1 && p.bsize <= 8192);
   const NarrowCarve k = narrow_carve(smem_raw, p.h, p.g, p.s, p.L, p.m);
-  const int tid = threadIdx.x, NT = kNarrowThreads;
+  // Persistent sweep: the thread index is a new value for the compiler at every step.  Everything a step derives from it alone
+  // (element offsets, role masks) is the same at every step, so the compiler would form it once in front of the step loop and keep
+  // it live across the whole loop: more values than there are registers, parked in scratch and fetched back on the chain.
+  int tid_step = threadIdx.x;
+  if (p.persist) {
+    asm volatile("" : "+v"(tid_step));
+    __builtin_assume(tid_step >= 0 && tid_step < kNarrowThreads);
+  }
+  const int tid = tid_step, NT = kNarrowThreads;
   // the wave index as a scalar: loops and role tests built on it become SALU control flow instead of EXEC-mask bookkeeping
   const int wave_u = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int D = kD, h = p.h, g = p.g, s = p.s, L = p.L, m = p.m, Bs = p.bsize;
@@ -190,7 +277,7 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
   if (p.zpoll_flag) {
     // zred belongs to the side stream (batch-side launch + all-reduce) until its sequence number says otherwise; bounded, and a
     // time-out is reported (status bit 64).  The acquire drops what this XCD's L2 holds of the buffer from the previous step.
-    if (threadIdx.x == 0) {
+    if (tid == 0) {
       bool ok = false;
       for (int spin = 0; spin < (1 << 22) && !ok; ++spin) {
         ok = (int)(__hip_atomic_load(p.zpoll_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - p.zpoll_want) >= 0;
@@ -203,7 +290,7 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
   }
   // metric sums of the batch-side workgroups: behind the gradient (classic) or behind the reduced pre-gradient (pipelined)
   // (pipelined: read NOW -- the batch-side workgroups of this launch overwrite zred once B_new is published)
-  if (p.pipe && !p.persist && threadIdx.x == 0)
+  if (p.pipe && !p.persist && tid == 0)
     for (int i = 0; i < kMetricSlots; ++i) k.sTail[i] = p.zred[p.zsize + i];      // LDS: the loads complete here
   auto ldtail = [&](int i) -> float { return p.pipe ? k.sTail[i] : ldred(p.bsize + i); };
   const int r = D * h, c = D * g * L;
@@ -982,7 +1069,11 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
   if (p.stamps && tid == 0) t_c2b = __builtin_amdgcn_s_memtime();
   // ---- adaptive truncation (not reference behaviour: the reference computes this index and never uses it,
   // Network_class.py:889-891): keep the fewest singular values whose cumulative share exceeds the threshold
+  // (the output pointers and strides as locals: the epilogues of the products below run per element)
   int mk = m, ob_s_h = p.ob_s_h, ob_s_d = p.ob_s_d, oa_s_d = p.oa_s_d, oa_s_g = p.oa_s_g;
+  const int ob_s_m = p.ob_s_m, oa_s_m = p.oa_s_m;
+  float *const out_behind = p.out_behind, *const out_ahead = p.out_ahead;
+  double *const Nh_new = p.Nh_new;
   if (p.trunc_thr > 0.0) {
     if (tid == 0) {
       double tot = 0.0;
@@ -1004,7 +1095,7 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
   }
   // ---- phase 9: the two new cores -----------------------------------------------------------------
   // (persistent sweep: the batch-side workgroups of this launch extend their environments with the behind core -> agent scope)
-  auto st_behind = [&](int off, float v) { if (p.persist) st_sc1(p.out_behind + off, v); else p.out_behind[off] = v; };
+  auto st_behind = [&](int off, float v) { if (p.persist) st_sc1(out_behind + off, v); else out_behind[off] = v; };
   const double lam_max = k.dLam[k.sOrd[0]];
   for (int sp = tid; sp < mk; sp += NT) {                 // sigma^(+-1/2) once per kept column (lam = sigma^2)
     const double lam = k.dLam[k.sOrd[sp]];
@@ -1026,10 +1117,10 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
     if (short_rows) {                       // kk = row index i = h_*D + dk  -> behind core
       k.sCb[kk * mk + sp] = v;
       if (p.persist) PL.Ad[kk * mk + sp] = vq * k.dSq[sp];
-      st_behind((kk / D) * ob_s_h + (kk % D) * ob_s_d + sp * p.ob_s_m, v);
+      st_behind((kk / D) * ob_s_h + (kk % D) * ob_s_d + sp * ob_s_m, v);
     } else {                                // kk = column index (dk1*g + g_)*L + l -> ahead core
       const int l = kk % L, q = kk / L;
-      p.out_ahead[sp * p.oa_s_m + (q / g) * oa_s_d + (q % g) * oa_s_g + l] = v;
+      out_ahead[sp * oa_s_m + (q / g) * oa_s_d + (q % g) * oa_s_g + l] = v;
     }
    }
   lds_barrier();
@@ -1047,10 +1138,10 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
       slot = mm_lds(L, D * g, mk, n, k.fB, 1, L, c, k.dVs, 0, mk, 1,
            [&](int l, int qq, int sp, double acc) {
              const int dk1 = qq >= g ? 1 : 0;                     // D == 2
-             p.out_ahead[__mul24(sp, p.oa_s_m) + dk1 * oa_s_d + __mul24(qq - dk1 * g, oa_s_g) + l] = (float)acc;
+             out_ahead[__mul24(sp, oa_s_m) + dk1 * oa_s_d + __mul24(qq - dk1 * g, oa_s_g) + l] = (float)acc;
            });
     // T2[h_, (d, s'')] = sum_h' Nh[h_, h'] Cb[h', (d, s'')]
-    if (p.Nh_new) mm_lds(1, h, DM, h, k.dNh, 0, h, 1, k.sCb, 0, DM, 1, store_T2, false, slot);
+    if (Nh_new) mm_lds(1, h, DM, h, k.dNh, 0, h, 1, k.sCb, 0, DM, 1, store_T2, false, slot);
   } else {
     // long index = behind group x = (h_, dk) = h_ * D + dk: dk is the batch, rows are h_
     mm_lds(D, h, mk, n, k.fBp, c + 1, D * (c + 1), 1, k.dVs, 0, mk, 1,
@@ -1058,7 +1149,7 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
              const float v = (float)acc;
              k.sCb[__mul24(h_ * D + dk, mk) + sp] = v;
              if (p.persist) PL.Ad[__mul24(h_ * D + dk, mk) + sp] = acc;
-             st_behind(__mul24(h_, ob_s_h) + dk * ob_s_d + __mul24(sp, p.ob_s_m), v);
+             st_behind(__mul24(h_, ob_s_h) + dk * ob_s_d + __mul24(sp, ob_s_m), v);
            });
   }
   lds_barrier();
@@ -1081,13 +1172,13 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
         st_sc1_b128(rP, (unsigned)(r * mk + 2 * e) * 8u, pack_d2(i0 * i0, i1 * i1));
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (ln == 0) __hip_atomic_store(p.aflag, p.coretoken, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (ln == 0) { unsigned *const aflag = p.aflag; __hip_atomic_store(aflag, (unsigned)p.coretoken, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
     }
   }
 
   if (p.stamps && tid == 0) t_c2c = __builtin_amdgcn_s_memtime();
   // ---- phase 10: behind norm environment of the next step ------------------------------------------
-  if (p.Nh_new) {
+  if (Nh_new) {
     if (!short_rows) {
       mm_lds(1, h, DM, h, k.dNh, 0, h, 1, k.sCb, 0, DM, 1, store_T2);
       lds_barrier();
@@ -1095,7 +1186,7 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
     // Nh_new[s', s''] = sum_{(h_, d)} Cb[(h_, d), s'] T2[(h_, d), s'']
     mm_lds(1, mk, mk, h * D, k.sCb, 0, 1, mk, k.dT2, 0, mk, 1,
            [&](int, int i, int j, double v) {
-             p.Nh_new[i * mk + j] = v;
+             Nh_new[i * mk + j] = v;
              if (p.persist) PL.Nh[i * mk + j] = v;
            });
     if (p.persist) {                      // the helpers' copy: 16-byte stores from the LDS copy, the last double padded where mk is odd
@@ -1132,7 +1223,7 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
     // phase 9) every storing wave drains, the workgroup meets, one lane raises the end-of-step token
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     lds_barrier();
-    if (tid == 0) __hip_atomic_store(p.coreflag, p.coretoken, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) { unsigned *const coreflag = p.coreflag; __hip_atomic_store(coreflag, (unsigned)p.coretoken, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
   }
   if (p.done_flag) {
     // everything this workgroup wrote (the two cores, the norm environment, the metrics) out to where the side stream's kernels read
@@ -1152,7 +1243,7 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
 __global__ __launch_bounds__(kNarrowThreads) void narrow_step_kernel(NarrowParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   if (p.fused && blockIdx.x > 0) { narrow_helper_block(p, smem_raw); return; }
-  narrow_body(p, smem_raw);
+  narrow_body(StepArgs(p), smem_raw);
 }
 
 void launch_narrow(const NarrowParams &p, size_t lds_bytes, hipStream_t st) {
@@ -1166,9 +1257,9 @@ void launch_narrow(const NarrowParams &p, size_t lds_bytes, hipStream_t st) {
 __global__ __launch_bounds__(kNarrowThreads) void step_pipe_kernel(NarrowParams p, WidePipeParams w) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int blk = blockIdx.x;
-  if (blk >= w.wg0) { wide_pipe_block(w, (float *)smem_raw); return; }
+  if (blk >= w.wg0) { wide_pipe_block(WidePipeArgs<0>(w), (float *)smem_raw); return; }
   if (blk > 0) { narrow_helper_block(p, smem_raw); return; }
-  narrow_body(p, smem_raw);
+  narrow_body(StepArgs(p), smem_raw);
 }
 
 void launch_step_pipe(const NarrowParams &p, const WidePipeParams &w, size_t lds_bytes, hipStream_t st) {
@@ -1235,7 +1326,10 @@ __device__ inline void st_sc1_rows(T *dst, const T *stage, int rows, int srs, in
 
 template <class HP>
 __device__ __forceinline__ bool persist_helper_block(const HP &t, int hid, int nH, unsigned char *smem_raw, bool do_part2) {
-  const int tid = threadIdx.x, NT = kNarrowThreads;
+  int tid_step = threadIdx.x;                 // a new value per call, as in narrow_body: nothing derived from it is kept across the step loop
+  asm volatile("" : "+v"(tid_step));
+  __builtin_assume(tid_step >= 0 && tid_step < kNarrowThreads);
+  const int tid = tid_step, NT = kNarrowThreads;
   const int D = kD, zr = t.zr, s = t.s, g = t.g, L = t.L, h = t.h;
   const int DG = D * g, RW = D * DG * L;
   __shared__ int sBad;
@@ -1399,17 +1493,13 @@ __device__ __forceinline__ bool persist_helper_block(const HP &t, int hid, int n
 
 __global__ __launch_bounds__(kNarrowThreads) void sweep_persist_kernel(const PersistStep *__restrict__ steps_g, int n_steps, int nH) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  // the host wrote the records before the launch and nothing in the kernel writes them: constant address space -> scalar loads
-  // Every role works on a by-value copy of its record for the step (scalar registers, as the per-step kernels' arguments): fields
-  // read on demand from memory would put scalar-load latencies into the inner loops.
+  // the host wrote the records before the launch and nothing in the kernel writes them: constant address space -> scalar loads.
+  // The update role reads its record through PersistArgs; the other two work on a by-value copy of theirs for the step.
   const int blk = blockIdx.x;
   if (blk == 0) {
 #pragma nounroll
-    for (int k = 0; k < n_steps; ++k) {
-      NarrowParams n;
-      __builtin_memcpy(&n, &steps_g[k].n, sizeof n);
-      if (narrow_body(n, smem_raw)) break;
-    }
+    for (int k = 0; k < n_steps; ++k)
+      if (narrow_body(PersistArgs(&steps_g[k].n), smem_raw)) break;
   } else if (blk <= nH) {
     // T_0; then per step: the projections of step k, and T_{k+1} once B_new(k) is there -- one call site (the body is inlined once)
 #pragma nounroll
@@ -1426,7 +1516,7 @@ __global__ __launch_bounds__(kNarrowThreads) void sweep_persist_kernel(const Per
       WidePipeParams w;
       __builtin_memcpy(&w, &steps_g[it == 0 ? n_steps : it - 1].w, sizeof w);
       lds_barrier();                                       // the previous iteration's LDS arrays are dead
-      if (wide_pipe_block(w, (float *)smem_raw)) break;
+      if (wide_pipe_block(WidePipeArgs<1>(w), (float *)smem_raw)) break;
     }
   }
 }
@@ -1436,29 +1526,16 @@ void launch_sweep_persist(const PersistStep *steps_dev, int n_steps, int n_helpe
 }
 
 // The same sweep as THREE launches, one per role, on three streams: the roles then get their own register allocation (inside one
-// kernel the batch-side loops spill and lose their unrolling to the update workgroup's code, and run ~2.4x slower than in the
-// per-step kernel).  The three grids communicate through the same flags; they need to be resident together, which holds when
+// kernel they share one: DESIGN.md 5.2 lists what each form carries).  The three grids communicate through the same flags; they
+// need to be resident together, which holds when
 // nothing serialises launches (88 workgroups on a 256-CU device) -- a dispatch-serialising profiler (rocprofv3 --pmc) makes the first
 // grid wait in vain: its bounded polls time out and the sweep fails with TNML_ERR_STATE; use tnml_set_persistent(ctx, 1) (one
 // kernel) or 0 (per-step launches) there.
-__global__ __launch_bounds__(kNarrowThreads) void persist_update_kernel(const PersistStep *__restrict__ steps_g, int n_steps, int rec_off) {
+__global__ __launch_bounds__(kNarrowThreads) void persist_update_kernel(const PersistStep *__restrict__ steps_g, int n_steps) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  // The record of step k+1 is fetched into LDS while step k runs (two waves, at the start of the step) and becomes the by-value
-  // argument of the next narrow_body from there: a fetch from memory between two steps is ~1.6 us on the critical path.
-  constexpr int kWords = (int)(sizeof(NarrowParams) / sizeof(unsigned));
-  static_assert(sizeof(NarrowParams) % sizeof(unsigned) == 0, "NarrowParams is copied word by word");
-  unsigned *rec = reinterpret_cast<unsigned *>(smem_raw + rec_off);
-  for (int e = threadIdx.x; e < kWords; e += kNarrowThreads) rec[e] = reinterpret_cast<const unsigned *>(&steps_g[0].n)[e];
-  lds_barrier();
 #pragma nounroll
-  for (int k = 0; k < n_steps; ++k) {
-    NarrowParams n;
-    __builtin_memcpy(&n, rec, sizeof n);
-    lds_barrier();                                         // everybody holds its copy: the buffer may take the next record
-    if (k + 1 < n_steps)
-      for (int e = threadIdx.x; e < kWords; e += kNarrowThreads) rec[e] = reinterpret_cast<const unsigned *>(&steps_g[k + 1].n)[e];
-    if (narrow_body(n, smem_raw)) break;
-  }
+  for (int k = 0; k < n_steps; ++k)
+    if (narrow_body(PersistArgs(&steps_g[k].n), smem_raw)) break;
 }
 __global__ __launch_bounds__(kNarrowThreads) void persist_helper_kernel(const PersistStep *__restrict__ steps_g, int n_steps, int nH) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -1478,14 +1555,14 @@ __global__ __launch_bounds__(kNarrowThreads) void persist_batch_kernel(const Per
     __builtin_memcpy(&w, &steps_g[it == 0 ? n_steps : it - 1].w, sizeof w);
     w.wg0 = 0;                                             // this grid holds batch-side workgroups only
     lds_barrier();
-    if (wide_pipe_block(w, (float *)smem_raw)) break;
+    if (wide_pipe_block(WidePipeArgs<1>(w), (float *)smem_raw)) break;
   }
 }
 void launch_sweep_persist_split(const PersistStep *steps_dev, int n_steps, int n_helpers, int n_wide, size_t lds_update, size_t lds_helper,
-                                size_t lds_wide, int rec_off, hipStream_t st_update, hipStream_t st_helper, hipStream_t st_wide) {
+                                size_t lds_wide, hipStream_t st_update, hipStream_t st_helper, hipStream_t st_wide) {
   hipLaunchKernelGGL(persist_batch_kernel, dim3(n_wide), dim3(kNarrowThreads), lds_wide, st_wide, steps_dev, n_steps);
   hipLaunchKernelGGL(persist_helper_kernel, dim3(n_helpers), dim3(kNarrowThreads), lds_helper, st_helper, steps_dev, n_steps, n_helpers);
-  hipLaunchKernelGGL(persist_update_kernel, dim3(1), dim3(kNarrowThreads), lds_update, st_update, steps_dev, n_steps, rec_off);
+  hipLaunchKernelGGL(persist_update_kernel, dim3(1), dim3(kNarrowThreads), lds_update, st_update, steps_dev, n_steps);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -17,6 +17,16 @@ namespace tnml {
 // ------------------------------------------------------------------------------------------
 typedef double dvec4 __attribute__((ext_vector_type(4)));
 
+// The thread index as a value of its own per product call.  Inside a kernel that loops over the steps of a sweep, lane maps and
+// operand addresses formed from threadIdx.x directly are the same at every step: the compiler forms them all in front of the step
+// loop and keeps them live across it, beyond the registers there are (scratch on the chain of the update workgroup).
+__device__ __forceinline__ int mm_call_tid() {
+  int t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  __builtin_assume(t >= 0 && t < 1024);
+  return t;
+}
+
 template <class FA, class FB, class FS>
 __device__ inline void small_gemm_f64(int nbatch, int M, int N, int K, FA loadA, FB loadB, FS store) {
   // C_b[M x N] = A_b[M x K] . B_b[K x N] for b < nbatch; loadA(b, i, k), loadB(b, k, j),
@@ -78,8 +88,9 @@ __device__ inline int mm_lds(int nbatch, int M, int N, int K, const TA *A, int a
   // upper_only: M == N and only tiles with ti <= tj are computed (symmetric products: the caller mirrors)
   // slot0 / return value: independent products issued back to back (no barrier between them) continue the round-robin deal
   // of tiles to waves where the previous one stopped
-  const int lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // uniform for the compiler: scalar tile bookkeeping
+  const int tid = mm_call_tid();
+  const int lane = tid & 63, nw = blockDim.x >> 6;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // uniform for the compiler: scalar tile bookkeeping
   const int tn = (N + 15) >> 4, tm = (M + 15) >> 4;
   const int r = lane & 15, q = lane >> 4;
   const int nk = (K + 3) >> 2;                         // k-steps of 4
@@ -147,8 +158,9 @@ __device__ inline int mm_lds(int nbatch, int M, int N, int K, const TA *A, int a
 typedef float fvec4_t __attribute__((ext_vector_type(4)));
 template <class FS>
 __device__ inline void mm_lds_f32(int M, int N, int K, const float *A, int a_rs, int a_ks, const float *B, int b_ks, int b_cs, FS store) {
-  const int lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int tid = mm_call_tid();
+  const int lane = tid & 63, nw = blockDim.x >> 6;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int tn = (N + 15) >> 4, tm = (M + 15) >> 4;
   const int r = lane & 15, q = lane >> 4;
   const int nk = (K + 3) >> 2;

@@ -1514,6 +1514,13 @@ static int finish_sweep(tnml_ctx *c, int left_dir, int n_steps, int l2_flag, int
 // position, label-core buffer -- advances through advance_frame.  Returns 1 if the sweep was enqueued, 0 if this sweep has to take
 // the per-step path (state untouched), < 0 on error.
 // ---------------------------------------------------------------------------------------------
+// What the update role of the persistent kernels takes as compile-time constants (PersistArgs, kernels_narrow.hip) must be what the
+// record says: a mode planned here later and not taught to the kernel would otherwise be ignored silently.
+static bool persist_record_ok(const NarrowParams &n) {
+  return n.pipe == 1 && n.persist == 1 && n.flag && !n.fused && !n.prep_ready && !n.Bdirect && !n.dbg && !n.stop_after_update &&
+         !(n.trunc_thr > 0.0) && !n.m_out && !n.zpoll_flag && !n.done_flag && !n.sync && n.wait_count == 0;
+}
+
 static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float weight_dec, int l2_flag, int act_fn, int loss_fn,
                          float T, int trunc_policy) {
   const int N = c->N, D = c->D, L = c->L;
@@ -1584,6 +1591,7 @@ static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float
     n.Apub = c->Apub;
     n.aflag = fl + 5; n.coreflag = fl + 3; n.coretoken = (unsigned)k + 1; n.abort_flag = fl + 4;
     n.Mcap = Mcap;
+    if (!persist_record_ok(n)) return give_up();             // (a plan the persistent kernels do not know: the per-step path runs it)
     lds_narrow = std::max(lds_narrow, nlds);
     // ---- batch-side workgroups: f from B_new(k), pre-gradient of step k+1
     wp.do_ext = k >= 1; wp.do_f = 1; wp.wait_flag = 1;
@@ -1629,10 +1637,7 @@ static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float
     HIP_TRY(hipEventRecord(c->ev_p0, c->stream));
     HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_p0, 0));
     HIP_TRY(hipStreamWaitEvent(c->stream3, c->ev_p0, 0));
-    // (the update grid keeps the next step's record in LDS behind the persistent region)
-    const size_t rec_bytes = (sizeof(NarrowParams) + 15) & ~(size_t)15;
-    if (lds + rec_bytes > 160 * 1024) return give_up();
-    launch_sweep_persist_split(c->pst_dev, n_steps, nH, nwide, lds + rec_bytes, lds_help, lds_wide, (int)lds, c->stream, c->stream2, c->stream3);
+    launch_sweep_persist_split(c->pst_dev, n_steps, nH, nwide, lds, lds_help, lds_wide, c->stream, c->stream2, c->stream3);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev_p2, c->stream2));
     HIP_TRY(hipEventRecord(c->ev_p3, c->stream3));

@@ -212,19 +212,33 @@ inline size_t persist_helper_lds_bytes(int zr, int s, int g, int L, int h, int n
 void launch_sweep_persist(const PersistStep *steps_dev, int n_steps, int n_helpers, int grid, size_t lds_bytes, hipStream_t st);
 // one launch per role on three streams (kernels_narrow.hip)
 void launch_sweep_persist_split(const PersistStep *steps_dev, int n_steps, int n_helpers, int n_wide, size_t lds_update, size_t lds_helper,
-                                size_t lds_wide, int rec_off, hipStream_t st_update, hipStream_t st_helper, hipStream_t st_wide);
+                                size_t lds_wide, hipStream_t st_update, hipStream_t st_helper, hipStream_t st_wide);
 
 
 // ------------------------------------------------------------------------------------------------------------------
 // One batch-side workgroup (1024 threads, 16 waves).  MFMA lane maps (v_mfma_f32_16x16x4_f32): A[row = lane & 15]
 // [k = lane >> 4], B[k = lane >> 4][col = lane & 15], C/D col = lane & 15, row = 4 (lane >> 4) + reg.
 // ------------------------------------------------------------------------------------------------------------------
+// The record as wide_pipe_block sees it, per launch mode: `persist` is a compile-time constant, so each kernel carries the hand-off
+// code of its own mode only.
+template <int PERSIST>
+struct WidePipeArgs : WidePipeParams {
+  __device__ __forceinline__ WidePipeArgs(const WidePipeParams &q) : WidePipeParams(q) {}
+  static constexpr int persist = PERSIST;
+};
 // returns true when the workgroup gave up (persistent sweep: a wait timed out here or elsewhere)
 template <class WP>
 __device__ __forceinline__ bool wide_pipe_block(const WP &p, float *smem) {
   const WidePipeDims dm = wide_pipe_dims(p);
   const WidePipeSmem w = wide_pipe_carve(smem, p, dm);
-  const int tid = threadIdx.x, NT = kPipeThreads;
+  // (persistent sweep: the thread index is a new value for the compiler at every step -- what a step derives from it alone is
+  // otherwise formed once in front of the step loop and kept live across it, in scratch; see narrow_body, kernels_narrow.hip)
+  int tid_step = threadIdx.x;
+  if (p.persist) {
+    asm volatile("" : "+v"(tid_step));
+    __builtin_assume(tid_step >= 0 && tid_step < kPipeThreads);
+  }
+  const int tid = tid_step, NT = kPipeThreads;
   const int lane = tid & 63, NWV = NT / 64;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // scalar: tile loops on it become SALU control flow
   const int r = lane & 15, q = lane >> 4;
