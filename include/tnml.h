@@ -168,6 +168,22 @@ int tnml_svd_split(tnml_ctx *ctx, const float *mat, int rows, int cols, int m, f
  * l_pos restriction as tnml_forward. */
 int tnml_predict(tnml_ctx *ctx, const float *X, int b, float *f_out);
 
+/* on = 1: tnml_forward, tnml_predict, tnml_predict_indices and tnml_eval_indices also run with the label at an
+ * intermediate site, and a forward there lets tnml_sweep start a segment (below).  Default 0: every call behaves
+ * as before.  With a communicator: TNML_ERR_STATE.
+ *   tnml_forward at 0 < l < N-1 builds Lenv[0..l-1] and Renv[l+1..N-1] into their usual slots (two half-chains, neither with a
+ *   label site) and f[l'][s] = sum_{a,d,c} Lenv[l-1][a][s] x_l[s][d] A_l[a][d][c][l'] Renv[l+1][c][s] (label_meet_kernel,
+ *   csrc/kernels_meet.hip); tnml_get_env then answers for both sides.  The three prediction calls run the same kernels and keep
+ *   nothing but the two environments next to the label site, in buffers of their own; their f is bit-equal to tnml_forward's.
+ *   At l = 0 and l = N-1 every call takes the path it takes with the switch off.  tnml_forward_logabsmax stays ends-only.
+ *   Segment start: after such a forward ONE tnml_sweep(first_of_sweep = 0) in either direction is accepted wherever the
+ *   position allows the step; it starts from the f of the forward (or of tnml_set_f), and the calls after it continue as any
+ *   mid-sweep call does.  Its first step takes the classic launch sequence on every path (the pipelined step resumes with the
+ *   second).  The stack behind the segment counts as rewritten once its first step is planned; a call refused or failed before
+ *   that leaves both stacks valid.  first_of_sweep = 1 stays ends-only; a direction change, or a sweep after a new batch, still needs a forward first.
+ *   tnml_update_B and tnml_l2_term run after an intermediate forward too.   */
+int tnml_set_any_position(tnml_ctx *ctx, int on);
+
 /* ---- device-resident dataset --------------------------------------------------------------- */
 /* A context can hold ONE dataset of n samples with labels in HBM; batches and evaluations are then formed on the device from
  * index lists, and only the lists and a few scalars cross the bus.  No reference analogue: the reference's

@@ -129,6 +129,13 @@ class Network():
     Attributes (as in the reference, Network_class.py:14-47): N, D, L, M, T, act_fn, loss_fn,
     As, l_pos, TX, r_cum_contraction, l_cum_contraction.
 
+    `any_position` (default False, not pickled; not in the reference): when set, `forward`, `predict`, `evaluate` and the dataset
+    calls also run with the label at an intermediate site -- `l_cum_contraction` then lists Lenv[0..l-1] and `r_cum_contraction`
+    Renv[l+1..N-1], both in site order, and f is only the return value -- and `sweep_step` may follow such a forward in either
+    direction (include/tnml.h, tnml_set_any_position).  `train_resident(steps_per_batch=k)` leaves in `segment_log` the list of
+    (l_pos, left_dir, n_steps) of the segments of its last call; the direction of the last segment is pickled with the network
+    (`seg_left`), so that a model saved mid-sweep goes on in the direction it was moving.
+
     D (2 <= D <= 8) is the local feature dimension (data_generator.psi(x, D) embeds pixels for it).  D != 2 runs the
     generic per-step device path (include/tnml.h).  Deviation from the reference: with normalize=True and no
     calibration_X the 16 random calibration samples are embedded with psi(u, D); the reference always embeds them
@@ -204,6 +211,9 @@ class Network():
         self._l_user = None
         self._dataset = None          # DeviceDataset attached to self._ctx (attach_dataset); lives and dies with the context
         self._X_idx = None            # dataset indices of the resident batch when it was formed on the device
+        self._any_position = False
+        self._seg_left = False        # direction of the last segment of train_resident(steps_per_batch=k) (pickled)
+        self.segment_log = []         # (l_pos, left_dir, n_steps) of the segments of the last train_resident(steps_per_batch=k)
 
     def _context(self, b):
         if self._ctx is None:
@@ -212,7 +222,51 @@ class Network():
                 self._ctx.set_svd_stop(self._svd_stop)
             if getattr(self, '_threshold', None) is not None:
                 self._ctx.set_trunc_threshold(self._threshold)
+            if self._any_position:
+                self._ctx.set_any_position(True)
         return self._ctx
+
+    @property
+    def any_position(self):
+        return self._any_position
+
+    @any_position.setter
+    def any_position(self, on):
+        self._any_position = bool(on)
+        if self._ctx is not None:
+            self._ctx.set_any_position(self._any_position)
+
+    def _check_forward_position(self, lp):
+        if lp != 0 and lp != self.N - 1 and not self._any_position:
+            raise Exception('### Error ###\n l =', lp, ' -> forward should not be called if l has an intermediate position')
+
+    def _entries_after_forward(self, lp):
+        """The environment lists a forward at label position lp leaves (Network_class.py:227-255); with the label inside the
+        chain (any_position) both stacks exist and f belongs to neither."""
+        S_R, S_L = _hip.SIDE_RIGHT, _hip.SIDE_LEFT
+        if lp == 0:
+            self._r_entries = [('f',)] + [('env', S_R, i) for i in range(1, self.N)]
+            self._l_entries = None
+        elif lp == self.N - 1:
+            self._l_entries = [('env', S_L, i) for i in range(self.N - 1)] + [('f',)]
+            self._r_entries = None
+        else:
+            self._l_entries = [('env', S_L, i) for i in range(lp)]
+            self._r_entries = [('env', S_R, i) for i in range(lp + 1, self.N)]
+
+    def _entries_after_steps(self, left_dir, lp):
+        """The list the sweep grows gains one entry per step, as the reference leaves it; with any_position the other list
+        is cut to what is still valid on the device (the environments beyond the label site)."""
+        S_R, S_L = _hip.SIDE_RIGHT, _hip.SIDE_LEFT
+        if left_dir:
+            # steps at l = N-2 .. 1 append Renv[l+1]; after reaching l_pos the deepest is Renv[lp+2]
+            self._r_entries = [('env', S_R, i) for i in range(self.N - 1, lp + 1, -1)]
+            if self._any_position:
+                self._l_entries, self._l_user = [('env', S_L, i) for i in range(lp)], None
+        else:
+            self._l_entries = [('env', S_L, i) for i in range(0, lp - 1)]
+            if self._any_position:
+                self._r_entries, self._r_user = [('env', S_R, i) for i in range(lp + 1, self.N)], None
 
     def _collect_user_edits(self):
         """If `net.As` was handed out, fold any edit of those Tensors back into the host cores."""
@@ -327,8 +381,7 @@ class Network():
         (Network_class.py:195-258).  Returns a Tensor ('l', 'b')."""
         assert self.N == X.shape[1], "The 1 dimension of the input data must be the flattened number of pixels"
         lp = self.l_pos
-        if lp != 0 and lp != self.N - 1:
-            raise Exception('### Error ###\n l =', lp, ' -> forward should not be called if l has an intermediate position')
+        self._check_forward_position(lp)
         ctx = self._sync_to_device(X.shape[0])
         self._X_host = X
         self._b = X.shape[0]
@@ -336,13 +389,7 @@ class Network():
         self._y_dev = None
         f = ctx.forward()
         self._invalidate_envs()
-        S_R, S_L = _hip.SIDE_RIGHT, _hip.SIDE_LEFT
-        if lp == 0:
-            self._r_entries = [('f',)] + [('env', S_R, i) for i in range(1, self.N)]
-            self._l_entries = None
-        else:
-            self._l_entries = [('env', S_L, i) for i in range(self.N - 1)] + [('f',)]
-            self._r_entries = None
+        self._entries_after_forward(lp)
         return Tensor(elem=f.astype(np.float64), axes_names=['l', 'b'])
 
     def predict(self, X):
@@ -350,9 +397,7 @@ class Network():
         rebuilt, `TX` and the training batch stay as they are (the validation loop of `train`,
         Network_class.py:339-346, only needs f).  Not in the reference."""
         assert self.N == X.shape[1], "The 1 dimension of the input data must be the flattened number of pixels"
-        lp = self.l_pos
-        if lp != 0 and lp != self.N - 1:
-            raise Exception('### Error ###\n l =', lp, ' -> forward should not be called if l has an intermediate position')
+        self._check_forward_position(self.l_pos)
         ctx = self._sync_to_device(max(self._b, 1))
         return Tensor(elem=ctx.predict(X).astype(np.float64), axes_names=['l', 'b'])
 
@@ -423,8 +468,7 @@ class Network():
         """forward() for the dataset samples idx, without any copy of X or f: the batch is formed on the device, the chain
         builds the environment stack, and (correct, sum |onehot - act(f)|, non-finite) of f come back."""
         lp = self.l_pos
-        if lp != 0 and lp != self.N - 1:
-            raise Exception('### Error ###\n l =', lp, ' -> forward should not be called if l has an intermediate position')
+        self._check_forward_position(lp)
         ctx = self._sync_to_device(len(idx))
         ctx.select_indices(idx)
         self._X_host, self._X_idx = None, np.array(idx, dtype=np.int64)
@@ -432,54 +476,87 @@ class Network():
         self._y_dev = None
         ctx.forward(want_f=False)
         self._invalidate_envs()
-        S_R, S_L = _hip.SIDE_RIGHT, _hip.SIDE_LEFT
-        if lp == 0:
-            self._r_entries = [('f',)] + [('env', S_R, i) for i in range(1, self.N)]
-            self._l_entries = None
-        else:
-            self._l_entries = [('env', S_L, i) for i in range(self.N - 1)] + [('f',)]
-            self._r_entries = None
+        self._entries_after_forward(lp)
         return ctx.resident_metrics(self.act_fn, self.T)
 
-    def _sweep_resident(self, lr, weight_dec, L2_flag, left_dir, var_hist):
-        """sweep() on the batch `_forward_indices` left resident: labels and f are already on the device."""
+    def _sweep_resident(self, lr, weight_dec, L2_flag, left_dir, var_hist, n_steps=None, first=True):
+        """sweep() on the batch `_forward_indices` left resident: labels and f are already on the device.  n_steps / first: a
+        segment of a sweep (train_resident(steps_per_batch=k)); first is set exactly when it starts at a chain end."""
         ctx = self._ctx
-        if left_dir:
-            self._r_entries, self._r_user = [], None
-        else:
-            self._l_entries, self._l_user = [], None
-        met, _ = ctx.sweep(left_dir, self.N - 1, True, lr, weight_dec, L2_flag, self.act_fn, self.loss_fn, self.T, self.trunc,
-                           want_metrics=True, want_f=False)
+        if first:
+            if left_dir:
+                self._r_entries, self._r_user = [], None
+            else:
+                self._l_entries, self._l_user = [], None
+        met, _ = ctx.sweep(left_dir, self.N - 1 if n_steps is None else n_steps, first, lr, weight_dec, L2_flag, self.act_fn, self.loss_fn,
+                           self.T, self.trunc, want_metrics=True, want_f=False)
         var_hist[0].extend(float(v) for v in met[:, 0])
         var_hist[1].extend(float(v) for v in met[:, 1])
         self._device_newer = True
         self._As = None
         self._env_epoch += 1
-        lp = ctx.l_pos
-        S_R, S_L = _hip.SIDE_RIGHT, _hip.SIDE_LEFT
-        if left_dir:
-            self._r_entries = [('env', S_R, i) for i in range(self.N - 1, lp + 1, -1)]
-        else:
-            self._l_entries = [('env', S_L, i) for i in range(0, lp - 1)]
+        self._entries_after_steps(left_dir, ctx.l_pos)
 
-    def train_resident(self, train_index_loader, val_index_loader, lr, n_epochs=10, weight_dec=0.001, L2_flag=True):
+    def _next_segment(self, k):
+        """(left_dir, n_steps, first) of the segment that starts at the current label position: right from site 0, left from
+        site N-1, otherwise the direction of the previous segment; at most k steps, never past the chain end."""
+        l = self.l_pos
+        if l == 0:
+            self._seg_left = False
+        elif l == self.N - 1:
+            self._seg_left = True
+        left = self._seg_left
+        return left, min(int(k), l if left else self.N - 1 - l), l == (self.N - 1 if left else 0)
+
+    def train_resident(self, train_index_loader, val_index_loader, lr, n_epochs=10, weight_dec=0.001, L2_flag=True,
+                       steps_per_batch=None):
         """`train` from the attached dataset: the loaders yield index arrays (data_generator.IndexLoader), and per batch
         only the index list goes to the device and the per-step metrics and three scalars come back -- X and f never
         cross the bus.  Same sweeps, same printed lines and same return value (val_acc, var_hist of shape
-        (n_epochs, 2, n_batches * (N-1))) as `train` on loaders that yield the same samples in the same order."""
+        (n_epochs, 2, n_batches * (N-1))) as `train` on loaders that yield the same samples in the same order.
+
+        steps_per_batch = k >= 1 (not in the reference) changes the batch every k steps instead of every sweep: per index
+        batch a forward at the current label position (its accuracy is the batch's training accuracy), then
+        min(k, steps left to the chain end in the current direction) steps.  The direction is right at site 0, left at
+        site N-1 and otherwise that of the previous segment; position and direction carry over from batch to batch and from
+        epoch to epoch, and a segment that reaches an end is not padded by turning round.  Validation runs wherever the
+        label stands.  `any_position` is set for the duration of the call.  var_hist is then a list of one
+        (2, n_epoch_steps) array per epoch (the step count may differ between epochs).  k = N-1 from a chain end is the
+        default schedule."""
+        if steps_per_batch is not None and (int(steps_per_batch) != steps_per_batch or int(steps_per_batch) < 1):
+            raise ValueError('steps_per_batch must be an integer >= 1')
         self._require_dataset()
+        if steps_per_batch is None:
+            return self._train_resident_loop(train_index_loader, val_index_loader, lr, n_epochs, weight_dec, L2_flag, None)
+        was = self._any_position
+        self.any_position = True
+        try:
+            return self._train_resident_loop(train_index_loader, val_index_loader, lr, n_epochs, weight_dec, L2_flag, int(steps_per_batch))
+        finally:
+            self.any_position = was
+
+    def _train_resident_loop(self, train_index_loader, val_index_loader, lr, n_epochs, weight_dec, L2_flag, k):
+        """The epoch loop of train_resident.  k = None: a whole sweep per batch from the chain end the label stands on (var_hist
+        an array); k: the segments of `_next_segment` (var_hist a list of one array per epoch), each noted in `segment_log`."""
         val_acc, var_hist = [], []
+        if k is not None:
+            self.segment_log = []
         print("\n --- TRAINING PROCEDURE ---")
         for epoch in range(n_epochs):
             epoch_train_acc = np.zeros(len(train_index_loader))
-            var_hist.append([[], []])
+            vh = [[], []]
             for i, idx in enumerate(train_index_loader, 0):
                 correct, _, _ = self._forward_indices(idx)
                 epoch_train_acc[i] = correct / len(idx)
-                left_dir = (self.l_pos == self.N - 1)
-                self._sweep_resident(lr, weight_dec, L2_flag, left_dir, var_hist[epoch])
+                if k is None:
+                    left_dir, n, first = (self.l_pos == self.N - 1), None, True
+                else:
+                    left_dir, n, first = self._next_segment(k)
+                    self.segment_log.append((self.l_pos, left_dir, n))
+                self._sweep_resident(lr, weight_dec, L2_flag, left_dir, vh, n_steps=n, first=first)
                 print('\r' + "Epoch %d/%d - train accuracy : %.4f - completed : %.2f "
                       % (epoch, n_epochs, epoch_train_acc[i], (i + 1) * 100 / len(train_index_loader)) + '%', end=' ')
+            var_hist.append(vh if k is None else np.array(vh))
             epoch_val_acc = np.zeros(len(val_index_loader))
             for i, idx in enumerate(val_index_loader, 0):
                 correct, _, _ = self._ctx.eval_indices(idx, self.act_fn, self.T)
@@ -487,7 +564,7 @@ class Network():
             val_acc.append(epoch_val_acc.mean())
             print('\r' + "Epoch %d/%d - train accuracy : %.4f - val accuracy: %.4f"
                   % (epoch, n_epochs, epoch_train_acc.mean(), val_acc[-1]))
-        return val_acc, np.array(var_hist)
+        return val_acc, (np.array(var_hist) if k is None else var_hist)
 
     def evaluate(self, indices, activated=True):
         """(accuracy, mean absolute error) of the network over samples of the attached dataset, reduced on the device.
@@ -496,9 +573,7 @@ class Network():
         when the last batch is ragged -- or an index array, for the overall figures.  The error is the mean over samples
         and labels of |onehot(y) - act(f)| (the MAE of `var_hist`); activated=False takes f itself."""
         ctx = self._require_dataset()
-        lp = self.l_pos
-        if lp != 0 and lp != self.N - 1:
-            raise Exception('### Error ###\n l =', lp, ' -> forward should not be called if l has an intermediate position')
+        self._check_forward_position(self.l_pos)
         act = self.act_fn if activated else 'linear'
 
         def one(idx):
@@ -568,13 +643,7 @@ class Network():
         self._As = None
         self._env_epoch += 1
         # environment lists as the reference leaves them: the grown one gains one entry per step
-        lp = ctx.l_pos
-        S_R, S_L = _hip.SIDE_RIGHT, _hip.SIDE_LEFT
-        if left_dir:
-            # steps at l = N-2 .. 1 append Renv[l+1]; after reaching l_pos the deepest is Renv[lp+2]
-            self._r_entries = [('env', S_R, i) for i in range(self.N - 1, lp + 1, -1)]
-        else:
-            self._l_entries = [('env', S_L, i) for i in range(0, lp - 1)]
+        self._entries_after_steps(left_dir, ctx.l_pos)
         return Tensor(elem=out.astype(np.float64), axes_names=['l', 'b'])
 
     def sweep(self, X, y, f, lr, weight_dec, L2_flag=True, left_dir=False, var_hist=None, debug=False):
@@ -762,7 +831,7 @@ class Network():
         As = self.As
         return dict(N=self.N, D=self.D, L=self.L, M=self.M, T=self.T, As=As, l_pos=self._l_pos,
                     act_fn=self.act_fn, loss_fn=self.loss_fn, TX=None, r_cum_contraction=None,
-                    l_cum_contraction=None, trunc=self.trunc)
+                    l_cum_contraction=None, trunc=self.trunc, seg_left=bool(getattr(self, '_seg_left', False)))
 
     def __setstate__(self, state):
         # accepts both our own pickles and the reference's (plain __dict__ with As as Tensors)
@@ -772,6 +841,7 @@ class Network():
         self._device = 0
         self._init_runtime()
         self._l_pos = state['l_pos']
+        self._seg_left = bool(state.get('seg_left', False))
         cores = []
         for i, Tn in enumerate(state['As']):
             c, _ = _tensor_to_core(Tn, i, self.N)

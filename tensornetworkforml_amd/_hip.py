@@ -31,7 +31,7 @@ SYMBOLS = [
     'tnml_set_sync_interval', 'tnml_set_step_pipeline', 'tnml_stage_batch', 'tnml_select_batch', 'tnml_get_counters',
     'tnml_svd_stats_ex', 'tnml_set_persistent', 'tnml_set_chain_path', 'tnml_marker', 'tnml_set_comm_overlap', 'tnml_comm_probe', 'tnml_set_flag_handoffs',
     'tnml_dataset_attach', 'tnml_dataset_detach', 'tnml_dataset_size', 'tnml_select_indices', 'tnml_predict_indices', 'tnml_eval_indices',
-    'tnml_resident_metrics', 'tnml_dataset_read',
+    'tnml_resident_metrics', 'tnml_dataset_read', 'tnml_set_any_position',
 ]
 
 
@@ -96,6 +96,7 @@ def lib():
         L.tnml_set_svd_stop.argtypes = [vp, C.c_double]
         L.tnml_set_narrow_path.argtypes = [vp, C.c_int]
         L.tnml_set_chain_path.argtypes = [vp, C.c_int]
+        L.tnml_set_any_position.argtypes = [vp, C.c_int]
         L.tnml_marker.argtypes = [vp, C.c_int]
         L.tnml_set_comm_overlap.argtypes = [vp, C.c_int]
         L.tnml_set_flag_handoffs.argtypes = [vp, C.c_int]
@@ -442,6 +443,11 @@ class Context:
     def set_chain_path(self, force_plain):
         """Forward chain as plain FMAs (True) instead of the matrix-core kernel (tests, diagnostics)."""
         _chk(lib().tnml_set_chain_path(self._h, int(bool(force_plain))))
+
+    def set_any_position(self, on=True):
+        """True: forward / predict / predict_indices / eval_indices also run with the label at an intermediate site, and a
+        forward there lets one sweep call start a segment in either direction (include/tnml.h); False (default): ends only."""
+        _chk(lib().tnml_set_any_position(self._h, int(bool(on))))
 
     def set_narrow_path(self, force_large):
         """True: every step takes the large-tensor (HBM-resident) path; False: automatic."""

@@ -183,9 +183,23 @@ static void check_chain(const ChainSite *sites, int n, const float *cores, const
     need((c.is_label ? lab : cores) + c.core_off, ext * 4, "chain core");
     need(X + (size_t)c.x_site * b_pad * kD, (size_t)b_pad * kD * 4, "chain features");
     if (c.env_out_off >= 0) { if (env) need(env + c.env_out_off, (size_t)c.n_out * b_pad * 4, "chain environment slot"); }
-    else need(f, (size_t)L * b_pad * 4, "chain f");
+    else need(f, (size_t)(c.is_label ? L : c.n_out) * b_pad * 4, c.is_label ? "chain f" : "chain: last environment of a half-chain");
     if (i + 1 < n && sites[i + 1].n_in != c.n_out) die("chain: site %d produces %d, site %d takes %d", i, c.n_out, i + 1, sites[i + 1].n_in);
   }
+}
+
+// the label site between two environments (kernels_meet.hip): every operand with the extent the kernel touches
+static void check_meet(const MeetParams &p, dim3 g, dim3 b, size_t shm) {
+  scan(&p, sizeof p, "MeetParams");
+  if (p.b < 1 || p.b > p.b_pad || p.b_pad % 64) die("MeetParams: b %d b_pad %d", p.b, p.b_pad);
+  if (p.D < 2 || p.D > kMaxD || p.L < 1 || p.ml < 1 || p.mr < 1) die("MeetParams: D %d L %d ml %d mr %d", p.D, p.L, p.ml, p.mr);
+  if (b.x != 64 || (size_t)g.x * 64 != (size_t)p.b_pad) die("label_meet_kernel: grid %u x %u lanes != b_pad %d", g.x, b.x, p.b_pad);
+  if (p.rows_per_chunk < 1 || p.rows_per_chunk > p.ml) die("MeetParams.rows_per_chunk %d for %d rows", p.rows_per_chunk, p.ml);
+  const size_t bp = p.b_pad;
+  if (shm < ((size_t)p.mr * 64 + (size_t)p.rows_per_chunk * p.D * p.mr * p.L) * 4) die("label_meet_kernel: %zu bytes of LDS for %d rows of %d x %d x %d and a tile of %d", shm, p.rows_per_chunk, p.D, p.mr, p.L, p.mr);
+  need(p.Lenv, (size_t)p.ml * bp * 4, "MeetParams.Lenv"); need(p.Renv, (size_t)p.mr * bp * 4, "MeetParams.Renv");
+  need(p.x, bp * p.D * 4, "MeetParams.x"); need(p.core, (size_t)p.ml * p.D * p.mr * p.L * 4, "MeetParams.core");
+  need(p.f, (size_t)p.L * bp * 4, "MeetParams.f");
 }
 
 // ---- call trace ----------------------------------------------------------------------------------------------------------------
@@ -242,6 +256,7 @@ static void tr_struct(const PersistHelperParams &p) {
 }
 static void tr_struct(const PersistStep &p) { tr(" n:"); tr_struct(p.n); tr(" w:"); tr_struct(p.w); tr(" t:"); tr_struct(p.t); }
 static void tr_struct(const PrepParams &p) { V(lab) V(pl) P(Nh) P(Ng) I(h) I(g) I(s) I(L) I(l2_flag) P(prepB) P(prepG) I(nparts) }
+static void tr_struct(const MeetParams &p) { P(Lenv) P(Renv) P(x) P(core) P(f) I(b) I(b_pad) I(ml) I(mr) I(D) I(L) I(rows_per_chunk) }
 static void tr_struct(const BigExtArgs &p) { P(Eprev) P(x_km1) P(x_k) V(A) I(b_pad) P(Ecur) P(Pk) }
 static void tr_struct(const ChainSite &p) { I(core_off) I(is_label) I(n_in) I(n_out) I(s_in) I(s_d) I(s_out) I(x_site) I(env_out_off) }
 static void tr_struct(const NormChainSite &p) { I(core_off) I(n_in) I(n_out) I(s_in) I(s_d) I(s_out) I(env_out_off) }
@@ -271,6 +286,7 @@ static void tr_launch(const std::string &name, dim3 g, dim3 b, size_t shm, hipSt
     else if (is("WidePipeParams")) tr_struct(*(const WidePipeParams *)args[i]);
     else if (is("WideParams")) tr_struct(*(const WideParams *)args[i]);
     else if (is("PrepParams")) tr_struct(*(const PrepParams *)args[i]);
+    else if (is("MeetParams")) tr_struct(*(const MeetParams *)args[i]);
     else if (is("BigExtArgs")) tr_struct(*(const BigExtArgs *)args[i]);
     else if (is("CoreView")) { const CoreView &v = *(const CoreView *)args[i]; tr(" [%s %d %d %d %d %d]", dp(v.base).c_str(), v.n_in, v.n_out, v.s_in, v.s_d, v.s_out); }
     else if (is("BigFrontTiles")) tr(" %d %d", ((int *)args[i])[0], ((int *)args[i])[1]);
@@ -335,6 +351,8 @@ hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t s
     if (n.bsize > 0) check_narrow(n);    // (a prologue launch carries no update)
     check_pipe(w);
     if (g.x > 256) die("step_pipe_kernel: %u workgroups cannot be co-resident on 256 CUs", g.x);
+  } else if (has("label_meet_kernel")) {
+    check_meet(*(const MeetParams *)args[0], g, b, shm);
   } else if (has("narrow_step_kernel")) {
     check_narrow(*(const NarrowParams *)args[0]);
   } else if (has("wide_step") || has("f_only_kernel")) {

@@ -128,6 +128,10 @@ struct tnml_ctx {
   bool big_ready = false;
   bool force_big = false;                    // tnml_set_narrow_path
   bool chain_plain = false;                  // tnml_set_chain_path
+  bool any_pos = false;                      // tnml_set_any_position
+  bool seg_starting = false;                 // the sweep call in flight starts a segment and has not planned its first step yet
+  float *predEnv = nullptr;                  // prediction at an intermediate label site: [2][Mmax][predenv_cap], the two environments next to it
+  int predenv_cap = 0;
   float *prepB = nullptr;                    // fused narrow launch: merged tensor / L2 term from the helper workgroups
   double *prepG = nullptr;
   unsigned *sync = nullptr;
@@ -336,7 +340,7 @@ extern "C" int tnml_destroy(tnml_ctx *c) {
   if (c->comm) ncclCommDestroy(c->comm);
   void *ptrs[] = {c->X, c->Xstage, c->y, c->f, c->ftmp, c->ftmp2, c->Lenv, c->Renv, c->cores, c->lab[0], c->lab[1],
                   c->Ln, c->Rn, c->Bnew, c->slabs, c->red, c->metrics, c->scal, c->dbg, c->status, c->tables, c->counters, c->Bscr, c->Bscr2,
-                  c->Xpred_stage, c->Xpred, c->fpred, c->prepB, c->prepG, c->sync, c->zslabs, c->gslabs, c->zred, c->pipe_cnt, c->big.Bf, c->big.T, c->big.part, c->big.gram, c->big.rotlog, c->big.lam, c->big.info, c->big.VW, c->big.Cb, c->big.T2, c->big.prog, c->bigflags, c->splitflags};
+                  c->Xpred_stage, c->Xpred, c->fpred, c->predEnv, c->prepB, c->prepG, c->sync, c->zslabs, c->gslabs, c->zred, c->pipe_cnt, c->big.Bf, c->big.T, c->big.part, c->big.gram, c->big.rotlog, c->big.lam, c->big.info, c->big.VW, c->big.Cb, c->big.T2, c->big.prog, c->bigflags, c->splitflags};
   for (void *p : ptrs) if (p) (void)hipFree(p);
   void *pptrs[] = {c->zred2, c->Tbuf[0], c->Tbuf[1], c->TNbuf[0], c->TNbuf[1], c->prepRaw, c->Apub, c->pst_dev, c->pst_cnt, c->pst_flags,
                    c->anyd_W, c->anyd_T2};
@@ -421,6 +425,7 @@ extern "C" int tnml_comm_init(tnml_ctx *c, int rank, int nranks, const void *uid
   if (!c || !uid128) return fail(TNML_ERR_ARG, "NULL argument");
   if (nranks < 1 || rank < 0 || rank >= nranks) return fail(TNML_ERR_ARG, "bad rank %d / %d", rank, nranks);
   if (c->D != kD) return fail(TNML_ERR_STATE, "multi-GPU runs are D == %d only (this context has D = %d)", kD, c->D);
+  if (c->any_pos) return fail(TNML_ERR_STATE, "sharded batches with the label at an intermediate site are not supported: tnml_set_any_position(ctx, 0) first");
   HIP_TRY(hipSetDevice(c->device));
   c->rank = rank;
   c->nranks = nranks;
@@ -674,11 +679,99 @@ static int upload_chain_table(tnml_ctx *c) {
   return TNML_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Label at an intermediate site (tnml_set_any_position): two half-chains that start at the chain ends and
+// stop next to the label site -- the chain kernels with a table that has no label entry -- and the contraction of the label core
+// with the environment on either side of it (kernels_meet.hip).
+// ---------------------------------------------------------------------------------------------
+static bool label_inside(const tnml_ctx *c) { return c->l_pos != 0 && c->l_pos != c->N - 1; }
+
+// sites 0 .. l-1 (left environments) followed by sites N-1 .. l+1 (right environments) in the context's table scratch.  keep:
+// every environment goes to its slot of the stack the launch is given; otherwise only the last one of either half is stored, as
+// the named output of its chain (the slot of the table entry that would carry the label site: env_out_off = -1)
+static int upload_half_tables(tnml_ctx *c, bool keep) {
+  const int N = c->N, D = c->D, l = c->l_pos;
+  std::vector<ChainSite> tab;
+  tab.reserve(N - 1);
+  for (int i = 0; i < l; ++i) {
+    ChainSite cs{};
+    const int ml = c->ml(i), mr = c->mr(i);
+    cs.x_site = i; cs.core_off = (int)((size_t)i * c->core_stride);
+    cs.n_in = ml; cs.n_out = mr; cs.s_in = D * mr; cs.s_d = mr; cs.s_out = 1;
+    cs.env_out_off = keep ? c->env_off(i) : (i == l - 1 ? -1 : 0);
+    tab.push_back(cs);
+  }
+  for (int i = N - 1; i > l; --i) {
+    ChainSite cs{};
+    const int ml = c->ml(i), mr = c->mr(i);
+    cs.x_site = i; cs.core_off = (int)((size_t)i * c->core_stride);
+    cs.n_in = mr; cs.n_out = ml; cs.s_in = 1; cs.s_d = mr; cs.s_out = D * mr;
+    cs.env_out_off = keep ? c->env_off(i) : (i == l + 1 ? -1 : 0);
+    tab.push_back(cs);
+  }
+  HIP_TRY(hipMemcpyAsync(c->tables, tab.data(), tab.size() * sizeof(ChainSite), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));   // tab is a stack object
+  return TNML_OK;
+}
+
+// one half-chain of the uploaded pair: `env` the stack it fills (keep) or nullptr, `last` the buffer of its last environment otherwise
+static int half_chain(tnml_ctx *c, bool right_half, const float *X, float *env, float *last, int b, int b_pad) {
+  const int l = c->l_pos, n = right_half ? c->N - 1 - l : l;
+  const ChainSite *tab = (const ChainSite *)c->tables + (right_half ? l : 0);
+  if (c->D != kD) {
+    if (!launch_env_chain_anyd(tab, n, c->cores, c->lab[c->lab_cur], X, env, last, b, b_pad, c->L, c->Mmax, c->D, nullptr, c->stream))
+      return fail(TNML_ERR_ARG, "forward chain at D = %d, M = %d: %zu bytes of LDS exceed 160 KB", c->D, c->Mmax, anyd_chain_lds_bytes(c->Mmax, c->D, c->L));
+  } else
+  launch_env_chain(tab, n, c->cores, c->lab[c->lab_cur], X, env, last, b, b_pad, c->L, c->Mmax, nullptr, c->stream, c->chain_plain);
+  HIP_TRY(hipGetLastError());
+  return TNML_OK;
+}
+
+static int label_meet(tnml_ctx *c, const float *Lenv, const float *Renv, const float *X, float *f, int b, int b_pad) {
+  MeetParams m{};
+  const int l = c->l_pos;
+  m.Lenv = Lenv; m.Renv = Renv; m.x = X + (size_t)l * b_pad * c->D; m.core = c->lab[c->lab_cur]; m.f = f;
+  m.b = b; m.b_pad = b_pad; m.ml = c->ml(l); m.mr = c->mr(l); m.D = c->D; m.L = c->L;
+  if (!launch_label_meet(m, c->stream))
+    return fail(TNML_ERR_ARG, "label site %d: one row of its core (%d x %d x %d floats) and the environment tile do not fit 160 KB of LDS", l, c->D, m.mr, c->L);
+  HIP_TRY(hipGetLastError());
+  return TNML_OK;
+}
+
+// tnml_forward with the label inside the chain: both stacks up to the label site, f from their meeting
+static int run_chain_inside(tnml_ctx *c) {
+  HIP_TRY(hipSetDevice(c->device));
+  const int N = c->N, l = c->l_pos;
+  int rc = upload_half_tables(c, true);
+  if (rc) return rc;
+  if (c->profile) HIP_TRY(hipEventRecord(c->pev0, c->stream));
+  if ((rc = half_chain(c, false, c->X, c->Lenv, c->f, c->b, c->b_pad))) return rc;
+  if ((rc = half_chain(c, true, c->X, c->Renv, c->f, c->b, c->b_pad))) return rc;
+  if ((rc = label_meet(c, c->env_slot(c->Lenv, l - 1), c->env_slot(c->Renv, l + 1), c->X, c->f, c->b, c->b_pad))) return rc;
+  if (c->profile) {
+    HIP_TRY(hipEventRecord(c->pev1, c->stream));
+    HIP_TRY(hipEventSynchronize(c->pev1));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, c->pev0, c->pev1));
+    c->prof_ms[0] += ms; c->prof_n[0]++;
+  }
+  c->cnt_fwd += 1;
+  for (int i = 0; i < N - 1; ++i) c->cnt_fwd_bytes += 4.0 * c->b * (2.0 * c->bond[i] + c->D);
+  c->envs_valid_L = c->envs_valid_R = true;
+  c->f_current = true;
+  c->Bnew_valid = false;
+  c->Z_valid = false; c->Zbig_valid = false;
+  return TNML_OK;
+}
+
 static int run_chain(tnml_ctx *c, bool logmode) {
   if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
   if (!c->have_input) return fail(TNML_ERR_STATE, "no input batch: call tnml_set_input first");
-  if (c->l_pos != 0 && c->l_pos != c->N - 1)
-    return fail(TNML_ERR_STATE, "forward should not be called if l has an intermediate position (l_pos = %d)", c->l_pos);
+  if (label_inside(c)) {
+    if (!c->any_pos || logmode)
+      return fail(TNML_ERR_STATE, "forward should not be called if l has an intermediate position (l_pos = %d)", c->l_pos);
+    return run_chain_inside(c);
+  }
   HIP_TRY(hipSetDevice(c->device));
   const int N = c->N, D = c->D, L = c->L;
   const bool right_envs = (c->l_pos == 0);
@@ -739,9 +832,38 @@ static int pred_ensure_buffers(tnml_ctx *c, int bp) {
   return TNML_OK;
 }
 
+// may a prediction run at this label position?
+static int pred_allowed(tnml_ctx *c) {
+  if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
+  if (label_inside(c) && !c->any_pos)
+    return fail(TNML_ERR_STATE, "forward should not be called if l has an intermediate position (l_pos = %d)", c->l_pos);
+  return TNML_OK;
+}
+
+// the chain table of a prediction (the prediction buffers exist): towards the label site, or the two half-chains and the buffers
+// of the two environments they leave
+static int pred_table(tnml_ctx *c) {
+  if (!label_inside(c)) return upload_chain_table(c);
+  if (c->predenv_cap < c->pred_cap) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->predEnv) (void)hipFree(c->predEnv);
+    c->predEnv = nullptr; c->predenv_cap = 0;
+    HIP_TRY(hipMalloc(&c->predEnv, (size_t)2 * c->Mmax * c->pred_cap * sizeof(float)));
+    c->predenv_cap = c->pred_cap;
+  }
+  return upload_half_tables(c, false);
+}
+
 // one chain towards the label site over Xpred -> fpred, no environment stored (the chain table must be uploaded)
 static int pred_chain(tnml_ctx *c, int b) {
   const int N = c->N, D = c->D, L = c->L, bpad = c->pred_cap;
+  if (label_inside(c)) {                      // (pred_table allocated the two environment buffers)
+    float *EL = c->predEnv, *ER = c->predEnv + (size_t)c->Mmax * c->predenv_cap;
+    int rc = half_chain(c, false, c->Xpred, nullptr, EL, b, bpad);
+    if (!rc) rc = half_chain(c, true, c->Xpred, nullptr, ER, b, bpad);
+    if (!rc) rc = label_meet(c, EL, ER, c->Xpred, c->fpred, b, bpad);
+    return rc;
+  }
   if (D != kD) {
     if (!launch_env_chain_anyd((const ChainSite *)c->tables, N, c->cores, c->lab[c->lab_cur], c->Xpred, nullptr, c->fpred, b, bpad, L,
                                c->Mmax, D, nullptr, c->stream))
@@ -759,18 +881,17 @@ extern "C" int tnml_predict(tnml_ctx *c, const float *X, int b, float *f_out) {
   // stay as they are.
   if (!c || !X || !f_out) return fail(TNML_ERR_ARG, "NULL argument");
   if (b < 1) return fail(TNML_ERR_ARG, "empty batch");
-  if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
-  if (c->l_pos != 0 && c->l_pos != c->N - 1)
-    return fail(TNML_ERR_STATE, "forward should not be called if l has an intermediate position (l_pos = %d)", c->l_pos);
+  int rc = pred_allowed(c);
+  if (rc) return rc;
   HIP_TRY(hipSetDevice(c->device));
   const int N = c->N, D = c->D, L = c->L;
-  int rc = pred_ensure_buffers(c, (b + 63) / 64 * 64);
+  rc = pred_ensure_buffers(c, (b + 63) / 64 * 64);
   if (rc) return rc;
   const int bpad = c->pred_cap;
   HIP_TRY(hipMemcpyAsync(c->Xpred_stage, X, (size_t)b * N * D * sizeof(float), hipMemcpyHostToDevice, c->stream));
   if (D != kD) launch_transpose_input_anyd(c->Xpred_stage, c->Xpred, b, bpad, N, D, c->stream);
   else launch_transpose_input(c->Xpred_stage, c->Xpred, b, bpad, N, c->stream);
-  rc = upload_chain_table(c);
+  rc = pred_table(c);
   if (rc) return rc;
   if ((rc = pred_chain(c, b))) return rc;
   HIP_TRY(hipMemcpy2DAsync(f_out, (size_t)b * sizeof(float), c->fpred, (size_t)bpad * sizeof(float), (size_t)b * sizeof(float),
@@ -994,12 +1115,7 @@ static int ds_ensure_metrics(tnml_ctx *c, int b_pad) {
   return TNML_OK;
 }
 
-static int ds_forward_allowed(tnml_ctx *c) {
-  if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
-  if (c->l_pos != 0 && c->l_pos != c->N - 1)
-    return fail(TNML_ERR_STATE, "forward should not be called if l has an intermediate position (l_pos = %d)", c->l_pos);
-  return TNML_OK;
-}
+static int ds_forward_allowed(tnml_ctx *c) { return pred_allowed(c); }
 
 extern "C" int tnml_predict_indices(tnml_ctx *c, const int32_t *idx, int b, float *f_out) {
   int rc = ds_usable(c);
@@ -1012,7 +1128,7 @@ extern "C" int tnml_predict_indices(tnml_ctx *c, const int32_t *idx, int b, floa
   if ((rc = ds_ensure_pred(c, (b + 63) / 64 * 64))) return rc;
   const int bpad = c->pred_cap;
   if ((rc = ds_gather(c, c->ds_idx, b, bpad, c->Xpred, nullptr))) return rc;
-  if ((rc = upload_chain_table(c))) return rc;
+  if ((rc = pred_table(c))) return rc;
   if ((rc = pred_chain(c, b))) return rc;
   HIP_TRY(hipMemcpy2DAsync(f_out, (size_t)b * sizeof(float), c->fpred, (size_t)bpad * sizeof(float), (size_t)b * sizeof(float),
                            c->L, hipMemcpyDeviceToHost, c->stream));
@@ -1044,7 +1160,7 @@ extern "C" int tnml_eval_indices(tnml_ctx *c, const int32_t *idx, int b, int act
   const int bpad = c->pred_cap;
   const int chunk = bpad >= kDsMetricThreads ? bpad / kDsMetricThreads * kDsMetricThreads : bpad;
   if ((rc = ds_ensure_metrics(c, bpad))) return rc;
-  if ((rc = upload_chain_table(c))) return rc;
+  if ((rc = pred_table(c))) return rc;
   for (int off = 0; off < b; off += chunk) {
     const int bc = std::min(chunk, b - off);
     if ((rc = ds_gather(c, c->ds_idx + off, bc, bpad, c->Xpred, c->ds_ypred))) return rc;
@@ -1447,6 +1563,10 @@ static int finish_step(tnml_ctx *c, const StepGeom &q, int trunc_policy, int ste
     if (m_kept < 1 || m_kept > q.m) return fail(TNML_ERR_NONFINITE, "adaptive truncation returned rank %d (cap %d)", m_kept, q.m);
   }
   advance_frame(c, q, m_kept);
+  if (c->seg_starting) {                           // first step of a segment (tnml_set_any_position): the behind stack is no longer forward's
+    (q.left_dir ? c->envs_valid_R : c->envs_valid_L) = false;
+    c->seg_starting = false;
+  }
   c->cnt_steps += 1;
   add_step_work(c, q, c->cnt_bytes, c->cnt_flops);
   c->Bnew_valid = true;
@@ -1661,6 +1781,8 @@ static int sweep_anyd(tnml_ctx *c, int left_dir, int n_steps, float lr, float we
                       int trunc_policy, float *metrics_out, float *f_out, int mode, const float *Bdirect_dev, hipEvent_t sw_ev1);
 static int standalone_anyd(tnml_ctx *c, NarrowParams &n);
 
+static int norm_envs_for_label_site(tnml_ctx *c);
+
 static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep, float lr, float weight_dec,
                       int l2_flag, int act_fn, int loss_fn, float T, int trunc_policy, float *metrics_out,
                       float *f_out, int mode, const float *Bdirect_dev) {
@@ -1680,20 +1802,28 @@ static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep
   if (!(left_dir ? c->envs_valid_L : c->envs_valid_R))
     return fail(TNML_ERR_STATE, "the %s environments are not built for this batch: call tnml_forward at l_pos = %d first",
                 left_dir ? "left" : "right", left_dir ? N - 1 : 0);
+  // segment start (tnml_set_any_position): a forward with the label inside the chain built BOTH stacks and left f; nothing of a
+  // previous step (B_new, a pre-gradient) is valid, and either direction may follow
+  const bool seg_start = !first_of_sweep && c->any_pos && label_inside(c) && c->envs_valid_L && c->envs_valid_R && !c->Bnew_valid;
   if (first_of_sweep) {
     if ((left_dir && c->l_pos != N - 1) || (!left_dir && c->l_pos != 0))
       return fail(TNML_ERR_STATE, "first_of_sweep set but l_pos = %d", c->l_pos);
     c->Bnew_valid = false;
-  } else if (!c->Bnew_valid || c->prev_left_dir != left_dir) {
+  } else if (!seg_start && (!c->Bnew_valid || c->prev_left_dir != left_dir)) {
     return fail(TNML_ERR_STATE, "mid-sweep continuation without a preceding step in the same direction");
   }
   if (!c->f_current && !c->Bnew_valid) return fail(TNML_ERR_STATE, "no f to start from: call tnml_forward or tnml_set_f");
   if (n_steps > c->metrics_cap) return fail(TNML_ERR_ARG, "n_steps > N");
-  // norm environments towards which the sweep runs
+  // norm environments towards which the sweep runs (a segment start has no previous step that left the one behind it either: both
+  // stacks are built up to the label site, and finish_sweep marks the one behind invalid again when the segment stops mid-chain)
   if (l2_flag) {
+    if (seg_start) { int rc = norm_envs_for_label_site(c); if (rc) return rc; }
     if (!left_dir && !c->Rn_valid) { int rc = build_norm_chain(c, true); if (rc) return rc; c->Rn_valid = true; }
     if (left_dir && !c->Ln_valid) { int rc = build_norm_chain(c, false); if (rc) return rc; c->Ln_valid = true; }
   }
+  // the stack behind a segment is rewritten from its first step on: finish_step marks it invalid once that step is planned (the
+  // opposite direction then needs a forward again); a call that fails before it leaves both stacks as forward built them
+  c->seg_starting = seg_start && mode == 0;
   const int nblk = c->b_pad / kTS;
   hipEvent_t sw_ev1 = nullptr;
   if (c->sweep_timing && mode == 0) {
@@ -1748,7 +1878,9 @@ static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep
     if (mode == 1) { n.Bnew = c->Bscr2; n.Nh_new = nullptr; }
     n.stamps = (c->debug || c->stamps) ? c->dbg + 4 * c->bmax + kDbgSigma + 5 : nullptr;
     // ---- pipelined step: ONE launch (update + SVD of step k next to the batch-side work of step k+1) ----------------
-    bool pipe = c->pipe_enabled && prep_ok;
+    // (the first step of a segment takes the classic sequence: its behind environment is extended again from the stack forward
+    //  built, its f is forward's; the pipelined step resumes with the second step, from its own prologue)
+    bool pipe = c->pipe_enabled && prep_ok && !(seg_start && step == 0);
     if (pipe && prep_slice_lds_bytes(h, g, s, L) > 160 * 1024) pipe = false;      // the slice workgroups of the launch must fit too
     WidePipeParams wp{}, wpro{};
     bool need_prologue = false;
@@ -2282,6 +2414,13 @@ extern "C" int tnml_set_flag_handoffs(tnml_ctx *c, int on) {
   if (c->stream2) HIP_TRY(hipStreamSynchronize(c->stream2));
   c->bigflags_enabled = on != 0; c->split_flags_enabled = on != 0;
   c->split_done_valid = false; c->split_zsig_valid = false;
+  return TNML_OK;
+}
+
+extern "C" int tnml_set_any_position(tnml_ctx *c, int on) {
+  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
+  if (c->comm) return fail(TNML_ERR_STATE, "sharded batches with the label at an intermediate site are not supported");
+  c->any_pos = on != 0;
   return TNML_OK;
 }
 

@@ -164,6 +164,19 @@ void launch_env_chain(const ChainSite *sites_dev, int n_sites, const float *core
                       const float *X, float *env_base, float *f, int b, int b_pad, int L, int Mmax,
                       float *logmax_out, hipStream_t st, bool force_plain = false);
 constexpr int kChainSamplesPerBlock = 16;
+// The label site between two environments (kernels_meet.hip): f[l][s] = sum_{a,d,c} Lenv[a][s] x[s][d] core[a][d][c][l] Renv[c][s]
+struct MeetParams {
+  const float *Lenv, *Renv;   // [ml][b_pad], [mr][b_pad]
+  const float *x;             // [b_pad][D] features of the label site
+  const float *core;          // [ml][D][mr][L]
+  float *f;                   // [L][b_pad]; samples b .. b_pad-1 receive 0
+  int b, b_pad, ml, mr, D, L;
+  int rows_per_chunk;         // a-rows of the core staged in LDS at a time; <= 0: as many as fit (label_meet_chunk_rows)
+};
+int label_meet_chunk_rows(int ml, int mr, int D, int L);
+size_t label_meet_lds_bytes(int rows_per_chunk, int mr, int D, int L);
+// false: refused (geometry, or not even one a-row of the core fits in LDS)
+bool launch_label_meet(MeetParams p, hipStream_t st);
 // slice-wise pre-computation of the merged tensor and its L2 term (small_gemm_device.h: prep_slice_block)
 struct PrepParams {
   CoreView lab, pl;        // as NarrowParams

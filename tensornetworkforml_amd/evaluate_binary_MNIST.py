@@ -33,6 +33,7 @@ def main(argv=None):
 
     with open(args.filename, 'rb') as fh:
         net = pickle.load(fh)
+    net.any_position = True        # a model saved mid-sweep carries its label inside the chain
     _, _, data, labels = gen.get_MNIST_dataset(args.data_dir)
     while data[0].size > net.N and min(data.shape[1:]) >= 2:
         data = pooling(data)

@@ -30,6 +30,7 @@ def main(argv=None):
 
     with open(args.filename, 'rb') as fh:
         net = pickle.load(fh)
+    net.any_position = True        # a model saved mid-sweep carries its label inside the chain
     linear_dim = int(round(np.sqrt(net.N)))
     if linear_dim * linear_dim != net.N:
         raise SystemExit('the network has N = %d sites, which is not a square image' % net.N)

@@ -40,8 +40,12 @@ def main(argv=None):
     ap.add_argument('--D', type=int, default=2, help='Local feature dimension (components of the feature map)')
     ap.add_argument('--resident', action='store_true',
                     help='upload the data set once and train from index batches formed on the device (Network.train_resident)')
+    ap.add_argument('--steps-per-batch', dest='steps_per_batch', type=int, default=None, metavar='K',
+                    help='change the batch every K sweep steps instead of every sweep (needs --resident)')
     ap.add_argument('--out', type=str, default='trained_MNIST_model.dat')
     args = ap.parse_args(argv)
+    if args.steps_per_batch is not None and not args.resident:
+        ap.error('--steps-per-batch needs --resident')
 
     train_data, train_labels, test_data, test_labels = gen.get_MNIST_dataset(args.data_dir)
     data = pooling(np.concatenate((train_data, test_data)))
@@ -63,7 +67,8 @@ def main(argv=None):
                      loss_fn=args.loss_fn, trunc=args.trunc)
     if args.resident:
         _, train_idx, val_idx, _ = gen.prepare_device_dataset(net, data01, labels01, 1, 0.2, train_batch, 128, 128, D=args.D)
-        val_acc, var_hist = net.train_resident(train_idx, val_idx, lr=args.lr, n_epochs=args.n_epochs, weight_dec=args.L2_decay)
+        val_acc, var_hist = net.train_resident(train_idx, val_idx, lr=args.lr, n_epochs=args.n_epochs, weight_dec=args.L2_decay,
+                                               steps_per_batch=args.steps_per_batch)
     else:
         val_acc, var_hist = net.train(train_loader, val_loader, lr=args.lr, n_epochs=args.n_epochs,
                                       weight_dec=args.L2_decay)

@@ -35,8 +35,12 @@ def main(argv=None):
     ap.add_argument('--D', type=int, default=2, help='Local feature dimension (components of the feature map)')
     ap.add_argument('--resident', action='store_true',
                     help='upload the data set once and train from index batches formed on the device (Network.train_resident)')
+    ap.add_argument('--steps-per-batch', dest='steps_per_batch', type=int, default=None, metavar='K',
+                    help='change the batch every K sweep steps instead of every sweep (needs --resident)')
     ap.add_argument('--out', type=str, default='trained_diag_model.dat')
     args = ap.parse_args(argv)
+    if args.steps_per_batch is not None and not args.resident:
+        ap.error('--steps-per-batch needs --resident')
 
     train_batch = int(args.n_samples * 0.8 / args.n_train_batch)
     data, label = gen.create_dataset(args.n_samples, args.linear_dim, args.sigma)
@@ -52,7 +56,8 @@ def main(argv=None):
                      act_fn=args.act_fn, loss_fn=args.loss_fn, trunc=args.trunc)
     if args.resident:
         _, train_idx, val_idx, _ = gen.prepare_device_dataset(net, data, label, 1, 0.2, train_batch, 128, 128, D=args.D)
-        val_acc, var_hist = net.train_resident(train_idx, val_idx, lr=args.lr, n_epochs=args.n_epochs, weight_dec=args.L2_decay)
+        val_acc, var_hist = net.train_resident(train_idx, val_idx, lr=args.lr, n_epochs=args.n_epochs, weight_dec=args.L2_decay,
+                                               steps_per_batch=args.steps_per_batch)
     else:
         val_acc, var_hist = net.train(train_loader, val_loader, lr=args.lr, n_epochs=args.n_epochs,
                                       weight_dec=args.L2_decay)
@@ -67,10 +72,11 @@ def main(argv=None):
         print('(matplotlib not installed: curves not drawn)')
         return val_acc, var_hist
     os.makedirs('results', exist_ok=True)
-    xs = np.arange(args.n_epochs * var_hist.shape[2]) / var_hist.shape[2]
+    # (with --steps-per-batch the epochs may differ in their number of steps: var_hist is then a list of one array per epoch)
+    xs = np.concatenate([e + np.arange(v.shape[1]) / v.shape[1] for e, v in enumerate(var_hist)])
     for row, name, ylabel in ((0, 'accuracy', 'Accuracy'), (1, 'MAE', '| f(x) - y |')):
         plt.figure()
-        plt.plot(xs, var_hist[:, row].reshape(-1), label='Train ' + name)
+        plt.plot(xs, np.concatenate([v[row] for v in var_hist]), label='Train ' + name)
         if row == 0:
             plt.plot(np.arange(1, args.n_epochs + 1), val_acc, 'ro', label='Validation acc')
         plt.xlabel('Epoch'); plt.ylabel(ylabel); plt.legend()

@@ -13,6 +13,16 @@ nothing waits inside the timed region).  Then `Network.evaluate` over all 25000 
 parent offers for it (`predict` + host argmax per batch of 5000).  One JSON line per measurement on stdout and, with --out, in a file.
 
     python tools/bench_train_epoch.py --out profiles/r05_bench_train_epoch.json
+
+--steps-per-batch K[,K...] measures `train_resident(steps_per_batch=K)` instead, at the headline shape: one context
+with the default schedule (a batch per sweep, four batches) and one per K, each on its own copy of the network and the uploaded
+dataset, timed in ALTERNATING single-epoch calls.  An epoch of the K schedule draws as many batches of 5000 as bring it to the default
+epoch's 4 (N-1) steps (4 at K = 783, 32 at K = 98, 112 at K = 28); segments that end at a chain end are short, so the steps actually
+run are reported and the time per step beside the epoch time.  Such an epoch draws its batches from several permutations of the
+training samples (`DrawLoader`): it sees a sample more than once.  The default schedule runs in the same build (its launches are the
+parent commit's: the call traces of the stand-in runtime are identical).
+
+    python tools/bench_train_epoch.py --steps-per-batch 783,98,28 --out profiles/r07_bench_steps_per_batch.json
 """
 import argparse
 import contextlib
@@ -126,6 +136,78 @@ def run_shape(name, n_epochs, emit):
     return out
 
 
+class DrawLoader:
+    """n_batches index batches of batch_size per pass, drawn from `indices` pass after pass of np.random.permutation (an IndexLoader
+    that does not stop after one pass over the samples)."""
+
+    def __init__(self, indices, batch_size, n_batches):
+        self.indices, self.batch_size, self.n_batches = np.asarray(indices), int(batch_size), int(n_batches)
+
+    def __len__(self):
+        return self.n_batches
+
+    def __iter__(self):
+        per = len(self.indices) // self.batch_size
+        order = None
+        for k in range(self.n_batches):
+            if k % per == 0:
+                order = self.indices[np.random.permutation(len(self.indices))]
+            yield order[(k % per) * self.batch_size:(k % per + 1) * self.batch_size]
+
+
+def run_steps_per_batch(ks, n_epochs, emit):
+    """The default schedule and train_resident(steps_per_batch=K) for every K, in alternating single-epoch calls."""
+    name = 'headline'
+    N, M, trunc, tb, n_train, vb, n_val = SHAPES[name]
+    n = n_train + n_val
+    pix, label = synth_pixels(n, N, 7)
+    sizes = dict(train_batch_size=tb, val_batch_size=vb, test_batch_size=vb)
+    val_perc = n_val / n
+    np.random.seed(0)
+    tr, va, _ = gen.split_indices(n, 1, val_perc)
+    x_cal = gen.psi(pix[:512], 2)
+    with quiet():
+        net0 = tn.Network(N=N, M=M, D=2, L=2, calibration_X=x_cal, normalize=True, act_fn='softmax', loss_fn='full_cross_ent', trunc=trunc)
+    blob = pickle.dumps(net0)
+    del net0
+    runs = []
+    for k in [None] + list(ks):
+        net = pickle.loads(blob)
+        with quiet():
+            _, tr_idx, va_idx, _ = gen.prepare_device_dataset(net, pix, label, 1, val_perc, D=2, pixels=True, **sizes)
+        if k is not None:
+            tr_idx = DrawLoader(tr, tb, max(len(tr_idx), int(round(len(tr_idx) * (N - 1) / k))))
+        net._ctx.profile_enable(2)
+        runs.append(dict(k=k, net=net, tr=tr_idx, va=va_idx, wall=[], dev=[], steps=[]))
+    for ep in range(n_epochs + 1):
+        for r in runs:                                 # alternating: one epoch of every schedule per round
+            net, ctx = r['net'], r['net']._ctx
+            np.random.seed(1000 + ep)
+            ctx.synchronize()
+            ctx.profile_reset()
+            t0 = time.perf_counter()
+            with quiet():
+                if r['k'] is None:
+                    net.train_resident(r['tr'], r['va'], n_epochs=1, **HP)
+                else:
+                    net.train_resident(r['tr'], r['va'], n_epochs=1, steps_per_batch=r['k'], **HP)
+            ctx.synchronize()
+            r['wall'].append(time.perf_counter() - t0)
+            r['dev'].append(ctx.profile_get(4)[0])
+            r['steps'].append(int(ctx.counters()['sweep_steps']))
+    out = {}
+    for r in runs:
+        wall, dev, steps = r['wall'][1:], r['dev'][1:], r['steps'][1:]
+        path = 'default' if r['k'] is None else 'steps_per_batch_%d' % r['k']
+        rec = summary(name, path, wall, dev, dict(N=N, bond=M, trunc=trunc, train_batch=tb, train_batches=len(r['tr']), val_batch=vb,
+                                                  val_batches=len(r['va']), steps_per_batch=r['k'], sweep_steps=steps,
+                                                  us_per_step_median=float(np.median(1e6 * np.array(wall) / np.array(steps)))))
+        rec['bench'] = 'train_epoch_steps_per_batch'
+        out[path] = rec
+        emit(rec)
+    return {name: out}
+
+
 def bench_evaluate(net, pix, label, emit, chunk=5000, reps=5):
     """Network.evaluate over every sample of the attached dataset against predict + host argmax per batch of `chunk`."""
     n = len(pix)
@@ -151,6 +233,8 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--epochs', type=int, default=4, help='timed epochs per path after the discarded first one (>= 3)')
     ap.add_argument('--shapes', default='headline,binary_mnist')
+    ap.add_argument('--steps-per-batch', dest='steps_per_batch', default=None, metavar='K[,K...]',
+                    help='measure train_resident(steps_per_batch=K) against the default schedule at the headline shape instead')
     ap.add_argument('--out', default=None, help='also write the JSON lines to this file')
     args = ap.parse_args(argv)
     assert args.epochs >= 3
@@ -160,7 +244,10 @@ def main(argv=None):
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
 
-    results = {s: run_shape(s, args.epochs, emit) for s in args.shapes.split(',')}
+    if args.steps_per_batch:
+        results = run_steps_per_batch([int(k) for k in args.steps_per_batch.split(',')], args.epochs, emit)
+    else:
+        results = {s: run_shape(s, args.epochs, emit) for s in args.shapes.split(',')}
     print('\n| shape | path | epoch median (s) | spread (s) | device busy in sweeps |')
     print('|---|---|---|---|---|')
     for s, paths in results.items():
