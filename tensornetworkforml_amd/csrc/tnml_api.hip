@@ -42,6 +42,38 @@ static int fail(int code, const char *fmt, ...) {
                                        ncclGetErrorString(r_), __FILE__, __LINE__);            \
   } while (0)
 
+static constexpr size_t kLdsMax = 160 * 1024;      // LDS of a workgroup on gfx950: what a launch may ask for
+
+// What one tnml_sweep call fixes for all its steps: the arguments of the call (mode 1: standalone update_B, Bdirect_dev: merged tensor
+// to use instead of the product of the two cores), whether it starts a segment, its sample tiles, its closing timing event.
+struct SweepCall {
+  int left_dir, n_steps;
+  float lr, weight_dec;
+  int l2_flag, act_fn, loss_fn;
+  float T;
+  int trunc_policy;
+  float *metrics_out, *f_out;
+  int mode;
+  const float *Bdirect_dev;
+  hipEvent_t sw_ev1;
+  bool seg_start;
+  int nblk;
+};
+
+// A reduced pre-gradient left in zred for the next step: the step (relative index k) of a sweep call with these arguments may start
+// from it.  rows / cols: its shape as a matrix, where the taker checks it (large-tensor pipeline).
+struct ZTicket {
+  bool valid = false;
+  int k = -1, left = 0, act = 0, loss = 0, rows = 0, cols = 0;
+  float T = 0.f;
+  bool matches(const SweepCall &s, int k_) const {
+    return valid && k == k_ && left == s.left_dir && act == s.act_fn && loss == s.loss_fn && T == s.T;
+  }
+  void leave(const SweepCall &s, int k_, bool valid_, int rows_ = 0, int cols_ = 0) {
+    valid = valid_; k = k_; left = s.left_dir; act = s.act_fn; loss = s.loss_fn; T = s.T; rows = rows_; cols = cols_;
+  }
+};
+
 struct tnml_ctx {
   int N = 0, D = 0, L = 0, Mmax = 0;   // Mmax = buffer capacity per bond
   int Mpol = 0;                         // the M of Network(N, M, ...): fixed-policy rank
@@ -54,30 +86,32 @@ struct tnml_ctx {
   int persist_mode = 1;                      // tnml_set_persistent: 0 per-step launches, 1 one kernel per sweep (default), 2 one kernel per role
   hipEvent_t ev_main = nullptr, ev_prep = nullptr;
   // communicator path of the pipelined step: update side on `stream`, batch side + all-reduce of the pre-gradient on `stream2`
-  // (ev_upd[i]: an update launch has ended; ev_bat[i]: a batch-side launch and the exchange behind it have ended)
-  hipEvent_t ev_upd[2] = {nullptr, nullptr}, ev_bat[2] = {nullptr, nullptr};
-  int split_upd = 0, split_bat = 0;          // index of the event recorded last
-  bool split_pending = false;                // stream2 holds batch-side work `stream` has not waited for yet
-  bool split_enabled = true;                 // tnml_set_comm_overlap
+  struct {
+    // (ev_upd[i]: an update launch has ended; ev_bat[i]: a batch-side launch and the exchange behind it have ended)
+    hipEvent_t ev_upd[2] = {nullptr, nullptr}, ev_bat[2] = {nullptr, nullptr};
+    int upd = 0, bat = 0;                    // index of the event recorded last
+    bool pending = false;                    // stream2 holds batch-side work `stream` has not waited for yet
+    bool enabled = true;                     // tnml_set_comm_overlap
+    // hand-offs without events, as in the large-tensor pipeline below: [0] "Z (all-reduced) is ready", [1] "update launch done"
+    unsigned *flags = nullptr;
+    unsigned zseq = 0, dseq = 0;
+    bool flags_enabled = true, done_valid = false, zsig_valid = false;
+  } split;
   // pipelined large-tensor step (kernels_big.hip): the batch kernel of step k+1 runs on stream2 beside the SVD of step k and leaves
   // the reduced pre-gradient Z_{k+1} in zred; the step then starts with the contraction A_k^T . Z instead of the batch kernel
-  bool bigpipe_enabled = true;               // tnml_set_step_pipeline(ctx, 0) turns it off together with the in-LDS pipeline
-  bool Zbig_valid = false;
-  int Zbig_k = -1, Zbig_left = 0, Zbig_act = 0, Zbig_loss = 0, Zbig_rows = 0, Zbig_cols = 0;
-  float Zbig_T = 0.f;
-  float *bigPk = nullptr;                    // [D * Mmax][b_pad]  E_k (x) x_k, the row operand of Z_{k+1}
-  hipEvent_t ev_upd_big = nullptr, ev_zbig = nullptr;
-  bool zbig_pending = false;                 // stream2 holds batch work of the pipelined large-tensor step the context's stream has not joined
-  // hand-offs of that pipeline without events (kernels_big.hip, big_signal_kernel): [0] "Z of the next step is ready" (side stream ->
-  // context's stream), [1] "B_new is ready" (context's stream -> side stream); sequence numbers
-  unsigned *bigflags = nullptr;
-  unsigned zsig_seq = 0, bsig_seq = 0;
-  bool bigflags_enabled = true;
-  bool ext_on_side = false;                  // the last environment extension of the pipeline ran on the side stream
-  // the same for the two-stream communicator path of the in-LDS step: [0] "Z (all-reduced) is ready", [1] "update launch done"
-  unsigned *splitflags = nullptr;
-  unsigned split_zseq = 0, split_dseq = 0;
-  bool split_flags_enabled = true, split_done_valid = false, split_zsig_valid = false;
+  struct {
+    bool enabled = true;                     // tnml_set_step_pipeline(ctx, 0) turns it off together with the in-LDS pipeline
+    ZTicket Z;
+    float *Pk = nullptr;                     // [D * Mmax][b_pad]  E_k (x) x_k, the row operand of Z_{k+1}
+    hipEvent_t ev_upd = nullptr, ev_z = nullptr;
+    bool pending = false;                    // stream2 holds batch work of the pipelined large-tensor step the context's stream has not joined
+    // hand-offs of that pipeline without events (kernels_big.hip, big_signal_kernel): [0] "Z of the next step is ready" (side stream ->
+    // context's stream), [1] "B_new is ready" (context's stream -> side stream); sequence numbers
+    unsigned *flags = nullptr;
+    unsigned zsig_seq = 0, bsig_seq = 0;
+    bool flags_enabled = true;
+    bool ext_on_side = false;                // the last environment extension of the pipeline ran on the side stream
+  } bigpipe;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, pev0 = nullptr, pev1 = nullptr;
   // host bookkeeping
   std::vector<int> bond;
@@ -136,15 +170,16 @@ struct tnml_ctx {
   double *prepG = nullptr;
   unsigned *sync = nullptr;
   // pipelined step (wide_pipe_device.h): partial / group / reduced pre-gradients, arrival counters, B_new flag
-  bool pipe_enabled = true;                  // tnml_set_step_pipeline
-  int pipe_tiles = 2;                        // sample tiles per batch-side workgroup where the SVD is long enough to hide them
   float *zslabs = nullptr, *gslabs = nullptr, *zred = nullptr;
-  unsigned *pipe_cnt = nullptr;              // [0..15] group counters, [16] top counter, [17] flag
-  int zstride = 0, pipe_nwide = 0, pipe_tpw = 1, pipe_ngroups = 0;
-  bool Z_valid = false;                      // zred holds the pre-gradient of relative step Z_k of a sweep in direction Z_left
-  int Z_k = -1, Z_left = 0, Z_act = 0, Z_loss = 0;
-  float Z_T = 0.f;
-  unsigned token = 0;
+  int zstride = 0;
+  struct {
+    bool enabled = true;                     // tnml_set_step_pipeline
+    int tiles = 2;                           // sample tiles per batch-side workgroup where the SVD is long enough to hide them
+    unsigned *cnt = nullptr;                 // [0..15] group counters, [16] top counter, [17] flag
+    int nwide = 0, tpw = 1, ngroups = 0;
+    ZTicket Z;                               // zred holds the pre-gradient of relative step Z.k of a sweep in direction Z.left
+    unsigned token = 0;
+  } pipe;
   // persistent sweep (sweep_persist_kernel): per-step records (device + two pinned host staging buffers), second buffers of the
   // reduced pre-gradient, T_k buffers, per-step arrival counters, the flag words of the launch
   bool persist_enabled = true;               // tnml_set_persistent
@@ -192,6 +227,9 @@ struct tnml_ctx {
   double *norm_slot(double *base, int site) const { return base + (size_t)site * Mmax * Mmax; }
 };
 
+// no step may start from a pre-gradient left earlier (cores, batch, labels or the launch form changed)
+static void drop_pregradients(tnml_ctx *c) { c->pipe.Z.valid = false; c->bigpipe.Z.valid = false; }
+
 // ---------------------------------------------------------------------------------------------
 extern "C" const char *tnml_last_error(void) { return g_err.c_str(); }
 extern "C" const char *tnml_version(void) { return "tnml-hip 0.1 (gfx950)"; }
@@ -225,12 +263,12 @@ static int alloc_batch_buffers(tnml_ctx *c, int b_cap) {
   {   // batch-side workgroups of the pipelined step: at most kPipeMaxWide (from the device's CU count), each looping over pipe_tpw sample tiles
     const int kPipeMaxWide = std::max(16, c->num_cus - 16);      // + update workgroup and its helpers: all resident, one per CU
     const int ntiles = b_pad / kTS;
-    c->pipe_tpw = (ntiles + kPipeMaxWide - 1) / kPipeMaxWide;
-    c->pipe_nwide = (ntiles + c->pipe_tpw - 1) / c->pipe_tpw;
-    c->pipe_ngroups = (c->pipe_nwide + kPipeGroupMax - 1) / kPipeGroupMax;
-    HIP_TRY(hipMalloc(&c->zslabs, (size_t)c->pipe_nwide * c->zstride * sizeof(float)));
+    c->pipe.tpw = (ntiles + kPipeMaxWide - 1) / kPipeMaxWide;
+    c->pipe.nwide = (ntiles + c->pipe.tpw - 1) / c->pipe.tpw;
+    c->pipe.ngroups = (c->pipe.nwide + kPipeGroupMax - 1) / kPipeGroupMax;
+    HIP_TRY(hipMalloc(&c->zslabs, (size_t)c->pipe.nwide * c->zstride * sizeof(float)));
   }
-  c->Z_valid = false; c->Zbig_valid = false;
+  drop_pregradients(c);
   HIP_TRY(hipMemsetAsync(c->y, 0, (size_t)b_pad * sizeof(int), c->stream));
   HIP_TRY(hipMemsetAsync(c->f, 0, (size_t)c->L * b_pad * sizeof(float), c->stream));
   c->have_input = c->have_labels = false;
@@ -254,7 +292,7 @@ extern "C" int tnml_create(tnml_ctx **out, int N, int D, int L, int Mmax, int b_
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return fail(TNML_ERR_NOGPU, "device %d is %s; this library carries gfx950 code only", device, prop.gcnArchName);
   tnml_ctx *c = new tnml_ctx();
-  if (getenv("TNML_EVENT_HANDOFFS") && atoi(getenv("TNML_EVENT_HANDOFFS"))) { c->bigflags_enabled = false; c->split_flags_enabled = false; }   // see tnml_set_flag_handoffs
+  if (getenv("TNML_EVENT_HANDOFFS") && atoi(getenv("TNML_EVENT_HANDOFFS"))) { c->bigpipe.flags_enabled = false; c->split.flags_enabled = false; }   // see tnml_set_flag_handoffs
   // Under the reference truncation policy the bond next to a chain end becomes len(S) =
   // min(D*left, D*L) (Network_class.py:907-910), which exceeds M when M < D*L (the MNIST script
   // runs M = 3, L = 2): size every buffer for that.
@@ -271,11 +309,11 @@ extern "C" int tnml_create(tnml_ctx **out, int N, int D, int L, int Mmax, int b_
   HIP_TRY(hipEventCreateWithFlags(&c->ev_p3, hipEventDisableTiming));
   HIP_TRY(hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming));
   HIP_TRY(hipEventCreateWithFlags(&c->ev_prep, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&c->ev_upd_big, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&c->ev_zbig, hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&c->bigpipe.ev_upd, hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&c->bigpipe.ev_z, hipEventDisableTiming));
   for (int i = 0; i < 2; ++i) {
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_upd[i], hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&c->ev_bat[i], hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&c->split.ev_upd[i], hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&c->split.ev_bat[i], hipEventDisableTiming));
   }
   HIP_TRY(hipEventCreate(&c->ev0)); HIP_TRY(hipEventCreate(&c->ev1));
   HIP_TRY(hipEventCreate(&c->pev0)); HIP_TRY(hipEventCreate(&c->pev1));
@@ -297,8 +335,8 @@ extern "C" int tnml_create(tnml_ctx **out, int N, int D, int L, int Mmax, int b_
   c->zstride = (int)((2 * c->bmax + kMetricSlots + 63) / 64 * 64);       // Z has up to D times the elements of the gradient
   HIP_TRY(hipMalloc(&c->gslabs, (size_t)kPipeGroupMax * c->zstride * sizeof(float)));
   HIP_TRY(hipMalloc(&c->zred, (size_t)c->zstride * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->pipe_cnt, 32 * sizeof(unsigned)));
-  HIP_TRY(hipMemset(c->pipe_cnt, 0, 32 * sizeof(unsigned)));
+  HIP_TRY(hipMalloc(&c->pipe.cnt, 32 * sizeof(unsigned)));
+  HIP_TRY(hipMemset(c->pipe.cnt, 0, 32 * sizeof(unsigned)));
   HIP_TRY(hipMalloc(&c->zred2, (size_t)c->zstride * sizeof(float)));
   HIP_TRY(hipMalloc(&c->Tbuf[0], (size_t)c->zstride * sizeof(double)));
   HIP_TRY(hipMalloc(&c->Tbuf[1], (size_t)c->zstride * sizeof(double)));
@@ -340,7 +378,7 @@ extern "C" int tnml_destroy(tnml_ctx *c) {
   if (c->comm) ncclCommDestroy(c->comm);
   void *ptrs[] = {c->X, c->Xstage, c->y, c->f, c->ftmp, c->ftmp2, c->Lenv, c->Renv, c->cores, c->lab[0], c->lab[1],
                   c->Ln, c->Rn, c->Bnew, c->slabs, c->red, c->metrics, c->scal, c->dbg, c->status, c->tables, c->counters, c->Bscr, c->Bscr2,
-                  c->Xpred_stage, c->Xpred, c->fpred, c->predEnv, c->prepB, c->prepG, c->sync, c->zslabs, c->gslabs, c->zred, c->pipe_cnt, c->big.Bf, c->big.T, c->big.part, c->big.gram, c->big.rotlog, c->big.lam, c->big.info, c->big.VW, c->big.Cb, c->big.T2, c->big.prog, c->bigflags, c->splitflags};
+                  c->Xpred_stage, c->Xpred, c->fpred, c->predEnv, c->prepB, c->prepG, c->sync, c->zslabs, c->gslabs, c->zred, c->pipe.cnt, c->big.Bf, c->big.T, c->big.part, c->big.gram, c->big.rotlog, c->big.lam, c->big.info, c->big.VW, c->big.Cb, c->big.T2, c->big.prog, c->bigpipe.flags, c->split.flags};
   for (void *p : ptrs) if (p) (void)hipFree(p);
   void *pptrs[] = {c->zred2, c->Tbuf[0], c->Tbuf[1], c->TNbuf[0], c->TNbuf[1], c->prepRaw, c->Apub, c->pst_dev, c->pst_cnt, c->pst_flags,
                    c->anyd_W, c->anyd_T2};
@@ -365,10 +403,10 @@ extern "C" int tnml_destroy(tnml_ctx *c) {
   if (c->pev1) (void)hipEventDestroy(c->pev1);
   if (c->ev_main) (void)hipEventDestroy(c->ev_main);
   if (c->ev_prep) (void)hipEventDestroy(c->ev_prep);
-  for (int i = 0; i < 2; ++i) { if (c->ev_upd[i]) (void)hipEventDestroy(c->ev_upd[i]); if (c->ev_bat[i]) (void)hipEventDestroy(c->ev_bat[i]); }
-  if (c->ev_upd_big) (void)hipEventDestroy(c->ev_upd_big);
-  if (c->ev_zbig) (void)hipEventDestroy(c->ev_zbig);
-  if (c->bigPk) (void)hipFree(c->bigPk);
+  for (int i = 0; i < 2; ++i) { if (c->split.ev_upd[i]) (void)hipEventDestroy(c->split.ev_upd[i]); if (c->split.ev_bat[i]) (void)hipEventDestroy(c->split.ev_bat[i]); }
+  if (c->bigpipe.ev_upd) (void)hipEventDestroy(c->bigpipe.ev_upd);
+  if (c->bigpipe.ev_z) (void)hipEventDestroy(c->bigpipe.ev_z);
+  if (c->bigpipe.Pk) (void)hipFree(c->bigpipe.Pk);
   if (c->ev_p0) (void)hipEventDestroy(c->ev_p0);
   if (c->ev_p2) (void)hipEventDestroy(c->ev_p2);
   if (c->ev_p3) (void)hipEventDestroy(c->ev_p3);
@@ -388,13 +426,13 @@ static int check_status(tnml_ctx *c) {
   if (st & 124) {       // 4: helpers late, 8: B_new flag never seen, 16: the replay workgroups never saw the rotation log grow,
                         // 32 / 64: the side stream / the context's stream of the large-tensor pipeline never saw the other's sequence number
     HIP_TRY(hipMemset(c->sync, 0, sizeof(unsigned)));          // a late helper may have left the arrival counter mid-count
-    HIP_TRY(hipMemset(c->pipe_cnt, 0, 17 * sizeof(unsigned)));
-    c->Z_valid = false; c->Zbig_valid = false;
+    HIP_TRY(hipMemset(c->pipe.cnt, 0, 17 * sizeof(unsigned)));
+    drop_pregradients(c);
     if ((st & 16) && c->big_ready) {
       unsigned pw[8] = {0};
       (void)hipMemcpy(pw, c->big.prog, sizeof pw, hipMemcpyDeviceToHost);
       return fail(TNML_ERR_STATE, "internal: a replay workgroup never saw the rotation log grow (status %d; its token %u, progress word %u:%u, final word %u:%u, "
-                  "rounds applied %u, vector %u; host token %u)", st, pw[2], pw[3] >> 12, pw[3] & 4095u, pw[4] >> 12, pw[4] & 4095u, pw[5], pw[6], c->token & 0xfffffu);
+                  "rounds applied %u, vector %u; host token %u)", st, pw[2], pw[3] >> 12, pw[3] & 4095u, pw[4] >> 12, pw[4] & 4095u, pw[5], pw[6], c->pipe.token & 0xfffffu);
     }
     return fail(TNML_ERR_STATE, "internal: a workgroup of a sweep-step launch never saw its hand-off (status %d)", st);
   }
@@ -481,7 +519,7 @@ extern "C" int tnml_set_cores(tnml_ctx *c, const float *flat, size_t n_floats, c
   c->Ln_valid = c->Rn_valid = false;
   c->f_current = false;
   c->Bnew_valid = false;
-  c->Z_valid = false; c->Zbig_valid = false;
+  drop_pregradients(c);
   return TNML_OK;
 }
 
@@ -527,7 +565,7 @@ extern "C" int tnml_scale_cores(tnml_ctx *c, double factor) {
   c->Ln_valid = c->Rn_valid = false;
   c->f_current = false;
   c->Bnew_valid = false;
-  c->Z_valid = false; c->Zbig_valid = false;
+  drop_pregradients(c);
   return TNML_OK;
 }
 
@@ -563,7 +601,7 @@ extern "C" int tnml_set_input(tnml_ctx *c, const float *X, const int32_t *y, int
   c->envs_valid_L = c->envs_valid_R = false;
   c->f_current = false;
   c->Bnew_valid = false;
-  c->Z_valid = false; c->Zbig_valid = false;
+  drop_pregradients(c);
   return TNML_OK;
 }
 
@@ -620,7 +658,7 @@ extern "C" int tnml_select_batch(tnml_ctx *c, int slot) {
   c->envs_valid_L = c->envs_valid_R = false;
   c->f_current = false;
   c->Bnew_valid = false;
-  c->Z_valid = false; c->Zbig_valid = false;
+  drop_pregradients(c);
   return TNML_OK;
 }
 
@@ -635,7 +673,7 @@ extern "C" int tnml_set_labels(tnml_ctx *c, const int32_t *y, int b) {
   HIP_TRY(hipMemcpyAsync(c->y, y, (size_t)b * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->have_labels = true;
-  c->Z_valid = false; c->Zbig_valid = false;             // the pre-gradient carries the loss derivative of the old labels
+  drop_pregradients(c);             // the pre-gradient carries the loss derivative of the old labels
   return TNML_OK;
 }
 
@@ -760,7 +798,7 @@ static int run_chain_inside(tnml_ctx *c) {
   c->envs_valid_L = c->envs_valid_R = true;
   c->f_current = true;
   c->Bnew_valid = false;
-  c->Z_valid = false; c->Zbig_valid = false;
+  drop_pregradients(c);
   return TNML_OK;
 }
 
@@ -801,7 +839,7 @@ static int run_chain(tnml_ctx *c, bool logmode) {
     c->envs_valid_L = !right_envs;
     c->f_current = true;
     c->Bnew_valid = false;
-    c->Z_valid = false; c->Zbig_valid = false;
+    drop_pregradients(c);
   }
   return TNML_OK;
 }
@@ -941,7 +979,7 @@ extern "C" int tnml_set_f(tnml_ctx *c, const float *f) {
                            (size_t)c->b * sizeof(float), c->L, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->f_current = true;
-  c->Z_valid = false; c->Zbig_valid = false;             // a pre-gradient computed from the device's own f no longer applies
+  drop_pregradients(c);             // a pre-gradient computed from the device's own f no longer applies
   return TNML_OK;
 }
 
@@ -1084,7 +1122,7 @@ extern "C" int tnml_select_indices(tnml_ctx *c, const int32_t *idx, int b) {
   c->envs_valid_L = c->envs_valid_R = false;
   c->f_current = false;
   c->Bnew_valid = false;
-  c->Z_valid = false; c->Zbig_valid = false;
+  drop_pregradients(c);
   return TNML_OK;
 }
 
@@ -1237,8 +1275,8 @@ static int ensure_big(tnml_ctx *c) {
   HIP_TRY(hipMalloc(&c->big.T2, rows_cols * c->Mmax * sizeof(double)));
   HIP_TRY(hipMalloc(&c->big.prog, 8 * sizeof(unsigned)));
   HIP_TRY(hipMemset(c->big.prog, 0, 8 * sizeof(unsigned)));
-  HIP_TRY(hipMalloc(&c->bigflags, 4 * sizeof(unsigned)));
-  HIP_TRY(hipMemset(c->bigflags, 0, 4 * sizeof(unsigned)));
+  HIP_TRY(hipMalloc(&c->bigpipe.flags, 4 * sizeof(unsigned)));
+  HIP_TRY(hipMemset(c->bigpipe.flags, 0, 4 * sizeof(unsigned)));
   c->big_ready = true;
   return TNML_OK;
 }
@@ -1248,7 +1286,7 @@ static int narrow_path(const tnml_ctx *c, int h, int g, int s, int L, int m) {
   const bool force_big = c->force_big;
   const int r = kD * h, cc = kD * g * L, nn = std::min(r, cc);
   const size_t lds = narrow_lds_bytes(h, g, s, L, m);
-  if (!force_big && nn <= 64 && lds <= 160 * 1024) return 0;
+  if (!force_big && nn <= 64 && lds <= kLdsMax) return 0;
   if (nn > kBigMaxN)
     return fail(TNML_ERR_ARG, "min(rows, cols) = %d > %d: the Jacobi kernels handle n <= %d", nn, kBigMaxN, kBigMaxN);
   if (nn % 2) return fail(TNML_ERR_ARG, "odd matrix side %d", nn);
@@ -1260,14 +1298,14 @@ static int run_narrow(tnml_ctx *c, NarrowParams &n, int path, bool skip_prep = f
   if (path == 0) {
     size_t lds = narrow_lds_bytes(n.h, n.g, n.s, n.L, n.m);
     if (n.fused && !n.prep_ready) lds = std::max(lds, prep_slice_lds_bytes(n.h, n.g, n.s, n.L));   // slice workgroups ride along
-    if (lds > 160 * 1024) return fail(TNML_ERR_ARG, "internal: update launch needs %zu bytes of LDS", lds);
+    if (lds > kLdsMax) return fail(TNML_ERR_ARG, "internal: update launch needs %zu bytes of LDS", lds);
     launch_narrow(n, lds, c->stream);
     return TNML_OK;
   }
   int rc = ensure_big(c);
   if (rc) return rc;
   n.dbg = c->dbg;                       // the capture block is this path's workspace
-  n.token = ++c->token;                 // (tags the progress words of the replay that rides in the Jacobi launch)
+  n.token = ++c->pipe.token;                 // (tags the progress words of the replay that rides in the Jacobi launch)
   if (!launch_narrow_big(n, c->big, c->stream, c->check_launches, false, skip_prep, after_update, front, sig_flag, sig_val)) return fail(TNML_ERR_HIP, "%s", big_launch_error());
   return TNML_OK;
 }
@@ -1350,8 +1388,8 @@ static double *norm_rel(const tnml_ctx *c, int left_dir, int dt) {
 // i.e. f from B_new(j) and the pre-gradient Z of step j+1; j is the step at the label site or the one before it.  E_t (behind
 // environment of step t) lives in the behind stack's slot of relative site t-1, the ahead environment of step t in the ahead stack's
 // slot of relative site t+2.
-static void fill_wide_pipe(tnml_ctx *c, WidePipeParams &w, int left_dir, int j, int act_fn, int loss_fn, float T) {
-  const int N = c->N, D = c->D;
+static void fill_wide_pipe(const tnml_ctx *c, WidePipeParams &w, const SweepCall &sc, int j) {
+  const int N = c->N, D = c->D, left_dir = sc.left_dir;
   const int o = j - (left_dir ? N - 1 - c->l_pos : c->l_pos);      // relative site j as an offset from the label site (0 or -1)
   w = WidePipeParams{};
   w.b = c->b; w.b_pad = c->b_pad; w.L = c->L;
@@ -1361,7 +1399,7 @@ static void fill_wide_pipe(tnml_ctx *c, WidePipeParams &w, int left_dir, int j, 
   w.gn = rel_bond(c, left_dir, o + 2);
   w.hprev = rel_bond(c, left_dir, o - 2);
   w.first_ext = (j == 1);
-  w.act_fn = act_fn; w.loss_fn = loss_fn; w.T = T;
+  w.act_fn = sc.act_fn; w.loss_fn = sc.loss_fn; w.T = sc.T;
   w.x_jm1 = x_rel(c, left_dir, o - 1); w.x_j = x_rel(c, left_dir, o); w.x_jp1 = x_rel(c, left_dir, o + 1); w.x_jp2 = x_rel(c, left_dir, o + 2);
   w.Eprev = env_rel(c, left_dir, o - 2);
   w.Ecur = env_rel(c, left_dir, o - 1);
@@ -1378,15 +1416,15 @@ static void fill_wide_pipe(tnml_ctx *c, WidePipeParams &w, int left_dir, int j, 
   w.zsize = (w.first ? 1 : w.hj * D) * D * D * w.gn * c->L;
   w.slab_stride = c->zstride;
   w.slabs = c->zslabs; w.gslabs = c->gslabs; w.zred = c->zred;
-  w.gcnt = c->pipe_cnt; w.tcnt = c->pipe_cnt + 16;
-  w.nwide = c->pipe_nwide; w.gsz = kPipeGroupMax; w.ngroups = c->pipe_ngroups;
-  w.tiles_per_wg = c->pipe_tpw; w.ntiles = c->b_pad / kTS;
-  w.flag = c->pipe_cnt + 17;
+  w.gcnt = c->pipe.cnt; w.tcnt = c->pipe.cnt + 16;
+  w.nwide = c->pipe.nwide; w.gsz = kPipeGroupMax; w.ngroups = c->pipe.ngroups;
+  w.tiles_per_wg = c->pipe.tpw; w.ntiles = c->b_pad / kTS;
+  w.flag = c->pipe.cnt + 17;
   w.status = c->status;
 }
 
 static bool wide_pipe_fits(const tnml_ctx *c, const WidePipeParams &w) {
-  if (wide_pipe_lds_bytes(w) > 160 * 1024) return false;
+  if (wide_pipe_lds_bytes(w) > kLdsMax) return false;
   if (w.do_z && (wide_pipe_ztiles(w) > 16 * kPipeMaxZT || w.zsize + kMetricSlots > c->zstride)) return false;
   return true;
 }
@@ -1398,18 +1436,24 @@ static void pipe_try_one_level(WidePipeParams &w) {
   }
 }
 
+// `tpw` sample tiles per batch-side workgroup: the workgroups and reduction groups of the launch
+static void set_pipe_tiles(WidePipeParams &w, int tpw) {
+  w.tiles_per_wg = tpw; w.nwide = (w.ntiles + tpw - 1) / tpw;
+  w.ngroups = (w.nwide + kPipeGroupMax - 1) / kPipeGroupMax; w.gsz = kPipeGroupMax;
+}
+
 // Communicator path: whatever the batch-side stream still holds (f, environments, the exchanged pre-gradient) has to be complete
 // before the context's stream touches it outside a split step.
 static int split_join(tnml_ctx *c, bool leave_zbig = false) {
-  if (c->zbig_pending && !leave_zbig) {
-    HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_zbig, 0));
-    c->zbig_pending = false;
+  if (c->bigpipe.pending && !leave_zbig) {
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->bigpipe.ev_z, 0));
+    c->bigpipe.pending = false;
   }
-  if (c->split_pending) {
-    HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_bat[c->split_bat], 0));
-    c->split_pending = false;
+  if (c->split.pending) {
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->split.ev_bat[c->split.bat], 0));
+    c->split.pending = false;
   }
-  c->split_done_valid = false; c->split_zsig_valid = false;
+  c->split.done_valid = false; c->split.zsig_valid = false;
   return TNML_OK;
 }
 
@@ -1419,22 +1463,22 @@ static int split_join(tnml_ctx *c, bool leave_zbig = false) {
 // stay for the first step of a run and for joining the side stream afterwards.
 // the side stream goes on once the last update launch has ended: gate kernel on its sequence number, or its event
 static int split_wait_update(tnml_ctx *c) {
-  if (c->split_flags_enabled && c->split_done_valid) {
-    if (!launch_big_gate(c->splitflags + 1, c->split_dseq, c->status, c->stream2)) return fail(TNML_ERR_HIP, "%s", big_launch_error());
-  } else HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_upd[c->split_upd], 0));
+  if (c->split.flags_enabled && c->split.done_valid) {
+    if (!launch_big_gate(c->split.flags + 1, c->split.dseq, c->status, c->stream2)) return fail(TNML_ERR_HIP, "%s", big_launch_error());
+  } else HIP_TRY(hipStreamWaitEvent(c->stream2, c->split.ev_upd[c->split.upd], 0));
   return TNML_OK;
 }
 // behind a batch-side launch: the pre-gradient summed over the ranks (zsize < 0: none), the sequence number and event the next update waits for
 static int split_exchange(tnml_ctx *c, int zsize) {
   if (zsize >= 0) NCCL_TRY(ncclAllReduce(c->zred, c->zred, zsize + kMetricSlots, ncclFloat, ncclSum, c->comm, c->stream2));
-  if (c->split_flags_enabled) {
-    ++c->split_zseq;
-    if (!launch_big_signal(c->splitflags, c->split_zseq, c->stream2)) return fail(TNML_ERR_HIP, "%s", big_launch_error());
-    c->split_zsig_valid = true;
+  if (c->split.flags_enabled) {
+    ++c->split.zseq;
+    if (!launch_big_signal(c->split.flags, c->split.zseq, c->stream2)) return fail(TNML_ERR_HIP, "%s", big_launch_error());
+    c->split.zsig_valid = true;
   }
-  c->split_bat ^= 1;
-  HIP_TRY(hipEventRecord(c->ev_bat[c->split_bat], c->stream2));
-  c->split_pending = true;
+  c->split.bat ^= 1;
+  HIP_TRY(hipEventRecord(c->split.ev_bat[c->split.bat], c->stream2));
+  c->split.pending = true;
   return TNML_OK;
 }
 
@@ -1470,8 +1514,8 @@ static int step_geom_error(const tnml_ctx *c, const StepGeom &q) {
   return fail(TNML_ERR_ARG, "new cores at sites (%d,%d) exceed the buffers sized for M = %d", q.p, q.p + 1, c->Mmax);
 }
 
-// Update side of the step: what every planner passes the same way.  The caller adds what is its own: red, out_ahead, metrics; dbg,
-// stamps, Bdirect, stop_after_update, chol_thr; the fused / pipelined / persistent and the adaptive fields.
+// Update side of the step: what every planner passes the same way.  The per-step planners go on with fill_step_update; the
+// persistent sweep adds its own red, out_ahead, metrics, stamps and hand-off fields.
 static void fill_update(const tnml_ctx *c, NarrowParams &n, const StepGeom &q, int l2_flag, float lr, float wd) {
   const int D = c->D, L = c->L, h = q.h, g = q.g, s = q.s, m = q.m;
   n.L = L; n.D = D; n.h = h; n.g = g; n.s = s; n.m = m; n.bsize = (int)q.bsize;
@@ -1500,14 +1544,30 @@ static void fill_update(const tnml_ctx *c, NarrowParams &n, const StepGeom &q, i
   n.status = c->status; n.counters = c->counters;
 }
 
+// The update record of a per-step launch (sweep_impl at D = 2, sweep_anyd): fill_update plus where the step reads its gradient and
+// writes its label core and metrics, the capture block (`dbg`: the caller's), the adaptive-rank triple, and mode 1's redirect of
+// B_new away from the chain.  The caller adds chol_thr and the fused / pipelined fields.
+static void fill_step_update(const tnml_ctx *c, NarrowParams &n, const StepGeom &q, const SweepCall &sc, int step, double *dbg) {
+  fill_update(c, n, q, sc.l2_flag, sc.lr, sc.weight_dec);
+  n.red = c->red;
+  n.out_ahead = c->lab[c->lab_cur ^ 1];
+  n.metrics = c->metrics + 2 * (size_t)step;
+  n.dbg = dbg;
+  n.stamps = (c->debug || c->stamps) ? c->dbg + 4 * c->bmax + kDbgSigma + 5 : nullptr;
+  n.Bdirect = sc.Bdirect_dev;
+  n.stop_after_update = sc.mode == 1;
+  if (sc.trunc_policy == TNML_TRUNC_ADAPTIVE && sc.mode == 0) { n.trunc_thr = c->trunc_thr; n.left_dir = sc.left_dir; n.m_out = c->status + 1; }
+  if (sc.mode == 1) { n.Bnew = c->Bscr2; n.Nh_new = nullptr; }
+}
+
 // Batch side of a classic step (wide kernel, generic-D batch kernel): gradient slabs of this step, the behind environment extended
 // by the core of relative site k - 1 and, where f is not current, f of the previous step from its updated B.  `stamps` is the caller's.
-static int fill_wide(const tnml_ctx *c, WideParams &w, const StepGeom &q, int act_fn, int loss_fn, float T) {
+static int fill_wide(const tnml_ctx *c, WideParams &w, const StepGeom &q, const SweepCall &sc) {
   const int D = c->D, ld = q.left_dir;
   w = WideParams{};
   w.b = c->b; w.b_pad = c->b_pad; w.L = c->L;
   w.h = q.h; w.g = q.g;
-  w.act_fn = act_fn; w.loss_fn = loss_fn; w.T = T;
+  w.act_fn = sc.act_fn; w.loss_fn = sc.loss_fn; w.T = sc.T;
   w.y = c->y; w.f = c->f;
   w.slabs = c->slabs; w.slab_stride = c->slab_stride; w.bsize = (int)q.bsize;
   w.x_k = x_rel(c, ld, 0);
@@ -1546,18 +1606,23 @@ static void add_step_work(const tnml_ctx *c, const StepGeom &q, double &bytes, d
 }
 
 // the step is planned: the label moves on to site sa, the bond between the two sites is the kept rank, the other label buffer is current
-static void advance_frame(tnml_ctx *c, const StepGeom &q, int m_kept, bool note_last = true) {
+static void advance_frame(tnml_ctx *c, const StepGeom &q, int m_kept) {
   c->bond[q.p] = m_kept;
   c->l_pos = q.sa;
   c->lab_cur ^= 1;
   c->prev_h = q.h; c->prev_g = q.g; c->prev_left_dir = q.left_dir;
-  if (note_last) { c->last_bsize = (int)q.bsize; c->last_n = q.nn; c->last_h = q.h; c->last_g = q.g; c->last_left_dir = q.left_dir; }
+}
+
+// the capture block (tnml_get_step_debug) describes this step
+static void note_last_step(tnml_ctx *c, const StepGeom &q) {
+  c->last_bsize = (int)q.bsize; c->last_n = q.nn; c->last_h = q.h; c->last_g = q.g; c->last_left_dir = q.left_dir;
 }
 
 // after the launches of a step of the per-step planners; f_stored: the batch-side work of the step stored its f already
-static int finish_step(tnml_ctx *c, const StepGeom &q, int trunc_policy, int step, bool f_stored) {
+static int finish_step(tnml_ctx *c, const StepGeom &q, const SweepCall &sc, int step, bool f_stored) {
   int m_kept = q.m;
-  if (trunc_policy == TNML_TRUNC_ADAPTIVE) {       // the kept rank is decided on the device: one sync per step
+  note_last_step(c, q);
+  if (sc.trunc_policy == TNML_TRUNC_ADAPTIVE) {       // the kept rank is decided on the device: one sync per step
     HIP_TRY(hipMemcpyAsync(&m_kept, c->status + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (m_kept < 1 || m_kept > q.m) return fail(TNML_ERR_NONFINITE, "adaptive truncation returned rank %d (cap %d)", m_kept, q.m);
@@ -1577,7 +1642,8 @@ static int finish_step(tnml_ctx *c, const StepGeom &q, int trunc_policy, int ste
 }
 
 // mode 1 (standalone update_B) ends here: the behind environment list grew (as update_B does, Network_class.py:637-652), nothing else changes
-static int finish_update_only(tnml_ctx *c, float *metrics_out) {
+static int finish_update_only(tnml_ctx *c, const StepGeom &q, float *metrics_out) {
+  note_last_step(c, q);
   HIP_TRY(hipGetLastError());
   if (metrics_out) {
     HIP_TRY(hipMemcpyAsync(metrics_out, c->metrics, 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -1587,7 +1653,9 @@ static int finish_update_only(tnml_ctx *c, float *metrics_out) {
 }
 
 // after the last step of a call: valid norm stacks, f from the last updated B (what sweep_step returns, Network_class.py:573), copies out
-static int finish_sweep(tnml_ctx *c, int left_dir, int n_steps, int l2_flag, int nblk, hipEvent_t sw_ev1, float *metrics_out, float *f_out) {
+static int finish_sweep(tnml_ctx *c, const SweepCall &sc) {
+  const int left_dir = sc.left_dir, l2_flag = sc.l2_flag, nblk = sc.nblk;
+  float *const metrics_out = sc.metrics_out, *const f_out = sc.f_out;
   // the behind norm stack is whole (the one valid for the opposite direction) once the sweep is complete; mid-sweep the ahead one stays usable
   bool &behind = left_dir ? c->Rn_valid : c->Ln_valid, &ahead = left_dir ? c->Ln_valid : c->Rn_valid;
   const bool complete = c->l_pos == (left_dir ? 0 : c->N - 1);
@@ -1616,8 +1684,8 @@ static int finish_sweep(tnml_ctx *c, int left_dir, int n_steps, int l2_flag, int
     HIP_TRY(hipGetLastError());
     c->f_current = true;
   }
-  if (sw_ev1) HIP_TRY(hipEventRecord(sw_ev1, c->stream));
-  if (metrics_out) HIP_TRY(hipMemcpyAsync(metrics_out, c->metrics, (size_t)n_steps * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (sc.sw_ev1) HIP_TRY(hipEventRecord(sc.sw_ev1, c->stream));
+  if (metrics_out) HIP_TRY(hipMemcpyAsync(metrics_out, c->metrics, (size_t)sc.n_steps * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   if (f_out) { int rc = copy_f_out(c, c->f, f_out); if (rc) return rc; }
   if (metrics_out || f_out) {
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1641,11 +1709,10 @@ static bool persist_record_ok(const NarrowParams &n) {
          !(n.trunc_thr > 0.0) && !n.m_out && !n.zpoll_flag && !n.done_flag && !n.sync && n.wait_count == 0;
 }
 
-static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float weight_dec, int l2_flag, int act_fn, int loss_fn,
-                         float T, int trunc_policy) {
-  const int N = c->N, D = c->D, L = c->L;
+static int sweep_persist(tnml_ctx *c, const SweepCall &sc) {
+  const int N = c->N, D = c->D, L = c->L, left_dir = sc.left_dir, n_steps = sc.n_steps, trunc_policy = sc.trunc_policy;
   // (cycle stamps alone -- tnml_debug_enable(ctx, 2) -- are allowed: they are taken at the middle step of the sweep)
-  if (!c->persist_enabled || !c->pipe_enabled || c->comm || c->debug || c->profile || c->check_launches) return 0;
+  if (!c->persist_enabled || !c->pipe.enabled || c->comm || c->debug || c->profile || c->check_launches) return 0;
   if (trunc_policy == TNML_TRUNC_ADAPTIVE || n_steps != N - 1 || c->force_big) return 0;
   if (!c->f_current || c->Bnew_valid) return 0;
   // state the planning loop advances; restored if some step does not fit
@@ -1661,7 +1728,7 @@ static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float
   // one sample tile per batch-side workgroup while the device has the CUs (the reduced pre-gradient of step k+1 has to be there
   // when step k ends: with two tiles per workgroup it arrived ~2 us late behind a 40-round SVD); fixed for the whole launch --
   // a workgroup keeps its samples from step to step
-  int tpw = c->pipe_tpw;
+  int tpw = c->pipe.tpw;
   while ((ntiles + tpw - 1) / tpw + 1 + kPersistHelpers > c->num_cus) ++tpw;
   const int nwide = (ntiles + tpw - 1) / tpw;
   const int nH = kPersistHelpers;
@@ -1672,9 +1739,9 @@ static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float
   float *zr2[2] = {c->zred, c->zred2};
   size_t lds_narrow = 0, lds_wide = 0, lds_help = 0;
   // prologue: Z_0 from forward's f
-  fill_wide_pipe(c, pro, left_dir, -1, act_fn, loss_fn, T);
+  fill_wide_pipe(c, pro, sc, -1);
   pro.do_ext = 0; pro.wait_flag = 0; pro.do_z = 1; pro.do_f = 0;
-  pro.tiles_per_wg = tpw; pro.nwide = nwide; pro.ngroups = (nwide + kPipeGroupMax - 1) / kPipeGroupMax; pro.gsz = kPipeGroupMax;
+  set_pipe_tiles(pro, tpw);
   pro.wg0 = 1 + nH; pro.persist = 1; pro.zred = zr2[0]; pro.zready = fl + 2; pro.zpublish = 1; pro.abort_flag = fl + 4;
   pro.gcnt = c->pst_cnt + (size_t)n_steps * 32; pro.tcnt = pro.gcnt + 16;
   if (!wide_pipe_fits(c, pro)) return give_up();
@@ -1686,12 +1753,12 @@ static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float
     if (q.fail) return give_up();                            // the per-step path reports it (the reference's ValueError, the buffers)
     const int h = q.h, g = q.g, s = q.s, m = q.m;
     const size_t nlds = narrow_lds_bytes(h, g, s, L, m);
-    if (q.nn > 64 || (q.nn & 1) || nlds + pbytes > 160 * 1024 || h > Mcap || m > Mcap || q.bsize > 8192) return give_up();
+    if (q.nn > 64 || (q.nn & 1) || nlds + pbytes > kLdsMax || h > Mcap || m > Mcap || q.bsize > 8192) return give_up();
     PersistStep &ps = st[k];
     ps = PersistStep{};
     // ---- update + SVD workgroup (Nh / Ng: only "is there one", the values are in LDS)
     NarrowParams &n = ps.n;
-    fill_update(c, n, q, l2_flag, lr, weight_dec);
+    fill_update(c, n, q, sc.l2_flag, sc.lr, sc.weight_dec);
     // the label core is written once, by the last step: into the buffer the per-step sequence would have ended on
     n.out_ahead = c->lab[(c->lab_cur + (n_steps - k)) & 1];
     n.write_ahead = (k == n_steps - 1);
@@ -1699,7 +1766,7 @@ static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float
     n.chol_thr = c->chol_thr;
     n.stamps = (c->stamps && k == n_steps / 2) ? c->dbg + 4 * c->bmax + kDbgSigma + 5 : nullptr;
     n.pipe = 1; n.persist = 1; n.z_first = (k == 0);
-    fill_wide_pipe(c, ps.w, left_dir, k, act_fn, loss_fn, T);
+    fill_wide_pipe(c, ps.w, sc, k);
     WidePipeParams &wp = ps.w;
     const int zr = k == 0 ? 1 : wp.hprev * D;
     if (zr > 64) return give_up();
@@ -1716,7 +1783,7 @@ static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float
     // ---- batch-side workgroups: f from B_new(k), pre-gradient of step k+1
     wp.do_ext = k >= 1; wp.do_f = 1; wp.wait_flag = 1;
     wp.do_z = (k + 1 <= N - 2);
-    wp.tiles_per_wg = tpw; wp.nwide = nwide; wp.ngroups = (nwide + kPipeGroupMax - 1) / kPipeGroupMax; wp.gsz = kPipeGroupMax;
+    set_pipe_tiles(wp, tpw);
     wp.wg0 = 1 + nH; wp.persist = 1; wp.flag = fl + 0; wp.token = (unsigned)k + 1;
     wp.coreflag = fl + 3; wp.corewant = (unsigned)k; wp.zready = fl + 2; wp.zpublish = (unsigned)k + 2; wp.abort_flag = fl + 4;
     wp.zred = zr2[(k + 1) & 1];
@@ -1738,11 +1805,12 @@ static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float
     lds_help = std::max(lds_help, persist_helper_lds_bytes(zr, s, g, L, h, nH));
     if ((size_t)zr * D * D * g * L + kMetricSlots > (size_t)c->zstride) return give_up();
     // ---- the bookkeeping of the per-step path (the capture block belongs to the stamped step, if there is one)
-    advance_frame(c, q, m, !c->stamps || k <= n_steps / 2);
+    advance_frame(c, q, m);
+    if (!c->stamps || k <= n_steps / 2) note_last_step(c, q);
     add_step_work(c, q, bytes, flops);
   }
   const size_t lds = c->persist_mode >= 2 ? lds_narrow + pbytes : std::max(std::max(lds_narrow + pbytes, lds_wide), lds_help);
-  if (lds > 160 * 1024 || lds_wide > 160 * 1024 || lds_help > 160 * 1024) return give_up();
+  if (lds > kLdsMax || lds_wide > kLdsMax || lds_help > kLdsMax) return give_up();
   const int persist_off = (int)((lds - pbytes) & ~(size_t)15);
   for (int k = 0; k < n_steps; ++k) st[k].n.persist_off = persist_off;
   // ---- enqueue: records, zeroed flags and counters, one launch
@@ -1769,7 +1837,7 @@ static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float
   }
   c->cnt_steps += n_steps; c->cnt_bytes += bytes; c->cnt_flops += flops;
   c->sweep_launches += 1; c->step_launches += n_steps; c->persist_sweeps += 1;
-  c->Bnew_valid = true; c->f_current = true; c->Z_valid = false; c->Zbig_valid = false;
+  c->Bnew_valid = true; c->f_current = true; drop_pregradients(c);
   return 1;
 }
 
@@ -1777,11 +1845,345 @@ static int sweep_persist(tnml_ctx *c, int left_dir, int n_steps, float lr, float
 // the merged tensor -- the behind environment is extended and B_new lands in the debug block, but no
 // SVD runs and cores, bonds and l_pos stay as they are.  Bdirect_dev: merged tensor to use instead of
 // the product of the two cores (relative layout), or nullptr.
-static int sweep_anyd(tnml_ctx *c, int left_dir, int n_steps, float lr, float weight_dec, int l2_flag, int act_fn, int loss_fn, float T,
-                      int trunc_policy, float *metrics_out, float *f_out, int mode, const float *Bdirect_dev, hipEvent_t sw_ev1);
+static int sweep_anyd(tnml_ctx *c, const SweepCall &sc);
 static int standalone_anyd(tnml_ctx *c, NarrowParams &n);
 
 static int norm_envs_for_label_site(tnml_ctx *c);
+
+// ---------------------------------------------------------------------------------------------
+// The per-step planner at D = 2 (every sweep step the persistent launch does not take).  The loop of sweep_impl plans the geometry
+// and the update record of a step and hands them to ONE of four launch paths:
+//   plan_pipe_step -> launch_pipe_step_fused    the single-launch in-LDS step on one stream
+//                  -> launch_pipe_step_split    the same step on two streams (communicator), both with launch_pipe_prologue
+//   step_classic_lds                            wide -> [reduce] -> [all-reduce] -> narrow, in LDS
+//   step_big                                    the chain through HBM and its pipeline (plan_next_z, launch_next_z)
+// Every path counts its own launches where it makes them.  The order of the runtime calls inside a path is part of its behaviour
+// (san/hip_stub.cpp writes it as a trace that is compared across changes of this file).
+// ---------------------------------------------------------------------------------------------
+// merge / L2 slices ride in the batch-side launch: an in-LDS step of a full sweep on the product of the two cores
+static bool slices_ride(const SweepCall &sc, int npath) { return npath == 0 && sc.mode == 0 && !sc.Bdirect_dev; }
+
+struct PipePlan {
+  WidePipeParams wp, wpro;     // batch side of the step; the prologue that forms Z of this step where none is waiting
+  bool need_prologue;
+};
+
+// Pipelined step: ONE launch (update + SVD of step k next to the batch-side work of step k+1).  Pure decision -- 1: the step is
+// pipelined and pp is filled, 0: it takes the classic sequence, < 0: an internal check failed; nothing is launched, no state changes.
+// (the first step of a segment takes the classic sequence: its behind environment is extended again from the stack forward
+//  built, its f is forward's; the pipelined step resumes with the second step, from its own prologue)
+static int plan_pipe_step(const tnml_ctx *c, const SweepCall &sc, const StepGeom &q, int step, int npath, PipePlan &pp) {
+  const int N = c->N, L = c->L, k = q.k;
+  if (!c->pipe.enabled || !slices_ride(sc, npath) || (sc.seg_start && step == 0)) return 0;
+  if (prep_slice_lds_bytes(q.h, q.g, q.s, L) > kLdsMax) return 0;      // the slice workgroups of the launch must fit too
+  WidePipeParams &wp = pp.wp, &wpro = pp.wpro;
+  fill_wide_pipe(c, wp, sc, k);
+  wp.do_ext = k >= 1; wp.do_f = 1; wp.wait_flag = 1;
+  wp.do_z = (k + 1 <= N - 2);
+  if (wp.do_z && !wide_pipe_fits(c, wp)) wp.do_z = 0;            // the next step will start from its own prologue
+  pipe_try_one_level(wp);
+  if (wp.do_z && c->pipe.tiles > wp.tiles_per_wg && q.nn >= 32) {
+    // the SVD of this step is long (short side >= 32): a batch-side workgroup accumulates several sample tiles in
+    // registers before it writes its partial pre-gradient -- proportionally fewer partial tensors to write and re-read
+    // (gsz / one_level stay as pipe_try_one_level left them: not set_pipe_tiles)
+    wp.tiles_per_wg = c->pipe.tiles;
+    wp.nwide = (wp.ntiles + wp.tiles_per_wg - 1) / wp.tiles_per_wg;
+    wp.ngroups = (wp.nwide + kPipeGroupMax - 1) / kPipeGroupMax;
+  }
+  if (!wide_pipe_fits(c, wp)) return 0;
+  pp.need_prologue = !c->pipe.Z.matches(sc, k);
+  if (pp.need_prologue) {
+    fill_wide_pipe(c, wpro, sc, k - 1);
+    wpro.do_ext = 0; wpro.wait_flag = 0; wpro.do_z = 1;
+    wpro.do_f = (k >= 1 && c->Bnew_valid && !c->f_current) ? 1 : 0;
+    if (wpro.do_f && (c->prev_h != wpro.hj || c->prev_g != wpro.gj))
+      return fail(TNML_ERR_STATE, "internal: previous-step dims (%d,%d) do not match (%d,%d)", c->prev_h, c->prev_g, wpro.hj, wpro.gj);
+    if (!wide_pipe_fits(c, wpro)) return 0;
+  }
+  return 1;
+}
+
+// Z of this step where no launch left it: the batch-side workgroups alone, on the stream the batch side of the step runs on
+static int launch_pipe_prologue(tnml_ctx *c, WidePipeParams &wpro, bool split) {
+  NarrowParams none{};
+  wpro.wg0 = 0;
+  if (split) { int rc = split_wait_update(c); if (rc) return rc; }
+  prof_begin(c);
+  launch_step_pipe(none, wpro, wide_pipe_lds_bytes(wpro), split ? c->stream2 : c->stream);
+  prof_end(c, 1);
+  c->sweep_launches++; c->step_launches++;
+  if (split) { int rc = split_exchange(c, wpro.zsize); if (rc) return rc; }
+  else if (c->comm) NCCL_TRY(ncclAllReduce(c->zred, c->zred, wpro.zsize + kMetricSlots, ncclFloat, ncclSum, c->comm, c->stream));
+  if (wpro.do_f) c->f_current = true;
+  return TNML_OK;
+}
+
+// What a pipelined launch adds to the update record and its batch side: the hand-off between the two and where the workgroups start.
+// merged tensor / L2 term of this step: from the slice workgroups this launch carries (a slice of more than 8 rows is
+// cut into two row parts: twice the workgroups, half the dependent tiles in each).  (Measured, round 2: preparing them
+// at the end of the PREVIOUS launch inside workgroup 0 cost it 23 k cycles and saved 16 k of waiting -- removed.)
+static void fill_pipe_update(tnml_ctx *c, NarrowParams &n, WidePipeParams &wp, const StepGeom &q) {
+  const int D = c->D, L = c->L;
+  n.fused = 1; n.nred = 0; n.sync = c->sync; n.red_out = nullptr;
+  n.prep_ready = 0;
+  n.wait_count = kD * kD * (q.h > 8 ? 2 : 1);
+  n.pipe = 1; n.z_first = (q.k == 0); n.z_rows = wp.hprev * D;
+  n.zsize = (q.k == 0 ? 1 : n.z_rows) * D * D * q.g * L;
+  n.zred = c->zred; n.red = c->zred; n.zcore = wp.ext_core;
+  n.flag = c->pipe.cnt + 17; n.token = ++c->pipe.token;
+  wp.token = n.token;
+  wp.wg0 = 1 + n.wait_count;
+}
+// LDS of the update side of a pipelined launch: the update workgroup and its slice helpers
+static size_t pipe_update_lds(const tnml_ctx *c, const StepGeom &q) {
+  return std::max(narrow_lds_bytes(q.h, q.g, q.s, c->L, q.m), prep_slice_lds_bytes(q.h, q.g, q.s, c->L));
+}
+
+static int launch_pipe_step_fused(tnml_ctx *c, const SweepCall &sc, const StepGeom &q, NarrowParams &n, PipePlan &pp) {
+  WidePipeParams &wp = pp.wp;
+  { int rc = split_join(c); if (rc) return rc; }
+  if (pp.need_prologue) { int rc = launch_pipe_prologue(c, pp.wpro, false); if (rc) return rc; }
+  fill_pipe_update(c, n, wp, q);
+  const size_t lds = std::max(pipe_update_lds(c, q), wide_pipe_lds_bytes(wp));
+  if (lds > kLdsMax) return fail(TNML_ERR_ARG, "internal: pipelined step needs %zu bytes of LDS", lds);
+  prof_begin(c);
+  launch_step_pipe(n, wp, lds, c->stream);
+  prof_end(c, 3);
+  c->sweep_launches++; c->step_launches++;
+  if (c->comm && wp.do_z) NCCL_TRY(ncclAllReduce(c->zred, c->zred, wp.zsize + kMetricSlots, ncclFloat, ncclSum, c->comm, c->stream));
+  c->bigpipe.Z.valid = false;
+  c->pipe.Z.leave(sc, q.k + 1, wp.do_z != 0);
+  return TNML_OK;
+}
+
+// Communicator path (batch shards over the ranks): the pre-gradient Z_{k+1} is final ~25 us into a ~57 us step, but behind
+// a fused launch its all-reduce could only start when the SVD of step k has ended -- on the critical path of every step.
+// So the step is launched in two parts: the update side (workgroup 0 + slice helpers) on the context's stream, the
+// batch side on stream2 followed by the all-reduce, which then travels beside the SVD; the next update launch waits
+// for its event.  Same kernels, same arithmetic as the fused launch (the B_new hand-off is a flag in memory either way).
+static int launch_pipe_step_split(tnml_ctx *c, const SweepCall &sc, const StepGeom &q, NarrowParams &n, PipePlan &pp) {
+  WidePipeParams &wp = pp.wp;
+  if (c->split.flags_enabled && !c->split.flags) {
+    HIP_TRY(hipMalloc(&c->split.flags, 4 * sizeof(unsigned)));
+    HIP_TRY(hipMemsetAsync(c->split.flags, 0, 4 * sizeof(unsigned), c->stream));
+  }
+  if (!c->split.pending) {                 // first split step after anything else: stream2 starts behind the context's stream
+    c->split.upd ^= 1;
+    HIP_TRY(hipEventRecord(c->split.ev_upd[c->split.upd], c->stream));
+    c->split.done_valid = false; c->split.zsig_valid = false;
+  }
+  if (pp.need_prologue) { int rc = launch_pipe_prologue(c, pp.wpro, true); if (rc) return rc; }
+  fill_pipe_update(c, n, wp, q);
+  const size_t lds_u = pipe_update_lds(c, q), lds_b = wide_pipe_lds_bytes(wp);
+  if (lds_u > kLdsMax || lds_b > kLdsMax) return fail(TNML_ERR_ARG, "internal: pipelined step needs %zu / %zu bytes of LDS", lds_u, lds_b);
+  const bool sflags = c->split.flags_enabled;
+  // batch side of step k: needs the behind core the update launch of step k-1 left, then B_new(k) (flag in memory)
+  { int rc = split_wait_update(c); if (rc) return rc; }
+  {
+    NarrowParams none{};
+    WidePipeParams wb = wp;
+    wb.wg0 = 0;
+    launch_step_pipe(none, wb, lds_b, c->stream2);
+  }
+  // update side of step k: needs Z_k summed over the ranks (the exchange enqueued behind the previous batch-side launch)
+  if (c->split.pending) {
+    if (sflags && c->split.zsig_valid) { n.zpoll_flag = c->split.flags; n.zpoll_want = c->split.zseq; }
+    else HIP_TRY(hipStreamWaitEvent(c->stream, c->split.ev_bat[c->split.bat], 0));
+  }
+  if (sflags) { n.done_flag = c->split.flags + 1; n.done_val = ++c->split.dseq; }
+  launch_step_pipe_update(n, wp, lds_u, c->stream);
+  if (sflags) c->split.done_valid = true;
+  else {
+    c->split.upd ^= 1;
+    HIP_TRY(hipEventRecord(c->split.ev_upd[c->split.upd], c->stream));
+  }
+  { int rc = split_exchange(c, wp.do_z ? wp.zsize : -1); if (rc) return rc; }
+  c->sweep_launches += 2; c->step_launches++;
+  c->bigpipe.Z.valid = false;
+  c->pipe.Z.leave(sc, q.k + 1, wp.do_z != 0);
+  return TNML_OK;
+}
+
+// Classic in-LDS sequence: wide kernel (gradient slabs, with the merge / L2 slice workgroups where they ride) -> [slab reduction]
+// -> [all-reduce over the batch shards] -> narrow kernel.
+// single GPU: the slab reduction rides in the narrow launch as helper workgroups (no separate reduce kernel, no boundary) and the
+// merge / L2 products ride in the wide launch (or, with the plain-FMA wide kernel, in the narrow launch as well)
+static int step_classic_lds(tnml_ctx *c, const SweepCall &sc, const StepGeom &q, NarrowParams &n) {
+  const int L = c->L;
+  { int rc = split_join(c); if (rc) return rc; }
+  drop_pregradients(c);
+  WideParams w{};
+  { int rc = fill_wide(c, w, q, sc); if (rc) return rc; }
+  w.stamps = c->stamps ? c->dbg + 4 * c->bmax + kDbgSigma + 5 + 17 : nullptr;
+  PrepParams prep{};
+  prep.lab = n.lab; prep.pl = n.pl; prep.Nh = n.Nh; prep.Ng = n.Ng; prep.h = q.h; prep.g = q.g; prep.s = q.s; prep.L = L;
+  prep.l2_flag = n.l2_flag; prep.prepB = c->prepB; prep.prepG = c->prepG;
+  prof_begin(c);
+  bool prep_done = false;
+  if (!launch_wide(w, sc.nblk, slices_ride(sc, 0) ? &prep : nullptr, c->stream, &prep_done))
+    return fail(TNML_ERR_ARG, "step at sites (%d,%d): a 32-sample tile of this bond dimension does not fit the batch kernels' LDS", q.p, q.p + 1);
+  c->sweep_launches++;
+  n.prep_ready = prep_done ? 1 : 0;
+  // slices the batch launch could not host would ride in the update launch -- unless they do not fit a workgroup's LDS
+  // either (bond 64 next to a chain end at three labels): then the update workgroup forms B and Ln.B.Rn itself, which
+  // the launch does only un-fused (separate reduction)
+  if (n.fused && !prep_done && prep_slice_lds_bytes(q.h, q.g, q.s, L) > kLdsMax) { n.fused = 0; n.nred = 0; }
+  if (n.fused) n.wait_count = n.nred + (n.prep_ready ? 0 : kD * kD);
+  prof_end(c, 1);
+  // ---- reduce (+ all-reduce over the batch shards)
+  if (!n.fused) {
+    prof_begin(c);
+    launch_reduce(c->slabs, sc.nblk, c->slab_stride, (int)q.bsize + kMetricSlots, c->red, c->stream);
+    prof_end(c, 2);
+    c->sweep_launches++;
+  }
+  if (c->comm) NCCL_TRY(ncclAllReduce(c->red, c->red, q.bsize + kMetricSlots, ncclFloat, ncclSum, c->comm, c->stream));
+  prof_begin(c);
+  { int rc = run_narrow(c, n, 0); if (rc) return rc; }
+  prof_end(c, 3);
+  c->sweep_launches++;
+  return TNML_OK;
+}
+
+// Pipelined large-tensor step: may the batch kernel of step k+1 run beside the SVD of this one?  Pure decision.
+// Needs: the next step is a large-tensor step too, both environments exist as arrays (k >= 2, an ahead environment two sites
+// on), the tiled batch kernel takes the doubled row operand (h -> D h), the slabs of Z fit the pre-gradient scratch.
+struct NextZ {
+  bool on;
+  int gnext;         // ahead bond of step k+1
+  size_t lds_z;      // LDS of its batch kernel
+};
+static NextZ plan_next_z(const tnml_ctx *c, const SweepCall &sc, const StepGeom &q) {
+  const int N = c->N, D = c->D, L = c->L, left_dir = sc.left_dir, h = q.h, g = q.g, m = q.m;
+  NextZ z{false, 0, 0};
+  if (!(c->bigpipe.enabled && c->pipe.enabled && sc.mode == 0 && !sc.Bdirect_dev && !c->debug && !c->profile && sc.trunc_policy != TNML_TRUNC_ADAPTIVE &&
+        q.k >= 2 && q.k + 1 <= N - 2 && sc.nblk <= c->pipe.nwide))
+    return z;
+  const int pn = std::min(q.sa, rel_site(c, left_dir, 2));   // sites (pn, pn + 1) of step k+1; g is the bond the two steps share
+  z.gnext = rel_bond(c, left_dir, 2);
+  const int mnext = tnml_trunc_rank(sc.trunc_policy, left_dir, pn, N, left_dir ? z.gnext : m, D, left_dir ? m : z.gnext, L, c->Mpol);
+  const size_t zs = (size_t)D * h * D * D * z.gnext * L;
+  z.lds_z = wide_tiled_lds_bytes(L, D * h, h, g, z.gnext, false);      // (its launch extends no environment and hands Hcur in)
+  z.on = mnext > 0 && narrow_path(c, m, z.gnext, g, L, mnext) == 1 && zs + kMetricSlots <= (size_t)c->zstride &&
+         z.lds_z > 0 && z.lds_z <= kLdsMax && D * h <= 2 * c->Mmax && (size_t)D * h * c->b_pad <= (size_t)2 * c->Mmax * c->b_pad;
+  return z;
+}
+
+// The side-stream chain of the large-tensor pipeline, behind B_new(k): E_k and P'_k = E_k (x) x_k (unless the step's first launch
+// formed them: ext_in_front); then the tiled batch kernel "of step k+1" with P'_k in the place of its behind environment (D h
+// rows): f of step k from B_new(k) and the slabs of Z_{k+1}; their sum; the exchange.  w: the batch side of step k (fill_wide).
+static int launch_next_z(tnml_ctx *c, const SweepCall &sc, const StepGeom &q, const WideParams &w, const NextZ &nz, bool ext_in_front, bool bsig) {
+  const int D = c->D, L = c->L, h = q.h, g = q.g;
+  if (bsig) { if (!launch_big_gate(c->bigpipe.flags + 1, c->bigpipe.bsig_seq, c->status, c->stream2)) return fail(TNML_ERR_HIP, "%s", big_launch_error()); }
+  else HIP_TRY(hipStreamWaitEvent(c->stream2, c->bigpipe.ev_upd, 0));
+  c->bigpipe.ext_on_side = !ext_in_front;
+  if (!ext_in_front && !launch_big_ext(w.Hprev, w.x_km1, w.x_k, w.ext_core, c->b_pad, w.Hcur, c->bigpipe.Pk, c->stream2)) return fail(TNML_ERR_HIP, "%s", big_launch_error());
+  WideParams z{};
+  z.b = c->b; z.b_pad = c->b_pad; z.L = L;
+  z.h = D * h; z.g = nz.gnext; z.hp = h; z.gp = g;
+  z.do_f = 1; z.do_ext = 0; z.first_ext = 0;
+  z.act_fn = sc.act_fn; z.loss_fn = sc.loss_fn; z.T = sc.T;
+  z.x_km1 = w.x_k; z.x_k = w.x_kp1;
+  z.x_kp1 = x_rel(c, sc.left_dir, 2);
+  z.Hprev = w.Hcur; z.Hcur = c->bigpipe.Pk;
+  z.Gprev = w.Gcur;
+  z.Gcur = env_rel(c, sc.left_dir, 3);
+  z.Bprev = c->Bnew;
+  z.y = c->y; z.f = c->f;
+  z.slabs = c->zslabs; z.slab_stride = c->zstride; z.bsize = (int)((size_t)D * h * D * D * nz.gnext * L);
+  launch_wide_tiled(z, sc.nblk, nz.lds_z, c->stream2);
+  launch_reduce(c->zslabs, sc.nblk, c->zstride, z.bsize + kMetricSlots, c->zred, c->stream2);
+  if (c->comm) NCCL_TRY(ncclAllReduce(c->zred, c->zred, z.bsize + kMetricSlots, ncclFloat, ncclSum, c->comm, c->stream2));
+  if (c->bigpipe.flags_enabled) { ++c->bigpipe.zsig_seq; if (!launch_big_signal(c->bigpipe.flags, c->bigpipe.zsig_seq, c->stream2)) return fail(TNML_ERR_HIP, "%s", big_launch_error()); }
+  HIP_TRY(hipEventRecord(c->bigpipe.ev_z, c->stream2));
+  c->bigpipe.pending = true;
+  c->bigpipe.Z.leave(sc, q.k + 1, true, D * h, D * D * nz.gnext * L);
+  c->sweep_launches += ext_in_front ? 2 : 3;
+  return TNML_OK;
+}
+
+// Large-tensor step, the chain through HBM: batch kernel + reduction (a step fed by Z has neither: its contraction rides in the
+// chain's first launch), then the update: seven launches in the factored form (front products [+ contraction, + next environment],
+// merged tensor + weight decay, update, Gram, Jacobi + replay + order, cores + T2, norm environment), eight with T = Nh^T . B.
+// f_stored: f of this step is stored by the batch kernel of the next one (launch_next_z).
+// (Kept apart from step_classic_lds: the two share fill_wide and the reduce / all-reduce lines only, and every line of the pipeline
+//  here would be a condition there.)
+static int step_big(tnml_ctx *c, const SweepCall &sc, const StepGeom &q, NarrowParams &n, bool &f_stored) {
+  const int D = c->D, L = c->L, k = q.k, g = q.g;
+  const bool whole = sc.mode == 0 && !sc.Bdirect_dev;         // a full sweep step on the product of the two cores
+  // is the reduced pre-gradient of THIS step waiting in zred (left there by the batch kernel that ran on stream2 beside the
+  // previous step's SVD)?
+  const bool zbig = whole && k >= 3 && c->bigpipe.Z.matches(sc, k) &&
+                    c->bigpipe.Z.cols == D * D * g * L && c->bigpipe.Z.rows == D * rel_bond(c, sc.left_dir, -2);
+  // (a step fed by Z does not wait for the side stream with an event: the workgroups of its first launch that need Z poll the
+  //  sequence number the side stream leaves behind its chain -- see big_signal_kernel; everything else of that launch starts at once)
+  const bool zpoll = zbig && c->bigpipe.flags_enabled && c->bigpipe.pending;
+  { int rc = split_join(c, zpoll); if (rc) return rc; }
+  drop_pregradients(c);
+  WideParams w{};
+  { int rc = fill_wide(c, w, q, sc); if (rc) return rc; }
+  w.stamps = c->stamps ? c->dbg + 4 * c->bmax + kDbgSigma + 5 + 17 : nullptr;
+  // The merged tensor and T = Nh^T . B need nothing this step's batch kernel produces -- they run on a second stream beside it
+  // (two of the chain's fourteen launches, 30 us of a 380 us C5 step), joined by an event before the weight-decay kernel reads them.
+  // (a step that takes its gradient from Z has no batch kernel to hide them behind: they stay on the context's stream, in front of
+  // the chain, and the two cross-queue hops -- 10 us each -- are saved)
+  const bool prep_ahead = whole && !zbig;
+  if (prep_ahead) {
+    { int rc = ensure_big(c); if (rc) return rc; }
+    HIP_TRY(hipEventRecord(c->ev_main, c->stream));                  // everything the previous step wrote
+    HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_main, 0));
+    if (!launch_narrow_big(n, c->big, c->stream2, c->check_launches, true, false)) return fail(TNML_ERR_HIP, "%s", big_launch_error());
+    HIP_TRY(hipEventRecord(c->ev_prep, c->stream2));
+  }
+  prof_begin(c);
+  BigFront front{};
+  if (zbig) {
+    // raw gradient = A_{k-1}^T . Z_k (+ the metric tail): no batch kernel, no slab reduction, no exchange on this stream; it rides
+    // in the launch that forms the merged tensor (run_narrow below)
+    front.Z = c->zred; front.A = w.ext_core; front.ncols = D * D * g * L; front.red = c->red;
+    if (zpoll) { front.poll_flag = c->bigpipe.flags; front.poll_want = c->bigpipe.zsig_seq; front.wait_ev = c->bigpipe.ev_z; }
+    prof_end(c, 1);
+    c->step_launches++;           // (counted with the single-launch steps: a step that took its gradient from Z)
+  } else {
+    bool prep_done = false;
+    if (!launch_wide(w, sc.nblk, nullptr, c->stream, &prep_done))
+      return fail(TNML_ERR_ARG, "step at sites (%d,%d): a 32-sample tile of this bond dimension does not fit the batch kernels' LDS", q.p, q.p + 1);
+    prof_end(c, 1);
+    prof_begin(c);
+    launch_reduce(c->slabs, sc.nblk, c->slab_stride, (int)q.bsize + kMetricSlots, c->red, c->stream);
+    prof_end(c, 2);
+    if (c->comm) NCCL_TRY(ncclAllReduce(c->red, c->red, q.bsize + kMetricSlots, ncclFloat, ncclSum, c->comm, c->stream));
+    c->sweep_launches += 2;
+  }
+  prof_begin(c);
+  if (prep_ahead) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_prep, 0));
+  const NextZ nz = plan_next_z(c, sc, q);
+  if (nz.on) { int rc = ensure_big(c); if (rc) return rc; }          // (the flag words of the hand-offs live with its scratch)
+  if (nz.on && !c->bigpipe.Pk) HIP_TRY(hipMalloc(&c->bigpipe.Pk, (size_t)D * c->Mmax * c->b_pad * sizeof(float)));
+  // (a step fed by Z launches no batch kernel of its own: the environment work for the NEXT step's batch kernel rides in this
+  //  step's first launch on this stream, and the side stream's chain starts with the batch kernel itself)
+  const bool ext_in_front = nz.on && zbig;
+  if (ext_in_front) {
+    front.ext_Eprev = w.Hprev; front.ext_x_km1 = w.x_km1; front.ext_x_k = w.x_k; front.ext_A = w.ext_core; front.b_pad = c->b_pad;
+    front.ext_Ecur = w.Hcur; front.ext_Pk = c->bigpipe.Pk;
+    front.ext_acquire = c->bigpipe.ext_on_side;
+  }
+  const bool bsig = nz.on && c->bigpipe.flags_enabled;
+  if (bsig) ++c->bigpipe.bsig_seq;
+  { int rc = run_narrow(c, n, 1, prep_ahead, nz.on ? c->bigpipe.ev_upd : nullptr, zbig ? &front : nullptr, bsig ? c->bigpipe.flags + 1 : nullptr, c->bigpipe.bsig_seq);
+    if (rc) return rc; }
+  prof_end(c, 3);
+  c->sweep_launches += (sc.Bdirect_dev || prep_ahead) ? 8 : 7;
+  if (zbig && !nz.on) {
+    // a step that took its gradient from Z launched no batch kernel, and none for the next step either: the behind environment
+    // E_k the next (classic) step extends has to be formed here
+    if (!launch_big_ext(w.Hprev, w.x_km1, w.x_k, w.ext_core, c->b_pad, w.Hcur, c->bigpipe.Pk, c->stream)) return fail(TNML_ERR_HIP, "%s", big_launch_error());
+    c->sweep_launches += 1;
+  }
+  if (nz.on) { int rc = launch_next_z(c, sc, q, w, nz, ext_in_front, bsig); if (rc) return rc; }
+  f_stored = nz.on;
+  return TNML_OK;
+}
 
 static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep, float lr, float weight_dec,
                       int l2_flag, int act_fn, int loss_fn, float T, int trunc_policy, float *metrics_out,
@@ -1824,7 +2226,6 @@ static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep
   // the stack behind a segment is rewritten from its first step on: finish_step marks it invalid once that step is planned (the
   // opposite direction then needs a forward again); a call that fails before it leaves both stacks as forward built them
   c->seg_starting = seg_start && mode == 0;
-  const int nblk = c->b_pad / kTS;
   hipEvent_t sw_ev1 = nullptr;
   if (c->sweep_timing && mode == 0) {
     if (c->sweep_ev_used + 2 > c->sweep_ev.size()) {
@@ -1836,301 +2237,47 @@ static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep
     sw_ev1 = c->sweep_ev[c->sweep_ev_used + 1];
     c->sweep_ev_used += 2;
   }
-  if (D != kD)
-    return sweep_anyd(c, left_dir, n_steps, lr, weight_dec, l2_flag, act_fn, loss_fn, T, trunc_policy, metrics_out, f_out, mode, Bdirect_dev,
-                      sw_ev1);
+  // (the generic-D batch kernel takes 64 samples per workgroup)
+  const SweepCall sc{left_dir, n_steps, lr, weight_dec, l2_flag, act_fn, loss_fn, T, trunc_policy, metrics_out, f_out, mode, Bdirect_dev,
+                     sw_ev1, seg_start, D != kD ? c->b_pad / kTS / 2 : c->b_pad / kTS};
+  if (D != kD) return sweep_anyd(c, sc);
 
   int done_persist = 0;
   if (mode == 0 && !Bdirect_dev && first_of_sweep) {
-    done_persist = sweep_persist(c, left_dir, n_steps, lr, weight_dec, l2_flag, act_fn, loss_fn, T, trunc_policy);
+    done_persist = sweep_persist(c, sc);
     if (done_persist < 0) return done_persist;
   }
+  const bool split = c->comm && c->split.enabled && !c->profile;      // a pipelined step goes out in two parts (launch_pipe_step_split)
   for (int step = 0; step < (done_persist ? 0 : n_steps); ++step) {
     const StepGeom q = step_geom(c, left_dir, trunc_policy);
     if (q.fail) return step_geom_error(c, q);
-    const int p = q.p, k = q.k, h = q.h, g = q.g, s = q.s, m = q.m, nn = q.nn;
-    const size_t bsize = q.bsize;
-    const int npath = narrow_path(c, h, g, s, L, m);
+    const int npath = narrow_path(c, q.h, q.g, q.s, L, q.m);
     if (npath < 0) return npath;
-    bool f_by_z = false;          // f of this step stored by the batch kernel of the next one (pipelined large-tensor step)
-
-    // ---- parameters of the narrow kernel (built first: the wide launch carries its slice workgroups) ---------
-    // single GPU + in-LDS path: the slab reduction rides in the narrow launch as helper workgroups (no separate
-    // reduce kernel, no boundary) and the merge / L2 products ride in the wide launch (or, with the plain-FMA wide
-    // kernel, in the narrow launch as well)
-    const bool prep_ok = npath == 0 && mode == 0 && !Bdirect_dev;     // merge / L2 slices in the wide launch
-    const bool fused = prep_ok && !c->comm;                           // + slab reduction in the narrow launch
+    // ---- the update record (built first: the wide launch carries its slice workgroups)
     NarrowParams n{};
-    fill_update(c, n, q, l2_flag, lr, weight_dec);
-    n.red = c->red;
-    n.out_ahead = c->lab[c->lab_cur ^ 1];
-    n.metrics = c->metrics + 2 * (size_t)step;
-    n.dbg = (c->debug || mode == 1) ? c->dbg : nullptr;
-    n.Bdirect = Bdirect_dev;
+    fill_step_update(c, n, q, sc, step, (c->debug || mode == 1) ? c->dbg : nullptr);
     n.chol_thr = c->chol_thr;
-    n.stop_after_update = mode == 1;
-    if (fused) {
-      n.fused = 1; n.slabs = c->slabs; n.nslabs = nblk; n.slab_stride = c->slab_stride;
-      n.nred = ((int)bsize + kMetricSlots + 63) / 64; n.red_out = c->red; n.sync = c->sync;
-    }
     n.prepB = c->prepB; n.prepG = c->prepG;
-    if (trunc_policy == TNML_TRUNC_ADAPTIVE && mode == 0) { n.trunc_thr = c->trunc_thr; n.left_dir = left_dir; n.m_out = c->status + 1; }
-    if (mode == 1) { n.Bnew = c->Bscr2; n.Nh_new = nullptr; }
-    n.stamps = (c->debug || c->stamps) ? c->dbg + 4 * c->bmax + kDbgSigma + 5 : nullptr;
-    // ---- pipelined step: ONE launch (update + SVD of step k next to the batch-side work of step k+1) ----------------
-    // (the first step of a segment takes the classic sequence: its behind environment is extended again from the stack forward
-    //  built, its f is forward's; the pipelined step resumes with the second step, from its own prologue)
-    bool pipe = c->pipe_enabled && prep_ok && !(seg_start && step == 0);
-    if (pipe && prep_slice_lds_bytes(h, g, s, L) > 160 * 1024) pipe = false;      // the slice workgroups of the launch must fit too
-    WidePipeParams wp{}, wpro{};
-    bool need_prologue = false;
-    if (pipe) {
-      fill_wide_pipe(c, wp, left_dir, k, act_fn, loss_fn, T);
-      wp.do_ext = k >= 1; wp.do_f = 1; wp.wait_flag = 1;
-      wp.do_z = (k + 1 <= N - 2);
-      if (wp.do_z && !wide_pipe_fits(c, wp)) wp.do_z = 0;            // the next step will start from its own prologue
-      pipe_try_one_level(wp);
-      if (wp.do_z && c->pipe_tiles > wp.tiles_per_wg && nn >= 32) {
-        // the SVD of this step is long (short side >= 32): a batch-side workgroup accumulates several sample tiles in
-        // registers before it writes its partial pre-gradient -- proportionally fewer partial tensors to write and re-read
-        wp.tiles_per_wg = c->pipe_tiles;
-        wp.nwide = (wp.ntiles + wp.tiles_per_wg - 1) / wp.tiles_per_wg;
-        wp.ngroups = (wp.nwide + kPipeGroupMax - 1) / kPipeGroupMax;
-      }
-      if (!wide_pipe_fits(c, wp)) pipe = false;
-      const bool zok = c->Z_valid && c->Z_k == k && c->Z_left == left_dir && c->Z_act == act_fn && c->Z_loss == loss_fn && c->Z_T == T;
-      if (pipe && !zok) {
-        fill_wide_pipe(c, wpro, left_dir, k - 1, act_fn, loss_fn, T);
-        wpro.do_ext = 0; wpro.wait_flag = 0; wpro.do_z = 1;
-        wpro.do_f = (k >= 1 && c->Bnew_valid && !c->f_current) ? 1 : 0;
-        if (wpro.do_f && (c->prev_h != wpro.hj || c->prev_g != wpro.gj))
-          return fail(TNML_ERR_STATE, "internal: previous-step dims (%d,%d) do not match (%d,%d)", c->prev_h, c->prev_g, wpro.hj, wpro.gj);
-        if (!wide_pipe_fits(c, wpro)) pipe = false; else need_prologue = true;
-      }
+    if (slices_ride(sc, npath) && !c->comm) {        // + slab reduction in the narrow launch (a pipelined launch keeps the slab fields as they are)
+      n.fused = 1; n.slabs = c->slabs; n.nslabs = sc.nblk; n.slab_stride = c->slab_stride;
+      n.nred = ((int)q.bsize + kMetricSlots + 63) / 64; n.red_out = c->red; n.sync = c->sync;
     }
-    // Communicator path (batch shards over the ranks): the pre-gradient Z_{k+1} is final ~25 us into a ~57 us step, but behind
-    // a fused launch its all-reduce could only start when the SVD of step k has ended -- on the critical path of every step.
-    // So the step is launched in two parts: the update side (workgroup 0 + slice helpers) on the context's stream, the
-    // batch side on stream2 followed by the all-reduce, which then travels beside the SVD; the next update launch waits
-    // for its event.  Same kernels, same arithmetic as the fused launch (the B_new hand-off is a flag in memory either way).
-    const bool split = pipe && c->comm && c->split_enabled && !c->profile;
-    if (pipe) {
-      if (!split) { int rc = split_join(c); if (rc) return rc; }
-      else {
-        if (c->split_flags_enabled && !c->splitflags) {
-          HIP_TRY(hipMalloc(&c->splitflags, 4 * sizeof(unsigned)));
-          HIP_TRY(hipMemsetAsync(c->splitflags, 0, 4 * sizeof(unsigned), c->stream));
-        }
-        if (!c->split_pending) {                 // first split step after anything else: stream2 starts behind the context's stream
-          c->split_upd ^= 1;
-          HIP_TRY(hipEventRecord(c->ev_upd[c->split_upd], c->stream));
-          c->split_done_valid = false; c->split_zsig_valid = false;
-        }
-      }
-      if (need_prologue) {
-        NarrowParams none{};
-        wpro.wg0 = 0;
-        if (split) { int rc = split_wait_update(c); if (rc) return rc; }
-        prof_begin(c);
-        launch_step_pipe(none, wpro, wide_pipe_lds_bytes(wpro), split ? c->stream2 : c->stream);
-        prof_end(c, 1);
-        c->sweep_launches++; c->step_launches++;
-        if (split) { int rc = split_exchange(c, wpro.zsize); if (rc) return rc; }
-        else if (c->comm) NCCL_TRY(ncclAllReduce(c->zred, c->zred, wpro.zsize + kMetricSlots, ncclFloat, ncclSum, c->comm, c->stream));
-        if (wpro.do_f) c->f_current = true;
-      }
-      // merged tensor / L2 term of this step: from the slice workgroups this launch carries (a slice of more than 8 rows is
-      // cut into two row parts: twice the workgroups, half the dependent tiles in each).  (Measured, round 2: preparing them
-      // at the end of the PREVIOUS launch inside workgroup 0 cost it 23 k cycles and saved 16 k of waiting -- removed.)
-      n.fused = 1; n.nred = 0; n.sync = c->sync; n.red_out = nullptr;
-      n.prep_ready = 0;
-      n.wait_count = kD * kD * (h > 8 ? 2 : 1);
-      n.pipe = 1; n.z_first = (k == 0); n.z_rows = wp.hprev * D;
-      n.zsize = (k == 0 ? 1 : n.z_rows) * D * D * g * L;
-      n.zred = c->zred; n.red = c->zred; n.zcore = wp.ext_core;
-      n.flag = c->pipe_cnt + 17; n.token = ++c->token;
-      wp.token = n.token;
-      wp.wg0 = 1 + n.wait_count;
-      const size_t lds_u = std::max(narrow_lds_bytes(h, g, s, L, m), prep_slice_lds_bytes(h, g, s, L));
-      const size_t lds_b = wide_pipe_lds_bytes(wp);
-      if (split) {
-        if (lds_u > 160 * 1024 || lds_b > 160 * 1024) return fail(TNML_ERR_ARG, "internal: pipelined step needs %zu / %zu bytes of LDS", lds_u, lds_b);
-        const bool sflags = c->split_flags_enabled;
-        // batch side of step k: needs the behind core the update launch of step k-1 left, then B_new(k) (flag in memory)
-        { int rc = split_wait_update(c); if (rc) return rc; }
-        {
-          NarrowParams none{};
-          WidePipeParams wb = wp;
-          wb.wg0 = 0;
-          launch_step_pipe(none, wb, lds_b, c->stream2);
-        }
-        // update side of step k: needs Z_k summed over the ranks (the exchange enqueued behind the previous batch-side launch)
-        if (c->split_pending) {
-          if (sflags && c->split_zsig_valid) { n.zpoll_flag = c->splitflags; n.zpoll_want = c->split_zseq; }
-          else HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_bat[c->split_bat], 0));
-        }
-        if (sflags) { n.done_flag = c->splitflags + 1; n.done_val = ++c->split_dseq; }
-        launch_step_pipe_update(n, wp, lds_u, c->stream);
-        if (sflags) c->split_done_valid = true;
-        else {
-          c->split_upd ^= 1;
-          HIP_TRY(hipEventRecord(c->ev_upd[c->split_upd], c->stream));
-        }
-        { int rc = split_exchange(c, wp.do_z ? wp.zsize : -1); if (rc) return rc; }
-        c->sweep_launches += 2; c->step_launches++;
-      } else {
-        const size_t lds = std::max(lds_u, lds_b);
-        if (lds > 160 * 1024) return fail(TNML_ERR_ARG, "internal: pipelined step needs %zu bytes of LDS", lds);
-        prof_begin(c);
-        launch_step_pipe(n, wp, lds, c->stream);
-        prof_end(c, 3);
-        c->sweep_launches++; c->step_launches++;
-        if (c->comm && wp.do_z) NCCL_TRY(ncclAllReduce(c->zred, c->zred, wp.zsize + kMetricSlots, ncclFloat, ncclSum, c->comm, c->stream));
-      }
-      c->Zbig_valid = false;
-      c->Z_valid = wp.do_z != 0; c->Z_k = k + 1; c->Z_left = left_dir; c->Z_act = act_fn; c->Z_loss = loss_fn; c->Z_T = T;
-    } else {
-      // pipelined large-tensor step: is the reduced pre-gradient of THIS step waiting in zred (left there by the batch kernel that
-      // ran on stream2 beside the previous step's SVD)?
-      bool zbig = false;
-      if (c->Zbig_valid && k >= 3 && c->Zbig_k == k && c->Zbig_left == left_dir && c->Zbig_act == act_fn && c->Zbig_loss == loss_fn && c->Zbig_T == T &&
-          npath == 1 && mode == 0 && !Bdirect_dev)
-        zbig = c->Zbig_cols == D * D * g * L && c->Zbig_rows == D * rel_bond(c, left_dir, -2);
-      // (a step fed by Z does not wait for the side stream with an event: the workgroups of its first launch that need Z poll the
-      //  sequence number the side stream leaves behind its chain -- see big_signal_kernel; everything else of that launch starts at once)
-      const bool zpoll = zbig && c->bigflags_enabled && c->zbig_pending;
-      { int rc = split_join(c, zpoll); if (rc) return rc; }
-      c->Z_valid = false; c->Zbig_valid = false;
-      // ---- wide kernel -----------------------------------------------------------------------
-      WideParams w{};
-      { int rc = fill_wide(c, w, q, act_fn, loss_fn, T); if (rc) return rc; }
-      w.stamps = c->stamps ? c->dbg + 4 * c->bmax + kDbgSigma + 5 + 17 : nullptr;
-      PrepParams prep{};
-      prep.lab = n.lab; prep.pl = n.pl; prep.Nh = n.Nh; prep.Ng = n.Ng; prep.h = h; prep.g = g; prep.s = s; prep.L = L;
-      prep.l2_flag = n.l2_flag; prep.prepB = c->prepB; prep.prepG = c->prepG;
-      // Large-tensor step: the merged tensor and T = Nh^T . B need nothing this step's batch kernel produces -- they run on
-      // a second stream beside it (two of the chain's fourteen launches, 30 us of a 380 us C5 step), joined by an event
-      // before the weight-decay kernel reads them.
-      // (a step that takes its gradient from Z has no batch kernel to hide them behind: they stay on the context's stream, in front of
-      // the chain, and the two cross-queue hops -- 10 us each -- are saved)
-      bool prep_ahead = false;
-      if (npath == 1 && mode == 0 && !Bdirect_dev && !zbig) {
-        { int rc = ensure_big(c); if (rc) return rc; }
-        HIP_TRY(hipEventRecord(c->ev_main, c->stream));                  // everything the previous step wrote
-        HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_main, 0));
-        if (!launch_narrow_big(n, c->big, c->stream2, c->check_launches, true, false)) return fail(TNML_ERR_HIP, "%s", big_launch_error());
-        HIP_TRY(hipEventRecord(c->ev_prep, c->stream2));
-        prep_ahead = true;
-      }
-      prof_begin(c);
-      bool prep_done = false;
-      BigFront front{};
-      if (zbig) {
-        // raw gradient = A_{k-1}^T . Z_k (+ the metric tail): no batch kernel, no slab reduction, no exchange on this stream; it rides
-        // in the launch that forms the merged tensor (run_narrow below)
-        front.Z = c->zred; front.A = w.ext_core; front.ncols = D * D * g * L; front.red = c->red;
-        if (zpoll) { front.poll_flag = c->bigflags; front.poll_want = c->zsig_seq; front.wait_ev = c->ev_zbig; }
-      } else if (!launch_wide(w, nblk, prep_ok ? &prep : nullptr, c->stream, &prep_done))
-        return fail(TNML_ERR_ARG, "step at sites (%d,%d): a 32-sample tile of this bond dimension does not fit the batch kernels' LDS", p, p + 1);
-      n.prep_ready = prep_done ? 1 : 0;
-      // slices the batch launch could not host would ride in the update launch -- unless they do not fit a workgroup's LDS
-      // either (bond 64 next to a chain end at three labels): then the update workgroup forms B and Ln.B.Rn itself, which
-      // the launch does only un-fused (separate reduction)
-      bool fused_now = fused;
-      if (fused_now && !prep_done && prep_slice_lds_bytes(h, g, s, L) > 160 * 1024) { fused_now = false; n.fused = 0; n.nred = 0; }
-      if (n.fused) n.wait_count = n.nred + (n.prep_ready ? 0 : kD * kD);
-      prof_end(c, 1);
-      // ---- reduce (+ all-reduce over the batch shards) -----------------------------------------
-      if (!fused_now && !zbig) {
-        prof_begin(c);
-        launch_reduce(c->slabs, nblk, c->slab_stride, (int)bsize + kMetricSlots, c->red, c->stream);
-        prof_end(c, 2);
-      }
-      if (c->comm && !zbig) NCCL_TRY(ncclAllReduce(c->red, c->red, bsize + kMetricSlots, ncclFloat, ncclSum, c->comm, c->stream));
-      prof_begin(c);
-      if (prep_ahead) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_prep, 0));
-      // ---- pipelined large-tensor step: may the batch kernel of step k+1 run beside the SVD of this one? ----------------------
-      // Needs: the next step is a large-tensor step too, both environments exist as arrays (k >= 2, an ahead environment two sites
-      // on), the tiled batch kernel takes the doubled row operand (h -> D h), the slabs of Z fit the pre-gradient scratch.
-      bool next_z = false;
-      int gnext = 0;
-      size_t lds_z = 0;
-      if (c->bigpipe_enabled && c->pipe_enabled && npath == 1 && mode == 0 && !Bdirect_dev && !c->debug && !c->profile && trunc_policy != TNML_TRUNC_ADAPTIVE &&
-          k >= 2 && k + 1 <= N - 2 && nblk <= c->pipe_nwide) {
-        const int pn = std::min(q.sa, rel_site(c, left_dir, 2));   // sites (pn, pn + 1) of step k+1; g is the bond the two steps share
-        gnext = rel_bond(c, left_dir, 2);
-        const int mnext = tnml_trunc_rank(trunc_policy, left_dir, pn, N, left_dir ? gnext : m, D, left_dir ? m : gnext, L, c->Mpol);
-        const size_t zs = (size_t)D * h * D * D * gnext * L;
-        lds_z = wide_tiled_lds_bytes(L, D * h, h, g, gnext, false);      // (its launch extends no environment and hands Hcur in)
-        next_z = mnext > 0 && narrow_path(c, m, gnext, g, L, mnext) == 1 && zs + kMetricSlots <= (size_t)c->zstride &&
-                 lds_z > 0 && lds_z <= 160 * 1024 && D * h <= 2 * c->Mmax && (size_t)D * h * c->b_pad <= (size_t)2 * c->Mmax * c->b_pad;
-      }
-      if (next_z) { int rc = ensure_big(c); if (rc) return rc; }          // (the flag words of the hand-offs live with its scratch)
-      if (next_z && !c->bigPk) HIP_TRY(hipMalloc(&c->bigPk, (size_t)D * c->Mmax * c->b_pad * sizeof(float)));
-      // (a step fed by Z launches no batch kernel of its own: the environment work for the NEXT step's batch kernel rides in this
-      //  step's first launch on this stream, and the side stream's chain starts with the batch kernel itself)
-      const bool ext_in_front = next_z && zbig;
-      if (ext_in_front) {
-        front.ext_Eprev = w.Hprev; front.ext_x_km1 = w.x_km1; front.ext_x_k = w.x_k; front.ext_A = w.ext_core; front.b_pad = c->b_pad;
-        front.ext_Ecur = w.Hcur; front.ext_Pk = c->bigPk;
-        front.ext_acquire = c->ext_on_side;
-      }
-      const bool bsig = next_z && c->bigflags_enabled;
-      if (bsig) ++c->bsig_seq;
-      { int rc = run_narrow(c, n, npath, prep_ahead, next_z ? c->ev_upd_big : nullptr, zbig ? &front : nullptr, bsig ? c->bigflags + 1 : nullptr, c->bsig_seq);
-        if (rc) return rc; }
-      prof_end(c, 3);
-      if (zbig && !next_z) {
-        // a step that took its gradient from Z launched no batch kernel, and none for the next step either: the behind environment
-        // E_k the next (classic) step extends has to be formed here
-        if (!launch_big_ext(w.Hprev, w.x_km1, w.x_k, w.ext_core, c->b_pad, w.Hcur, c->bigPk, c->stream)) return fail(TNML_ERR_HIP, "%s", big_launch_error());
-        c->sweep_launches += 1;
-      }
-      if (next_z) {
-        // stream2, behind B_new(k): E_k and P'_k = E_k (x) x_k; then the tiled batch kernel "of step k+1" with P'_k in the place of its
-        // behind environment (D h rows): f of step k from B_new(k) and the slabs of Z_{k+1}; their sum; the exchange.
-        if (bsig) { if (!launch_big_gate(c->bigflags + 1, c->bsig_seq, c->status, c->stream2)) return fail(TNML_ERR_HIP, "%s", big_launch_error()); }
-        else HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_upd_big, 0));
-        c->ext_on_side = !ext_in_front;
-        if (!ext_in_front && !launch_big_ext(w.Hprev, w.x_km1, w.x_k, w.ext_core, c->b_pad, w.Hcur, c->bigPk, c->stream2)) return fail(TNML_ERR_HIP, "%s", big_launch_error());
-        WideParams z{};
-        z.b = c->b; z.b_pad = c->b_pad; z.L = L;
-        z.h = D * h; z.g = gnext; z.hp = h; z.gp = g;
-        z.do_f = 1; z.do_ext = 0; z.first_ext = 0;
-        z.act_fn = act_fn; z.loss_fn = loss_fn; z.T = T;
-        z.x_km1 = w.x_k; z.x_k = w.x_kp1;
-        z.x_kp1 = x_rel(c, left_dir, 2);
-        z.Hprev = w.Hcur; z.Hcur = c->bigPk;
-        z.Gprev = w.Gcur;
-        z.Gcur = env_rel(c, left_dir, 3);
-        z.Bprev = c->Bnew;
-        z.y = c->y; z.f = c->f;
-        z.slabs = c->zslabs; z.slab_stride = c->zstride; z.bsize = (int)((size_t)D * h * D * D * gnext * L);
-        launch_wide_tiled(z, nblk, lds_z, c->stream2);
-        launch_reduce(c->zslabs, nblk, c->zstride, z.bsize + kMetricSlots, c->zred, c->stream2);
-        if (c->comm) NCCL_TRY(ncclAllReduce(c->zred, c->zred, z.bsize + kMetricSlots, ncclFloat, ncclSum, c->comm, c->stream2));
-        if (c->bigflags_enabled) { ++c->zsig_seq; if (!launch_big_signal(c->bigflags, c->zsig_seq, c->stream2)) return fail(TNML_ERR_HIP, "%s", big_launch_error()); }
-        HIP_TRY(hipEventRecord(c->ev_zbig, c->stream2));
-        c->zbig_pending = true;
-        c->Zbig_valid = true; c->Zbig_k = k + 1; c->Zbig_left = left_dir; c->Zbig_act = act_fn; c->Zbig_loss = loss_fn; c->Zbig_T = T;
-        c->Zbig_rows = D * h; c->Zbig_cols = D * D * gnext * L;
-        c->sweep_launches += ext_in_front ? 2 : 3;
-        f_by_z = true;
-      }
-      // batch kernel + reduction (a step fed by Z has neither: its contraction rides in the chain's first launch), then the update:
-      // one launch in LDS; through HBM seven in the factored form (front products [+ contraction, + next environment], merged tensor +
-      // weight decay, update, Gram, Jacobi + replay + order, cores + T2, norm environment), eight with T = Nh^T . B
-      c->sweep_launches += (zbig ? 0 : ((fused_now && npath == 0) ? 1 : 2)) + (npath == 1 ? ((Bdirect_dev || prep_ahead) ? 8 : 7) : 1);
-      if (zbig) c->step_launches++;           // (counted with the single-launch steps: a step that took its gradient from Z)
-      c->last_bsize = (int)bsize; c->last_n = nn; c->last_h = h; c->last_g = g; c->last_left_dir = left_dir;
-      if (mode == 1) return finish_update_only(c, metrics_out);
-    }
-    // (the batch-side work of a pipelined step stored f of this step already)
-    { int rc = finish_step(c, q, trunc_policy, step, pipe || f_by_z); if (rc) return rc; }
+    // ---- one of the four paths
+    PipePlan pp{};
+    const int piped = plan_pipe_step(c, sc, q, step, npath, pp);
+    if (piped < 0) return piped;
+    bool f_stored = piped != 0;      // (the batch-side work of a pipelined step stored f of this step already)
+    int rc;
+    if (piped) rc = split ? launch_pipe_step_split(c, sc, q, n, pp) : launch_pipe_step_fused(c, sc, q, n, pp);
+    else if (npath == 0) rc = step_classic_lds(c, sc, q, n);
+    else rc = step_big(c, sc, q, n, f_stored);
+    if (rc) return rc;
+    if (mode == 1) return finish_update_only(c, q, metrics_out);
+    if ((rc = finish_step(c, q, sc, step, f_stored))) return rc;
   }
   HIP_TRY(hipGetLastError());
   { int rc = split_join(c); if (rc) return rc; }
-  return finish_sweep(c, left_dir, n_steps, l2_flag, nblk, sw_ev1, metrics_out, f_out);
+  return finish_sweep(c, sc);
 }
 
 extern "C" int tnml_sweep(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep, float lr, float weight_dec,
@@ -2293,13 +2440,11 @@ static int standalone_anyd(tnml_ctx *c, NarrowParams &n) {
   return TNML_OK;
 }
 
-static int sweep_anyd(tnml_ctx *c, int left_dir, int n_steps, float lr, float weight_dec, int l2_flag, int act_fn, int loss_fn, float T,
-                      int trunc_policy, float *metrics_out, float *f_out, int mode, const float *Bdirect_dev, hipEvent_t sw_ev1) {
-  const int D = c->D, L = c->L;
-  const int nblk = c->b_pad / kTS / 2;                       // 64 samples per batch-side workgroup
+static int sweep_anyd(tnml_ctx *c, const SweepCall &sc) {
+  const int D = c->D, L = c->L, nblk = sc.nblk;              // (64 samples per batch-side workgroup)
   { int rc = anyd_scratch(c); if (rc) return rc; }
-  for (int step = 0; step < n_steps; ++step) {
-    const StepGeom q = step_geom(c, left_dir, trunc_policy);
+  for (int step = 0; step < sc.n_steps; ++step) {
+    const StepGeom q = step_geom(c, sc.left_dir, sc.trunc_policy);
     if (q.fail) return step_geom_error(c, q);
     const int p = q.p, h = q.h, g = q.g;
     if (q.nn > kBigMaxN)
@@ -2307,7 +2452,7 @@ static int sweep_anyd(tnml_ctx *c, int left_dir, int n_steps, float lr, float we
                   kBigMaxN, kBigMaxN);
     // ---- batch side: f of the previous step, activation / metrics, behind environment, gradient slabs ----
     WideParams w{};
-    { int rc = fill_wide(c, w, q, act_fn, loss_fn, T); if (rc) return rc; }
+    { int rc = fill_wide(c, w, q, sc); if (rc) return rc; }
     prof_begin(c);
     if (!launch_batch_anyd(w, D, nblk, true, c->stream))
       return fail(TNML_ERR_ARG, "step at sites (%d,%d): the batch kernel at D = %d needs %zu bytes of LDS", p, p + 1, D,
@@ -2316,30 +2461,20 @@ static int sweep_anyd(tnml_ctx *c, int left_dir, int n_steps, float lr, float we
     prof_begin(c);
     launch_reduce(c->slabs, nblk, c->slab_stride, (int)q.bsize + kMetricSlots, c->red, c->stream);
     prof_end(c, 2);
-    // ---- update side (chol_thr stays 0: the generic-D update kernel has no Cholesky step) ----
+    // ---- update side (chol_thr stays 0: the generic-D update kernel has no Cholesky step; the capture block is its workspace) ----
     NarrowParams n{};
-    fill_update(c, n, q, l2_flag, lr, weight_dec);
-    n.red = c->red;
-    n.out_ahead = c->lab[c->lab_cur ^ 1];
-    n.metrics = c->metrics + 2 * (size_t)step;
-    n.dbg = c->dbg;                              // the capture block is the update kernel's workspace
-    n.stamps = (c->debug || c->stamps) ? c->dbg + 4 * c->bmax + kDbgSigma + 5 : nullptr;
-    n.Bdirect = Bdirect_dev;
-    n.stop_after_update = mode == 1;
-    if (trunc_policy == TNML_TRUNC_ADAPTIVE && mode == 0) { n.trunc_thr = c->trunc_thr; n.left_dir = left_dir; n.m_out = c->status + 1; }
-    if (mode == 1) { n.Bnew = c->Bscr2; n.Nh_new = nullptr; }
+    fill_step_update(c, n, q, sc, step, c->dbg);
     prof_begin(c);
     if (!launch_update_anyd(n, c->anyd_W, c->anyd_T2, c->stream))
       return fail(TNML_ERR_ARG, "step at sites (%d,%d): update kernel at D = %d refused a %d x %d matrix", p, p + 1, D, D * h, D * g * L);
     prof_end(c, 3);
     c->sweep_launches += 3;
-    c->last_bsize = (int)q.bsize; c->last_n = q.nn; c->last_h = h; c->last_g = g; c->last_left_dir = left_dir;
-    if (mode == 1) return finish_update_only(c, metrics_out);
-    { int rc = finish_step(c, q, trunc_policy, step, false); if (rc) return rc; }
-    c->Z_valid = false; c->Zbig_valid = false;
+    if (sc.mode == 1) return finish_update_only(c, q, sc.metrics_out);
+    { int rc = finish_step(c, q, sc, step, false); if (rc) return rc; }
+    drop_pregradients(c);
   }
   HIP_TRY(hipGetLastError());
-  return finish_sweep(c, left_dir, n_steps, l2_flag, nblk, sw_ev1, metrics_out, f_out);
+  return finish_sweep(c, sc);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2403,7 +2538,7 @@ extern "C" int tnml_comm_probe(tnml_ctx *c, int n_floats, int reps, double *us_p
 
 extern "C" int tnml_set_comm_overlap(tnml_ctx *c, int on) {
   if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
-  c->split_enabled = on != 0;
+  c->split.enabled = on != 0;
   return TNML_OK;
 }
 
@@ -2412,8 +2547,8 @@ extern "C" int tnml_set_flag_handoffs(tnml_ctx *c, int on) {
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));          // nothing of either form in flight while the form changes
   if (c->stream2) HIP_TRY(hipStreamSynchronize(c->stream2));
-  c->bigflags_enabled = on != 0; c->split_flags_enabled = on != 0;
-  c->split_done_valid = false; c->split_zsig_valid = false;
+  c->bigpipe.flags_enabled = on != 0; c->split.flags_enabled = on != 0;
+  c->split.done_valid = false; c->split.zsig_valid = false;
   return TNML_OK;
 }
 
@@ -2432,10 +2567,10 @@ extern "C" int tnml_set_chain_path(tnml_ctx *c, int force_plain) {
 
 extern "C" int tnml_set_step_pipeline(tnml_ctx *c, int on) {
   if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
-  c->pipe_enabled = on != 0;
-  c->bigpipe_enabled = on != 0;
-  c->pipe_tiles = on >= 2 ? on : (on == 1 ? 2 : 1);
-  c->Z_valid = false; c->Zbig_valid = false;
+  c->pipe.enabled = on != 0;
+  c->bigpipe.enabled = on != 0;
+  c->pipe.tiles = on >= 2 ? on : (on == 1 ? 2 : 1);
+  drop_pregradients(c);
   return TNML_OK;
 }
 
