@@ -98,7 +98,12 @@ int tnml_set_comm_overlap(tnml_ctx *ctx, int on);
 int tnml_comm_probe(tnml_ctx *ctx, int n_floats, int reps, double *us_per_allreduce);
 
 /* ---- parameters ------------------------------------------------------------------------- */
-/* replaces assignments to Network.As / Network.l_pos */
+/* replaces assignments to Network.As / Network.l_pos
+ * cores_flat: the N cores one after another, (ml, D, mr) row-major, the one on site l_pos (ml, D, mr, L); bond[i] joins sites i
+ * and i + 1.  Every bond must lie in [1, capacity], where capacity = max(M, D * min(L, M)) for the M given to tnml_create (the
+ * reference truncation policy legitimately reaches D * min(L, M) next to a chain end).  A bond above the capacity is refused
+ * with TNML_ERR_ARG even where both cores next to it fit their slots -- the environment slots, and the tiles of the chain
+ * kernels, hold `capacity` rows.  A refused call leaves the context's cores, bonds and label position as they were. */
 int tnml_set_cores(tnml_ctx *ctx, const float *cores_flat, size_t n_floats, const int32_t *bond,
                    int l_pos);
 int tnml_cores_size(tnml_ctx *ctx, size_t *n_floats);

@@ -147,6 +147,29 @@ static void run_entry_points(int N, int M, int b, int L) {
   OK(tnml_set_cores(ctx, cores.data(), total, bond.data(), 0));
   FAILS(tnml_set_cores(ctx, cores.data(), total - 1, bond.data(), 0));          // size does not match the bonds
   FAILS(tnml_set_cores(ctx, cores.data(), total, bond.data(), N));              // label site out of range
+  {
+    // a bond above the capacity between two cores that are narrow on their other side: either core fits its slot, the bond does not
+    const int cap = M > D * (L < M ? L : M) ? M : D * (L < M ? L : M);
+    for (int at = 0; at < 2; ++at) {                                             // next to the label site, and one bond further on
+      std::vector<int> wide(N - 1, 1);
+      wide[at] = cap + 1;
+      size_t n = 0;
+      for (int i = 0; i < N; ++i) n += (size_t)(i == 0 ? 1 : wide[i - 1]) * D * (i == N - 1 ? 1 : wide[i]) * (i == 0 ? L : 1);
+      std::vector<float> narrow(n, 0.05f);
+      FAILS(tnml_set_cores(ctx, narrow.data(), n, wide.data(), 0));
+      if (!strstr(tnml_last_error(), "exceeds the capacity")) { fprintf(stderr, "refused for another reason: %s\n", tnml_last_error()); exit(1); }
+    }
+    {
+      std::vector<int> none(N - 1, 1);                                           // ... and the lower end of the rule: a bond of 0
+      none[1] = 0;
+      std::vector<float> few((size_t)D * (L + N), 0.05f);
+      FAILS(tnml_set_cores(ctx, few.data(), few.size(), none.data(), 0));
+      if (!strstr(tnml_last_error(), "bond dimension < 1")) { fprintf(stderr, "refused for another reason: %s\n", tnml_last_error()); exit(1); }
+    }
+    size_t kept = 0;                                                             // the context keeps the cores it had
+    OK(tnml_cores_size(ctx, &kept));
+    if (kept != total || tnml_l_pos(ctx) != 0) { fprintf(stderr, "a refused tnml_set_cores changed the context\n"); exit(1); }
+  }
   std::vector<float> X((size_t)b * N * D, 0.5f), f((size_t)L * b), act((size_t)L * b), der((size_t)L * b);
   std::vector<int> y(b, 0);
   FAILS(tnml_forward(ctx, f.data()));                                           // no batch yet

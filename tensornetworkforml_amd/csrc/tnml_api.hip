@@ -489,6 +489,12 @@ extern "C" int tnml_set_cores(tnml_ctx *c, const float *flat, size_t n_floats, c
   if (l_pos < 0 || l_pos >= c->N) return fail(TNML_ERR_ARG, "l_pos %d out of range", l_pos);
   HIP_TRY(hipSetDevice(c->device));
   std::vector<int> nb(bond, bond + c->N - 1);
+  // every buffer indexed by a bond (environment slots of Mmax rows, the LDS tiles and operand layouts of the chain kernels, the
+  // norm environments) is sized by the capacity; a core that is narrow on its other side would pass the size check below
+  for (int i = 0; i < c->N - 1; ++i)
+    if (nb[i] > c->Mmax)
+      return fail(TNML_ERR_ARG, "bond %d between sites %d and %d exceeds the capacity %d of this context (created with M = %d)",
+                  nb[i], i, i + 1, c->Mmax, c->Mpol);
   size_t total = 0;
   for (int i = 0; i < c->N; ++i) {
     const int ml = i == 0 ? 1 : nb[i - 1], mr = i == c->N - 1 ? 1 : nb[i];
