@@ -81,6 +81,9 @@ int tnml_device_count(void);
  * and the same limit (short side of the matricised merged tensor <= 128: bond <= 42 at D = 3, <= 32 at D = 4, <= 16 at
  * D = 8).  On a D != 2 context tnml_set_persistent, tnml_set_step_pipeline, tnml_set_chain_path and tnml_set_narrow_path
  * accept their arguments and have no effect, and tnml_comm_init returns TNML_ERR_STATE (multi-GPU is D = 2 only). */
+/* A call that fails with TNML_ERR_HIP because an allocation failed leaves the context usable: it holds no half-sized buffer, and the
+ * call may be made again (a sweep that stopped inside the chain: from tnml_set_cores on).  A failed tnml_create leaves *out NULL and
+ * nothing allocated. */
 int tnml_create(tnml_ctx **out, int N, int D, int L, int Mmax, int b_capacity, int device);
 int tnml_destroy(tnml_ctx *ctx);
 int tnml_synchronize(tnml_ctx *ctx);

@@ -10,6 +10,8 @@
 //   * with TNML_SAN_TRACE=<file>, every runtime call is written there as one line of text, in call order: launches with every argument
 //     (the planners' structs field by field, record arrays and site tables on continuation lines), copies, memsets, all-reduces, event
 //     and stream calls; device pointers as offsets from the arena base, streams and events by their order of creation.
+//   * san_stub_fail_alloc(n) makes the n-th allocation call from now on fail once: the mains fail every allocation of a call in turn
+//     (san/fail_each.h) and the final "live allocations" count, with LeakSanitizer behind it, shows what a failed call left behind.
 // A violation prints what and where and aborts.  Test infrastructure only; never linked into libtnml_hip.so.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -39,6 +41,13 @@ static std::map<std::string, long> &launch_map() { static auto *m = new std::map
 #define g_kernels kernel_map()
 #define g_launches launch_map()
 static long g_checked_ptrs = 0, g_allreduces = 0;
+// injected failure: the allocation call (hipMalloc / hipHostMalloc) with this number returns hipErrorOutOfMemory, once (0: none)
+static long g_alloc_calls = 0, g_fail_call = 0;
+static bool alloc_fails() {
+  if (++g_alloc_calls != g_fail_call) return false;
+  g_fail_call = 0;
+  return true;
+}
 static const char *g_ctx = "";
 
 [[noreturn]] static void die(const char *fmt, ...) {
@@ -447,6 +456,7 @@ hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t s
 
 // ---- memory ----------------------------------------------------------------------------------------------------------------------
 hipError_t hipMalloc(void **p, size_t n) {
+  if (alloc_fails()) return hipErrorOutOfMemory;
   if (!g_base) {
     g_base = (char *)mmap(nullptr, kArena, PROT_NONE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
     if (g_base == MAP_FAILED) { perror("mmap"); abort(); }
@@ -469,7 +479,7 @@ hipError_t hipFree(void *p) {
   g_alloc.erase(it);
   return hipSuccess;
 }
-hipError_t hipHostMalloc(void **p, size_t n, unsigned) { *p = malloc(n); return *p ? hipSuccess : hipErrorOutOfMemory; }
+hipError_t hipHostMalloc(void **p, size_t n, unsigned) { if (alloc_fails()) return hipErrorOutOfMemory; *p = malloc(n); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipHostFree(void *p) { free(p); return hipSuccess; }
 static void copy_checked(void *d, const void *s, size_t n, hipMemcpyKind k, const char *what) {
   g_ctx = what;
@@ -557,5 +567,9 @@ long san_stub_launches(const char *substr) {
   for (auto &kv : g_launches) if (kv.first.find(substr) != std::string::npos) n += kv.second;
   return n;
 }
+long san_stub_alloc_calls(void) { return g_alloc_calls; }
+// the nth allocation call from now on fails once (0: withdraw a failure that has not fired); pending: it has not fired yet
+void san_stub_fail_alloc(long nth) { g_fail_call = nth > 0 ? g_alloc_calls + nth : 0; }
+int san_stub_fail_pending(void) { return g_fail_call != 0; }
 void san_stub_poke_int(void *dev, int v) { need(dev, 4, "poke"); memcpy(dev, &v, 4); }
 }

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../tnml_internal.h"
+#include "fail_each.h"
 
 using namespace tnml;
 
@@ -292,6 +293,36 @@ static void run_limits() {
   fflush(stdout);
 }
 
+// Failed allocations (injected by the stand-in, see fail_each.h): the scratch of the update kernel is two buffers allocated on first
+// use, from a sweep or from a standalone sub-step -- a failure of either leaves none, and the call repeated plans its launches with
+// both; then the batch group grows under failure and a sweep is planned over the new buffers
+static void run_alloc_failures() {
+  const int N = 6, D = 3, L = 2, M = 6, b = 64, b2 = 300;
+  std::vector<float> X, f((size_t)L * b2), met((size_t)2 * (N - 1));
+  std::vector<int> y;
+  auto sweep = [&](tnml_ctx *ctx) {
+    return tnml_sweep(ctx, tnml_l_pos(ctx) == N - 1, N - 1, 1, 1e-3f, 1e-3f, 1, TNML_ACT_SOFTMAX, TNML_LOSS_FULL_CROSS_ENT, 0.1f, TNML_TRUNC_FIXED, met.data(), f.data());
+  };
+  tnml_ctx *ctx = make(N, D, L, M, b, X, y);
+  OK(tnml_forward(ctx, f.data()));
+  fail_each_alloc("first generic-D sweep", [&] { return sweep(ctx); });
+  std::vector<float> X2((size_t)b2 * N * D, 0.5f);
+  std::vector<int> y2(b2, 0);
+  fail_each_alloc("tnml_set_input, b 64 -> 300 (D = 3)", [&] { return tnml_set_input(ctx, X2.data(), y2.data(), b2); });
+  OK(tnml_forward(ctx, f.data()));
+  OK(sweep(ctx));
+  OK(tnml_destroy(ctx));
+  ctx = make(N, D, L, M, b, X, y);
+  OK(tnml_forward(ctx, f.data()));
+  const size_t nB = (size_t)1 * D * D * M * L;
+  std::vector<float> B(nB, 0.01f);
+  std::vector<double> grad(nB);
+  double loss = 0;
+  fail_each_alloc("first standalone sub-step (tnml_l2_term)", [&] { return tnml_l2_term(ctx, B.data(), 0, 1e-3f, &loss, grad.data(), nB); });
+  OK(sweep(ctx));
+  OK(tnml_destroy(ctx));
+}
+
 int main() {
   FAILS_WITH(TNML_ERR_ARG, tnml_create(nullptr, 8, 3, 2, 4, 16, 0));
   tnml_ctx *bad = nullptr;
@@ -308,6 +339,7 @@ int main() {
   run_entry_points(8, 3, 2, 6, 50);
   run_entry_points(7, 4, 3, 5, 40);
   run_limits();
+  run_alloc_failures();
   san_stub_report();
   const char *paths[] = {"anyd_batch_kernel", "anyd_update_kernel", "anyd_chain_kernel", "anyd_norm_chain_kernel", "anyd_transpose_input_kernel",
                          "reduce_slabs_kernel"};

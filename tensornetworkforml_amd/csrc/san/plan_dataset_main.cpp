@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../tnml_internal.h"
+#include "fail_each.h"
 
 using namespace tnml;
 
@@ -253,6 +254,35 @@ static void run_comm() {
   printf("communicator attached: dataset calls refused\n");
 }
 
+// Failed allocations (injected by the stand-in, see fail_each.h) in every group the dataset calls size: the dataset itself, the index
+// list, the batch group a larger selection grows, the metrics partials, the prediction group, the temporary of tnml_dataset_read.
+// Each call fails once per allocation, then succeeds; a forward and a full sweep over the grown buffers close the sequence.
+static void run_alloc_failures(int D) {
+  const int N = 6, L = 2, M = 6, b_cap = 64, n = 500;
+  tnml_ctx *ctx = nullptr;
+  OK(tnml_create(&ctx, N, D, L, M, b_cap, 0));
+  g_L = L;
+  std::vector<int> bond(N - 1, M);
+  size_t total = 0;
+  for (int i = 0; i < N; ++i) total += (size_t)(i == 0 ? 1 : M) * D * (i == N - 1 ? 1 : M) * (i == 0 ? L : 1);
+  std::vector<float> cores(total, 0.1f), data((size_t)n * N * D, 0.5f), f((size_t)L * 2500), X((size_t)300 * N * D), met((size_t)2 * (N - 1));
+  OK(tnml_set_cores(ctx, cores.data(), total, bond.data(), 0));
+  std::vector<int> lab(n, 1), few = indices(40, n, 1), more = indices(300, n, 2), many = indices(2500, n, 3);
+  double out3[3];
+  g_n = n;
+  fail_each_alloc("tnml_dataset_attach", [&] { return tnml_dataset_attach(ctx, data.data(), lab.data(), n, N, D, TNML_DATASET_FEATURES); });
+  fail_each_alloc("tnml_select_indices, first index list", [&] { return tnml_select_indices(ctx, few.data(), 40); });
+  fail_each_alloc("tnml_select_indices, b 40 -> 300", [&] { return tnml_select_indices(ctx, more.data(), 300); });
+  OK(tnml_forward(ctx, f.data()));
+  fail_each_alloc("tnml_resident_metrics", [&] { return tnml_resident_metrics(ctx, TNML_ACT_SOFTMAX, 0.1f, out3); });
+  fail_each_alloc("tnml_predict_indices, b 300", [&] { return tnml_predict_indices(ctx, more.data(), 300, f.data()); });
+  fail_each_alloc("tnml_eval_indices, longer index list", [&] { return tnml_eval_indices(ctx, many.data(), 2500, TNML_ACT_SOFTMAX, 0.1f, out3); });
+  fail_each_alloc("tnml_dataset_read", [&] { return tnml_dataset_read(ctx, more.data(), 300, X.data()); });
+  OK(tnml_sweep(ctx, 0, N - 1, 1, 1e-3f, 1e-3f, 1, TNML_ACT_SOFTMAX, TNML_LOSS_FULL_CROSS_ENT, 0.1f, TNML_TRUNC_FIXED, met.data(), nullptr));
+  OK(tnml_destroy(ctx));
+  g_n = 0;
+}
+
 int main() {
   run(12, 2, 2, 6, 100);
   run(37, 2, 3, 5, 64);            // more than one site tile, odd bond, three labels
@@ -260,6 +290,8 @@ int main() {
   run(33, 3, 10, 4, 70);           // ten labels: the metrics kernel's LDS tile
   run(9, 8, 2, 4, 64);
   run_comm();
+  run_alloc_failures(2);
+  run_alloc_failures(3);
   san_stub_report();
   const char *paths[] = {"dataset_gather_d2_kernel<true>", "dataset_gather_d2_kernel<false>", "dataset_gather_anyd_kernel<true>",
                          "dataset_gather_anyd_kernel<false>", "dataset_metrics_kernel", "dataset_metrics_sum_kernel"};

@@ -7,6 +7,7 @@
 #include <vector>
 #include <cmath>
 #include "../../../include/tnml.h"
+#include "fail_each.h"
 
 extern "C" void san_stub_report(void);
 extern "C" long san_stub_launches(const char *substr);
@@ -262,6 +263,84 @@ static void run_entry_points(int N, int M, int b, int L) {
   fflush(stdout);
 }
 
+// Who owns what: buffer growth and failed allocations, at tiny shapes.
+//   * growth after a large-tensor sweep: the pipelined large-tensor step keeps a buffer of the batch's width of its own, which a larger
+//     batch has to replace with everything else of that width;
+//   * tnml_create with every one of its allocations failing in turn: TNML_ERR_HIP, no context, nothing left behind (the stand-in's
+//     final count of live allocations and LeakSanitizer see streams and events too);
+//   * every call that grows a capacity group with every one of its allocations failing in turn: TNML_ERR_HIP, then the same call
+//     succeeds, then a forward and a full sweep are planned, every extent checked against what is allocated now.
+struct Tiny {
+  int N, M, L, b_max;
+  std::vector<int> bond;
+  std::vector<float> cores, X, f, met;
+  std::vector<int> y;
+  Tiny(int N_, int M_, int L_, int b_max_) : N(N_), M(M_), L(L_), b_max(b_max_), bond(start_bonds(N_, M_, 2, L_)) {
+    size_t total = 0;
+    for (int i = 0; i < N; ++i) total += (size_t)(i == 0 ? 1 : M) * 2 * (i == N - 1 ? 1 : M) * (i == 0 ? L : 1);
+    cores.assign(total, 0.05f);
+    X.assign((size_t)b_max * N * 2, 0.5f); f.resize((size_t)L * b_max); met.resize((size_t)2 * (N - 1));
+    y.resize(b_max);
+    for (int s = 0; s < b_max; ++s) y[s] = s % L;
+  }
+  tnml_ctx *context(int b, bool large) {
+    tnml_ctx *ctx = nullptr;
+    OK(tnml_create(&ctx, N, 2, L, M, b, 0));
+    if (large) { OK(tnml_set_narrow_path(ctx, 1)); OK(tnml_set_persistent(ctx, 0)); }
+    OK(tnml_set_input(ctx, X.data(), y.data(), b));
+    return ctx;
+  }
+  // the cores again (label back on site 0), a forward and a full right sweep -> the first status that is not TNML_OK
+  int sweep(tnml_ctx *ctx) {
+    int rc = tnml_set_cores(ctx, cores.data(), cores.size(), bond.data(), 0);
+    if (!rc) rc = tnml_forward(ctx, f.data());
+    if (!rc) rc = tnml_sweep(ctx, 0, N - 1, 1, 1e-3f, 1e-3f, 1, TNML_ACT_SOFTMAX, TNML_LOSS_FULL_CROSS_ENT, 0.1f, TNML_TRUNC_FIXED, met.data(), f.data());
+    return rc;
+  }
+};
+
+static void run_ownership() {
+  const int b = 64, b2 = 300;
+  {
+    Tiny t(12, 12, 2, b2);
+    tnml_ctx *ctx = t.context(b, true);
+    OK(t.sweep(ctx));
+    OK(tnml_set_input(ctx, t.X.data(), t.y.data(), b2));
+    OK(t.sweep(ctx));
+    OK(tnml_destroy(ctx));
+    printf("growth after a large-tensor sweep, b %d -> %d: ok\n", b, b2);
+  }
+  Tiny t(6, 6, 2, b2);
+  {
+    tnml_ctx *ctx = nullptr;
+    fail_each_alloc("tnml_create", [&] {
+      const int rc = tnml_create(&ctx, t.N, 2, t.L, t.M, b, 0);
+      if (rc != TNML_OK && ctx) { fprintf(stderr, "a failed tnml_create handed a context out\n"); exit(1); }
+      return rc;
+    });
+    OK(tnml_destroy(ctx));
+  }
+  for (int large = 0; large < 2; ++large) {
+    const char *path = large ? "large-tensor path" : "default path";
+    char what[96];
+    auto grown = [&](const char *call) { snprintf(what, sizeof what, "%s (%s)", call, path); return what; };
+    tnml_ctx *ctx = t.context(b, large);
+    if (large) fail_each_alloc(grown("first sweep"), [&] { return t.sweep(ctx); });
+    else OK(t.sweep(ctx));
+    fail_each_alloc(grown("tnml_predict, b 300"), [&] { return tnml_predict(ctx, t.X.data(), b2, t.f.data()); });
+    OK(t.sweep(ctx));
+    fail_each_alloc(grown("tnml_set_input, b 64 -> 300"), [&] { return tnml_set_input(ctx, t.X.data(), t.y.data(), b2); });
+    fail_each_alloc(grown("sweep after that growth"), [&] { return t.sweep(ctx); });     // (the large-tensor pipeline's own buffer again)
+    OK(tnml_destroy(ctx));
+    ctx = t.context(b, large);
+    OK(t.sweep(ctx));
+    fail_each_alloc(grown("tnml_stage_batch, b 300"), [&] { return tnml_stage_batch(ctx, 0, t.X.data(), t.y.data(), b2); });
+    fail_each_alloc(grown("tnml_select_batch, b 64 -> 300"), [&] { return tnml_select_batch(ctx, 0); });
+    OK(t.sweep(ctx));
+    OK(tnml_destroy(ctx));
+  }
+}
+
 int main(int argc, char **argv) {
   const bool quick = argc > 1 && !strcmp(argv[1], "quick");
   // BASELINE.json's single-GPU configurations at their true sizes, both directions (two sweeps), plus ragged small shapes
@@ -293,6 +372,7 @@ int main(int argc, char **argv) {
   run_entry_points(12, 20, 300, 3);
   run_entry_points(6, 50, 64, 10);
   run_entry_points(5, 64, 40, 2);
+  run_ownership();
   san_stub_report();
   if (san_stub_launches("sweep_persist") < 1 || san_stub_launches("step_pipe_kernel") < 1 || san_stub_launches("big_jacobi") < 1 ||
       san_stub_launches("narrow_step_kernel") < 1) {

@@ -9,6 +9,9 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <initializer_list>
+#include <memory>
+#include <utility>
 
 #include "tnml_internal.h"
 #include "small_gemm_device.h"
@@ -74,7 +77,70 @@ struct ZTicket {
   }
 };
 
+// Who owns what ("Who owns what").  Everything a context creates in the runtime -- device memory, pinned host memory,
+// events, streams -- is created by Owner::make and recorded there; the members of tnml_ctx stay the raw handles the argument blocks
+// of the kernels copy by value.  ~Owner releases what is still recorded, newest first, so `delete ctx` is the whole teardown and a
+// tnml_create that fails half-way leaks nothing.  No other code of this file calls the runtime's create / destroy functions.
+//
+// Capacity groups.  Buffers sized from the same quantity are (re)sized by ONE function, which writes each member's size once and
+// hands the list to make().  make() frees every member first and creates them afterwards (the batch group's two environment stacks
+// are ~0.8 GB each at C5: old and new together would double the peak), and frees them all again when one creation fails.  The rule
+// for every group: after a failed (re)size the group is completely empty, its capacity field is 0 and every flag that depends on it
+// (have_input, have_labels, envs_valid_*, f_current, big_ready, ...) is cleared -- the group's function does that BEFORE it calls
+// make(); the call returns TNML_ERR_HIP; the same call repeated later succeeds; and no call in between launches with a null or
+// undersized member, because every reader goes through that capacity field or one of those flags.
+struct Owner {
+  enum Kind { kDev, kPinned, kEvent, kStream };
+  struct Member { void **slot; size_t arg; Kind kind; };       // arg: bytes (memory) or creation flags (event)
+  std::vector<std::pair<void *, Kind>> held;                   // by value: the slots may be locals or move (sweep_ev)
+
+  Owner() = default;
+  Owner(const Owner &) = delete;
+  Owner &operator=(const Owner &) = delete;
+  ~Owner() { for (; !held.empty(); held.pop_back()) destroy(held.back().first, held.back().second); }
+
+  static void destroy(void *h, Kind k) {
+    switch (k) {
+      case kDev: (void)hipFree(h); break;
+      case kPinned: (void)hipHostFree(h); break;
+      case kEvent: (void)hipEventDestroy((hipEvent_t)h); break;
+      case kStream: (void)hipStreamDestroy((hipStream_t)h); break;
+    }
+  }
+  template <class T> void release(T *&p) {                     // free, un-record, null
+    for (size_t i = held.size(); p && i-- > 0;)
+      if (held[i].first == (void *)p) { destroy(held[i].first, held[i].second); held.erase(held.begin() + i); break; }
+    p = nullptr;
+  }
+  // all of the list or none of it: whatever the slots hold is released first
+  hipError_t make(std::initializer_list<Member> group) {
+    for (const Member &m : group) release(*m.slot);
+    for (const Member &m : group) {
+      void *h = nullptr;
+      hipError_t e = hipSuccess;
+      switch (m.kind) {
+        case kDev: e = hipMalloc(&h, m.arg); break;
+        case kPinned: e = hipHostMalloc(&h, m.arg); break;
+        case kEvent: e = hipEventCreateWithFlags((hipEvent_t *)&h, (unsigned)m.arg); break;
+        case kStream: e = hipStreamCreateWithFlags((hipStream_t *)&h, hipStreamNonBlocking); break;
+      }
+      if (e != hipSuccess) {
+        for (const Member &u : group) release(*u.slot);
+        return e;
+      }
+      held.emplace_back(h, m.kind);
+      *m.slot = h;
+    }
+    return hipSuccess;
+  }
+};
+template <class T> static Owner::Member own_dev(T *&p, size_t count) { return {(void **)&p, count * sizeof(T), Owner::kDev}; }
+template <class T> static Owner::Member own_pinned(T *&p, size_t count) { return {(void **)&p, count * sizeof(T), Owner::kPinned}; }
+static Owner::Member own_event(hipEvent_t &e, unsigned flags) { return {(void **)&e, flags, Owner::kEvent}; }
+static Owner::Member own_stream(hipStream_t &s) { return {(void **)&s, 0, Owner::kStream}; }
+
 struct tnml_ctx {
+  Owner own;                            // (first member: destroyed last)
   int N = 0, D = 0, L = 0, Mmax = 0;   // Mmax = buffer capacity per bond
   int Mpol = 0;                         // the M of Network(N, M, ...): fixed-policy rank
   int b = 0, b_pad = 0, b_cap = 0;
@@ -164,8 +230,7 @@ struct tnml_ctx {
   bool chain_plain = false;                  // tnml_set_chain_path
   bool any_pos = false;                      // tnml_set_any_position
   bool seg_starting = false;                 // the sweep call in flight starts a segment and has not planned its first step yet
-  float *predEnv = nullptr;                  // prediction at an intermediate label site: [2][Mmax][predenv_cap], the two environments next to it
-  int predenv_cap = 0;
+  float *predEnv = nullptr;                  // prediction at an intermediate label site: [2][Mmax][pred_cap], the two environments next to it
   float *prepB = nullptr;                    // fused narrow launch: merged tensor / L2 term from the helper workgroups
   double *prepG = nullptr;
   unsigned *sync = nullptr;
@@ -198,7 +263,7 @@ struct tnml_ctx {
   size_t dbg_elems = 0;
   int *status = nullptr;
   unsigned long long *counters = nullptr;
-  void *tables = nullptr;      // device scratch for ChainSite / NormChainSite tables
+  char *tables = nullptr;      // device scratch for ChainSite / NormChainSite tables
   size_t tables_bytes = 0;
   double *anyd_W = nullptr, *anyd_T2 = nullptr;   // generic-D update kernel: Jacobi vectors beyond LDS, behind core + its norm product
   // device-resident dataset (tnml_dataset_attach): features [n][N][D] or pixels [n][N], labels [n]; the index list of the call in
@@ -211,8 +276,7 @@ struct tnml_ctx {
   hipEvent_t ds_idx_ev[2] = {nullptr, nullptr};
   bool ds_idx_busy[2] = {false, false};
   int ds_idx_cap = 0, ds_idx_cur = 0;
-  int *ds_ypred = nullptr;                   // labels of the chunk tnml_eval_indices is evaluating, beside Xpred / fpred
-  int ds_ypred_cap = 0;
+  int *ds_ypred = nullptr;                   // [pred_cap] labels of the chunk tnml_eval_indices is evaluating, beside Xpred / fpred
   double *ds_part = nullptr, *ds_acc = nullptr;   // block partials and the four accumulators of the metrics kernels
   int ds_part_cap = 0;
   // multi-GPU
@@ -242,39 +306,49 @@ extern "C" int tnml_device_count(void) {
 
 #include "host_plan.inc"      // tnml_trunc_rank, canon_to_rel: pure host arithmetic, also built with sanitizers (make san)
 
-static int alloc_batch_buffers(tnml_ctx *c, int b_cap) {
-  const int b_pad = (b_cap + 63) / 64 * 64;
-  auto freep = [](auto *&p) { if (p) { (void)hipFree(p); p = nullptr; } };
-  freep(c->X); freep(c->Xstage); freep(c->y); freep(c->f); freep(c->ftmp); freep(c->ftmp2);
-  freep(c->Lenv); freep(c->Renv); freep(c->slabs); freep(c->zslabs);
-  c->b_cap = b_cap;
-  c->b_pad = b_pad;
-  const size_t env_elems = (size_t)c->N * c->Mmax * b_pad;
-  HIP_TRY(hipMalloc(&c->X, (size_t)c->N * b_pad * c->D * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->Xstage, (size_t)c->N * b_pad * c->D * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->y, (size_t)b_pad * sizeof(int)));
-  HIP_TRY(hipMalloc(&c->f, (size_t)c->L * b_pad * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->ftmp, (size_t)c->L * b_pad * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->ftmp2, (size_t)c->L * b_pad * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->Lenv, env_elems * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->Renv, env_elems * sizeof(float)));
-  c->nblk_cap = b_pad / kTS;
-  HIP_TRY(hipMalloc(&c->slabs, (size_t)c->nblk_cap * c->slab_stride * sizeof(float)));
-  {   // batch-side workgroups of the pipelined step: at most kPipeMaxWide (from the device's CU count), each looping over pipe_tpw sample tiles
-    const int kPipeMaxWide = std::max(16, c->num_cus - 16);      // + update workgroup and its helpers: all resident, one per CU
-    const int ntiles = b_pad / kTS;
-    c->pipe.tpw = (ntiles + kPipeMaxWide - 1) / kPipeMaxWide;
-    c->pipe.nwide = (ntiles + c->pipe.tpw - 1) / c->pipe.tpw;
-    c->pipe.ngroups = (c->pipe.nwide + kPipeGroupMax - 1) / kPipeGroupMax;
-    HIP_TRY(hipMalloc(&c->zslabs, (size_t)c->pipe.nwide * c->zstride * sizeof(float)));
-  }
-  drop_pregradients(c);
-  HIP_TRY(hipMemsetAsync(c->y, 0, (size_t)b_pad * sizeof(int), c->stream));
-  HIP_TRY(hipMemsetAsync(c->f, 0, (size_t)c->L * b_pad * sizeof(float), c->stream));
+// one (re)size of a group: the message names the group
+static int make_group(tnml_ctx *c, const char *what, std::initializer_list<Owner::Member> group) {
+  const hipError_t e = c->own.make(group);
+  return e == hipSuccess ? TNML_OK : fail(TNML_ERR_HIP, "allocating %s failed: %s", what, hipGetErrorString(e));
+}
+
+// Batch group: everything sized from b_pad (bigpipe.Pk too: batch_Pk below creates it on first use, this releases it)
+static int size_batch_group(tnml_ctx *c, int b_cap) {
+  const int b_pad = (b_cap + 63) / 64 * 64, ntiles = b_pad / kTS;
+  c->b = c->b_cap = c->b_pad = c->nblk_cap = 0;
   c->have_input = c->have_labels = false;
   c->envs_valid_L = c->envs_valid_R = false;
-  c->f_current = false;
+  c->f_current = c->Bnew_valid = false;
+  drop_pregradients(c);
+  c->own.release(c->bigpipe.Pk);
+  // batch-side workgroups of the pipelined step: at most kPipeMaxWide (from the device's CU count), each looping over pipe_tpw sample tiles
+  const int kPipeMaxWide = std::max(16, c->num_cus - 16);      // + update workgroup and its helpers: all resident, one per CU
+  c->pipe.tpw = (ntiles + kPipeMaxWide - 1) / kPipeMaxWide;
+  c->pipe.nwide = (ntiles + c->pipe.tpw - 1) / c->pipe.tpw;
+  c->pipe.ngroups = (c->pipe.nwide + kPipeGroupMax - 1) / kPipeGroupMax;
+  const size_t x_elems = (size_t)c->N * b_pad * c->D, f_elems = (size_t)c->L * b_pad, env_elems = (size_t)c->N * c->Mmax * b_pad;
+  int rc = make_group(c, "the batch buffers", {
+      own_dev(c->X, x_elems), own_dev(c->Xstage, x_elems), own_dev(c->y, (size_t)b_pad),
+      own_dev(c->f, f_elems), own_dev(c->ftmp, f_elems), own_dev(c->ftmp2, f_elems),
+      own_dev(c->Lenv, env_elems), own_dev(c->Renv, env_elems),
+      own_dev(c->slabs, (size_t)ntiles * c->slab_stride), own_dev(c->zslabs, (size_t)c->pipe.nwide * c->zstride)});
+  if (rc) return rc;
+  c->b_cap = b_cap;
+  c->b_pad = b_pad;
+  c->nblk_cap = ntiles;
+  HIP_TRY(hipMemsetAsync(c->y, 0, (size_t)b_pad * sizeof(int), c->stream));
+  HIP_TRY(hipMemsetAsync(c->f, 0, f_elems * sizeof(float), c->stream));
   return TNML_OK;
+}
+
+// [D * Mmax][b_pad]  E_k (x) x_k of the pipelined large-tensor step, on its first use after a (re)size of the batch group
+static int batch_Pk(tnml_ctx *c) {
+  return c->bigpipe.Pk ? TNML_OK : make_group(c, "the row operand of the pipelined large-tensor step", {own_dev(c->bigpipe.Pk, (size_t)c->D * c->Mmax * c->b_pad)});
+}
+
+// a call that reads the batch group without asking for an input batch: refused while the group is empty
+static int batch_group_there(const tnml_ctx *c) {
+  return c->b_pad ? TNML_OK : fail(TNML_ERR_STATE, "the batch buffers are empty (an earlier growth failed): call tnml_set_input again");
 }
 
 extern "C" int tnml_create(tnml_ctx **out, int N, int D, int L, int Mmax, int b_capacity, int device) {
@@ -291,7 +365,7 @@ extern "C" int tnml_create(tnml_ctx **out, int N, int D, int L, int Mmax, int b_
   HIP_TRY(hipGetDeviceProperties(&prop, device));
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return fail(TNML_ERR_NOGPU, "device %d is %s; this library carries gfx950 code only", device, prop.gcnArchName);
-  tnml_ctx *c = new tnml_ctx();
+  std::unique_ptr<tnml_ctx> c(new tnml_ctx());                 // every early return below releases what exists so far
   if (getenv("TNML_EVENT_HANDOFFS") && atoi(getenv("TNML_EVENT_HANDOFFS"))) { c->bigpipe.flags_enabled = false; c->split.flags_enabled = false; }   // see tnml_set_flag_handoffs
   // Under the reference truncation policy the bond next to a chain end becomes len(S) =
   // min(D*left, D*L) (Network_class.py:907-910), which exceeds M when M < D*L (the MNIST script
@@ -301,73 +375,46 @@ extern "C" int tnml_create(tnml_ctx **out, int N, int D, int L, int Mmax, int b_
   c->N = N; c->D = D; c->L = L; c->Mmax = Mmax; c->device = device;
   c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   c->bond.assign(N - 1, 1);
-  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  HIP_TRY(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-  HIP_TRY(hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking));
-  HIP_TRY(hipEventCreateWithFlags(&c->ev_p0, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&c->ev_p2, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&c->ev_p3, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&c->ev_prep, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&c->bigpipe.ev_upd, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&c->bigpipe.ev_z, hipEventDisableTiming));
-  for (int i = 0; i < 2; ++i) {
-    HIP_TRY(hipEventCreateWithFlags(&c->split.ev_upd[i], hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&c->split.ev_bat[i], hipEventDisableTiming));
-  }
-  HIP_TRY(hipEventCreate(&c->ev0)); HIP_TRY(hipEventCreate(&c->ev1));
-  HIP_TRY(hipEventCreate(&c->pev0)); HIP_TRY(hipEventCreate(&c->pev1));
   c->core_stride = (size_t)Mmax * D * Mmax;
   c->lab_elems = (size_t)Mmax * D * Mmax * L;
   c->bmax = (size_t)Mmax * D * D * Mmax * L;
   c->slab_stride = (int)((c->bmax + kMetricSlots + 63) / 64 * 64);
-  HIP_TRY(hipMalloc(&c->cores, (size_t)N * c->core_stride * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->lab[0], c->lab_elems * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->lab[1], c->lab_elems * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->Ln, (size_t)N * Mmax * Mmax * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->Rn, (size_t)N * Mmax * Mmax * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->Bnew, c->bmax * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->Bscr, c->bmax * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->prepB, c->bmax * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->prepG, c->bmax * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->sync, sizeof(unsigned)));
-  HIP_TRY(hipMemset(c->sync, 0, sizeof(unsigned)));
   c->zstride = (int)((2 * c->bmax + kMetricSlots + 63) / 64 * 64);       // Z has up to D times the elements of the gradient
-  HIP_TRY(hipMalloc(&c->gslabs, (size_t)kPipeGroupMax * c->zstride * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->zred, (size_t)c->zstride * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->pipe.cnt, 32 * sizeof(unsigned)));
-  HIP_TRY(hipMemset(c->pipe.cnt, 0, 32 * sizeof(unsigned)));
-  HIP_TRY(hipMalloc(&c->zred2, (size_t)c->zstride * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->Tbuf[0], (size_t)c->zstride * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->Tbuf[1], (size_t)c->zstride * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->TNbuf[0], (size_t)c->zstride * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->TNbuf[1], (size_t)c->zstride * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->prepRaw, c->bmax * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->Apub, persist_pub_doubles(D * Mmax * Mmax, Mmax) * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->pst_dev, (size_t)(N + 1) * sizeof(PersistStep)));
-  for (int i = 0; i < 2; ++i) {
-    HIP_TRY(hipHostMalloc(&c->pst_host[i], (size_t)(N + 1) * sizeof(PersistStep)));
-    HIP_TRY(hipEventCreateWithFlags(&c->pst_ev[i], hipEventDisableTiming));
-  }
-  HIP_TRY(hipMalloc(&c->pst_cnt, (size_t)(N + 1) * 32 * sizeof(unsigned)));
-  HIP_TRY(hipMalloc(&c->pst_flags, 8 * sizeof(unsigned)));
-  HIP_TRY(hipMalloc(&c->Bscr2, c->bmax * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->red, (size_t)c->slab_stride * sizeof(float)));
   c->metrics_cap = N;
-  HIP_TRY(hipMalloc(&c->metrics, (size_t)c->metrics_cap * 2 * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->scal, 64 * sizeof(float)));
   c->dbg_elems = 4 * c->bmax + kDbgSigma + kDbgScalars + 8;   // 4 tensors, sigma[kDbgSigma], 5 scalars, stamps
-  HIP_TRY(hipMalloc(&c->dbg, c->dbg_elems * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->status, 2 * sizeof(int)));      // [0] status word, [1] kept rank of the last adaptive step
-  HIP_TRY(hipMemsetAsync(c->status, 0, 2 * sizeof(int), c->stream));
-  HIP_TRY(hipMalloc(&c->counters, kCounterSlots * sizeof(unsigned long long)));     // see kCounterSlots (tnml_internal.h)
-  HIP_TRY(hipMemsetAsync(c->counters, 0, kCounterSlots * sizeof(unsigned long long), c->stream));
   c->tables_bytes = (size_t)N * std::max(sizeof(ChainSite), sizeof(NormChainSite));
-  HIP_TRY(hipMalloc(&c->tables, c->tables_bytes));
-  int rc = alloc_batch_buffers(c, b_capacity);
-  if (rc != TNML_OK) return rc;
+  // Fixed group: streams, events and everything sized from N, D, L and the bond capacity alone; it lives as long as the context
+  const unsigned notime = hipEventDisableTiming;
+  const size_t bmax = c->bmax, zstride = (size_t)c->zstride, norm_elems = (size_t)N * Mmax * Mmax, nrec = (size_t)N + 1;
+  int rc = make_group(c.get(), "the context's streams, events and fixed buffers", {
+      own_stream(c->stream), own_stream(c->stream2), own_stream(c->stream3),
+      own_event(c->ev_p0, notime), own_event(c->ev_p2, notime), own_event(c->ev_p3, notime),
+      own_event(c->ev_main, notime), own_event(c->ev_prep, notime), own_event(c->bigpipe.ev_upd, notime), own_event(c->bigpipe.ev_z, notime),
+      own_event(c->split.ev_upd[0], notime), own_event(c->split.ev_bat[0], notime),
+      own_event(c->split.ev_upd[1], notime), own_event(c->split.ev_bat[1], notime),
+      own_event(c->ev0, hipEventDefault), own_event(c->ev1, hipEventDefault), own_event(c->pev0, hipEventDefault), own_event(c->pev1, hipEventDefault),
+      own_dev(c->cores, (size_t)N * c->core_stride), own_dev(c->lab[0], c->lab_elems), own_dev(c->lab[1], c->lab_elems),
+      own_dev(c->Ln, norm_elems), own_dev(c->Rn, norm_elems),
+      own_dev(c->Bnew, bmax), own_dev(c->Bscr, bmax), own_dev(c->prepB, bmax), own_dev(c->prepG, bmax), own_dev(c->sync, 1),
+      own_dev(c->gslabs, (size_t)kPipeGroupMax * zstride), own_dev(c->zred, zstride), own_dev(c->pipe.cnt, 32), own_dev(c->zred2, zstride),
+      own_dev(c->Tbuf[0], zstride), own_dev(c->Tbuf[1], zstride), own_dev(c->TNbuf[0], zstride), own_dev(c->TNbuf[1], zstride),
+      own_dev(c->prepRaw, bmax), own_dev(c->Apub, persist_pub_doubles(D * Mmax * Mmax, Mmax)),
+      own_dev(c->pst_dev, nrec), own_pinned(c->pst_host[0], nrec), own_event(c->pst_ev[0], notime),
+      own_pinned(c->pst_host[1], nrec), own_event(c->pst_ev[1], notime),
+      own_dev(c->pst_cnt, nrec * 32), own_dev(c->pst_flags, 8), own_dev(c->Bscr2, bmax), own_dev(c->red, (size_t)c->slab_stride),
+      own_dev(c->metrics, (size_t)c->metrics_cap * 2), own_dev(c->scal, 64), own_dev(c->dbg, c->dbg_elems),
+      own_dev(c->status, 2),                                   // [0] status word, [1] kept rank of the last adaptive step
+      own_dev(c->counters, (size_t)kCounterSlots),             // see kCounterSlots (tnml_internal.h)
+      own_dev(c->tables, c->tables_bytes)});
+  if (rc) return rc;
+  HIP_TRY(hipMemset(c->sync, 0, sizeof(unsigned)));
+  HIP_TRY(hipMemset(c->pipe.cnt, 0, 32 * sizeof(unsigned)));
+  HIP_TRY(hipMemsetAsync(c->status, 0, 2 * sizeof(int), c->stream));
+  HIP_TRY(hipMemsetAsync(c->counters, 0, kCounterSlots * sizeof(unsigned long long), c->stream));
+  rc = size_batch_group(c.get(), b_capacity);
+  if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
-  *out = c;
+  *out = c.release();
   return TNML_OK;
 }
 
@@ -376,44 +423,7 @@ extern "C" int tnml_destroy(tnml_ctx *c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->comm) ncclCommDestroy(c->comm);
-  void *ptrs[] = {c->X, c->Xstage, c->y, c->f, c->ftmp, c->ftmp2, c->Lenv, c->Renv, c->cores, c->lab[0], c->lab[1],
-                  c->Ln, c->Rn, c->Bnew, c->slabs, c->red, c->metrics, c->scal, c->dbg, c->status, c->tables, c->counters, c->Bscr, c->Bscr2,
-                  c->Xpred_stage, c->Xpred, c->fpred, c->predEnv, c->prepB, c->prepG, c->sync, c->zslabs, c->gslabs, c->zred, c->pipe.cnt, c->big.Bf, c->big.T, c->big.part, c->big.gram, c->big.rotlog, c->big.lam, c->big.info, c->big.VW, c->big.Cb, c->big.T2, c->big.prog, c->bigpipe.flags, c->split.flags};
-  for (void *p : ptrs) if (p) (void)hipFree(p);
-  void *pptrs[] = {c->zred2, c->Tbuf[0], c->Tbuf[1], c->TNbuf[0], c->TNbuf[1], c->prepRaw, c->Apub, c->pst_dev, c->pst_cnt, c->pst_flags,
-                   c->anyd_W, c->anyd_T2};
-  for (void *p : pptrs) if (p) (void)hipFree(p);
-  for (int i = 0; i < 2; ++i) {
-    if (c->pst_host[i]) (void)hipHostFree(c->pst_host[i]);
-    if (c->pst_ev[i]) (void)hipEventDestroy(c->pst_ev[i]);
-  }
-  for (int i = 0; i < tnml_ctx::kStageSlots; ++i) { if (c->stageX[i]) (void)hipFree(c->stageX[i]); if (c->stageY[i]) (void)hipFree(c->stageY[i]); }
-  {
-    void *dptrs[] = {c->ds_data, c->ds_labels, c->ds_idx, c->ds_ypred, c->ds_part, c->ds_acc};
-    for (void *p : dptrs) if (p) (void)hipFree(p);
-    for (int i = 0; i < 2; ++i) {
-      if (c->ds_idx_host[i]) (void)hipHostFree(c->ds_idx_host[i]);
-      if (c->ds_idx_ev[i]) (void)hipEventDestroy(c->ds_idx_ev[i]);
-    }
-  }
-  for (hipEvent_t e : c->sweep_ev) (void)hipEventDestroy(e);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
-  if (c->pev0) (void)hipEventDestroy(c->pev0);
-  if (c->pev1) (void)hipEventDestroy(c->pev1);
-  if (c->ev_main) (void)hipEventDestroy(c->ev_main);
-  if (c->ev_prep) (void)hipEventDestroy(c->ev_prep);
-  for (int i = 0; i < 2; ++i) { if (c->split.ev_upd[i]) (void)hipEventDestroy(c->split.ev_upd[i]); if (c->split.ev_bat[i]) (void)hipEventDestroy(c->split.ev_bat[i]); }
-  if (c->bigpipe.ev_upd) (void)hipEventDestroy(c->bigpipe.ev_upd);
-  if (c->bigpipe.ev_z) (void)hipEventDestroy(c->bigpipe.ev_z);
-  if (c->bigpipe.Pk) (void)hipFree(c->bigpipe.Pk);
-  if (c->ev_p0) (void)hipEventDestroy(c->ev_p0);
-  if (c->ev_p2) (void)hipEventDestroy(c->ev_p2);
-  if (c->ev_p3) (void)hipEventDestroy(c->ev_p3);
-  if (c->stream3) (void)hipStreamDestroy(c->stream3);
-  if (c->stream2) (void)hipStreamDestroy(c->stream2);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  delete c;                                                    // ~Owner releases every buffer, event and stream
   return TNML_OK;
 }
 
@@ -587,7 +597,7 @@ extern "C" int tnml_set_input(tnml_ctx *c, const float *X, const int32_t *y, int
   HIP_TRY(hipSetDevice(c->device));
   if (b > c->b_cap) {
     HIP_TRY(hipStreamSynchronize(c->stream));
-    int rc = alloc_batch_buffers(c, b);
+    int rc = size_batch_group(c, b);
     if (rc != TNML_OK) return rc;
   }
   // keep the padding of a previous, larger batch from leaking: b_pad is per-capacity, the live
@@ -619,25 +629,18 @@ extern "C" int tnml_stage_batch(tnml_ctx *c, int slot, const float *X, const int
     if (y[i] < 0 || y[i] >= c->L) return fail(TNML_ERR_ARG, "label %d of sample %d outside [0, %d)", y[i], i, c->L);
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  // the slot is either complete (both arrays, its size) or empty: any failure below leaves it empty
-  auto drop = [&]() {
-    if (c->stageX[slot]) (void)hipFree(c->stageX[slot]);
-    if (c->stageY[slot]) (void)hipFree(c->stageY[slot]);
-    c->stageX[slot] = nullptr; c->stageY[slot] = nullptr; c->stageB[slot] = 0;
-  };
-  drop();
-  float *sx = nullptr;
-  int *sy = nullptr;
-  hipError_t e = hipMalloc(&sx, (size_t)b * c->N * c->D * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&sy, (size_t)b * sizeof(int));
+  // Stage-slot group (one per slot, sized from its batch): complete (both arrays, its size) or empty
+  float *&sx = c->stageX[slot];
+  int *&sy = c->stageY[slot];
+  c->stageB[slot] = 0;
+  hipError_t e = c->own.make({own_dev(sx, (size_t)b * c->N * c->D), own_dev(sy, (size_t)b)});
   if (e == hipSuccess) e = hipMemcpy(sx, X, (size_t)b * c->N * c->D * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(sy, y, (size_t)b * sizeof(int), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
-    if (sx) (void)hipFree(sx);
-    if (sy) (void)hipFree(sy);
+    c->own.release(sx); c->own.release(sy);
     return fail(TNML_ERR_HIP, "staging a batch of %d samples failed: %s", b, hipGetErrorString(e));
   }
-  c->stageX[slot] = sx; c->stageY[slot] = sy; c->stageB[slot] = b;
+  c->stageB[slot] = b;
   return TNML_OK;
 }
 
@@ -649,7 +652,7 @@ extern "C" int tnml_select_batch(tnml_ctx *c, int slot) {
   const int b = c->stageB[slot];
   if (b > c->b_cap) {
     HIP_TRY(hipStreamSynchronize(c->stream));
-    int rc = alloc_batch_buffers(c, b);
+    int rc = size_batch_group(c, b);
     if (rc != TNML_OK) return rc;
   }
   c->b = b;
@@ -858,17 +861,18 @@ extern "C" int tnml_forward(tnml_ctx *c, float *f_out) {
   return TNML_OK;
 }
 
-// tnml_predict's own batch: Xpred_stage [b][N][D] as uploaded, Xpred [N][pred_cap][D], fpred [L][pred_cap]; grown to bp samples
+// Prediction group, grown to bp samples: tnml_predict's own batch -- Xpred_stage [b][N][D] as uploaded, Xpred [N][pred_cap][D],
+// fpred [L][pred_cap] -- with the two environments next to an intermediate label site (predEnv) and the labels of the chunk
+// tnml_eval_indices is evaluating (ds_ypred)
 static int pred_ensure_buffers(tnml_ctx *c, int bp) {
   if (bp <= c->pred_cap) return TNML_OK;
   const int N = c->N, D = c->D, L = c->L;
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->Xpred_stage) { (void)hipFree(c->Xpred_stage); (void)hipFree(c->Xpred); (void)hipFree(c->fpred); }
-  c->Xpred_stage = c->Xpred = c->fpred = nullptr;
   c->pred_cap = 0;
-  HIP_TRY(hipMalloc(&c->Xpred_stage, (size_t)bp * N * D * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->Xpred, (size_t)bp * N * D * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->fpred, (size_t)bp * L * sizeof(float)));
+  int rc = make_group(c, "the prediction buffers", {
+      own_dev(c->Xpred_stage, (size_t)bp * N * D), own_dev(c->Xpred, (size_t)bp * N * D), own_dev(c->fpred, (size_t)bp * L),
+      own_dev(c->predEnv, (size_t)2 * c->Mmax * bp), own_dev(c->ds_ypred, (size_t)bp)});
+  if (rc) return rc;
   // on the context's stream: a memset on the null stream is not ordered against this (non-blocking) stream and could land behind
   // the re-tiling kernel that follows
   HIP_TRY(hipMemsetAsync(c->Xpred, 0, (size_t)bp * N * D * sizeof(float), c->stream));
@@ -884,25 +888,14 @@ static int pred_allowed(tnml_ctx *c) {
   return TNML_OK;
 }
 
-// the chain table of a prediction (the prediction buffers exist): towards the label site, or the two half-chains and the buffers
-// of the two environments they leave
-static int pred_table(tnml_ctx *c) {
-  if (!label_inside(c)) return upload_chain_table(c);
-  if (c->predenv_cap < c->pred_cap) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->predEnv) (void)hipFree(c->predEnv);
-    c->predEnv = nullptr; c->predenv_cap = 0;
-    HIP_TRY(hipMalloc(&c->predEnv, (size_t)2 * c->Mmax * c->pred_cap * sizeof(float)));
-    c->predenv_cap = c->pred_cap;
-  }
-  return upload_half_tables(c, false);
-}
+// the chain table of a prediction: towards the label site, or the two half-chains
+static int pred_table(tnml_ctx *c) { return label_inside(c) ? upload_half_tables(c, false) : upload_chain_table(c); }
 
 // one chain towards the label site over Xpred -> fpred, no environment stored (the chain table must be uploaded)
 static int pred_chain(tnml_ctx *c, int b) {
   const int N = c->N, D = c->D, L = c->L, bpad = c->pred_cap;
-  if (label_inside(c)) {                      // (pred_table allocated the two environment buffers)
-    float *EL = c->predEnv, *ER = c->predEnv + (size_t)c->Mmax * c->predenv_cap;
+  if (label_inside(c)) {
+    float *EL = c->predEnv, *ER = c->predEnv + (size_t)c->Mmax * c->pred_cap;
     int rc = half_chain(c, false, c->Xpred, nullptr, EL, b, bpad);
     if (!rc) rc = half_chain(c, true, c->Xpred, nullptr, ER, b, bpad);
     if (!rc) rc = label_meet(c, EL, ER, c->Xpred, c->fpred, b, bpad);
@@ -966,6 +959,7 @@ extern "C" int tnml_forward_logabsmax(tnml_ctx *c, double *out) {
 
 extern "C" int tnml_f_absmax(tnml_ctx *c, double *out) {
   if (!c || !out) return fail(TNML_ERR_ARG, "NULL argument");
+  if (int rc = batch_group_there(c)) return rc;
   HIP_TRY(hipSetDevice(c->device));
   launch_absmax(c->f, c->L, c->b, c->b_pad, c->scal, c->stream);
   HIP_TRY(hipGetLastError());
@@ -991,6 +985,7 @@ extern "C" int tnml_set_f(tnml_ctx *c, const float *f) {
 
 extern "C" int tnml_get_f(tnml_ctx *c, float *f_out) {
   if (!c || !f_out) return fail(TNML_ERR_ARG, "NULL argument");
+  if (int rc = batch_group_there(c)) return rc;
   HIP_TRY(hipSetDevice(c->device));
   return copy_f_out(c, c->f, f_out);
 }
@@ -1020,11 +1015,7 @@ static int ds_usable(tnml_ctx *c) {
   return TNML_OK;
 }
 
-static void ds_drop(tnml_ctx *c) {
-  if (c->ds_data) (void)hipFree(c->ds_data);
-  if (c->ds_labels) (void)hipFree(c->ds_labels);
-  c->ds_data = nullptr; c->ds_labels = nullptr; c->ds_n = 0;
-}
+static void ds_drop(tnml_ctx *c) { c->own.release(c->ds_data); c->own.release(c->ds_labels); c->ds_n = 0; }
 
 extern "C" int tnml_dataset_attach(tnml_ctx *c, const float *data, const int32_t *labels, int n, int N, int D, int form) {
   if (!c || !data || !labels) return fail(TNML_ERR_ARG, "NULL argument");
@@ -1036,20 +1027,17 @@ extern "C" int tnml_dataset_attach(tnml_ctx *c, const float *data, const int32_t
     if (labels[i] < 0 || labels[i] >= c->L) return fail(TNML_ERR_ARG, "label %d of sample %d outside [0, %d)", labels[i], i, c->L);
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));          // an earlier dataset may still be read
-  ds_drop(c);
+  // Dataset group (sized from n): both arrays or none (ds_usable asks for ds_data)
   const size_t per = (size_t)c->N * (form == TNML_DATASET_PIXELS ? 1 : c->D);
-  float *dd = nullptr;
-  int *dl = nullptr;
-  hipError_t e = hipMalloc(&dd, (size_t)n * per * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&dl, (size_t)n * sizeof(int));
-  if (e == hipSuccess) e = hipMemcpy(dd, data, (size_t)n * per * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dl, labels, (size_t)n * sizeof(int), hipMemcpyHostToDevice);
+  c->ds_n = 0;
+  hipError_t e = c->own.make({own_dev(c->ds_data, (size_t)n * per), own_dev(c->ds_labels, (size_t)n)});
+  if (e == hipSuccess) e = hipMemcpy(c->ds_data, data, (size_t)n * per * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(c->ds_labels, labels, (size_t)n * sizeof(int), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
-    if (dd) (void)hipFree(dd);
-    if (dl) (void)hipFree(dl);
+    ds_drop(c);
     return fail(TNML_ERR_HIP, "uploading a dataset of %d samples failed: %s", n, hipGetErrorString(e));
   }
-  c->ds_data = dd; c->ds_labels = dl; c->ds_n = n; c->ds_form = form;
+  c->ds_n = n; c->ds_form = form;
   double binom = 1.0;                                 // C(D-1, s), exact in float64 for D <= kMaxD
   for (int s = 0; s < c->D; ++s) {
     c->ds_coef[s] = std::sqrt(binom);
@@ -1073,19 +1061,16 @@ extern "C" int tnml_dataset_size(tnml_ctx *c) { return c ? c->ds_n : TNML_ERR_AR
 static int ds_upload_indices(tnml_ctx *c, const int32_t *idx, int b) {
   for (int i = 0; i < b; ++i)
     if (idx[i] < 0 || idx[i] >= c->ds_n) return fail(TNML_ERR_ARG, "index %d at position %d outside [0, %d)", idx[i], i, c->ds_n);
-  if (b > c->ds_idx_cap) {
+  if (b > c->ds_idx_cap) {                   // Index-list group: the device list, its two pinned buffers and their events
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->ds_idx) (void)hipFree(c->ds_idx);
-    c->ds_idx = nullptr; c->ds_idx_cap = 0;
-    for (int i = 0; i < 2; ++i) {
-      if (c->ds_idx_host[i]) (void)hipHostFree(c->ds_idx_host[i]);
-      c->ds_idx_host[i] = nullptr; c->ds_idx_busy[i] = false;
-      if (!c->ds_idx_ev[i]) HIP_TRY(hipEventCreateWithFlags(&c->ds_idx_ev[i], hipEventDisableTiming));
-    }
-    const int cap = (b + 1023) / 1024 * 1024;
-    HIP_TRY(hipMalloc(&c->ds_idx, (size_t)cap * sizeof(int)));
-    for (int i = 0; i < 2; ++i) HIP_TRY(hipHostMalloc(&c->ds_idx_host[i], (size_t)cap * sizeof(int)));
-    c->ds_idx_cap = cap;
+    const size_t cap = ((size_t)b + 1023) / 1024 * 1024;
+    c->ds_idx_cap = 0;
+    c->ds_idx_busy[0] = c->ds_idx_busy[1] = false;
+    int rc = make_group(c, "the index list", {
+        own_dev(c->ds_idx, cap), own_pinned(c->ds_idx_host[0], cap), own_pinned(c->ds_idx_host[1], cap),
+        own_event(c->ds_idx_ev[0], hipEventDisableTiming), own_event(c->ds_idx_ev[1], hipEventDisableTiming)});
+    if (rc) return rc;
+    c->ds_idx_cap = (int)cap;
   }
   const int slot = (c->ds_idx_cur ^= 1);
   if (c->ds_idx_busy[slot]) HIP_TRY(hipEventSynchronize(c->ds_idx_ev[slot]));
@@ -1116,7 +1101,7 @@ extern "C" int tnml_select_indices(tnml_ctx *c, const int32_t *idx, int b) {
   if (rc) return rc;
   if (b > c->b_cap) {
     HIP_TRY(hipStreamSynchronize(c->stream));
-    rc = alloc_batch_buffers(c, b);
+    rc = size_batch_group(c, b);
     if (rc != TNML_OK) return rc;
   }
   c->b = b;
@@ -1132,30 +1117,15 @@ extern "C" int tnml_select_indices(tnml_ctx *c, const int32_t *idx, int b) {
   return TNML_OK;
 }
 
-// tnml_predict's buffers, at least bp samples wide, plus the labels tnml_eval_indices gathers beside them
-static int ds_ensure_pred(tnml_ctx *c, int bp) {
-  int rc = pred_ensure_buffers(c, bp);
-  if (rc) return rc;
-  if (c->ds_ypred_cap < c->pred_cap) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->ds_ypred) (void)hipFree(c->ds_ypred);
-    c->ds_ypred = nullptr; c->ds_ypred_cap = 0;
-    HIP_TRY(hipMalloc(&c->ds_ypred, (size_t)c->pred_cap * sizeof(int)));
-    c->ds_ypred_cap = c->pred_cap;
-  }
-  return TNML_OK;
-}
-
+// Metrics group: the block partials of b_pad samples and the four accumulators (restarted by every call that uses them)
 static int ds_ensure_metrics(tnml_ctx *c, int b_pad) {
   const int nblk = (b_pad + kDsMetricThreads - 1) / kDsMetricThreads;
-  if (!c->ds_acc) HIP_TRY(hipMalloc(&c->ds_acc, 4 * sizeof(double)));
-  if (nblk > c->ds_part_cap) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->ds_part) (void)hipFree(c->ds_part);
-    c->ds_part = nullptr; c->ds_part_cap = 0;
-    HIP_TRY(hipMalloc(&c->ds_part, (size_t)nblk * 4 * sizeof(double)));
-    c->ds_part_cap = nblk;
-  }
+  if (nblk <= c->ds_part_cap) return TNML_OK;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->ds_part_cap = 0;
+  int rc = make_group(c, "the metrics partials", {own_dev(c->ds_part, (size_t)nblk * 4), own_dev(c->ds_acc, 4)});
+  if (rc) return rc;
+  c->ds_part_cap = nblk;
   return TNML_OK;
 }
 
@@ -1169,7 +1139,7 @@ extern "C" int tnml_predict_indices(tnml_ctx *c, const int32_t *idx, int b, floa
   if ((rc = ds_forward_allowed(c))) return rc;
   HIP_TRY(hipSetDevice(c->device));
   if ((rc = ds_upload_indices(c, idx, b))) return rc;
-  if ((rc = ds_ensure_pred(c, (b + 63) / 64 * 64))) return rc;
+  if ((rc = pred_ensure_buffers(c, (b + 63) / 64 * 64))) return rc;
   const int bpad = c->pred_cap;
   if ((rc = ds_gather(c, c->ds_idx, b, bpad, c->Xpred, nullptr))) return rc;
   if ((rc = pred_table(c))) return rc;
@@ -1200,7 +1170,7 @@ extern "C" int tnml_eval_indices(tnml_ctx *c, const int32_t *idx, int b, int act
   if ((rc = ds_upload_indices(c, idx, b))) return rc;
   // chunks as wide as the prediction buffers (at least the resident batch's capacity); whole 256-sample blocks of the metrics
   // kernel where they are wide enough, so that a sample's block does not depend on the chunking
-  if ((rc = ds_ensure_pred(c, std::max(c->pred_cap, c->b_pad)))) return rc;
+  if ((rc = pred_ensure_buffers(c, std::max({c->pred_cap, c->b_pad, 64})))) return rc;     // (64: both groups may be empty after a failed growth)
   const int bpad = c->pred_cap;
   const int chunk = bpad >= kDsMetricThreads ? bpad / kDsMetricThreads * kDsMetricThreads : bpad;
   if ((rc = ds_ensure_metrics(c, bpad))) return rc;
@@ -1240,8 +1210,8 @@ extern "C" int tnml_dataset_read(tnml_ctx *c, const int32_t *idx, int b, float *
   HIP_TRY(hipSetDevice(c->device));
   if ((rc = ds_upload_indices(c, idx, b))) return rc;
   const int N = c->N, D = c->D, bp = (b + 63) / 64 * 64;
-  float *tmp = nullptr;
-  HIP_TRY(hipMalloc(&tmp, (size_t)N * bp * D * sizeof(float)));
+  float *tmp = nullptr;                    // owned for the length of this call
+  if ((rc = make_group(c, "the gathered samples", {own_dev(tmp, (size_t)N * bp * D)}))) return rc;
   rc = ds_gather(c, c->ds_idx, b, bp, tmp, nullptr);
   std::vector<float> host;
   if (!rc) {
@@ -1252,7 +1222,7 @@ extern "C" int tnml_dataset_read(tnml_ctx *c, const int32_t *idx, int b, float *
   } else {
     (void)hipStreamSynchronize(c->stream);
   }
-  (void)hipFree(tmp);
+  c->own.release(tmp);
   if (rc) return rc;
   for (int s = 0; s < b; ++s)              // [N][bp][D] as the device forms it -> [b][N][D]
     for (int n = 0; n < N; ++n)
@@ -1266,22 +1236,19 @@ extern "C" int tnml_dataset_read(tnml_ctx *c, const int32_t *idx, int b, float *
 // ---------------------------------------------------------------------------------------------
 // narrow step: in-LDS kernel, or the large-tensor path when the merged tensor does not fit
 // ---------------------------------------------------------------------------------------------
+// Large-tensor group: the HBM scratch of the path and the flag words of its pipeline, sized from the bond capacity on first use
 static int ensure_big(tnml_ctx *c) {
   if (c->big_ready) return TNML_OK;
   const size_t rows_cols = (size_t)c->D * c->Mmax * (1 + c->L);
-  HIP_TRY(hipMalloc(&c->big.Bf, c->bmax * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->big.T, c->bmax * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->big.part, (3 * kBigParts + 8) * sizeof(double)));      // block partials, then {step factor, the three sums}
-  HIP_TRY(hipMalloc(&c->big.gram, (size_t)8 * kBigMaxN * kBigMaxN * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->big.rotlog, ((size_t)30 * (kBigMaxN - 1) + 2) * (kBigMaxN / 2) * sizeof(double2)));
-  HIP_TRY(hipMalloc(&c->big.lam, 3 * kBigMaxN * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->big.info, (4 + kBigMaxN) * sizeof(int)));
-  HIP_TRY(hipMalloc(&c->big.VW, rows_cols * kBigMaxN * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->big.Cb, rows_cols * c->Mmax * sizeof(float)));
-  HIP_TRY(hipMalloc(&c->big.T2, rows_cols * c->Mmax * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->big.prog, 8 * sizeof(unsigned)));
-  HIP_TRY(hipMemset(c->big.prog, 0, 8 * sizeof(unsigned)));
-  HIP_TRY(hipMalloc(&c->bigpipe.flags, 4 * sizeof(unsigned)));
+  BigScratch &g = c->big;
+  int rc = make_group(c, "the large-tensor scratch", {
+      own_dev(g.Bf, c->bmax), own_dev(g.T, c->bmax),
+      own_dev(g.part, 3 * kBigParts + 8),                      // block partials, then {step factor, the three sums}
+      own_dev(g.gram, (size_t)8 * kBigMaxN * kBigMaxN), own_dev(g.rotlog, ((size_t)30 * (kBigMaxN - 1) + 2) * (kBigMaxN / 2)),
+      own_dev(g.lam, 3 * kBigMaxN), own_dev(g.info, 4 + kBigMaxN), own_dev(g.VW, rows_cols * kBigMaxN),
+      own_dev(g.Cb, rows_cols * c->Mmax), own_dev(g.T2, rows_cols * c->Mmax), own_dev(g.prog, 8), own_dev(c->bigpipe.flags, 4)});
+  if (rc) return rc;
+  HIP_TRY(hipMemset(g.prog, 0, 8 * sizeof(unsigned)));
   HIP_TRY(hipMemset(c->bigpipe.flags, 0, 4 * sizeof(unsigned)));
   c->big_ready = true;
   return TNML_OK;
@@ -1970,7 +1937,7 @@ static int launch_pipe_step_fused(tnml_ctx *c, const SweepCall &sc, const StepGe
 static int launch_pipe_step_split(tnml_ctx *c, const SweepCall &sc, const StepGeom &q, NarrowParams &n, PipePlan &pp) {
   WidePipeParams &wp = pp.wp;
   if (c->split.flags_enabled && !c->split.flags) {
-    HIP_TRY(hipMalloc(&c->split.flags, 4 * sizeof(unsigned)));
+    { int rc = make_group(c, "the hand-off words of the two-stream step", {own_dev(c->split.flags, 4)}); if (rc) return rc; }
     HIP_TRY(hipMemsetAsync(c->split.flags, 0, 4 * sizeof(unsigned), c->stream));
   }
   if (!c->split.pending) {                 // first split step after anything else: stream2 starts behind the context's stream
@@ -2165,7 +2132,7 @@ static int step_big(tnml_ctx *c, const SweepCall &sc, const StepGeom &q, NarrowP
   if (prep_ahead) HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_prep, 0));
   const NextZ nz = plan_next_z(c, sc, q);
   if (nz.on) { int rc = ensure_big(c); if (rc) return rc; }          // (the flag words of the hand-offs live with its scratch)
-  if (nz.on && !c->bigpipe.Pk) HIP_TRY(hipMalloc(&c->bigpipe.Pk, (size_t)D * c->Mmax * c->b_pad * sizeof(float)));
+  if (nz.on) { int rc = batch_Pk(c); if (rc) return rc; }
   // (a step fed by Z launches no batch kernel of its own: the environment work for the NEXT step's batch kernel rides in this
   //  step's first launch on this stream, and the side stream's chain starts with the batch kernel itself)
   const bool ext_in_front = nz.on && zbig;
@@ -2235,8 +2202,8 @@ static int sweep_impl(tnml_ctx *c, int left_dir, int n_steps, int first_of_sweep
   hipEvent_t sw_ev1 = nullptr;
   if (c->sweep_timing && mode == 0) {
     if (c->sweep_ev_used + 2 > c->sweep_ev.size()) {
-      hipEvent_t a, b2;
-      HIP_TRY(hipEventCreate(&a)); HIP_TRY(hipEventCreate(&b2));
+      hipEvent_t a = nullptr, b2 = nullptr;
+      { int rc = make_group(c, "a pair of timing events", {own_event(a, hipEventDefault), own_event(b2, hipEventDefault)}); if (rc) return rc; }
       c->sweep_ev.push_back(a); c->sweep_ev.push_back(b2);
     }
     HIP_TRY(hipEventRecord(c->sweep_ev[c->sweep_ev_used], c->stream));
@@ -2427,11 +2394,9 @@ extern "C" int tnml_svd_split(tnml_ctx *c, const float *mat, int rows, int cols,
 // go through the shared frame functions (step_geom, fill_wide, fill_update, finish_step, finish_sweep), the capture block is laid
 // out as on the D == 2 path; the update kernel takes any short side up to kBigMaxN (odd sides padded to even inside it).
 // ---------------------------------------------------------------------------------------------
-static int anyd_scratch(tnml_ctx *c) {
-  if (c->anyd_W) return TNML_OK;
-  HIP_TRY(hipMalloc(&c->anyd_W, (size_t)kBigMaxN * kBigMaxN * sizeof(double)));
-  HIP_TRY(hipMalloc(&c->anyd_T2, 2 * (size_t)c->D * c->Mmax * c->Mmax * sizeof(double)));
-  return TNML_OK;
+static int anyd_scratch(tnml_ctx *c) {           // Generic-D group, on first use: both or none
+  return c->anyd_W ? TNML_OK : make_group(c, "the scratch of the generic-D update", {
+      own_dev(c->anyd_W, (size_t)kBigMaxN * kBigMaxN), own_dev(c->anyd_T2, 2 * (size_t)c->D * c->Mmax * c->Mmax)});
 }
 
 // update kernel in "stop after the update" / "given matrix" mode (tnml_l2_term, tnml_svd_split)
@@ -2492,6 +2457,7 @@ extern "C" int tnml_batch(tnml_ctx *c) { return c ? c->b : TNML_ERR_ARG; }
 extern "C" int tnml_get_env(tnml_ctx *c, int side, int site, float *out, size_t capacity, int *m_out) {
   if (!c || !out) return fail(TNML_ERR_ARG, "NULL argument");
   if (site < 0 || site >= c->N) return fail(TNML_ERR_ARG, "site out of range");
+  if (int rc = batch_group_there(c)) return rc;
   HIP_TRY(hipSetDevice(c->device));
   const int m = side == TNML_SIDE_LEFT ? c->mr(site) : c->ml(site);
   if (capacity < (size_t)m * c->b) return fail(TNML_ERR_ARG, "capacity too small");

@@ -50,6 +50,13 @@ def run_sweeps(N, M, b, flags, large, comm):
     if comm:
         tdist.attach_comm(ctx, 0, 1)
     ctx.set_flag_handoffs(flags)
+    out = two_sweeps(ctx, N)
+    ctx.close()
+    return out
+
+
+def two_sweeps(ctx, N):
+    """forward + right sweep, forward + left sweep -> dict of arrays: f and metrics of both, bonds and cores at the end"""
     out = {}
     for sw in range(2):
         ctx.forward()
@@ -60,7 +67,6 @@ def run_sweeps(N, M, b, flags, large, comm):
     out['l_pos'] = np.array([lp])
     for i, c in enumerate(cs):
         out['core%d' % i] = c
-    ctx.close()
     return out
 
 
@@ -76,6 +82,37 @@ def test_large_tensor_pipeline_flags_equal_events():
     res = [run_sweeps(N, 6, 96, flags, large=True, comm=False) for flags in (True, False)]
     assert res[0]['met0'].shape == (N - 1, 2) and int(res[0]['l_pos'][0]) == 0
     assert_same(res[0], res[1])
+
+
+def test_large_tensor_pipeline_after_batch_growth():
+    """The pipelined large-tensor step keeps one buffer of the batch's padded width of its own (E_k (x) x_k, allocated at its first
+    use).  A context that has run such sweeps at 96 samples (padded width 128) and then takes 200 (256) must hand the kernels a
+    buffer of the new width: its sweeps on the 200 samples agree bit for bit with those of a context created at 200 that starts
+    from the same cores.  (Before the buffer was sized with the rest of the batch's buffers the first context wrote past its end.)"""
+    from tensornetworkforml_amd import _hip
+    N, M, L, D = 8, 6, 2, 2
+    X1, y1, cores = problem(N, M, 96)
+    X2, y2, _ = problem(N, M, 200)
+
+    def context(cap, cores, l_pos):
+        ctx = _hip.Context(N, D, L, M, cap)
+        ctx.set_cores(cores, l_pos)
+        ctx.set_persistent(0)
+        ctx.set_narrow_path(1)
+        return ctx
+    a = context(96, cores, 0)
+    a.set_input(X1, y1)
+    two_sweeps(a, N)
+    cores1, _, l_pos1 = a.get_cores()
+    a.set_input(X2, y2)
+    grown = two_sweeps(a, N)
+    a.close()
+    b = context(200, cores1, l_pos1)
+    b.set_input(X2, y2)
+    fresh = two_sweeps(b, N)
+    b.close()
+    assert grown['met0'].shape == (N - 1, 2) and grown['f0'].shape == (L, 200) and l_pos1 == 0
+    assert_same(grown, fresh)
 
 
 def test_two_stream_communicator_step_flags_equal_events(tmp_path):
