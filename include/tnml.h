@@ -228,6 +228,31 @@ int tnml_resident_metrics(tnml_ctx *ctx, int act_fn, float T, double *out3);
 /* The embedded samples idx[0..b) as the device forms them, X_out [b][N][D]: for tests and inspection, not a hot path. */
 int tnml_dataset_read(tnml_ctx *ctx, const int32_t *idx, int b, float *X_out);
 
+/* ---- input gradients ------------------------------------------------------------------------- */
+/* Which inputs a decision rests on: the gradient of the network output with respect to the embedded inputs (saliency maps, the
+ * direction of an adversarial step, the cotangent for a layer in front of the MPS).  No reference analogue.  Two chains per sample on
+ * the matrix cores -- one from the left that stores its environments, one from the right that meets them site by site -- in one
+ * kernel (csrc/kernels_inputgrad.hip).
+ * RANGE: the stored environments are float32 without renormalisation, as tnml_forward's are: the call is meant for calibrated
+ * networks (max |f| of order 1); an un-calibrated chain at N = 784 underflows here as it does there.
+ * LIMITS: single GPU (TNML_ERR_STATE with a communicator, the rule of the dataset block); the kernel's LDS tiles are sized from the
+ * largest bond of the chain, and a shape that needs more than 160 KB is refused with TNML_ERR_ARG and a message naming the bytes
+ * (D = 2, two labels, N = 784: bonds up to 85).  Every refusal happens before anything is launched. */
+enum { TNML_WRT_FEATURES = 0, TNML_WRT_PIXELS = 1 };
+/* g[s][i][d] = sum_l' cot[l'][s] d f[l'][s] / d X[s][i][d] for a batch that is NOT made resident.
+ * X [b][N][D], cot [L][b] or NULL (= one-hot of the first maximum of f per sample), grad_out [b][N][D],
+ * cf_out [b] or NULL (= sum_l' cot f).  Any l_pos, with or without tnml_set_any_position.
+ * b may exceed every batch capacity: the call works in chunks (tnml_set_input_grad_chunk).  Like tnml_predict it leaves the
+ * resident batch, its environments, f, the cores and l_pos exactly as they were, and it synchronises before returning. */
+int tnml_input_grad(tnml_ctx *ctx, const float *X, int b, const float *cot, float *grad_out, float *cf_out);
+/* the same for samples of the attached dataset; wrt = TNML_WRT_FEATURES -> grad_out [b][N][D];
+ * wrt = TNML_WRT_PIXELS (dataset in TNML_DATASET_PIXELS form only, TNML_ERR_STATE otherwise) -> grad_out [b][N],
+ * the chain rule through the feature map psi, its derivative evaluated in float64 on the device */
+int tnml_input_grad_indices(tnml_ctx *ctx, const int32_t *idx, int b, const float *cot, int wrt, float *grad_out, float *cf_out);
+/* samples per pass (rounded up to a multiple of 64); 0 = default: the largest multiple of 64 whose stack of stored environments
+ * (N x bond capacity x samples floats) stays within 256 MiB, at least 64.  Tests and diagnostics. */
+int tnml_set_input_grad_chunk(tnml_ctx *ctx, int samples);
+
 /* Accuracy / speed of the in-kernel Jacobi SVD (no reference analogue: the reference calls LAPACK,
  * Network_class.py:887).  The iteration ends after a sweep in which every rotation had
  * g^2 <= stop2 * scale^2; the off-diagonals left behind are of relative size ~stop2.  Default 1e-6

@@ -402,6 +402,41 @@ class Network():
         return Tensor(elem=ctx.predict(X).astype(np.float64), axes_names=['l', 'b'])
 
     # ------------------------------------------------------------------------------------------
+    # input gradients (not in the reference)
+    # ------------------------------------------------------------------------------------------
+    def _cotangent(self, cotangent, b):
+        """None (the predicted class), an integer array (b,) of classes, or a float array (L, b) used as given -> what the
+        device call takes."""
+        if cotangent is None:
+            return None
+        cot = np.asarray(cotangent)
+        if cot.dtype.kind in 'iu':
+            assert cot.shape == (b,), "one class per sample"
+            assert cot.size == 0 or (cot.min() >= 0 and cot.max() < self.L), "class outside [0, L)"
+            onehot = np.zeros((self.L, b), dtype=np.float32)
+            onehot[cot, np.arange(b)] = 1.0
+            return onehot
+        assert cot.shape == (self.L, b), "a dense cotangent has shape (L, b)"
+        return cot.astype(np.float32)
+
+    def input_gradient(self, X, cotangent=None, return_cf=False):
+        """g (b, N, D): g[s, i, d] = sum_l cotangent[l, s] d f[l, s] / d X[s, i, d], computed on the device for a batch that
+        does not become resident (saliency, adversarial direction, the cotangent for a layer in front of the MPS).  Works at any
+        label position.  cotangent: None = one-hot of the predicted class, an integer array (b,) = one-hot of those classes, a
+        float array (L, b) = used as given.  return_cf: also cf (b,) = sum_l cotangent[l, s] f[l, s]."""
+        assert self.N == X.shape[1], "The 1 dimension of the input data must be the flattened number of pixels"
+        ctx = self._sync_to_device(max(self._b, 1))
+        g, cf = ctx.input_grad(X, self._cotangent(cotangent, X.shape[0]))
+        return (g, cf) if return_cf else g
+
+    def input_gradient_indices(self, indices, cotangent=None, wrt='pixels'):
+        """input_gradient for samples of the attached dataset.  wrt='pixels' (a dataset attached with pixels=True): (b, N),
+        the chain rule through the feature map on the device; wrt='features': (b, N, D)."""
+        ctx = self._require_dataset()
+        idx = np.asarray(indices)
+        return ctx.input_grad_indices(idx, self._cotangent(cotangent, idx.size), wrt)[0]
+
+    # ------------------------------------------------------------------------------------------
     # training
     # ------------------------------------------------------------------------------------------
     def train(self, train_loader, val_loader, lr, n_epochs=10, weight_dec=0.001, L2_flag=True, debug=False):

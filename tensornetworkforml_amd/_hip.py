@@ -17,6 +17,7 @@ LOSS = {'MSE': 0, 'cross_entropy': 1, 'full_cross_ent': 2}
 TRUNC = {'reference': 0, 'fixed': 1, 'adaptive': 2}
 SIDE_LEFT, SIDE_RIGHT = 0, 1
 DATASET_FORM = {'features': 0, 'pixels': 1}
+WRT = {'features': 0, 'pixels': 1}
 DBG = {'B': 0, 'dB_raw': 1, 'B_new': 2, 'sigma': 3, 'scalars': 4, 'L2_grad': 5}
 
 # every symbol include/tnml.h declares (tests check the library exports all of them)
@@ -32,6 +33,7 @@ SYMBOLS = [
     'tnml_svd_stats_ex', 'tnml_set_persistent', 'tnml_set_chain_path', 'tnml_marker', 'tnml_set_comm_overlap', 'tnml_comm_probe', 'tnml_set_flag_handoffs',
     'tnml_dataset_attach', 'tnml_dataset_detach', 'tnml_dataset_size', 'tnml_select_indices', 'tnml_predict_indices', 'tnml_eval_indices',
     'tnml_resident_metrics', 'tnml_dataset_read', 'tnml_set_any_position',
+    'tnml_input_grad', 'tnml_input_grad_indices', 'tnml_set_input_grad_chunk',
 ]
 
 
@@ -117,6 +119,9 @@ def lib():
         L.tnml_eval_indices.argtypes = [vp, i32p, C.c_int, C.c_int, C.c_float, f64p]
         L.tnml_resident_metrics.argtypes = [vp, C.c_int, C.c_float, f64p]
         L.tnml_dataset_read.argtypes = [vp, i32p, C.c_int, f32p]
+        L.tnml_input_grad.argtypes = [vp, f32p, C.c_int, f32p, f32p, f32p]
+        L.tnml_input_grad_indices.argtypes = [vp, i32p, C.c_int, f32p, C.c_int, f32p, f32p]
+        L.tnml_set_input_grad_chunk.argtypes = [vp, C.c_int]
         _lib = L
     return _lib
 
@@ -300,6 +305,42 @@ class Context:
         X = np.empty((idx.size, self.N, self.D), dtype=np.float32)
         _chk(lib().tnml_dataset_read(self._h, _ptr(idx, C.c_int32), idx.size, _ptr(X, C.c_float)))
         return X
+
+    # ---- input gradients
+    def _cot(self, cot, b):
+        if cot is None:
+            return None, None
+        cot = _f32(cot)
+        assert cot.shape == (self.L, b), "the cotangent has shape (L, b)"
+        return cot, _ptr(cot, C.c_float)
+
+    def input_grad(self, X, cot=None):
+        """(g (b, N, D), cf (b,)): g[s, i, d] = sum_l cot[l, s] d f[l, s] / d X[s, i, d] and cf = sum_l cot f, for a batch that does
+        not become resident.  cot (L, b), or None for the one-hot of the predicted class."""
+        X = _f32(X)
+        assert X.ndim == 3 and X.shape[1] == self.N and X.shape[2] == self.D, \
+            "The 1 dimension of the input data must be the flattened number of pixels"
+        b = X.shape[0]
+        cot, cp = self._cot(cot, b)
+        g = np.empty((b, self.N, self.D), dtype=np.float32)
+        cf = np.empty(b, dtype=np.float32)
+        _chk(lib().tnml_input_grad(self._h, _ptr(X, C.c_float), b, cp, _ptr(g, C.c_float), _ptr(cf, C.c_float)))
+        return g, cf
+
+    def input_grad_indices(self, idx, cot=None, wrt='features'):
+        """The same for the dataset samples idx.  wrt='features': g (b, N, D); wrt='pixels' (pixels-form dataset): g (b, N), the
+        chain rule through the feature map."""
+        idx = self._idx(idx)
+        b = idx.size
+        cot, cp = self._cot(cot, b)
+        g = np.empty((b, self.N, self.D) if WRT[wrt] == 0 else (b, self.N), dtype=np.float32)
+        cf = np.empty(b, dtype=np.float32)
+        _chk(lib().tnml_input_grad_indices(self._h, _ptr(idx, C.c_int32), b, cp, WRT[wrt], _ptr(g, C.c_float), _ptr(cf, C.c_float)))
+        return g, cf
+
+    def set_input_grad_chunk(self, n):
+        """Samples per pass of the input-gradient calls (rounded up to a multiple of 64); 0: the default (tests, diagnostics)."""
+        _chk(lib().tnml_set_input_grad_chunk(self._h, int(n)))
 
     # ---- hot path
     def forward(self, want_f=True):

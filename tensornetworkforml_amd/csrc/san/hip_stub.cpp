@@ -211,6 +211,30 @@ static void check_meet(const MeetParams &p, dim3 g, dim3 b, size_t shm) {
   need(p.f, (size_t)p.L * bp * 4, "MeetParams.f");
 }
 
+// input gradients (kernels_inputgrad.hip): every operand with the extent the kernel touches, the cores through the bond table the host
+// uploaded (the stand-in's device memory is host memory)
+static void check_input_grad(const InputGradParams &p, dim3 g, dim3 b, size_t shm) {
+  scan(&p, sizeof p, "InputGradParams");
+  if (p.b < 1 || p.b > p.b_pad || p.b_pad % 64 || p.x_bpad < p.b_pad) die("InputGradParams: b %d b_pad %d x_bpad %d", p.b, p.b_pad, p.x_bpad);
+  if (p.N < 2 || p.D < 2 || p.D > kMaxD || p.L < 1 || p.l_pos < 0 || p.l_pos >= p.N) die("InputGradParams: N %d D %d L %d l_pos %d", p.N, p.D, p.L, p.l_pos);
+  if (p.mb < 1 || p.mb > p.cap) die("InputGradParams: largest bond %d, capacity %d", p.mb, p.cap);
+  if (b.x != 256 || g.x != (unsigned)((p.b + 63) / 64) || g.y != 1 || g.z != 1) die("input_grad_kernel: grid %u block %u for b %d", g.x, b.x, p.b);
+  if (shm < input_grad_lds_bytes(p.mb, p.D, p.L, p.N)) die("input_grad_kernel: %zu bytes of LDS, %zu wanted (bond %d, D %d, L %d)", shm, input_grad_lds_bytes(p.mb, p.D, p.L, p.N), p.mb, p.D, p.L);
+  const size_t bp = p.b_pad;
+  need(p.bond, (size_t)(p.N - 1) * 4, "InputGradParams.bond");
+  need(p.stack, (size_t)p.N * p.cap * bp * 4, "InputGradParams.stack");
+  need(p.X, (size_t)p.N * p.x_bpad * p.D * 4, "InputGradParams.X");
+  need(p.cot, (size_t)p.L * bp * 4, "InputGradParams.cot");
+  need(p.g, (size_t)p.b * p.N * p.D * 4, "InputGradParams.g");
+  opt(p.cf, (size_t)p.b * 4, "InputGradParams.cf");
+  for (int i = 0; i < p.N; ++i) {
+    const int ml = i == 0 ? 1 : p.bond[i - 1], mr = i == p.N - 1 ? 1 : p.bond[i];
+    if (ml < 1 || ml > p.mb || mr < 1 || mr > p.mb) die("InputGradParams: site %d is %d x %d, largest bond %d", i, ml, mr, p.mb);
+    if (i == p.l_pos) need(p.labcore, (size_t)ml * p.D * mr * p.L * 4, "InputGradParams.labcore");
+    else need(p.cores + (size_t)i * p.core_stride, (size_t)ml * p.D * mr * 4, "InputGradParams.cores");
+  }
+}
+
 // ---- call trace ----------------------------------------------------------------------------------------------------------------
 static FILE *g_tr = nullptr;
 static long g_tr_lines = 0;
@@ -266,6 +290,10 @@ static void tr_struct(const PersistHelperParams &p) {
 static void tr_struct(const PersistStep &p) { tr(" n:"); tr_struct(p.n); tr(" w:"); tr_struct(p.w); tr(" t:"); tr_struct(p.t); }
 static void tr_struct(const PrepParams &p) { V(lab) V(pl) P(Nh) P(Ng) I(h) I(g) I(s) I(L) I(l2_flag) P(prepB) P(prepG) I(nparts) }
 static void tr_struct(const MeetParams &p) { P(Lenv) P(Renv) P(x) P(core) P(f) I(b) I(b_pad) I(ml) I(mr) I(D) I(L) I(rows_per_chunk) }
+static void tr_struct(const InputGradParams &p) {
+  P(bond) P(cores) P(labcore) P(X) P(cot) P(stack) P(g) P(cf) I(core_stride) I(b) I(b_pad) I(x_bpad) I(N) I(D) I(L) I(l_pos) I(cap) I(mb)
+}
+static void tr_struct(const InputGradPixels &p) { P(g) P(data) P(idx) P(out) I(b) I(N) I(D) }
 static void tr_struct(const BigExtArgs &p) { P(Eprev) P(x_km1) P(x_k) V(A) I(b_pad) P(Ecur) P(Pk) }
 static void tr_struct(const ChainSite &p) { I(core_off) I(is_label) I(n_in) I(n_out) I(s_in) I(s_d) I(s_out) I(x_site) I(env_out_off) }
 static void tr_struct(const NormChainSite &p) { I(core_off) I(n_in) I(n_out) I(s_in) I(s_d) I(s_out) I(env_out_off) }
@@ -296,6 +324,8 @@ static void tr_launch(const std::string &name, dim3 g, dim3 b, size_t shm, hipSt
     else if (is("WideParams")) tr_struct(*(const WideParams *)args[i]);
     else if (is("PrepParams")) tr_struct(*(const PrepParams *)args[i]);
     else if (is("MeetParams")) tr_struct(*(const MeetParams *)args[i]);
+    else if (is("InputGradParams")) tr_struct(*(const InputGradParams *)args[i]);
+    else if (is("InputGradPixels")) tr_struct(*(const InputGradPixels *)args[i]);
     else if (is("BigExtArgs")) tr_struct(*(const BigExtArgs *)args[i]);
     else if (is("CoreView")) { const CoreView &v = *(const CoreView *)args[i]; tr(" [%s %d %d %d %d %d]", dp(v.base).c_str(), v.n_in, v.n_out, v.s_in, v.s_d, v.s_out); }
     else if (is("BigFrontTiles")) tr(" %d %d", ((int *)args[i])[0], ((int *)args[i])[1]);
@@ -362,6 +392,18 @@ hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t s
     if (g.x > 256) die("step_pipe_kernel: %u workgroups cannot be co-resident on 256 CUs", g.x);
   } else if (has("label_meet_kernel")) {
     check_meet(*(const MeetParams *)args[0], g, b, shm);
+  } else if (has("input_grad_kernel")) {
+    check_input_grad(*(const InputGradParams *)args[0], g, b, shm);
+  } else if (has("input_grad_onehot_kernel")) {   // (f, f_bpad, L, b, cot, b_pad)
+    const int fbp = *(int *)args[1], L = *(int *)args[2], bb = *(int *)args[3], bp = *(int *)args[5];
+    if (bb < 1 || bb > bp || bp > fbp || (size_t)g.x * b.x < (size_t)bp) die("input_grad_onehot_kernel: b %d b_pad %d f_bpad %d grid %u x %u", bb, bp, fbp, g.x, b.x);
+    need(*(const float **)args[0], ((size_t)(L - 1) * fbp + bb) * 4, "one-hot: f"); need(*(float **)args[4], (size_t)L * bp * 4, "one-hot: cot");
+  } else if (has("input_grad_pixels_kernel")) {
+    const InputGradPixels &q = *(const InputGradPixels *)args[0];
+    scan(&q, sizeof q, "InputGradPixels");
+    if (q.b < 1 || q.N < 1 || q.D < 2 || q.D > kMaxD || (size_t)g.x * b.x < (size_t)q.b * q.N) die("input_grad_pixels_kernel: b %d N %d D %d grid %u x %u", q.b, q.N, q.D, g.x, b.x);
+    need(q.g, (size_t)q.b * q.N * q.D * 4, "pixels: g"); need(q.out, (size_t)q.b * q.N * 4, "pixels: out"); need(q.idx, (size_t)q.b * 4, "pixels: index list");
+    for (int i = 0; i < q.b; ++i) need(q.data + (size_t)q.idx[i] * q.N, (size_t)q.N * 4, "pixels: dataset row");
   } else if (has("narrow_step_kernel")) {
     check_narrow(*(const NarrowParams *)args[0]);
   } else if (has("wide_step") || has("f_only_kernel")) {

@@ -279,6 +279,11 @@ struct tnml_ctx {
   int *ds_ypred = nullptr;                   // [pred_cap] labels of the chunk tnml_eval_indices is evaluating, beside Xpred / fpred
   double *ds_part = nullptr, *ds_acc = nullptr;   // block partials and the four accumulators of the metrics kernels
   int ds_part_cap = 0;
+  // input gradients (tnml_input_grad): one group sized from ig_cap samples -- the stack of pass A
+  // [N][Mmax][ig_cap], cot [L][ig_cap], g [ig_cap][N][D], its pixel form [ig_cap][N], cf [ig_cap] -- and the bond table [N]
+  float *ig_stack = nullptr, *ig_cot = nullptr, *ig_g = nullptr, *ig_gpix = nullptr, *ig_cf = nullptr;
+  int *ig_bond = nullptr;
+  int ig_cap = 0, ig_chunk = 0;              // ig_chunk: tnml_set_input_grad_chunk (0 = default)
   // multi-GPU
   ncclComm_t comm = nullptr;
   int rank = 0, nranks = 1;
@@ -1227,6 +1232,119 @@ extern "C" int tnml_dataset_read(tnml_ctx *c, const int32_t *idx, int b, float *
   for (int s = 0; s < b; ++s)              // [N][bp][D] as the device forms it -> [b][N][D]
     for (int n = 0; n < N; ++n)
       memcpy(X_out + ((size_t)s * N + n) * D, host.data() + ((size_t)n * bp + s) * D, (size_t)D * sizeof(float));
+  return TNML_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// input gradients: g[s][i][d] = sum_l' cot[l'][s] d f[l'][s] / d X[s][i][d] (kernels_inputgrad.hip)
+// ---------------------------------------------------------------------------------------------
+static constexpr size_t kIgStackBytes = (size_t)256 << 20;     // the default chunk keeps the stack of pass A within this
+
+// samples per pass: the caller's (rounded up to 64) or the largest multiple of 64 whose stack stays within kIgStackBytes, at least 64
+static int ig_chunk_samples(const tnml_ctx *c) {
+  if (c->ig_chunk > 0) return (c->ig_chunk + 63) / 64 * 64;
+  const size_t per_sample = (size_t)c->N * c->Mmax * sizeof(float);
+  return (int)std::max<size_t>(64, kIgStackBytes / per_sample / 64 * 64);
+}
+
+// Input-gradient group, grown to bp samples (a multiple of 64): everything the call sizes from its chunk, and the bond table.  The
+// chunk's site-major X, its staging buffer and (cot == NULL) its f are the prediction group's.
+static int ig_ensure_buffers(tnml_ctx *c, int bp) {
+  if (bp <= c->ig_cap) return TNML_OK;
+  const size_t N = c->N, D = c->D, L = c->L;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->ig_cap = 0;
+  int rc = make_group(c, "the input-gradient buffers", {
+      own_dev(c->ig_stack, N * c->Mmax * bp), own_dev(c->ig_cot, L * bp), own_dev(c->ig_g, (size_t)bp * N * D),
+      own_dev(c->ig_gpix, (size_t)bp * N), own_dev(c->ig_cf, (size_t)bp), own_dev(c->ig_bond, N)});
+  if (rc) return rc;
+  HIP_TRY(hipMemsetAsync(c->ig_cot, 0, L * bp * sizeof(float), c->stream));     // the columns behind a chunk's samples stay finite
+  c->ig_cap = bp;
+  return TNML_OK;
+}
+
+// X [b][N][D] on the host, or the dataset rows idx[0..b) when X is NULL
+static int input_grad_impl(tnml_ctx *c, const float *X, const int32_t *idx, int b, const float *cot, int wrt, float *grad_out, float *cf_out) {
+  const int N = c->N, D = c->D, L = c->L;
+  if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
+  int mb = 1;
+  for (int v : c->bond) mb = std::max(mb, v);
+  const size_t lds = input_grad_lds_bytes(mb, D, L, N);
+  if (lds > kLdsMax)
+    return fail(TNML_ERR_ARG, "input gradient at D = %d, bond %d, L = %d: %zu bytes of LDS exceed 160 KB", D, mb, L, lds);
+  HIP_TRY(hipSetDevice(c->device));
+  int rc;
+  if (idx && (rc = ds_upload_indices(c, idx, b))) return rc;    // refuses a bad index before anything is launched
+  const int chunk = std::min(ig_chunk_samples(c), (b + 63) / 64 * 64);
+  if ((rc = pred_ensure_buffers(c, chunk))) return rc;
+  if ((rc = ig_ensure_buffers(c, chunk))) return rc;
+  const int bp = c->ig_cap, xbp = c->pred_cap;
+  HIP_TRY(hipMemcpyAsync(c->ig_bond, c->bond.data(), (size_t)(N - 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if (!cot && (rc = pred_table(c))) return rc;
+  const bool pixels = idx && wrt == TNML_WRT_PIXELS;
+  for (int off = 0; off < b; off += chunk) {
+    const int bc = std::min(chunk, b - off);
+    if (idx) {
+      if ((rc = ds_gather(c, c->ds_idx + off, bc, xbp, c->Xpred, nullptr))) return rc;
+    } else {
+      HIP_TRY(hipMemcpyAsync(c->Xpred_stage, X + (size_t)off * N * D, (size_t)bc * N * D * sizeof(float), hipMemcpyHostToDevice, c->stream));
+      if (D != kD) launch_transpose_input_anyd(c->Xpred_stage, c->Xpred, bc, xbp, N, D, c->stream);
+      else launch_transpose_input(c->Xpred_stage, c->Xpred, bc, xbp, N, c->stream);
+      HIP_TRY(hipGetLastError());
+    }
+    if (cot) {
+      HIP_TRY(hipMemcpy2DAsync(c->ig_cot, (size_t)bp * sizeof(float), cot + off, (size_t)b * sizeof(float), (size_t)bc * sizeof(float), L,
+                               hipMemcpyHostToDevice, c->stream));
+    } else {
+      // the predicted class: the prediction chain as it is, then the one-hot of its first maximum
+      if ((rc = pred_chain(c, bc))) return rc;
+      if (!launch_input_grad_onehot(c->fpred, xbp, L, bc, c->ig_cot, bp, c->stream)) return fail(TNML_ERR_ARG, "internal: one-hot launch refused");
+      HIP_TRY(hipGetLastError());
+    }
+    InputGradParams p{};
+    p.bond = c->ig_bond; p.cores = c->cores; p.labcore = c->lab[c->lab_cur]; p.X = c->Xpred; p.cot = c->ig_cot;
+    p.stack = c->ig_stack; p.g = c->ig_g; p.cf = c->ig_cf; p.core_stride = c->core_stride;
+    p.b = bc; p.b_pad = bp; p.x_bpad = xbp; p.N = N; p.D = D; p.L = L; p.l_pos = c->l_pos; p.cap = c->Mmax; p.mb = mb;
+    if (!launch_input_grad(p, c->stream)) return fail(TNML_ERR_ARG, "internal: input-gradient launch refused (b %d, b_pad %d)", bc, bp);
+    HIP_TRY(hipGetLastError());
+    if (pixels) {
+      InputGradPixels q{};
+      q.g = c->ig_g; q.data = c->ds_data; q.idx = c->ds_idx + off; q.out = c->ig_gpix; q.b = bc; q.N = N; q.D = D;
+      for (int s = 0; s < kMaxD; ++s) q.coef[s] = c->ds_coef[s];
+      if (!launch_input_grad_pixels(q, c->stream)) return fail(TNML_ERR_ARG, "internal: pixel chain-rule launch refused");
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(grad_out + (size_t)off * N, c->ig_gpix, (size_t)bc * N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    } else {
+      HIP_TRY(hipMemcpyAsync(grad_out + (size_t)off * N * D, c->ig_g, (size_t)bc * N * D * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (cf_out) HIP_TRY(hipMemcpyAsync(cf_out + off, c->ig_cf, (size_t)bc * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return TNML_OK;
+}
+
+extern "C" int tnml_input_grad(tnml_ctx *c, const float *X, int b, const float *cot, float *grad_out, float *cf_out) {
+  if (!c || !X || !grad_out) return fail(TNML_ERR_ARG, "NULL argument");
+  if (c->comm) return fail(TNML_ERR_STATE, "input gradients are single-GPU only: a communicator is attached");
+  if (b < 1) return fail(TNML_ERR_ARG, "empty batch");
+  return input_grad_impl(c, X, nullptr, b, cot, TNML_WRT_FEATURES, grad_out, cf_out);
+}
+
+extern "C" int tnml_input_grad_indices(tnml_ctx *c, const int32_t *idx, int b, const float *cot, int wrt, float *grad_out, float *cf_out) {
+  int rc = ds_usable(c);
+  if (rc) return rc;
+  if (!idx || !grad_out) return fail(TNML_ERR_ARG, "NULL argument");
+  if (b < 1) return fail(TNML_ERR_ARG, "empty index list");
+  if (wrt != TNML_WRT_FEATURES && wrt != TNML_WRT_PIXELS) return fail(TNML_ERR_ARG, "unknown wrt %d", wrt);
+  if (wrt == TNML_WRT_PIXELS && c->ds_form != TNML_DATASET_PIXELS)
+    return fail(TNML_ERR_STATE, "gradients with respect to pixels need a dataset in TNML_DATASET_PIXELS form");
+  return input_grad_impl(c, nullptr, idx, b, cot, wrt, grad_out, cf_out);
+}
+
+extern "C" int tnml_set_input_grad_chunk(tnml_ctx *c, int samples) {
+  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
+  if (samples < 0) return fail(TNML_ERR_ARG, "samples per pass %d < 0", samples);
+  c->ig_chunk = samples;
   return TNML_OK;
 }
 

@@ -278,4 +278,34 @@ size_t dataset_metrics_lds_bytes(int L);
 bool launch_dataset_metrics(const float *f, const int *y, int L, int b, int b_pad, int act_fn, float T, double *part, int reset, double *acc,
                             hipStream_t st);
 
+// Input gradients (kernels_inputgrad.hip): both chains of 64 samples per workgroup, see the head of that file.
+struct InputGradParams {
+  const int *bond;         // [N-1] bond dimensions of the chain
+  const float *cores;      // plain cores, core i at i * core_stride, [ml][D][mr]
+  const float *labcore;    // [ml][D][mr][L] of site l_pos
+  const float *X;          // [N][x_bpad][D]; samples b .. b_pad-1 are zero
+  const float *cot;        // [L][b_pad]
+  float *stack;            // [N][cap][b_pad]: slot i receives P_i, i = 1 .. N-1
+  float *g;                // [b][N][D]
+  float *cf;               // [b] or nullptr
+  size_t core_stride;
+  int b, b_pad, x_bpad, N, D, L, l_pos;
+  int cap;                 // rows of a stack slot: the context's bond capacity
+  int mb;                  // largest bond of the chain: what the LDS tiles are sized for
+};
+size_t input_grad_lds_bytes(int mb, int D, int L, int N);
+// false: refused (geometry / LDS)
+bool launch_input_grad(const InputGradParams &p, hipStream_t st);
+// cot [L][b_pad] = one-hot of the first maximum of f [L][f_bpad] per sample, zero for samples b .. b_pad-1
+bool launch_input_grad_onehot(const float *f, int f_bpad, int L, int b, float *cot, int b_pad, hipStream_t st);
+struct InputGradPixels {
+  const float *g;          // [b][N][D]
+  const float *data;       // pixels [n][N] of the dataset
+  const int *idx;          // [b] sample rows
+  float *out;              // [b][N]
+  int b, N, D;
+  double coef[kMaxD];      // sqrt(C(D-1, k))
+};
+bool launch_input_grad_pixels(const InputGradPixels &p, hipStream_t st);
+
 }  // namespace tnml

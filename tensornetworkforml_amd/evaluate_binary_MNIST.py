@@ -3,6 +3,8 @@
 (training_binary_MNIST.py --out), prepares the digits 0 / 1 of the MNIST test files the way the training script does (2x2
 max-pooling while the network has fewer sites than the images have pixels), uploads them once and reports accuracy and mean
 absolute error through `Network.evaluate`.  MNIST is read from local IDX files under --data_dir (nothing is downloaded).
+--saliency OUT.npy also writes the saliency maps of the test digits: the gradient of the predicted class's output with respect to
+the pixels, (n, h, w), from `Network.input_gradient_indices` (needs the pixels form of the dataset, the default).
 
     python tensornetworkforml_amd/evaluate_binary_MNIST.py [--filename trained_MNIST_model.dat --data_dir datasets ...]
 """
@@ -29,6 +31,7 @@ def main(argv=None):
     ap.add_argument('--batch_size', type=int, default=128, help='Samples per evaluation batch')
     ap.add_argument('--normalise', action='store_true', help='scale pixels to [0, 1] before the feature map (as in training)')
     ap.add_argument('--features', action='store_true', help='upload host-embedded features instead of pixels')
+    ap.add_argument('--saliency', metavar='OUT.npy', default=None, help='write d f[predicted class] / d pixel of every test digit, (n, h, w)')
     args = ap.parse_args(argv)
 
     with open(args.filename, 'rb') as fh:
@@ -48,6 +51,13 @@ def main(argv=None):
     acc, mae = net.evaluate(test_loader)
     print('\tAccuracy:            ', acc)
     print('\tMean Absolute Error: ', mae)
+    if args.saliency:
+        import numpy as np
+        if args.features:
+            raise SystemExit('--saliency differentiates through the feature map on the device: it needs the pixels form (drop --features)')
+        sal = net.input_gradient_indices(np.arange(len(data01)), wrt='pixels')
+        np.save(args.saliency, sal.reshape((len(data01),) + data01.shape[1:]))
+        print('\tSaliency maps:       ', args.saliency, sal.shape)
     return acc, mae
 
 
