@@ -253,6 +253,29 @@ int tnml_input_grad_indices(tnml_ctx *ctx, const int32_t *idx, int b, const floa
  * (N x bond capacity x samples floats) stays within 256 MiB, at least 64.  Tests and diagnostics. */
 int tnml_set_input_grad_chunk(tnml_ctx *ctx, int samples);
 
+/* ---- core gradients -------------------------------------------------------------------------- */
+/* The gradient with respect to the parameters themselves, all N cores in one call: what gradient descent over all cores, Adam in a
+ * host framework, one-site updates, a fine-tuning pass after sweeping or a sensitivity analysis need.  No reference analogue.
+ *   G_i[a][d][c]     = sum_s P_i[s][a] x_i[s][d] Q_i[s][c]                      (i != l_pos)
+ *   G_l[a][d][c][l'] = sum_s cot[l'][s] P_l[s][a] x_l[s][d] Q_l[s][c]           (i == l_pos)
+ * the derivative of sum_s cf[s], cf[s] = sum_l' cot[l'][s] f[l'][s], with P and Q the two per-sample chains of the input
+ * gradients.  A chain kernel stores both chains to HBM, a reduction kernel sums over the samples on the matrix cores, one fixed
+ * left-to-right sum per element: the result does not depend on the chunk size (csrc/kernels_coregrad.hip).
+ * RANGE and LIMITS: those of the input gradients above (calibrated networks; single GPU; a shape whose LDS tiles need more than
+ * 160 KB is refused with TNML_ERR_ARG and a message naming the bytes).  Every refusal happens before anything is launched.
+ * X [b][N][D], cot [L][b] or NULL (= one-hot of the first maximum of f per sample), grad_flat in the layout of tnml_get_cores (the
+ * cores follow one another, each (ml, D, mr) row-major, the core on l_pos (ml, D, mr, L)), capacity in floats, at least
+ * tnml_cores_size (TNML_ERR_ARG otherwise; floats behind the gradient are left alone), cf_out [b] or NULL.  Any l_pos, with or
+ * without tnml_set_any_position.  b may exceed every batch capacity: the call works in chunks (tnml_set_core_grad_chunk).  It
+ * leaves the resident batch, its environments, f, the cores, l_pos and the input-gradient buffers exactly as they were, and it
+ * synchronises before returning. */
+int tnml_core_grad(tnml_ctx *ctx, const float *X, int b, const float *cot, float *grad_flat, size_t capacity, float *cf_out);
+/* the same for samples of the attached dataset */
+int tnml_core_grad_indices(tnml_ctx *ctx, const int32_t *idx, int b, const float *cot, float *grad_flat, size_t capacity, float *cf_out);
+/* samples per pass (rounded up to a multiple of 64); 0 = default: the largest multiple of 64 for which each of the two stacks of
+ * stored environments (N x bond capacity x samples floats) stays within 256 MiB, at least 64.  Tests and diagnostics. */
+int tnml_set_core_grad_chunk(tnml_ctx *ctx, int samples);
+
 /* Accuracy / speed of the in-kernel Jacobi SVD (no reference analogue: the reference calls LAPACK,
  * Network_class.py:887).  The iteration ends after a sweep in which every rotation had
  * g^2 <= stop2 * scale^2; the off-diagonals left behind are of relative size ~stop2.  Default 1e-6

@@ -437,6 +437,28 @@ class Network():
         return ctx.input_grad_indices(idx, self._cotangent(cotangent, idx.size), wrt)[0]
 
     # ------------------------------------------------------------------------------------------
+    # core gradients (not in the reference)
+    # ------------------------------------------------------------------------------------------
+    def core_gradient(self, X, cotangent=None, return_cf=False):
+        """G, a list of N float32 arrays in the canonical layouts (ml, D, mr) and, on l_pos, (ml, D, mr, L): the derivative of
+        sum_s sum_l cotangent[l, s] f[l, s] with respect to every core, computed on the device for a batch that does not become
+        resident.  Works at any label position.  cotangent as in input_gradient (a Tensor ('l', 'b'), such as
+        compute_loss_derivate's, is taken by its elements); return_cf: also cf (b,) = sum_l cotangent[l, s] f[l, s].
+        The gradient of a loss: f = net.predict(X); cot = net.compute_loss_derivate(net.apply_act_func(f), y);
+        G = net.core_gradient(X, cot)."""
+        assert self.N == X.shape[1], "The 1 dimension of the input data must be the flattened number of pixels"
+        ctx = self._sync_to_device(max(self._b, 1))
+        G, cf = ctx.core_grad(X, self._cotangent(getattr(cotangent, 'elem', cotangent), X.shape[0]))
+        return (G, cf) if return_cf else G
+
+    def core_gradient_indices(self, indices, cotangent=None, return_cf=False):
+        """core_gradient for samples of the attached dataset."""
+        ctx = self._require_dataset()
+        idx = np.asarray(indices)
+        G, cf = ctx.core_grad_indices(idx, self._cotangent(getattr(cotangent, 'elem', cotangent), idx.size))
+        return (G, cf) if return_cf else G
+
+    # ------------------------------------------------------------------------------------------
     # training
     # ------------------------------------------------------------------------------------------
     def train(self, train_loader, val_loader, lr, n_epochs=10, weight_dec=0.001, L2_flag=True, debug=False):

@@ -34,6 +34,7 @@ SYMBOLS = [
     'tnml_dataset_attach', 'tnml_dataset_detach', 'tnml_dataset_size', 'tnml_select_indices', 'tnml_predict_indices', 'tnml_eval_indices',
     'tnml_resident_metrics', 'tnml_dataset_read', 'tnml_set_any_position',
     'tnml_input_grad', 'tnml_input_grad_indices', 'tnml_set_input_grad_chunk',
+    'tnml_core_grad', 'tnml_core_grad_indices', 'tnml_set_core_grad_chunk',
 ]
 
 
@@ -122,6 +123,9 @@ def lib():
         L.tnml_input_grad.argtypes = [vp, f32p, C.c_int, f32p, f32p, f32p]
         L.tnml_input_grad_indices.argtypes = [vp, i32p, C.c_int, f32p, C.c_int, f32p, f32p]
         L.tnml_set_input_grad_chunk.argtypes = [vp, C.c_int]
+        L.tnml_core_grad.argtypes = [vp, f32p, C.c_int, f32p, f32p, C.c_size_t, f32p]
+        L.tnml_core_grad_indices.argtypes = [vp, i32p, C.c_int, f32p, f32p, C.c_size_t, f32p]
+        L.tnml_set_core_grad_chunk.argtypes = [vp, C.c_int]
         _lib = L
     return _lib
 
@@ -341,6 +345,41 @@ class Context:
     def set_input_grad_chunk(self, n):
         """Samples per pass of the input-gradient calls (rounded up to a multiple of 64); 0: the default (tests, diagnostics)."""
         _chk(lib().tnml_set_input_grad_chunk(self._h, int(n)))
+
+    # ---- core gradients
+    def _core_grad(self, call, b, cot):
+        """The flat gradient of `call(cot pointer, G pointer, capacity, cf pointer)` cut into the canonical core shapes."""
+        cores, bond, lp = self.get_cores()                         # (for the bonds: the C ABI hands them out with the cores)
+        cot, cp = self._cot(cot, b)
+        flat = np.empty(sum(c.size for c in cores), dtype=np.float32)
+        cf = np.empty(b, dtype=np.float32)
+        _chk(call(cp, _ptr(flat, C.c_float), flat.size, _ptr(cf, C.c_float)))
+        G, off = [], 0
+        for shp in core_shapes(bond, lp, self.D, self.L):
+            k = int(np.prod(shp))
+            G.append(flat[off:off + k].reshape(shp).copy())
+            off += k
+        return G, cf
+
+    def core_grad(self, X, cot=None):
+        """(G, cf): G a list of N arrays in the canonical core shapes (ml, D, mr[, L]), the derivative of sum_s cf[s] with respect to
+        every core, cf (b,) = sum_l cot f, for a batch that does not become resident.  cot (L, b), or None for the one-hot of the
+        predicted class."""
+        X = _f32(X)
+        assert X.ndim == 3 and X.shape[1] == self.N and X.shape[2] == self.D, \
+            "The 1 dimension of the input data must be the flattened number of pixels"
+        b = X.shape[0]
+        return self._core_grad(lambda cp, gp, cap, cfp: lib().tnml_core_grad(self._h, _ptr(X, C.c_float), b, cp, gp, cap, cfp), b, cot)
+
+    def core_grad_indices(self, idx, cot=None):
+        """The same for the dataset samples idx."""
+        idx = self._idx(idx)
+        b = idx.size
+        return self._core_grad(lambda cp, gp, cap, cfp: lib().tnml_core_grad_indices(self._h, _ptr(idx, C.c_int32), b, cp, gp, cap, cfp), b, cot)
+
+    def set_core_grad_chunk(self, n):
+        """Samples per pass of the core-gradient calls (rounded up to a multiple of 64); 0: the default (tests, diagnostics)."""
+        _chk(lib().tnml_set_core_grad_chunk(self._h, int(n)))
 
     # ---- hot path
     def forward(self, want_f=True):

@@ -235,6 +235,45 @@ static void check_input_grad(const InputGradParams &p, dim3 g, dim3 b, size_t sh
   }
 }
 
+// core gradients (kernels_coregrad.hip): one block for both kernels.  The chain kernel touches every core, X, cot, both stacks and cf;
+// the reduction both stacks, X, cot and every core's extent of G through the offset half of the table.
+static void check_core_grad(const CoreGradParams &p, dim3 g, dim3 b, size_t shm, bool reduce) {
+  scan(&p, sizeof p, "CoreGradParams");
+  if (p.b < 1 || p.b > p.b_pad || p.b_pad % 64 || p.x_bpad < p.b_pad) die("CoreGradParams: b %d b_pad %d x_bpad %d", p.b, p.b_pad, p.x_bpad);
+  if (p.N < 2 || p.D < 2 || p.D > kMaxD || p.L < 1 || p.l_pos < 0 || p.l_pos >= p.N) die("CoreGradParams: N %d D %d L %d l_pos %d", p.N, p.D, p.L, p.l_pos);
+  if (p.mb < 1 || p.mb > p.cap) die("CoreGradParams: largest bond %d, capacity %d", p.mb, p.cap);
+  if (p.first != 0 && p.first != 1) die("CoreGradParams: first %d", p.first);
+  const size_t bp = p.b_pad, tiles = (size_t)(p.b + 63) / 64 * 64;       // both kernels work on whole tiles of 64 samples
+  if (tiles > bp) die("CoreGradParams: %zu samples in tiles, b_pad %zu", tiles, bp);
+  if (!reduce) {
+    if (b.x != 256 || g.x != (unsigned)((p.b + 63) / 64) || g.y != 1 || g.z != 1) die("core_grad_chain_kernel: grid %u block %u for b %d", g.x, b.x, p.b);
+    if (shm < core_grad_chain_lds_bytes(p.mb, p.D, p.L, p.N)) die("core_grad_chain_kernel: %zu bytes of LDS, %zu wanted", shm, core_grad_chain_lds_bytes(p.mb, p.D, p.L, p.N));
+  } else {
+    if (b.x != 256 || g.x != (unsigned)p.N || g.y != (unsigned)core_grad_reduce_blocks(p.mb, p.D) || g.z != (unsigned)p.L)
+      die("core_grad_reduce_kernel: grid (%u, %u, %u) block %u for N %d bond %d D %d L %d", g.x, g.y, g.z, b.x, p.N, p.mb, p.D, p.L);
+    if (shm < core_grad_reduce_lds_bytes(p.mb, p.D)) die("core_grad_reduce_kernel: %zu bytes of LDS, %zu wanted", shm, core_grad_reduce_lds_bytes(p.mb, p.D));
+  }
+  need(p.tab, (size_t)2 * p.N * 4, "CoreGradParams.tab");
+  need(p.stackP, (size_t)p.N * p.cap * bp * 4, "CoreGradParams.stackP");
+  need(p.stackQ, (size_t)p.N * p.cap * bp * 4, "CoreGradParams.stackQ");
+  need(p.X, (size_t)p.N * p.x_bpad * p.D * 4, "CoreGradParams.X");
+  need(p.cot, (size_t)p.L * bp * 4, "CoreGradParams.cot");
+  opt(p.cf, (size_t)p.b * 4, "CoreGradParams.cf");
+  size_t off = 0;
+  for (int i = 0; i < p.N; ++i) {
+    const int ml = i == 0 ? 1 : p.tab[i - 1], mr = i == p.N - 1 ? 1 : p.tab[i];
+    if (ml < 1 || ml > p.mb || mr < 1 || mr > p.mb) die("CoreGradParams: site %d is %d x %d, largest bond %d", i, ml, mr, p.mb);
+    // the reduction covers a site's output with ceil(ml D / 16) x ceil(ceil(mr / 16) / 2) wave pairs, four to a workgroup
+    if (reduce && (size_t)((ml * p.D + 15) / 16) * (((mr + 15) / 16 + 1) / 2) > (size_t)4 * g.y) die("core_grad_reduce_kernel: site %d (%d x %d) is not covered by %u workgroups", i, ml, mr, g.y);
+    const size_t ne = (size_t)ml * p.D * mr * (i == p.l_pos ? p.L : 1);
+    if ((size_t)p.tab[p.N + i] != off) die("CoreGradParams: core %d at offset %d, the flat layout has it at %zu", i, p.tab[p.N + i], off);
+    if (reduce) need(p.G + off, ne * 4, "CoreGradParams.G");
+    else if (i == p.l_pos) need(p.labcore, ne * 4, "CoreGradParams.labcore");
+    else need(p.cores + (size_t)i * p.core_stride, ne * 4, "CoreGradParams.cores");
+    off += ne;
+  }
+}
+
 // ---- call trace ----------------------------------------------------------------------------------------------------------------
 static FILE *g_tr = nullptr;
 static long g_tr_lines = 0;
@@ -293,6 +332,10 @@ static void tr_struct(const MeetParams &p) { P(Lenv) P(Renv) P(x) P(core) P(f) I
 static void tr_struct(const InputGradParams &p) {
   P(bond) P(cores) P(labcore) P(X) P(cot) P(stack) P(g) P(cf) I(core_stride) I(b) I(b_pad) I(x_bpad) I(N) I(D) I(L) I(l_pos) I(cap) I(mb)
 }
+static void tr_struct(const CoreGradParams &p) {
+  P(tab) P(cores) P(labcore) P(X) P(cot) P(stackP) P(stackQ) P(G) P(cf) I(core_stride) I(b) I(b_pad) I(x_bpad) I(N) I(D) I(L) I(l_pos) I(cap)
+  I(mb) I(first)
+}
 static void tr_struct(const InputGradPixels &p) { P(g) P(data) P(idx) P(out) I(b) I(N) I(D) }
 static void tr_struct(const BigExtArgs &p) { P(Eprev) P(x_km1) P(x_k) V(A) I(b_pad) P(Ecur) P(Pk) }
 static void tr_struct(const ChainSite &p) { I(core_off) I(is_label) I(n_in) I(n_out) I(s_in) I(s_d) I(s_out) I(x_site) I(env_out_off) }
@@ -325,6 +368,7 @@ static void tr_launch(const std::string &name, dim3 g, dim3 b, size_t shm, hipSt
     else if (is("PrepParams")) tr_struct(*(const PrepParams *)args[i]);
     else if (is("MeetParams")) tr_struct(*(const MeetParams *)args[i]);
     else if (is("InputGradParams")) tr_struct(*(const InputGradParams *)args[i]);
+    else if (is("CoreGradParams")) tr_struct(*(const CoreGradParams *)args[i]);
     else if (is("InputGradPixels")) tr_struct(*(const InputGradPixels *)args[i]);
     else if (is("BigExtArgs")) tr_struct(*(const BigExtArgs *)args[i]);
     else if (is("CoreView")) { const CoreView &v = *(const CoreView *)args[i]; tr(" [%s %d %d %d %d %d]", dp(v.base).c_str(), v.n_in, v.n_out, v.s_in, v.s_d, v.s_out); }
@@ -394,6 +438,8 @@ hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t s
     check_meet(*(const MeetParams *)args[0], g, b, shm);
   } else if (has("input_grad_kernel")) {
     check_input_grad(*(const InputGradParams *)args[0], g, b, shm);
+  } else if (has("core_grad_chain_kernel") || has("core_grad_reduce_kernel")) {
+    check_core_grad(*(const CoreGradParams *)args[0], g, b, shm, has("core_grad_reduce_kernel"));
   } else if (has("input_grad_onehot_kernel")) {   // (f, f_bpad, L, b, cot, b_pad)
     const int fbp = *(int *)args[1], L = *(int *)args[2], bb = *(int *)args[3], bp = *(int *)args[5];
     if (bb < 1 || bb > bp || bp > fbp || (size_t)g.x * b.x < (size_t)bp) die("input_grad_onehot_kernel: b %d b_pad %d f_bpad %d grid %u x %u", bb, bp, fbp, g.x, b.x);

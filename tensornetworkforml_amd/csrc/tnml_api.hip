@@ -4,6 +4,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -284,6 +285,12 @@ struct tnml_ctx {
   float *ig_stack = nullptr, *ig_cot = nullptr, *ig_g = nullptr, *ig_gpix = nullptr, *ig_cf = nullptr;
   int *ig_bond = nullptr;
   int ig_cap = 0, ig_chunk = 0;              // ig_chunk: tnml_set_input_grad_chunk (0 = default)
+  // core gradients (tnml_core_grad): one group sized from cg_cap samples -- the stacks of both passes
+  // [N][Mmax][cg_cap], cot [L][cg_cap], cf [cg_cap] -- with the table [2N] (bonds, then every core's offset in the flat layout) and
+  // G, the gradient in the layout of tnml_get_cores, sized for every bond at its capacity
+  float *cg_stackP = nullptr, *cg_stackQ = nullptr, *cg_cot = nullptr, *cg_cf = nullptr, *cg_G = nullptr;
+  int *cg_tab = nullptr;
+  int cg_cap = 0, cg_chunk = 0;              // cg_chunk: tnml_set_core_grad_chunk (0 = default)
   // multi-GPU
   ncclComm_t comm = nullptr;
   int rank = 0, nranks = 1;
@@ -1345,6 +1352,117 @@ extern "C" int tnml_set_input_grad_chunk(tnml_ctx *c, int samples) {
   if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
   if (samples < 0) return fail(TNML_ERR_ARG, "samples per pass %d < 0", samples);
   c->ig_chunk = samples;
+  return TNML_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// core gradients: G_i = d sum_s cf[s] / d A_i for every site (kernels_coregrad.hip)
+// ---------------------------------------------------------------------------------------------
+// samples per pass: the rule of ig_chunk_samples -- each of the two stacks stays within kIgStackBytes
+static int cg_chunk_samples(const tnml_ctx *c) {
+  if (c->cg_chunk > 0) return (c->cg_chunk + 63) / 64 * 64;
+  const size_t per_sample = (size_t)c->N * c->Mmax * sizeof(float);
+  return (int)std::max<size_t>(64, kIgStackBytes / per_sample / 64 * 64);
+}
+
+// Core-gradient group, grown to bp samples (a multiple of 64).  G and the table do not depend on bp; they are members all the same,
+// so that a failed growth leaves nothing behind.  The chunk's site-major X, its staging buffer and (cot == NULL) its f are the
+// prediction group's.
+static int cg_ensure_buffers(tnml_ctx *c, int bp) {
+  if (bp <= c->cg_cap) return TNML_OK;
+  const size_t N = c->N, L = c->L;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->cg_cap = 0;
+  int rc = make_group(c, "the core-gradient buffers", {
+      own_dev(c->cg_stackP, N * c->Mmax * bp), own_dev(c->cg_stackQ, N * c->Mmax * bp), own_dev(c->cg_cot, L * bp),
+      own_dev(c->cg_cf, (size_t)bp), own_dev(c->cg_tab, 2 * N), own_dev(c->cg_G, N * c->core_stride + c->lab_elems)});
+  if (rc) return rc;
+  HIP_TRY(hipMemsetAsync(c->cg_cot, 0, L * bp * sizeof(float), c->stream));     // the columns behind a chunk's samples stay finite
+  c->cg_cap = bp;
+  return TNML_OK;
+}
+
+// X [b][N][D] on the host, or the dataset rows idx[0..b) when X is NULL
+static int core_grad_impl(tnml_ctx *c, const float *X, const int32_t *idx, int b, const float *cot, float *grad_flat, size_t capacity, float *cf_out) {
+  const int N = c->N, D = c->D, L = c->L;
+  if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
+  size_t total = 0;
+  std::vector<int> tab(2 * (size_t)N, 0);
+  int mb = 1;
+  for (int i = 0; i < N; ++i) {
+    if (i < N - 1) { tab[i] = c->bond[i]; mb = std::max(mb, c->bond[i]); }
+    if (total > (size_t)INT_MAX) return fail(TNML_ERR_ARG, "core gradient: %zu floats of cores are beyond the offset table", total);
+    tab[N + i] = (int)total;
+    total += core_elems(c, c->bond, i, c->l_pos);
+  }
+  if (capacity < total) return fail(TNML_ERR_ARG, "capacity %zu < %zu floats", capacity, total);
+  const size_t lds = core_grad_chain_lds_bytes(mb, D, L, N);
+  if (lds > kLdsMax)
+    return fail(TNML_ERR_ARG, "core gradient at D = %d, bond %d, L = %d: %zu bytes of LDS exceed 160 KB", D, mb, L, lds);
+  HIP_TRY(hipSetDevice(c->device));
+  int rc;
+  if (idx && (rc = ds_upload_indices(c, idx, b))) return rc;    // refuses a bad index before anything is launched
+  const int chunk = std::min(cg_chunk_samples(c), (b + 63) / 64 * 64);
+  if ((rc = pred_ensure_buffers(c, chunk))) return rc;
+  if ((rc = cg_ensure_buffers(c, chunk))) return rc;
+  const int bp = c->cg_cap, xbp = c->pred_cap;
+  HIP_TRY(hipMemcpyAsync(c->cg_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));                     // (`tab` is a local: no return below leaves the copy reading it)
+  if (!cot && (rc = pred_table(c))) return rc;
+  for (int off = 0; off < b; off += chunk) {
+    const int bc = std::min(chunk, b - off);
+    if (idx) {
+      if ((rc = ds_gather(c, c->ds_idx + off, bc, xbp, c->Xpred, nullptr))) return rc;
+    } else {
+      HIP_TRY(hipMemcpyAsync(c->Xpred_stage, X + (size_t)off * N * D, (size_t)bc * N * D * sizeof(float), hipMemcpyHostToDevice, c->stream));
+      if (D != kD) launch_transpose_input_anyd(c->Xpred_stage, c->Xpred, bc, xbp, N, D, c->stream);
+      else launch_transpose_input(c->Xpred_stage, c->Xpred, bc, xbp, N, c->stream);
+      HIP_TRY(hipGetLastError());
+    }
+    if (cot) {
+      HIP_TRY(hipMemcpy2DAsync(c->cg_cot, (size_t)bp * sizeof(float), cot + off, (size_t)b * sizeof(float), (size_t)bc * sizeof(float), L,
+                               hipMemcpyHostToDevice, c->stream));
+    } else {
+      // the predicted class: the prediction chain as it is, then the one-hot of its first maximum
+      if ((rc = pred_chain(c, bc))) return rc;
+      if (!launch_input_grad_onehot(c->fpred, xbp, L, bc, c->cg_cot, bp, c->stream)) return fail(TNML_ERR_ARG, "internal: one-hot launch refused");
+      HIP_TRY(hipGetLastError());
+    }
+    CoreGradParams p{};
+    p.tab = c->cg_tab; p.cores = c->cores; p.labcore = c->lab[c->lab_cur]; p.X = c->Xpred; p.cot = c->cg_cot;
+    p.stackP = c->cg_stackP; p.stackQ = c->cg_stackQ; p.G = c->cg_G; p.cf = c->cg_cf; p.core_stride = c->core_stride;
+    p.b = bc; p.b_pad = bp; p.x_bpad = xbp; p.N = N; p.D = D; p.L = L; p.l_pos = c->l_pos; p.cap = c->Mmax; p.mb = mb;
+    p.first = off == 0;
+    if (!launch_core_grad_chain(p, c->stream)) return fail(TNML_ERR_ARG, "internal: core-gradient chain launch refused (b %d, b_pad %d)", bc, bp);
+    HIP_TRY(hipGetLastError());
+    if (!launch_core_grad_reduce(p, c->stream)) return fail(TNML_ERR_ARG, "internal: core-gradient reduction launch refused (b %d, b_pad %d)", bc, bp);
+    HIP_TRY(hipGetLastError());
+    if (cf_out) HIP_TRY(hipMemcpyAsync(cf_out + off, c->cg_cf, (size_t)bc * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(hipMemcpyAsync(grad_flat, c->cg_G, total * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return TNML_OK;
+}
+
+extern "C" int tnml_core_grad(tnml_ctx *c, const float *X, int b, const float *cot, float *grad_flat, size_t capacity, float *cf_out) {
+  if (!c || !X || !grad_flat) return fail(TNML_ERR_ARG, "NULL argument");
+  if (c->comm) return fail(TNML_ERR_STATE, "core gradients are single-GPU only: a communicator is attached");
+  if (b < 1) return fail(TNML_ERR_ARG, "empty batch");
+  return core_grad_impl(c, X, nullptr, b, cot, grad_flat, capacity, cf_out);
+}
+
+extern "C" int tnml_core_grad_indices(tnml_ctx *c, const int32_t *idx, int b, const float *cot, float *grad_flat, size_t capacity, float *cf_out) {
+  int rc = ds_usable(c);
+  if (rc) return rc;
+  if (!idx || !grad_flat) return fail(TNML_ERR_ARG, "NULL argument");
+  if (b < 1) return fail(TNML_ERR_ARG, "empty index list");
+  return core_grad_impl(c, nullptr, idx, b, cot, grad_flat, capacity, cf_out);
+}
+
+extern "C" int tnml_set_core_grad_chunk(tnml_ctx *c, int samples) {
+  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
+  if (samples < 0) return fail(TNML_ERR_ARG, "samples per pass %d < 0", samples);
+  c->cg_chunk = samples;
   return TNML_OK;
 }
 

@@ -308,4 +308,29 @@ struct InputGradPixels {
 };
 bool launch_input_grad_pixels(const InputGradPixels &p, hipStream_t st);
 
+// Core gradients (kernels_coregrad.hip): one parameter block for the chain kernel (both stacks, cf) and the reduction kernel (G).
+struct CoreGradParams {
+  const int *tab;          // [2N]: tab[0 .. N-2] bond dimensions of the chain; tab[N + i] offset of core i in the flat layout of G
+  const float *cores;      // plain cores, core i at i * core_stride, [ml][D][mr]
+  const float *labcore;    // [ml][D][mr][L] of site l_pos
+  const float *X;          // [N][x_bpad][D]; samples b .. b_pad-1 are zero
+  const float *cot;        // [L][b_pad]
+  float *stackP;           // [N][cap][b_pad]: slot i receives P_i, i = 1 .. N-1
+  float *stackQ;           // [N][cap][b_pad]: slot i receives Q_i, i = 0 .. N-2
+  float *G;                // the layout of tnml_get_cores: core after core, (ml, D, mr), on l_pos (ml, D, mr, L)
+  float *cf;               // [b] or nullptr
+  size_t core_stride;
+  int b, b_pad, x_bpad, N, D, L, l_pos;
+  int cap;                 // rows of a stack slot: the context's bond capacity
+  int mb;                  // largest bond of the chain: what the LDS tiles are sized for
+  int first;               // reduction: 1 = the accumulators start at zero, 0 = they start from G (a chunk after the first)
+};
+size_t core_grad_chain_lds_bytes(int mb, int D, int L, int N);
+size_t core_grad_reduce_lds_bytes(int mb, int D);
+// workgroups of the reduction along y: four waves, each with two 16 x 16 output tiles side by side, cover a site of bonds <= mb
+int core_grad_reduce_blocks(int mb, int D);
+// false: refused (geometry / LDS)
+bool launch_core_grad_chain(const CoreGradParams &p, hipStream_t st);
+bool launch_core_grad_reduce(const CoreGradParams &p, hipStream_t st);
+
 }  // namespace tnml
