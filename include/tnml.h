@@ -113,6 +113,10 @@ int tnml_cores_size(tnml_ctx *ctx, size_t *n_floats);
 int tnml_get_cores(tnml_ctx *ctx, float *cores_flat, size_t capacity, int32_t *bond, int *l_pos);
 /* every core *= factor: the calibration loop of Network.__init__ (Network_class.py:175-176) */
 int tnml_scale_cores(tnml_ctx *ctx, double factor);
+/* Tests and diagnostics: the core slots as the device holds them, padding included -- slots [N][core_stride] with
+ * core_stride = Mcap D Mcap floats (Mcap: the bond capacity, max(M, D min(L, M))) and the label buffer [Mcap D Mcap L]; the
+ * capacities are in floats (TNML_ERR_ARG when too small). */
+int tnml_get_core_slots(tnml_ctx *ctx, float *slots, size_t slots_capacity, float *label_buffer, size_t label_capacity);
 
 /* ---- batch ------------------------------------------------------------------------------ */
 /* X [b][N][D] float32, y [b] int32 (may be NULL when only forward is wanted) */
@@ -275,6 +279,43 @@ int tnml_core_grad_indices(tnml_ctx *ctx, const int32_t *idx, int b, const float
 /* samples per pass (rounded up to a multiple of 64); 0 = default: the largest multiple of 64 for which each of the two stacks of
  * stored environments (N x bond capacity x samples floats) stays within 256 MiB, at least 64.  Tests and diagnostics. */
 int tnml_set_core_grad_chunk(tnml_ctx *ctx, int samples);
+
+/* ---- gradient training over all cores --------------------------------------------------------- */
+/* Optimiser steps on the device from the core gradients above (csrc/kernels_optim.hip): whole-chain gradient
+ * descent at fixed bonds, at any l_pos, without an SVD -- the companion of the two-site sweep (sweep to find the bonds, then
+ * fine-tune).  No reference analogue.  Per batch: the prediction chain, the metrics of the batch BEFORE the step, the library's own
+ * loss derivative (compute_loss_derivate of apply_act_func, all nine activation / loss pairs) as the cotangent, the core gradients
+ * G, then one update of every core in its slot.  The loss derivative is the descent direction, so the update ADDS:
+ *   TNML_OPT_SGD   d = G - wd A;  clip: per core, if sum|d| > sum|A| then d *= sum|A| / sum|d| (the reference's rule for the merged
+ *                  tensor, applied to each core);  momentum mu > 0: vel = mu vel + d, A += lr vel;  mu == 0: A += lr d (no state)
+ *   TNML_OPT_ADAM  t += 1; m = b1 m + (1 - b1) G; v = b2 v + (1 - b2) G G;
+ *                  A += lr ((m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps) - wd A)          (decoupled decay; no clip)
+ * in float64 from the float32 G, rounded once on the store; sum|.| in float64 in a fixed order.
+ * tnml_optim_config: momentum in [0, 1), betas in [0, 1), eps > 0, clip 0 / 1 (TNML_ERR_ARG otherwise, and for ADAM with clip != 0).
+ * Default: SGD, momentum 0, betas 0.9 / 0.999, eps 1e-8, clip 1.  It also does what tnml_optim_reset does.
+ * STATE: vel / m / v are device buffers in the layout of tnml_get_cores, allocated on the first step of a stateful optimiser and
+ * bound to the bonds and l_pos of that step (or of the last tnml_optim_reset / tnml_optim_config).  A step at other bonds or another
+ * l_pos -- after a sweep, say -- returns TNML_ERR_STATE until tnml_optim_reset, which zeroes the state, sets t = 0 and binds it to
+ * the current bonds and l_pos.  SGD without momentum has no state and is never refused for this reason. */
+enum { TNML_OPT_SGD = 0, TNML_OPT_ADAM = 1 };
+int tnml_optim_config(tnml_ctx *ctx, int kind, double momentum, double beta1, double beta2, double eps, int clip);
+int tnml_optim_reset(tnml_ctx *ctx);
+/* n_steps = ceil(n / batch) optimiser steps from the attached dataset: step k uses the samples idx[k * batch .. min((k + 1) * batch, n)).
+ * metrics_out [n_steps][3] = (correct, sum |onehot - act(f)|, non-finite samples) of each batch BEFORE its step, or NULL.
+ * The index list and the tables are uploaded once, every step is enqueued without waiting, and the call synchronises once at the
+ * end.  A batch may exceed every buffer: it is worked in the chunks of tnml_set_core_grad_chunk, and the updated cores do not
+ * depend on the chunk size.  If a step saw a non-finite activated output the call returns TNML_ERR_NONFINITE after all steps ran:
+ * the cores are then what they became (as after a diverged sweep: set them again); metrics_out is filled all the same.
+ * AFTER a call the context is as after tnml_scale_cores: the cores changed, so the environments, f and the norm environments of
+ * the resident batch are stale -- tnml_sweep returns TNML_ERR_STATE until a tnml_forward; the resident batch and its labels stay.
+ * REFUSALS, all before anything is launched: NULL pointers, n < 1, batch < 1, an index outside the dataset, unknown act_fn /
+ * loss_fn, a shape beyond the LDS limit of the core gradients or more labels than the metrics kernel's tile holds -> TNML_ERR_ARG;
+ * no dataset, cores never set, a communicator attached, state bound to other bonds -> TNML_ERR_STATE. */
+int tnml_gd_train_indices(tnml_ctx *ctx, const int32_t *idx, int n, int batch, float lr, float weight_dec, int act_fn, int loss_fn,
+                          float T, double *metrics_out);
+/* one step on a host batch X [b][N][D], y [b] (labels outside [0, L): TNML_ERR_ARG); metrics3 [3] or NULL */
+int tnml_gd_step(tnml_ctx *ctx, const float *X, const int32_t *y, int b, float lr, float weight_dec, int act_fn, int loss_fn, float T,
+                 double *metrics3);
 
 /* Accuracy / speed of the in-kernel Jacobi SVD (no reference analogue: the reference calls LAPACK,
  * Network_class.py:887).  The iteration ends after a sweep in which every rotation had

@@ -623,6 +623,80 @@ class Network():
                   % (epoch, n_epochs, epoch_train_acc.mean(), val_acc[-1]))
         return val_acc, (np.array(var_hist) if k is None else var_hist)
 
+    # ------------------------------------------------------------------------------------------
+    # gradient training over all cores at fixed bonds (not in the reference)
+    # ------------------------------------------------------------------------------------------
+    def _after_device_update(self):
+        """Host bookkeeping after the device changed every core in place (that of _sweep_resident; no environment survives)."""
+        self._device_newer = True
+        self._As = None
+        self._invalidate_envs()
+
+    def configure_optimizer(self, optimizer='sgd', momentum=0.0, betas=(0.9, 0.999), eps=1e-8, clip=True):
+        """The optimiser of gradient_step / train_gradient: 'sgd' (momentum, the reference's clip per core) or 'adam' (decoupled
+        weight decay, no clip).  Resets the optimiser state."""
+        self._sync_to_device().optim_config(optimizer, momentum, betas[0], betas[1], eps, clip and optimizer != 'adam')
+
+    def gradient_step(self, indices_or_X, y=None, lr=1e-3, weight_dec=0.0):
+        """One optimiser step over all cores on the device, at the current bonds and label position: the library's loss
+        derivative of the batch as the cotangent of the core gradients, then A += lr * (...) in place.
+        indices_or_X: indices into the attached dataset (y None), or a batch X (b, N, D) with its labels y.  Returns
+        (accuracy, MAE) of the batch BEFORE the step.  A forward is needed before the next sweep."""
+        if y is None:
+            ctx = self._require_dataset()
+            idx = np.asarray(indices_or_X)
+            b = idx.size
+            correct, abs_sum, _ = ctx.gd_train_indices(idx, max(b, 1), lr, weight_dec, self.act_fn, self.loss_fn, self.T)[0]
+        else:
+            X = getattr(indices_or_X, 'elem', indices_or_X)
+            assert self.N == X.shape[1], "The 1 dimension of the input data must be the flattened number of pixels"
+            ctx = self._sync_to_device(max(self._b, 1))
+            b = X.shape[0]
+            correct, abs_sum, _ = ctx.gd_step(X, y, lr, weight_dec, self.act_fn, self.loss_fn, self.T)
+        self._after_device_update()
+        return correct / b, abs_sum / (b * self.L)
+
+    def train_gradient(self, train_index_loader, val_index_loader, lr, n_epochs=10, weight_dec=0.0, optimizer='sgd', momentum=0.0,
+                       betas=(0.9, 0.999), eps=1e-8, clip=True):
+        """Gradient descent over all cores from the attached dataset, the companion of `train_resident`: sweep to find the
+        bonds, then fine-tune at fixed bonds (no SVD, any label position).  Every batch of the index loader is one optimiser
+        step; an epoch is one device call over the concatenated batches (a ragged last batch is a call of its own).  Validation
+        and the printed lines are train_resident's.  Returns (val_acc, hist), hist of shape (n_epochs, 2, n_batches): accuracy
+        and MAE of every batch before its step."""
+        ctx = self._require_dataset()
+        self._check_forward_position(self.l_pos)
+        ctx.optim_config(optimizer, momentum, betas[0], betas[1], eps, clip and optimizer != 'adam')
+        val_acc, hist = [], []
+        print("\n --- TRAINING PROCEDURE ---")
+        for epoch in range(n_epochs):
+            batches = [np.asarray(idx).ravel() for idx in train_index_loader]
+            acc, mae = np.zeros(len(batches)), np.zeros(len(batches))
+            i = 0
+            while i < len(batches):
+                # batches of one size in a row are one call: step k of it takes samples [k * size, (k + 1) * size)
+                j = i + 1
+                while j < len(batches) and len(batches[j]) == len(batches[i]):
+                    j += 1
+                try:
+                    met = ctx.gd_train_indices(np.concatenate(batches[i:j]), len(batches[i]), lr, weight_dec, self.act_fn, self.loss_fn, self.T)
+                finally:
+                    self._after_device_update()
+                sizes = np.array([len(b) for b in batches[i:j]], dtype=np.float64)
+                acc[i:j] = met[:, 0] / sizes
+                mae[i:j] = met[:, 1] / (sizes * self.L)
+                print('\r' + "Epoch %d/%d - train accuracy : %.4f - completed : %.2f "
+                      % (epoch, n_epochs, acc[j - 1], j * 100 / len(batches)) + '%', end=' ')
+                i = j
+            hist.append([acc, mae])
+            epoch_val_acc = np.zeros(len(val_index_loader))
+            for i, idx in enumerate(val_index_loader, 0):
+                correct, _, _ = ctx.eval_indices(idx, self.act_fn, self.T)
+                epoch_val_acc[i] = correct / len(idx)
+            val_acc.append(epoch_val_acc.mean())
+            print('\r' + "Epoch %d/%d - train accuracy : %.4f - val accuracy: %.4f"
+                  % (epoch, n_epochs, acc.mean(), val_acc[-1]))
+        return val_acc, np.array(hist)
+
     def evaluate(self, indices, activated=True):
         """(accuracy, mean absolute error) of the network over samples of the attached dataset, reduced on the device.
         `indices` is an index loader -- the result is then the mean over its batches of the per-batch accuracy and error,

@@ -18,6 +18,7 @@ TRUNC = {'reference': 0, 'fixed': 1, 'adaptive': 2}
 SIDE_LEFT, SIDE_RIGHT = 0, 1
 DATASET_FORM = {'features': 0, 'pixels': 1}
 WRT = {'features': 0, 'pixels': 1}
+OPTIM = {'sgd': 0, 'adam': 1}
 DBG = {'B': 0, 'dB_raw': 1, 'B_new': 2, 'sigma': 3, 'scalars': 4, 'L2_grad': 5}
 
 # every symbol include/tnml.h declares (tests check the library exports all of them)
@@ -35,6 +36,7 @@ SYMBOLS = [
     'tnml_resident_metrics', 'tnml_dataset_read', 'tnml_set_any_position',
     'tnml_input_grad', 'tnml_input_grad_indices', 'tnml_set_input_grad_chunk',
     'tnml_core_grad', 'tnml_core_grad_indices', 'tnml_set_core_grad_chunk',
+    'tnml_optim_config', 'tnml_optim_reset', 'tnml_gd_train_indices', 'tnml_gd_step', 'tnml_get_core_slots',
 ]
 
 
@@ -126,6 +128,11 @@ def lib():
         L.tnml_core_grad.argtypes = [vp, f32p, C.c_int, f32p, f32p, C.c_size_t, f32p]
         L.tnml_core_grad_indices.argtypes = [vp, i32p, C.c_int, f32p, f32p, C.c_size_t, f32p]
         L.tnml_set_core_grad_chunk.argtypes = [vp, C.c_int]
+        L.tnml_optim_config.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int]
+        L.tnml_optim_reset.argtypes = [vp]
+        L.tnml_get_core_slots.argtypes = [vp, f32p, C.c_size_t, f32p, C.c_size_t]
+        L.tnml_gd_train_indices.argtypes = [vp, i32p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, f64p]
+        L.tnml_gd_step.argtypes = [vp, f32p, i32p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, f64p]
         _lib = L
     return _lib
 
@@ -212,6 +219,14 @@ class Context:
             cores.append(flat[off:off + k].reshape(shp).copy())
             off += k
         return cores, bond, lp.value
+
+    def core_slots(self):
+        """(slots (N, Mcap * D * Mcap), label buffer (Mcap * D * Mcap * L,)) as the device holds them, padding included (tests)."""
+        cap = max(self.M, self.D * min(self.L, self.M))
+        slots = np.empty((self.N, cap * self.D * cap), dtype=np.float32)
+        lab = np.empty(cap * self.D * cap * self.L, dtype=np.float32)
+        _chk(lib().tnml_get_core_slots(self._h, _ptr(slots, C.c_float), slots.size, _ptr(lab, C.c_float), lab.size))
+        return slots, lab
 
     def scale_cores(self, factor):
         _chk(lib().tnml_scale_cores(self._h, float(factor)))
@@ -380,6 +395,42 @@ class Context:
     def set_core_grad_chunk(self, n):
         """Samples per pass of the core-gradient calls (rounded up to a multiple of 64); 0: the default (tests, diagnostics)."""
         _chk(lib().tnml_set_core_grad_chunk(self._h, int(n)))
+
+    # ---- gradient training over all cores
+    def optim_config(self, kind='sgd', momentum=0.0, beta1=0.9, beta2=0.999, eps=1e-8, clip=True):
+        """The optimiser of gd_train_indices / gd_step: 'sgd' (momentum, per-core clip) or 'adam' (clip must be off).  Also
+        resets the optimiser state."""
+        if kind not in OPTIM:
+            raise TnmlError(-1, 'unknown optimiser %r' % (kind,))
+        _chk(lib().tnml_optim_config(self._h, OPTIM[kind], float(momentum), float(beta1), float(beta2), float(eps), int(bool(clip))))
+
+    def optim_reset(self):
+        """Zero vel / m / v, t = 0, and bind the state to the current bonds and l_pos."""
+        _chk(lib().tnml_optim_reset(self._h))
+
+    def gd_train_indices(self, idx, batch, lr, weight_dec, act_fn, loss_fn, T):
+        """ceil(n / batch) optimiser steps over the dataset samples idx, batch after batch, in one call with one
+        synchronisation.  -> float64 (n_steps, 3): (correct, sum |onehot - act(f)|, non-finite samples) of every batch before
+        its step."""
+        idx = self._idx(idx)
+        batch = int(batch)
+        met = np.zeros((max(-(-idx.size // batch), 1) if batch >= 1 else 1, 3), dtype=np.float64)
+        _chk(lib().tnml_gd_train_indices(self._h, _ptr(idx, C.c_int32), idx.size, batch, float(lr), float(weight_dec), ACT[act_fn],
+                                         LOSS[loss_fn], float(T), _ptr(met, C.c_double)))
+        return met
+
+    def gd_step(self, X, y, lr, weight_dec, act_fn, loss_fn, T):
+        """One optimiser step on a host batch X (b, N, D), y (b,) -> (correct, sum |onehot - act(f)|, non-finite samples)
+        of the batch before the step."""
+        X = _f32(X)
+        assert X.ndim == 3 and X.shape[1] == self.N and X.shape[2] == self.D, \
+            "The 1 dimension of the input data must be the flattened number of pixels"
+        y = np.ascontiguousarray(y, dtype=np.int32)
+        assert y.shape == (X.shape[0],)
+        out = (C.c_double * 3)()
+        _chk(lib().tnml_gd_step(self._h, _ptr(X, C.c_float), _ptr(y, C.c_int32), X.shape[0], float(lr), float(weight_dec), ACT[act_fn],
+                                LOSS[loss_fn], float(T), out))
+        return int(out[0]), float(out[1]), int(out[2])
 
     # ---- hot path
     def forward(self, want_f=True):

@@ -274,6 +274,45 @@ static void check_core_grad(const CoreGradParams &p, dim3 g, dim3 b, size_t shm,
   }
 }
 
+// gradient training (kernels_optim.hip).  loss_cot_kernel: f and cot at their own strides, the labels of the chunk, one thread per
+// column of cot.  optim_step_kernel: one workgroup per site; every core's slot and its part of G, vel / m / v through the table.
+static void check_loss_cot(const LossCotParams &p, dim3 g, dim3 b, size_t shm) {
+  scan(&p, sizeof p, "LossCotParams");
+  if (p.b < 1 || p.b > p.b_pad || p.b_pad % 64 || p.f_bpad < p.b_pad || p.L < 1) die("LossCotParams: b %d b_pad %d f_bpad %d L %d", p.b, p.b_pad, p.f_bpad, p.L);
+  if (p.act_fn < 0 || p.act_fn > 2 || p.loss_fn < 0 || p.loss_fn > 2) die("LossCotParams: act_fn %d loss_fn %d", p.act_fn, p.loss_fn);
+  if (g.y != 1 || g.z != 1 || (size_t)g.x * b.x < (size_t)p.b_pad) die("loss_cot_kernel: grid %u x %u for b_pad %d", g.x, b.x, p.b_pad);
+  if (shm < loss_cot_lds_bytes(p.L) || shm < (size_t)2 * p.L * b.x * 4) die("loss_cot_kernel: %zu bytes of LDS for L %d", shm, p.L);
+  need(p.f, ((size_t)(p.L - 1) * p.f_bpad + p.b) * 4, "LossCotParams.f");
+  need(p.y, (size_t)p.b * 4, "LossCotParams.y");
+  need(p.cot, (size_t)p.L * p.b_pad * 4, "LossCotParams.cot");
+}
+static void check_optim_step(const OptimStepParams &p, dim3 g, dim3 b) {
+  scan(&p, sizeof p, "OptimStepParams");
+  if (p.N < 2 || p.D < 2 || p.D > kMaxD || p.L < 1 || p.l_pos < 0 || p.l_pos >= p.N) die("OptimStepParams: N %d D %d L %d l_pos %d", p.N, p.D, p.L, p.l_pos);
+  if (g.x != (unsigned)p.N || g.y != 1 || g.z != 1 || b.x != 256) die("optim_step_kernel: grid %u block %u for N %d", g.x, b.x, p.N);
+  if (p.kind != TNML_OPT_SGD && p.kind != TNML_OPT_ADAM) die("OptimStepParams: kind %d", p.kind);
+  if (p.kind == TNML_OPT_ADAM && (p.clip || !p.s0 || !p.s1)) die("OptimStepParams: Adam with clip %d, m %p, v %p", p.clip, (void *)p.s0, (void *)p.s1);
+  if (p.kind == TNML_OPT_ADAM && !(p.corr1 > 0 && p.corr1 <= 1 && p.corr2 > 0 && p.corr2 <= 1)) die("OptimStepParams: bias corrections %g %g", p.corr1, p.corr2);
+  if (p.kind == TNML_OPT_SGD && (p.mu > 0) != (p.s0 != nullptr)) die("OptimStepParams: momentum %g with vel %p", p.mu, (void *)p.s0);
+  need(p.tab, (size_t)2 * p.N * 4, "OptimStepParams.tab");
+  size_t off = 0;
+  for (int i = 0; i < p.N; ++i) {
+    const int ml = i == 0 ? 1 : p.tab[i - 1], mr = i == p.N - 1 ? 1 : p.tab[i];
+    if (ml < 1 || mr < 1) die("OptimStepParams: site %d is %d x %d", i, ml, mr);
+    const size_t ne = (size_t)ml * p.D * mr * (i == p.l_pos ? p.L : 1);
+    if ((size_t)p.tab[p.N + i] != off) die("OptimStepParams: core %d at offset %d, the flat layout has it at %zu", i, p.tab[p.N + i], off);
+    if (i == p.l_pos) need(p.labcore, ne * 4, "OptimStepParams.labcore");
+    else {
+      if (ne > p.core_stride) die("OptimStepParams: core %d of %zu floats in a slot of %zu", i, ne, p.core_stride);
+      need(p.cores + (size_t)i * p.core_stride, ne * 4, "OptimStepParams.cores");
+    }
+    need(p.G + off, ne * 4, "OptimStepParams.G");
+    if (p.s0) need(p.s0 + off, ne * 4, "OptimStepParams.s0");
+    if (p.s1) need(p.s1 + off, ne * 4, "OptimStepParams.s1");
+    off += ne;
+  }
+}
+
 // ---- call trace ----------------------------------------------------------------------------------------------------------------
 static FILE *g_tr = nullptr;
 static long g_tr_lines = 0;
@@ -336,6 +375,11 @@ static void tr_struct(const CoreGradParams &p) {
   P(tab) P(cores) P(labcore) P(X) P(cot) P(stackP) P(stackQ) P(G) P(cf) I(core_stride) I(b) I(b_pad) I(x_bpad) I(N) I(D) I(L) I(l_pos) I(cap)
   I(mb) I(first)
 }
+static void tr_struct(const LossCotParams &p) { P(f) P(y) P(cot) I(L) I(b) I(b_pad) I(f_bpad) I(act_fn) I(loss_fn) R(T) }
+static void tr_struct(const OptimStepParams &p) {
+  P(tab) P(cores) P(labcore) P(G) P(s0) P(s1) I(core_stride) I(N) I(D) I(L) I(l_pos) I(kind) I(clip) R(lr) R(wd) R(mu) R(beta1) R(beta2) R(eps)
+  R(corr1) R(corr2)
+}
 static void tr_struct(const InputGradPixels &p) { P(g) P(data) P(idx) P(out) I(b) I(N) I(D) }
 static void tr_struct(const BigExtArgs &p) { P(Eprev) P(x_km1) P(x_k) V(A) I(b_pad) P(Ecur) P(Pk) }
 static void tr_struct(const ChainSite &p) { I(core_off) I(is_label) I(n_in) I(n_out) I(s_in) I(s_d) I(s_out) I(x_site) I(env_out_off) }
@@ -370,6 +414,8 @@ static void tr_launch(const std::string &name, dim3 g, dim3 b, size_t shm, hipSt
     else if (is("InputGradParams")) tr_struct(*(const InputGradParams *)args[i]);
     else if (is("CoreGradParams")) tr_struct(*(const CoreGradParams *)args[i]);
     else if (is("InputGradPixels")) tr_struct(*(const InputGradPixels *)args[i]);
+    else if (is("LossCotParams")) tr_struct(*(const LossCotParams *)args[i]);
+    else if (is("OptimStepParams")) tr_struct(*(const OptimStepParams *)args[i]);
     else if (is("BigExtArgs")) tr_struct(*(const BigExtArgs *)args[i]);
     else if (is("CoreView")) { const CoreView &v = *(const CoreView *)args[i]; tr(" [%s %d %d %d %d %d]", dp(v.base).c_str(), v.n_in, v.n_out, v.s_in, v.s_d, v.s_out); }
     else if (is("BigFrontTiles")) tr(" %d %d", ((int *)args[i])[0], ((int *)args[i])[1]);
@@ -440,6 +486,10 @@ hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t s
     check_input_grad(*(const InputGradParams *)args[0], g, b, shm);
   } else if (has("core_grad_chain_kernel") || has("core_grad_reduce_kernel")) {
     check_core_grad(*(const CoreGradParams *)args[0], g, b, shm, has("core_grad_reduce_kernel"));
+  } else if (has("loss_cot_kernel")) {
+    check_loss_cot(*(const LossCotParams *)args[0], g, b, shm);
+  } else if (has("optim_step_kernel")) {
+    check_optim_step(*(const OptimStepParams *)args[0], g, b);
   } else if (has("input_grad_onehot_kernel")) {   // (f, f_bpad, L, b, cot, b_pad)
     const int fbp = *(int *)args[1], L = *(int *)args[2], bb = *(int *)args[3], bp = *(int *)args[5];
     if (bb < 1 || bb > bp || bp > fbp || (size_t)g.x * b.x < (size_t)bp) die("input_grad_onehot_kernel: b %d b_pad %d f_bpad %d grid %u x %u", bb, bp, fbp, g.x, b.x);

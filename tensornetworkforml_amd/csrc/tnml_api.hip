@@ -291,6 +291,20 @@ struct tnml_ctx {
   float *cg_stackP = nullptr, *cg_stackQ = nullptr, *cg_cot = nullptr, *cg_cf = nullptr, *cg_G = nullptr;
   int *cg_tab = nullptr;
   int cg_cap = 0, cg_chunk = 0;              // cg_chunk: tnml_set_core_grad_chunk (0 = default)
+  // gradient training (tnml_gd_train_indices).  State group: opt_s0 / opt_s1 (SGD vel / Adam m, v) in the
+  // layout and of the size of cg_G, created by the first step of a stateful optimiser and bound to that step's bonds and l_pos.
+  // Metrics group: [opt_met_cap][4] doubles, one row per step of the call in flight.
+  struct {
+    int kind = TNML_OPT_SGD, clip = 1;
+    double momentum = 0.0, beta1 = 0.9, beta2 = 0.999, eps = 1e-8;
+    long long t = 0;                         // Adam steps taken since the last reset
+    std::vector<int> bond;                   // what the state is bound to (meaningful while opt_s0 exists)
+    int l_pos = -1;
+  } opt;
+  float *opt_s0 = nullptr, *opt_s1 = nullptr;
+  double *opt_met = nullptr;
+  int opt_met_cap = 0;
+  std::vector<int> opt_tab;                  // host copy of cg_tab for the call in flight (outlives the asynchronous upload)
   // multi-GPU
   ncclComm_t comm = nullptr;
   int rank = 0, nranks = 1;
@@ -579,6 +593,18 @@ extern "C" int tnml_get_cores(tnml_ctx *c, float *flat, size_t capacity, int32_t
   }
   if (bond) for (int i = 0; i < c->N - 1; ++i) bond[i] = c->bond[i];
   if (l_pos) *l_pos = c->l_pos;
+  return TNML_OK;
+}
+
+extern "C" int tnml_get_core_slots(tnml_ctx *c, float *slots, size_t slots_capacity, float *label_buffer, size_t label_capacity) {
+  if (!c || !slots || !label_buffer) return fail(TNML_ERR_ARG, "NULL argument");
+  const size_t ns = (size_t)c->N * c->core_stride;
+  if (slots_capacity < ns || label_capacity < c->lab_elems)
+    return fail(TNML_ERR_ARG, "capacities %zu and %zu < %zu and %zu floats", slots_capacity, label_capacity, ns, c->lab_elems);
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(slots, c->cores, ns * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(label_buffer, c->lab[c->lab_cur], c->lab_elems * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return TNML_OK;
 }
 
@@ -1464,6 +1490,189 @@ extern "C" int tnml_set_core_grad_chunk(tnml_ctx *c, int samples) {
   if (samples < 0) return fail(TNML_ERR_ARG, "samples per pass %d < 0", samples);
   c->cg_chunk = samples;
   return TNML_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// gradient training: optimiser steps over all cores from the core gradients (kernels_optim.hip)
+// ---------------------------------------------------------------------------------------------
+static bool opt_stateful(const tnml_ctx *c) { return c->opt.kind == TNML_OPT_ADAM || c->opt.momentum > 0.0; }
+static size_t opt_state_elems(const tnml_ctx *c) { return (size_t)c->N * c->core_stride + c->lab_elems; }     // cg_G's
+
+// zero vel / m / v (when they exist), t = 0, bound to the current bonds and l_pos
+static int opt_reset(tnml_ctx *c) {
+  c->opt.t = 0;
+  c->opt.bond = c->bond;
+  c->opt.l_pos = c->l_pos;
+  if (!c->opt_s0) return TNML_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemsetAsync(c->opt_s0, 0, opt_state_elems(c) * sizeof(float), c->stream));
+  HIP_TRY(hipMemsetAsync(c->opt_s1, 0, opt_state_elems(c) * sizeof(float), c->stream));
+  return TNML_OK;
+}
+
+extern "C" int tnml_optim_config(tnml_ctx *c, int kind, double momentum, double beta1, double beta2, double eps, int clip) {
+  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
+  if (kind != TNML_OPT_SGD && kind != TNML_OPT_ADAM) return fail(TNML_ERR_ARG, "unknown optimiser %d", kind);
+  if (!(momentum >= 0.0 && momentum < 1.0)) return fail(TNML_ERR_ARG, "momentum %g outside [0, 1)", momentum);
+  if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(TNML_ERR_ARG, "betas (%g, %g) outside [0, 1)", beta1, beta2);
+  if (!(eps > 0.0) || !std::isfinite(eps)) return fail(TNML_ERR_ARG, "eps %g is not a positive number", eps);
+  if (clip != 0 && clip != 1) return fail(TNML_ERR_ARG, "clip %d is neither 0 nor 1", clip);
+  if (kind == TNML_OPT_ADAM && clip) return fail(TNML_ERR_ARG, "the clip belongs to TNML_OPT_SGD: configure TNML_OPT_ADAM with clip = 0");
+  c->opt.kind = kind; c->opt.clip = clip;
+  c->opt.momentum = momentum; c->opt.beta1 = beta1; c->opt.beta2 = beta2; c->opt.eps = eps;
+  return opt_reset(c);
+}
+
+extern "C" int tnml_optim_reset(tnml_ctx *c) {
+  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
+  return opt_reset(c);
+}
+
+// State group, on the first step of a stateful optimiser: a failed allocation leaves it empty and the call repeatable
+static int opt_ensure_state(tnml_ctx *c) {
+  if (!opt_stateful(c) || c->opt_s0) return TNML_OK;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  int rc = make_group(c, "the optimiser state", {own_dev(c->opt_s0, opt_state_elems(c)), own_dev(c->opt_s1, opt_state_elems(c))});
+  if (rc) return rc;
+  return opt_reset(c);
+}
+
+static int opt_ensure_metrics(tnml_ctx *c, int n_steps) {
+  if (n_steps <= c->opt_met_cap) return TNML_OK;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->opt_met_cap = 0;
+  int rc = make_group(c, "the per-step metrics", {own_dev(c->opt_met, (size_t)n_steps * 4)});
+  if (rc) return rc;
+  c->opt_met_cap = n_steps;
+  return TNML_OK;
+}
+
+// n_steps = ceil(n / batch) steps over X [n][N][D], y [n] on the host, or over the dataset rows idx[0..n) when X is NULL.  The
+// per-chunk body is core_grad_impl's with the loss derivative as the cotangent (a copy: that function's call sequence stays as it is).
+static int gd_impl(tnml_ctx *c, const float *X, const int32_t *y, const int32_t *idx, int n, int batch, float lr, float wd, int act_fn,
+                   int loss_fn, float T, double *metrics_out) {
+  const int N = c->N, D = c->D, L = c->L;
+  if (act_fn < 0 || act_fn > 2 || loss_fn < 0 || loss_fn > 2) return fail(TNML_ERR_ARG, "unknown activation / loss");
+  if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
+  if (y)
+    for (int i = 0; i < n; ++i)
+      if (y[i] < 0 || y[i] >= L) return fail(TNML_ERR_ARG, "label %d of sample %d outside [0, %d)", y[i], i, L);
+  size_t total = 0;
+  std::vector<int> &tab = c->opt_tab;
+  tab.assign(2 * (size_t)N, 0);
+  int mb = 1;
+  for (int i = 0; i < N; ++i) {
+    if (i < N - 1) { tab[i] = c->bond[i]; mb = std::max(mb, c->bond[i]); }
+    if (total > (size_t)INT_MAX) return fail(TNML_ERR_ARG, "gradient step: %zu floats of cores are beyond the offset table", total);
+    tab[N + i] = (int)total;
+    total += core_elems(c, c->bond, i, c->l_pos);
+  }
+  const size_t lds = core_grad_chain_lds_bytes(mb, D, L, N);
+  if (lds > kLdsMax)
+    return fail(TNML_ERR_ARG, "gradient step at D = %d, bond %d, L = %d: %zu bytes of LDS exceed 160 KB", D, mb, L, lds);
+  if (dataset_metrics_lds_bytes(L) > 64 * 1024 || loss_cot_lds_bytes(L) > 64 * 1024)
+    return fail(TNML_ERR_ARG, "metrics / loss-derivative kernel: %d labels exceed its LDS tile", L);
+  const bool stateful = opt_stateful(c);
+  if (stateful && c->opt_s0 && (c->opt.bond != c->bond || c->opt.l_pos != c->l_pos))
+    return fail(TNML_ERR_STATE, "the optimiser state belongs to other bonds or another l_pos (l_pos %d then, %d now): call tnml_optim_reset",
+                c->opt.l_pos, c->l_pos);
+  HIP_TRY(hipSetDevice(c->device));
+  int rc;
+  if (idx && (rc = ds_upload_indices(c, idx, n))) return rc;    // refuses a bad index before anything is launched
+  const int n_steps = (n + batch - 1) / batch;
+  const int chunk = std::min(cg_chunk_samples(c), (std::min(batch, n) + 63) / 64 * 64);
+  if ((rc = pred_ensure_buffers(c, chunk))) return rc;
+  if ((rc = cg_ensure_buffers(c, chunk))) return rc;
+  if ((rc = ds_ensure_metrics(c, c->pred_cap))) return rc;
+  if ((rc = opt_ensure_state(c))) return rc;
+  if ((rc = opt_ensure_metrics(c, n_steps))) return rc;
+  const int bp = c->cg_cap, xbp = c->pred_cap;
+  HIP_TRY(hipMemcpyAsync(c->cg_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if ((rc = pred_table(c))) return rc;
+  // the cores change from here on: what tnml_scale_cores leaves
+  c->envs_valid_L = c->envs_valid_R = false;
+  c->Ln_valid = c->Rn_valid = false;
+  c->f_current = false;
+  c->Bnew_valid = false;
+  drop_pregradients(c);
+  for (int k = 0; k < n_steps; ++k) {
+    const int s0 = k * batch, bk = std::min(batch, n - s0);
+    for (int off = 0; off < bk; off += chunk) {
+      const int bc = std::min(chunk, bk - off);
+      if (idx) {
+        if ((rc = ds_gather(c, c->ds_idx + s0 + off, bc, xbp, c->Xpred, c->ds_ypred))) return rc;
+      } else {
+        HIP_TRY(hipMemcpyAsync(c->Xpred_stage, X + (size_t)(s0 + off) * N * D, (size_t)bc * N * D * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->ds_ypred, y + s0 + off, (size_t)bc * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        if (D != kD) launch_transpose_input_anyd(c->Xpred_stage, c->Xpred, bc, xbp, N, D, c->stream);
+        else launch_transpose_input(c->Xpred_stage, c->Xpred, bc, xbp, N, c->stream);
+        HIP_TRY(hipGetLastError());
+      }
+      if ((rc = pred_chain(c, bc))) return rc;
+      if (!launch_dataset_metrics(c->fpred, c->ds_ypred, L, bc, xbp, act_fn, T, c->ds_part, off == 0, c->ds_acc, c->stream))
+        return fail(TNML_ERR_ARG, "internal: metrics launch refused");
+      HIP_TRY(hipGetLastError());
+      LossCotParams q{};
+      q.f = c->fpred; q.y = c->ds_ypred; q.cot = c->cg_cot; q.L = L; q.b = bc; q.b_pad = bp; q.f_bpad = xbp;
+      q.act_fn = act_fn; q.loss_fn = loss_fn; q.T = T;
+      if (!launch_loss_cot(q, c->stream)) return fail(TNML_ERR_ARG, "internal: loss-derivative launch refused (b %d, b_pad %d)", bc, bp);
+      HIP_TRY(hipGetLastError());
+      CoreGradParams p{};
+      p.tab = c->cg_tab; p.cores = c->cores; p.labcore = c->lab[c->lab_cur]; p.X = c->Xpred; p.cot = c->cg_cot;
+      p.stackP = c->cg_stackP; p.stackQ = c->cg_stackQ; p.G = c->cg_G; p.cf = c->cg_cf; p.core_stride = c->core_stride;
+      p.b = bc; p.b_pad = bp; p.x_bpad = xbp; p.N = N; p.D = D; p.L = L; p.l_pos = c->l_pos; p.cap = c->Mmax; p.mb = mb;
+      p.first = off == 0;
+      if (!launch_core_grad_chain(p, c->stream)) return fail(TNML_ERR_ARG, "internal: core-gradient chain launch refused (b %d, b_pad %d)", bc, bp);
+      HIP_TRY(hipGetLastError());
+      if (!launch_core_grad_reduce(p, c->stream)) return fail(TNML_ERR_ARG, "internal: core-gradient reduction launch refused (b %d, b_pad %d)", bc, bp);
+      HIP_TRY(hipGetLastError());
+    }
+    OptimStepParams o{};
+    o.tab = c->cg_tab; o.cores = c->cores; o.labcore = c->lab[c->lab_cur]; o.G = c->cg_G;
+    o.s0 = stateful ? c->opt_s0 : nullptr; o.s1 = c->opt.kind == TNML_OPT_ADAM ? c->opt_s1 : nullptr;
+    o.core_stride = c->core_stride; o.N = N; o.D = D; o.L = L; o.l_pos = c->l_pos;
+    o.kind = c->opt.kind; o.clip = c->opt.clip; o.lr = lr; o.wd = wd;
+    o.mu = c->opt.momentum; o.beta1 = c->opt.beta1; o.beta2 = c->opt.beta2; o.eps = c->opt.eps;
+    o.corr1 = o.corr2 = 1.0;
+    if (c->opt.kind == TNML_OPT_ADAM) {
+      const double t = (double)++c->opt.t;
+      o.corr1 = 1.0 - std::pow(c->opt.beta1, t);
+      o.corr2 = 1.0 - std::pow(c->opt.beta2, t);
+    }
+    if (!launch_optim_step(o, c->stream)) return fail(TNML_ERR_ARG, "internal: optimiser step launch refused");
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->opt_met + (size_t)k * 4, c->ds_acc, 4 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  }
+  std::vector<double> met((size_t)n_steps * 4);
+  HIP_TRY(hipMemcpyAsync(met.data(), c->opt_met, met.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  int bad = -1;
+  for (int k = 0; k < n_steps; ++k) {
+    if (metrics_out) for (int j = 0; j < 3; ++j) metrics_out[(size_t)k * 3 + j] = met[(size_t)k * 4 + j];
+    if (met[(size_t)k * 4 + 2] > 0 && bad < 0) bad = k;
+  }
+  if (bad >= 0)
+    return fail(TNML_ERR_NONFINITE, "step %d of %d saw %g samples with a non-finite activated output; every step ran and the cores are what they became",
+                bad, n_steps, met[(size_t)bad * 4 + 2]);
+  return TNML_OK;
+}
+
+extern "C" int tnml_gd_train_indices(tnml_ctx *c, const int32_t *idx, int n, int batch, float lr, float weight_dec, int act_fn, int loss_fn,
+                                     float T, double *metrics_out) {
+  int rc = ds_usable(c);
+  if (rc) return rc;
+  if (!idx) return fail(TNML_ERR_ARG, "NULL argument");
+  if (n < 1) return fail(TNML_ERR_ARG, "empty index list");
+  if (batch < 1) return fail(TNML_ERR_ARG, "batch %d < 1", batch);
+  return gd_impl(c, nullptr, nullptr, idx, n, batch, lr, weight_dec, act_fn, loss_fn, T, metrics_out);
+}
+
+extern "C" int tnml_gd_step(tnml_ctx *c, const float *X, const int32_t *y, int b, float lr, float weight_dec, int act_fn, int loss_fn, float T,
+                            double *metrics3) {
+  if (!c || !X || !y) return fail(TNML_ERR_ARG, "NULL argument");
+  if (c->comm) return fail(TNML_ERR_STATE, "gradient training is single-GPU only: a communicator is attached");
+  if (b < 1) return fail(TNML_ERR_ARG, "empty batch");
+  return gd_impl(c, X, y, nullptr, b, b, lr, weight_dec, act_fn, loss_fn, T, metrics3);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -333,4 +333,31 @@ int core_grad_reduce_blocks(int mb, int D);
 bool launch_core_grad_chain(const CoreGradParams &p, hipStream_t st);
 bool launch_core_grad_reduce(const CoreGradParams &p, hipStream_t st);
 
+// Gradient training (kernels_optim.hip): the loss derivative of a chunk as the cotangent of the core gradients, and one optimiser
+// step over all cores.
+struct LossCotParams {
+  const float *f;          // [L][f_bpad]: the prediction chain's output for the chunk
+  const int *y;            // [b] labels of the chunk's samples
+  float *cot;              // [L][b_pad]: loss derivative of samples 0 .. b-1, zero for b .. b_pad-1
+  int L, b, b_pad, f_bpad, act_fn, loss_fn;
+  float T;
+};
+struct OptimStepParams {
+  const int *tab;          // the table of CoreGradParams: bonds, then every core's offset in the flat layout
+  float *cores;            // plain cores, core i at i * core_stride; only the first ml D mr floats of a slot are touched
+  float *labcore;          // [ml][D][mr][L] of site l_pos
+  const float *G;          // gradient, flat layout
+  float *s0, *s1;          // optimiser state, flat layout: SGD vel (nullptr without momentum) / Adam m and v
+  size_t core_stride;
+  int N, D, L, l_pos;
+  int kind, clip;          // TNML_OPT_SGD / TNML_OPT_ADAM; SGD: the per-core clip
+  float lr, wd;
+  double mu, beta1, beta2, eps;
+  double corr1, corr2;     // Adam: 1 - beta1^t and 1 - beta2^t of this step
+};
+size_t loss_cot_lds_bytes(int L);
+// false: refused (geometry / LDS)
+bool launch_loss_cot(const LossCotParams &p, hipStream_t st);
+bool launch_optim_step(const OptimStepParams &p, hipStream_t st);
+
 }  // namespace tnml

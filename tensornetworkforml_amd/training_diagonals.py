@@ -37,8 +37,12 @@ def main(argv=None):
                     help='upload the data set once and train from index batches formed on the device (Network.train_resident)')
     ap.add_argument('--steps-per-batch', dest='steps_per_batch', type=int, default=None, metavar='K',
                     help='change the batch every K sweep steps instead of every sweep (needs --resident)')
+    ap.add_argument('--optimizer', type=str, default=None, choices=['sgd', 'adam'],
+                    help='gradient descent over all cores at fixed bonds instead of sweeps (Network.train_gradient; needs --resident)')
     ap.add_argument('--out', type=str, default='trained_diag_model.dat')
     args = ap.parse_args(argv)
+    if args.optimizer is not None and not args.resident:
+        ap.error('--optimizer needs --resident')
     if args.steps_per_batch is not None and not args.resident:
         ap.error('--steps-per-batch needs --resident')
 
@@ -56,8 +60,12 @@ def main(argv=None):
                      act_fn=args.act_fn, loss_fn=args.loss_fn, trunc=args.trunc)
     if args.resident:
         _, train_idx, val_idx, _ = gen.prepare_device_dataset(net, data, label, 1, 0.2, train_batch, 128, 128, D=args.D)
-        val_acc, var_hist = net.train_resident(train_idx, val_idx, lr=args.lr, n_epochs=args.n_epochs, weight_dec=args.L2_decay,
-                                               steps_per_batch=args.steps_per_batch)
+        if args.optimizer is not None:
+            val_acc, var_hist = net.train_gradient(train_idx, val_idx, lr=args.lr, n_epochs=args.n_epochs, weight_dec=args.L2_decay,
+                                                   optimizer=args.optimizer)
+        else:
+            val_acc, var_hist = net.train_resident(train_idx, val_idx, lr=args.lr, n_epochs=args.n_epochs, weight_dec=args.L2_decay,
+                                                   steps_per_batch=args.steps_per_batch)
     else:
         val_acc, var_hist = net.train(train_loader, val_loader, lr=args.lr, n_epochs=args.n_epochs,
                                       weight_dec=args.L2_decay)
