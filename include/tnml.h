@@ -427,6 +427,31 @@ int tnml_svd_stats(tnml_ctx *ctx, int reset, double *out3);
  * the fourth are left untouched */
 int tnml_svd_stats_ex(tnml_ctx *ctx, int reset, double *out, int capacity);
 
+/* ---- orthogonal form about the label, compression, bond spectra ------ */
+/* ("canonical" names the array layout (ml, D, mr[, L]) in this library; the gauge is called orthogonal form.)
+ * Float64 inside, float32 cores in and out, the label site l = l_pos stays where it is.  tnml_orthogonalize rewrites the cores so that
+ * every core left of l, as a (ml D) x mr matrix, is g Q with Q^T Q = 1, every core right of l, as ml x (D mr), is g Q with Q Q^T = 1,
+ * and the label core is g C with |C|_F = 1; g = exp(log|W| / N) is shared by all N cores, f(x) is unchanged, log|W| (natural log of
+ * the chain's norm) goes to *log_norm_out.  Every bond is decomposed with the orthogonality centre on it and shrinks to its Schmidt
+ * rank: directions with sigma_j <= rank_tol * sigma_1 are dropped (the arithmetic resolves no direction below 3e-8 sigma_1: a
+ * smaller rank_tol acts as that), so a second call keeps every bond.
+ * tnml_compress additionally cuts every bond to min(m_max, adaptive rank at `threshold`) -- the rule of TNML_TRUNC_ADAPTIVE on the
+ * bond's Schmidt spectrum, threshold = 1 disables it -- with the orthogonality centre on the bond at the moment it is cut and earlier
+ * cuts applied.  sigma_out [N-1][Mcap] (Mcap = the context's bond capacity, max(M, D min(L, M))) receives every bond's normalised
+ * spectrum before the cut (sum sigma^2 = 1, zero-padded), discarded_out [N-1] the weight sum_{j > m} sigma_j^2 that was cut,
+ * log_norm_out the log-norm of the compressed chain.  tnml_bond_spectra computes the same spectra, ranks and log-norm on a scratch
+ * copy: cores, bonds and every piece of state stay bit for bit.
+ * bond_out / rank_out [N-1].  A committed call leaves the context in the state tnml_scale_cores leaves (the resident batch and its
+ * labels stay, a tnml_forward is needed before a sweep) with every slot float behind the new core zero, and unbinds the optimiser
+ * state (tnml_optim_reset before the next stateful step).  A call that fails -- TNML_ERR_ARG (NULL output, m_max < 1, threshold
+ * outside (0, 1], rank_tol outside [0, 1)), TNML_ERR_STATE (cores never set, communicator attached), TNML_ERR_SHAPE (a bond the
+ * kernel's LDS has no room for), TNML_ERR_NONFINITE (a core element that is not finite or beyond 1.8e19 in magnitude, a zero chain,
+ * a result beyond float32), TNML_ERR_HIP -- leaves cores, bonds and l_pos as they were. */
+int tnml_orthogonalize(tnml_ctx *ctx, double rank_tol, int32_t *bond_out, double *log_norm_out);
+int tnml_compress(tnml_ctx *ctx, int m_max, double threshold, double rank_tol, int32_t *bond_out, double *sigma_out,
+                  double *discarded_out, double *log_norm_out);
+int tnml_bond_spectra(tnml_ctx *ctx, double rank_tol, int32_t *rank_out, double *sigma_out, double *log_norm_out);
+
 /* Host-side planning helper, exported so that CPU tests can check the bond bookkeeping without a
  * GPU: truncation rank kept by tensor_svd (Network_class.py:894-945) for a step on sites
  * (p, p+1).  Returns m >= 1, or TNML_ERR_SHAPE where the reference itself raises. */

@@ -632,6 +632,39 @@ class Network():
         self._As = None
         self._invalidate_envs()
 
+    # ------------------------------------------------------------------------------------------
+    # orthogonal form about the label, compression, bond spectra (not in the reference)
+    # ------------------------------------------------------------------------------------------
+    def orthogonalize(self, rank_tol=1e-6):
+        """Put the MPS on the device into orthogonal form about the label site: every core left of it becomes g times a left
+        isometry, every core right of it g times a right isometry, the label core g times a tensor of norm 1, with
+        g = exp(log|W| / N) on all N cores; bonds shrink to the rank of what they cut (directions below rank_tol of the largest
+        singular value are dropped).  f is unchanged.  Returns log|W|.  A forward is needed before the next sweep.  The state of a
+        stateful optimiser (momentum, Adam) refers to the old gauge: call configure_optimizer again before the next gradient_step
+        (it resets the state, as tnml_optim_reset does; train_gradient configures on entry).  The same holds after compress."""
+        ctx = self._sync_to_device(max(self._b, 1))
+        _, log_norm = ctx.orthogonalize(rank_tol)
+        self._after_device_update()
+        return log_norm
+
+    def compress(self, max_bond=None, threshold=None, rank_tol=1e-6):
+        """Cut every bond to min(max_bond, adaptive rank at `threshold`) on its Schmidt decomposition (the rule of
+        trunc='adaptive' on the bond's normalised spectrum) and leave the MPS in orthogonal form about the label.  Returns
+        (bonds, discarded): the new bond dimensions and, per bond, the discarded weight sum_{j > m} sigma_j^2."""
+        if max_bond is None and threshold is None:
+            raise ValueError("compress needs max_bond, threshold or both")
+        ctx = self._sync_to_device(max(self._b, 1))
+        m_max = ctx.bond_capacity if max_bond is None else int(max_bond)
+        bonds, _, discarded, _ = ctx.compress(m_max, 1.0 if threshold is None else threshold, rank_tol)
+        self._after_device_update()
+        return [int(v) for v in bonds], discarded
+
+    def bond_spectra(self, rank_tol=1e-6):
+        """(list of N-1 arrays: the normalised Schmidt spectrum of every bond, log|W|).  Nothing on the device changes."""
+        ctx = self._sync_to_device(max(self._b, 1))
+        ranks, sigma, log_norm = ctx.bond_spectra(rank_tol)
+        return [sigma[i, :int(r)].copy() for i, r in enumerate(ranks)], log_norm
+
     def configure_optimizer(self, optimizer='sgd', momentum=0.0, betas=(0.9, 0.999), eps=1e-8, clip=True):
         """The optimiser of gradient_step / train_gradient: 'sgd' (momentum, the reference's clip per core) or 'adam' (decoupled
         weight decay, no clip).  Resets the optimiser state."""

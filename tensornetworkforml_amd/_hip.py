@@ -37,6 +37,7 @@ SYMBOLS = [
     'tnml_input_grad', 'tnml_input_grad_indices', 'tnml_set_input_grad_chunk',
     'tnml_core_grad', 'tnml_core_grad_indices', 'tnml_set_core_grad_chunk',
     'tnml_optim_config', 'tnml_optim_reset', 'tnml_gd_train_indices', 'tnml_gd_step', 'tnml_get_core_slots',
+    'tnml_orthogonalize', 'tnml_compress', 'tnml_bond_spectra',
 ]
 
 
@@ -133,6 +134,9 @@ def lib():
         L.tnml_get_core_slots.argtypes = [vp, f32p, C.c_size_t, f32p, C.c_size_t]
         L.tnml_gd_train_indices.argtypes = [vp, i32p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, f64p]
         L.tnml_gd_step.argtypes = [vp, f32p, i32p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, f64p]
+        L.tnml_orthogonalize.argtypes = [vp, C.c_double, i32p, f64p]
+        L.tnml_compress.argtypes = [vp, C.c_int, C.c_double, C.c_double, i32p, f64p, f64p, f64p]
+        L.tnml_bond_spectra.argtypes = [vp, C.c_double, i32p, f64p, f64p]
         _lib = L
     return _lib
 
@@ -230,6 +234,37 @@ class Context:
 
     def scale_cores(self, factor):
         _chk(lib().tnml_scale_cores(self._h, float(factor)))
+
+    # ---- orthogonal form about the label, compression, bond spectra
+    @property
+    def bond_capacity(self):
+        return max(self.M, self.D * min(self.L, self.M))
+
+    def orthogonalize(self, rank_tol=1e-6):
+        """-> (bonds (N-1,), log|W|).  Every core becomes g times an isometry towards the label site, the label core g times a
+        tensor of norm 1, g = exp(log|W| / N); f is unchanged."""
+        bond = np.empty(self.N - 1, dtype=np.int32)
+        logn = C.c_double()
+        _chk(lib().tnml_orthogonalize(self._h, float(rank_tol), _ptr(bond, C.c_int32), C.byref(logn)))
+        return bond, logn.value
+
+    def compress(self, m_max, threshold=1.0, rank_tol=1e-6):
+        """-> (bonds (N-1,), sigma (N-1, capacity) normalised spectra before the cut, discarded (N-1,), log|W| afterwards)"""
+        bond = np.empty(self.N - 1, dtype=np.int32)
+        sigma = np.zeros((self.N - 1, self.bond_capacity))
+        disc = np.zeros(self.N - 1)
+        logn = C.c_double()
+        _chk(lib().tnml_compress(self._h, int(m_max), float(threshold), float(rank_tol), _ptr(bond, C.c_int32), _ptr(sigma, C.c_double),
+                                 _ptr(disc, C.c_double), C.byref(logn)))
+        return bond, sigma, disc, logn.value
+
+    def bond_spectra(self, rank_tol=1e-6):
+        """-> (ranks (N-1,), sigma (N-1, capacity), log|W|); the context is left bit for bit as it was"""
+        rank = np.empty(self.N - 1, dtype=np.int32)
+        sigma = np.zeros((self.N - 1, self.bond_capacity))
+        logn = C.c_double()
+        _chk(lib().tnml_bond_spectra(self._h, float(rank_tol), _ptr(rank, C.c_int32), _ptr(sigma, C.c_double), C.byref(logn)))
+        return rank, sigma, logn.value
 
     # ---- batch
     def set_input(self, X, y=None):

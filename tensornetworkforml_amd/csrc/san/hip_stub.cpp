@@ -274,6 +274,60 @@ static void check_core_grad(const CoreGradParams &p, dim3 g, dim3 b, size_t shm,
   }
 }
 
+// orthogonal form / compression / bond spectra (kernels_orth.hip): one parameter block for the load, chain and store kernels.  The
+// operation list is walked the way the chain kernel walks it: every decomposition hands its carried factor to the neighbouring site,
+// which the next operation must name; the list ends with the centre on the label site.  Every slot of the context, of the float64
+// work copy and of the float32 result, the absorbed site, the carried factors and the outputs with their extents.
+static void check_orth(const OrthParams &p, dim3 g, dim3 b, size_t shm, int which) {       // which: 0 load, 1 chain, 2 store
+  scan(&p, sizeof p, "OrthParams");
+  if (p.N < 2 || p.D < 2 || p.D > kMaxD || p.L < 1 || p.l_pos < 0 || p.l_pos >= p.N) die("OrthParams: N %d D %d L %d l_pos %d", p.N, p.D, p.L, p.l_pos);
+  need(p.bond, (size_t)(p.N - 1) * 4, "OrthParams.bond");
+  int mb = 1;
+  for (int i = 0; i < p.N - 1; ++i) {
+    if (p.bond[i] < 1) die("OrthParams: bond %d is %d", i, p.bond[i]);
+    mb = p.bond[i] > mb ? p.bond[i] : mb;
+  }
+  if (which == 1) {
+    if (g.x != 1 || g.y != 1 || g.z != 1 || b.x != 1024) die("orth_chain_kernel: grid %u block %u", g.x, b.x);
+    if (shm < orth_chain_lds_bytes(mb)) die("orth_chain_kernel: %zu bytes of LDS for bond %d", shm, mb);
+    if (p.npad < mb || p.npad % 2 || p.ld <= p.npad || shm < ((size_t)2 * p.npad * p.ld + 1024 + 4 * (size_t)p.npad) * 8 + 64)
+      die("orth_chain_kernel: npad %d ld %d lds %zu for bond %d", p.npad, p.ld, shm, mb);
+  } else if (g.x != (unsigned)p.N || g.y != 1 || g.z != 1 || b.x != 256) die("orth load / store kernel: grid %u block %u for N %d", g.x, b.x, p.N);
+  if (!(p.threshold > 0.0 && p.threshold <= 1.0) || !(p.rank_tol >= 0.0 && p.rank_tol < 1.0) || p.m_max < 1) die("OrthParams: m_max %d threshold %g rank_tol %g", p.m_max, p.threshold, p.rank_tol);
+  if (p.n_ops < 1) die("OrthParams: %d operations", p.n_ops);
+  need(p.ops, (size_t)p.n_ops * sizeof(OrthOp), "OrthParams.ops");
+  int pending = -1;
+  for (int o = 0; o < p.n_ops; ++o) {
+    const OrthOp &op = p.ops[o];
+    if (op.site < 0 || op.site >= p.N || op.kind < kOrthRight || op.kind > kOrthCentre || op.cut < 0 || op.cut > 2) die("OrthOp %d: site %d kind %d cut %d", o, op.site, op.kind, op.cut);
+    if (pending >= 0 && op.site != pending) die("OrthOp %d names site %d, the carried factor belongs to site %d", o, op.site, pending);
+    pending = -1;
+    if (op.kind == kOrthRight) { if (op.site == p.N - 1) die("OrthOp %d: the last site has no right bond", o); pending = op.site + 1; }
+    if (op.kind == kOrthLeft) { if (op.site == 0) die("OrthOp %d: the first site has no left bond", o); pending = op.site - 1; }
+    if (op.kind == kOrthCentre && (op.site != p.l_pos || o != p.n_ops - 1)) die("OrthOp %d: centre on site %d (label on %d, %d operations)", o, op.site, p.l_pos, p.n_ops);
+  }
+  if (p.ops[p.n_ops - 1].kind != kOrthCentre) die("OrthParams: the list does not end with the centre");
+  if (p.aux_stride < (size_t)mb * mb) die("OrthParams: carried factors of %zu doubles for bond %d", p.aux_stride, mb);
+  need(p.aux, 4 * p.aux_stride * 8, "OrthParams.aux");
+  need(p.Mbuf, p.lab_elems * 8, "OrthParams.Mbuf");
+  need(p.W, ((size_t)p.N * p.core_stride + p.lab_elems) * 8, "OrthParams.W");
+  need(p.out_cores, (size_t)p.N * p.core_stride * 4, "OrthParams.out_cores");
+  need(p.out_lab, p.lab_elems * 4, "OrthParams.out_lab");
+  for (int i = 0; i < p.N; ++i) {
+    const int ml = i == 0 ? 1 : p.bond[i - 1], mr = i == p.N - 1 ? 1 : p.bond[i];
+    const size_t ne = (size_t)ml * p.D * mr * (i == p.l_pos ? p.L : 1);
+    if (ne > (i == p.l_pos ? p.lab_elems : p.core_stride)) die("OrthParams: core %d of %zu floats beyond its slot", i, ne);
+    if (i == p.l_pos) need(p.labcore, ne * 4, "OrthParams.labcore");
+    else need(p.cores + (size_t)i * p.core_stride, ne * 4, "OrthParams.cores");
+  }
+  if (p.sigma_ld < mb) die("OrthParams: spectra rows of %d for bond %d", p.sigma_ld, mb);
+  need(p.sigma_out, (size_t)(p.N - 1) * p.sigma_ld * 8, "OrthParams.sigma_out");
+  need(p.discarded_out, (size_t)(p.N - 1) * 8, "OrthParams.discarded_out");
+  need(p.rank_out, (size_t)(p.N - 1) * 4, "OrthParams.rank_out");
+  need(p.result, 2 * 8, "OrthParams.result");
+  need(p.status, 4, "OrthParams.status");
+}
+
 // gradient training (kernels_optim.hip).  loss_cot_kernel: f and cot at their own strides, the labels of the chunk, one thread per
 // column of cot.  optim_step_kernel: one workgroup per site; every core's slot and its part of G, vel / m / v through the table.
 static void check_loss_cot(const LossCotParams &p, dim3 g, dim3 b, size_t shm) {
@@ -490,6 +544,8 @@ hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t s
     check_loss_cot(*(const LossCotParams *)args[0], g, b, shm);
   } else if (has("optim_step_kernel")) {
     check_optim_step(*(const OptimStepParams *)args[0], g, b);
+  } else if (has("orth_load_kernel") || has("orth_chain_kernel") || has("orth_store_kernel")) {
+    check_orth(*(const OrthParams *)args[0], g, b, shm, has("orth_chain_kernel") ? 1 : has("orth_store_kernel") ? 2 : 0);
   } else if (has("input_grad_onehot_kernel")) {   // (f, f_bpad, L, b, cot, b_pad)
     const int fbp = *(int *)args[1], L = *(int *)args[2], bb = *(int *)args[3], bp = *(int *)args[5];
     if (bb < 1 || bb > bp || bp > fbp || (size_t)g.x * b.x < (size_t)bp) die("input_grad_onehot_kernel: b %d b_pad %d f_bpad %d grid %u x %u", bb, bp, fbp, g.x, b.x);

@@ -305,6 +305,16 @@ struct tnml_ctx {
   double *opt_met = nullptr;
   int opt_met_cap = 0;
   std::vector<int> opt_tab;                  // host copy of cg_tab for the call in flight (outlives the asynchronous upload)
+  // orthogonal form / compression / bond spectra.  One group, created by the first call: the float64 work copy
+  // of the slots and the label buffer, the absorbed site, the carried factors, the float32 result the commit copies from, the
+  // operation list, the scratch bond table and the outputs of the call.
+  struct {
+    double *W = nullptr, *Mbuf = nullptr, *aux = nullptr, *sigma = nullptr, *disc = nullptr, *result = nullptr;
+    float *out_cores = nullptr, *out_lab = nullptr;
+    OrthOp *ops = nullptr;
+    int *bond = nullptr, *rank = nullptr, *status = nullptr;
+    bool ready = false;
+  } orth;
   // multi-GPU
   ncclComm_t comm = nullptr;
   int rank = 0, nranks = 1;
@@ -1678,6 +1688,122 @@ extern "C" int tnml_gd_step(tnml_ctx *c, const float *X, const int32_t *y, int b
 // ---------------------------------------------------------------------------------------------
 // norm environments of the side a sweep runs towards (only when not inherited from the last sweep)
 // ---------------------------------------------------------------------------------------------
+// ---------------------------------------------------------------------------------------------
+// orthogonal form about the label, compression, bond spectra (kernels_orth.hip)
+// ---------------------------------------------------------------------------------------------
+// Scratch group, on the first call: all of it or none (a failed allocation leaves it empty and the call repeatable)
+static int orth_ensure(tnml_ctx *c) {
+  if (c->orth.ready) return TNML_OK;
+  const size_t N = (size_t)c->N, cap = (size_t)c->Mmax;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  int rc = make_group(c, "the scratch of the orthogonal form", {
+      own_dev(c->orth.W, N * c->core_stride + c->lab_elems), own_dev(c->orth.Mbuf, c->lab_elems), own_dev(c->orth.aux, 4 * cap * cap),
+      own_dev(c->orth.sigma, N * cap), own_dev(c->orth.disc, N), own_dev(c->orth.result, 2),
+      own_dev(c->orth.out_cores, N * c->core_stride), own_dev(c->orth.out_lab, c->lab_elems),
+      own_dev(c->orth.ops, 3 * N + 2), own_dev(c->orth.bond, N), own_dev(c->orth.rank, N), own_dev(c->orth.status, 1)});
+  if (rc) return rc;
+  c->orth.ready = true;
+  return TNML_OK;
+}
+
+// mode 0: orthogonal form, 1: compression, 2: spectra only (nothing is committed)
+static int orth_impl(tnml_ctx *c, int mode, int m_max, double threshold, double rank_tol, int32_t *bond_out, double *sigma_out,
+                     double *discarded_out, double *log_norm_out) {
+  const char *what = mode == 0 ? "tnml_orthogonalize" : mode == 1 ? "tnml_compress" : "tnml_bond_spectra";
+  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
+  if (!bond_out || !log_norm_out || (mode != 0 && !sigma_out) || (mode == 1 && !discarded_out))
+    return fail(TNML_ERR_ARG, "%s: an output pointer is NULL", what);
+  if (mode == 1 && m_max < 1) return fail(TNML_ERR_ARG, "%s: m_max %d < 1", what, m_max);
+  if (mode == 1 && !(threshold > 0.0 && threshold <= 1.0)) return fail(TNML_ERR_ARG, "%s: threshold %g outside (0, 1]", what, threshold);
+  if (!(rank_tol >= 0.0 && rank_tol < 1.0)) return fail(TNML_ERR_ARG, "%s: rank_tol %g outside [0, 1)", what, rank_tol);
+  if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
+  if (c->comm) return fail(TNML_ERR_STATE, "%s runs on one GPU: this context has a communicator attached", what);
+  const int N = c->N, l = c->l_pos;
+  int mb = 1;
+  for (int i = 0; i < N - 1; ++i) mb = std::max(mb, c->bond[i]);
+  const size_t lds = orth_chain_lds_bytes(mb);
+  if (lds > kLdsMax)
+    return fail(TNML_ERR_SHAPE, "%s at bond %d: the Gram matrix and its eigenvectors take %zu bytes of LDS, beyond 160 KB", what, mb, lds);
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = orth_ensure(c);
+  if (rc) return rc;
+  // the operations: every decomposition hands its carried factor to the next operation's site
+  std::vector<OrthOp> ops;
+  // (all three calls walk the same way -- centre to site 0, to site N-1 with the centre on every bond in turn, back to the label:
+  // a bond then ends at its Schmidt rank, not at the rank one side shows, and a second call keeps every bond)
+  const int cut = mode == 0 ? 0 : mode == 1 ? 2 : 1;
+  for (int i = N - 1; i > 0; --i) ops.push_back({i, kOrthLeft, 0, 0});      // rank rule only
+  for (int i = 0; i < N - 1; ++i) ops.push_back({i, kOrthRight, cut, 0});   // every bond with the centre on it
+  for (int i = N - 1; i > l; --i) ops.push_back({i, kOrthLeft, 0, 0});      // back to the label
+  ops.push_back({l, kOrthCentre, 0, 0});
+  OrthParams p{};
+  p.ops = c->orth.ops; p.n_ops = (int)ops.size();
+  p.N = N; p.D = c->D; p.L = c->L; p.l_pos = l;
+  p.bond = c->orth.bond; p.cores = c->cores; p.labcore = c->lab[c->lab_cur];
+  p.W = c->orth.W; p.Mbuf = c->orth.Mbuf; p.aux = c->orth.aux;
+  p.core_stride = c->core_stride; p.lab_elems = c->lab_elems; p.aux_stride = (size_t)c->Mmax * c->Mmax;
+  p.m_max = mode == 1 ? m_max : INT_MAX; p.threshold = mode == 1 ? threshold : 1.0; p.rank_tol = rank_tol;
+  p.sigma_out = c->orth.sigma; p.sigma_ld = c->Mmax; p.discarded_out = c->orth.disc; p.rank_out = c->orth.rank;
+  p.result = c->orth.result; p.status = c->orth.status;
+  p.out_cores = c->orth.out_cores; p.out_lab = c->orth.out_lab;
+  HIP_TRY(hipMemcpyAsync(c->orth.ops, ops.data(), ops.size() * sizeof(OrthOp), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->orth.bond, c->bond.data(), (size_t)(N - 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(c->orth.status, 0, sizeof(int), c->stream));
+  if (!launch_orth(p, mb, c->stream)) {
+    (void)hipStreamSynchronize(c->stream);                     // (the uploads read locals of this call)
+    return fail(TNML_ERR_SHAPE, "%s: the launch was refused (bond %d)", what, mb);
+  }
+  HIP_TRY(hipGetLastError());
+  int st = 0;
+  double res[2] = {0, 0};
+  std::vector<int> nb((size_t)N - 1), rk((size_t)N - 1);
+  HIP_TRY(hipMemcpyAsync(&st, c->orth.status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(res, c->orth.result, sizeof res, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(nb.data(), c->orth.bond, nb.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(rk.data(), c->orth.rank, rk.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));                    // (ops is a local: the upload has completed as well)
+  if (st == 1 || (st == 0 && !std::isfinite(res[0])))
+    return fail(TNML_ERR_NONFINITE, "%s: a core is not finite, beyond 1.8e19 in magnitude or zero, or the result does not fit float32", what);
+  if (st) return fail(TNML_ERR_NONFINITE, "%s: the Jacobi iteration or the re-orthogonalisation did not converge (status %d)", what, st);
+  for (int i = 0; i < N - 1; ++i)
+    if (nb[i] < 1 || nb[i] > c->bond[i]) return fail(TNML_ERR_STATE, "internal: %s produced bond %d at %d (was %d)", what, nb[i], i, c->bond[i]);
+  if (mode != 0) {
+    HIP_TRY(hipMemcpyAsync(sigma_out, c->orth.sigma, (size_t)(N - 1) * c->Mmax * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (mode == 1) HIP_TRY(hipMemcpyAsync(discarded_out, c->orth.disc, (size_t)(N - 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  *log_norm_out = res[0];
+  if (mode == 2) {
+    for (int i = 0; i < N - 1; ++i) bond_out[i] = rk[i];
+    return TNML_OK;
+  }
+  // commit: device-to-device copy, then the bond table
+  HIP_TRY(hipMemcpyAsync(c->cores, c->orth.out_cores, (size_t)N * c->core_stride * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->lab[c->lab_cur], c->orth.out_lab, c->lab_elems * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  c->bond = nb;
+  for (int i = 0; i < N - 1; ++i) bond_out[i] = nb[i];
+  c->envs_valid_L = c->envs_valid_R = false;
+  c->Ln_valid = c->Rn_valid = false;
+  c->f_current = false;
+  c->Bnew_valid = false;
+  drop_pregradients(c);
+  if (c->opt_s0) c->opt.l_pos = -1;                            // vel / m / v refer to the old gauge: unbound until tnml_optim_reset
+  return TNML_OK;
+}
+
+extern "C" int tnml_orthogonalize(tnml_ctx *c, double rank_tol, int32_t *bond_out, double *log_norm_out) {
+  return orth_impl(c, 0, 0, 1.0, rank_tol, bond_out, nullptr, nullptr, log_norm_out);
+}
+
+extern "C" int tnml_compress(tnml_ctx *c, int m_max, double threshold, double rank_tol, int32_t *bond_out, double *sigma_out,
+                             double *discarded_out, double *log_norm_out) {
+  return orth_impl(c, 1, m_max, threshold, rank_tol, bond_out, sigma_out, discarded_out, log_norm_out);
+}
+
+extern "C" int tnml_bond_spectra(tnml_ctx *c, double rank_tol, int32_t *rank_out, double *sigma_out, double *log_norm_out) {
+  return orth_impl(c, 2, 0, 1.0, rank_tol, rank_out, sigma_out, nullptr, log_norm_out);
+}
+
 // ---------------------------------------------------------------------------------------------
 // narrow step: in-LDS kernel, or the large-tensor path when the merged tensor does not fit
 // ---------------------------------------------------------------------------------------------

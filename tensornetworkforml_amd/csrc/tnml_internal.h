@@ -360,4 +360,41 @@ size_t loss_cot_lds_bytes(int L);
 bool launch_loss_cot(const LossCotParams &p, hipStream_t st);
 bool launch_optim_step(const OptimStepParams &p, hipStream_t st);
 
+// Orthogonal form, compression, bond spectra (kernels_orth.hip): the operations of a call in the order the one
+// workgroup performs them, and the parameter block shared by the three kernels of the call.
+constexpr int kOrthRight = 0;    // decompose the site towards the right: it becomes a left isometry, the bond on its right is cut
+constexpr int kOrthLeft = 1;     // towards the left: right isometry, the bond on its left is cut
+constexpr int kOrthCentre = 2;   // absorb, normalise to Frobenius norm 1 (its log joins the log-norm) and store
+struct OrthOp {
+  int site, kind;
+  int cut;                 // decompositions: 0 rank rule only, 1 and the bond's spectrum is recorded, 2 and the bond is cut (m_max / threshold)
+  int pad;
+};
+struct OrthParams {
+  const OrthOp *ops;       // [n_ops]
+  int n_ops;
+  int N, D, L, l_pos;
+  int *bond;               // [N-1] scratch copy of the bond table: the chain kernel rewrites it as it goes
+  const float *cores;      // the context's slots (read by the load kernel only), core i at i * core_stride
+  const float *labcore;
+  double *W;               // float64 work copy: N slots of core_stride doubles, then the label site's lab_elems
+  double *Mbuf;            // [lab_elems] the site with its carried factor absorbed
+  double *aux;             // [4][aux_stride]: two carried factors (r x n), P and its inverse of the re-orthogonalisation (r x r)
+  size_t core_stride, lab_elems, aux_stride;
+  int ld, npad;            // LDS geometry (launch_orth fills them from the largest bond)
+  int m_max;
+  double threshold, rank_tol;
+  double *sigma_out;       // [N-1][sigma_ld] normalised spectrum of every bond whose decomposition has cut >= 1
+  int sigma_ld;
+  double *discarded_out;   // [N-1]
+  int *rank_out;           // [N-1] rank by the rank rule, before a cut
+  double *result;          // [0] log-norm, [1] g = exp(log-norm / N)
+  int *status;             // [0]: 1 non-finite (or zero) input / result, 2 the Jacobi iteration or the re-orthogonalisation did not converge
+  float *out_cores;        // float32 scratch copy of the slots: g . W, zero behind core_elems
+  float *out_lab;
+};
+size_t orth_chain_lds_bytes(int mb);
+// load, chain and store kernel of one call; mb: largest bond of the chain.  false: refused (geometry / LDS)
+bool launch_orth(const OrthParams &p, int mb, hipStream_t st);
+
 }  // namespace tnml

@@ -32,6 +32,8 @@ def main(argv=None):
     ap.add_argument('--normalise', action='store_true', help='scale pixels to [0, 1] before the feature map (as in training)')
     ap.add_argument('--features', action='store_true', help='upload host-embedded features instead of pixels')
     ap.add_argument('--saliency', metavar='OUT.npy', default=None, help='write d f[predicted class] / d pixel of every test digit, (n, h, w)')
+    ap.add_argument('--spectra', metavar='OUT.npy', default=None,
+                    help='write the normalised Schmidt spectrum of every bond, (N - 1, largest rank), zero-padded (Network.bond_spectra)')
     args = ap.parse_args(argv)
 
     with open(args.filename, 'rb') as fh:
@@ -51,6 +53,9 @@ def main(argv=None):
     acc, mae = net.evaluate(test_loader)
     print('\tAccuracy:            ', acc)
     print('\tMean Absolute Error: ', mae)
+    if args.spectra:
+        from tensornetworkforml_amd.evaluate_diagonals import write_spectra
+        write_spectra(net, args.spectra)
     if args.saliency:
         import numpy as np
         if args.features:

@@ -19,6 +19,17 @@ import tensornetworkforml_amd  # noqa: E402,F401  (registers the bare module nam
 import data_generator as gen   # noqa: E402
 
 
+def write_spectra(net, path):
+    spectra, log_norm = net.bond_spectra()
+    out = np.zeros((len(spectra), max(len(s) for s in spectra)))
+    for i, s in enumerate(spectra):
+        out[i, :len(s)] = s
+    np.save(path, out)
+    entropy = [float(-(s[s > 0] ** 2 * np.log(s[s > 0] ** 2)).sum()) for s in spectra]
+    print('\tlog-norm of the chain: %.6g; largest bond entropy %.4f at bond %d; spectra written to %s'
+          % (log_norm, max(entropy), int(np.argmax(entropy)), path))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Evaluate a trained Tensor Network on a generated dataset of diagonals')
     ap.add_argument('--filename', type=str, default='trained_diag_model.dat', help='Pickled network to load')
@@ -26,6 +37,8 @@ def main(argv=None):
     ap.add_argument('--sigma', type=float, default=0.6, help='Sigma of the noise added to the dataset')
     ap.add_argument('--batch_size', type=int, default=128, help='Samples per evaluation batch')
     ap.add_argument('--features', action='store_true', help='upload host-embedded features instead of pixels')
+    ap.add_argument('--spectra', metavar='OUT.npy', default=None,
+                    help='write the normalised Schmidt spectrum of every bond, (N - 1, largest rank), zero-padded (Network.bond_spectra)')
     args = ap.parse_args(argv)
 
     with open(args.filename, 'rb') as fh:
@@ -38,6 +51,8 @@ def main(argv=None):
     _, _, _, test_loader = gen.prepare_device_dataset(net, data, label, 0, 0, 1, 1, args.batch_size, D=net.D,
                                                       pixels=not args.features)
     acc, mae = net.evaluate(test_loader)
+    if args.spectra:
+        write_spectra(net, args.spectra)
     print('\tAccuracy:            ', acc)
     print('\tMean Absolute Error: ', mae)
     return acc, mae

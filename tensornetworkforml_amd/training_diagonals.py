@@ -39,8 +39,12 @@ def main(argv=None):
                     help='change the batch every K sweep steps instead of every sweep (needs --resident)')
     ap.add_argument('--optimizer', type=str, default=None, choices=['sgd', 'adam'],
                     help='gradient descent over all cores at fixed bonds instead of sweeps (Network.train_gradient; needs --resident)')
+    ap.add_argument('--compress', type=int, default=None, metavar='M',
+                    help='after training, cut every bond to M on its Schmidt decomposition (Network.compress; needs --resident)')
     ap.add_argument('--out', type=str, default='trained_diag_model.dat')
     args = ap.parse_args(argv)
+    if args.compress is not None and not args.resident:
+        ap.error('--compress needs --resident')
     if args.optimizer is not None and not args.resident:
         ap.error('--optimizer needs --resident')
     if args.steps_per_batch is not None and not args.resident:
@@ -66,6 +70,12 @@ def main(argv=None):
         else:
             val_acc, var_hist = net.train_resident(train_idx, val_idx, lr=args.lr, n_epochs=args.n_epochs, weight_dec=args.L2_decay,
                                                    steps_per_batch=args.steps_per_batch)
+        if args.compress is not None:
+            before = np.mean([net._ctx.eval_indices(idx, net.act_fn, net.T)[0] / len(idx) for idx in val_idx])
+            bonds, discarded = net.compress(max_bond=args.compress)
+            after = np.mean([net._ctx.eval_indices(idx, net.act_fn, net.T)[0] / len(idx) for idx in val_idx])
+            print('compressed to bond %d (largest bond now %d, discarded weight %.3g): validation accuracy %.4f -> %.4f'
+                  % (args.compress, max(bonds), float(np.sum(discarded)), before, after))
     else:
         val_acc, var_hist = net.train(train_loader, val_loader, lr=args.lr, n_epochs=args.n_epochs,
                                       weight_dec=args.L2_decay)
