@@ -26,6 +26,7 @@
 #include <cxxabi.h>
 #include "../tnml_internal.h"
 #include "../wide_pipe_device.h"
+#include "../grad_chain_device.h"
 
 using namespace tnml;
 
@@ -211,44 +212,57 @@ static void check_meet(const MeetParams &p, dim3 g, dim3 b, size_t shm) {
   need(p.f, (size_t)p.L * bp * 4, "MeetParams.f");
 }
 
-// input gradients (kernels_inputgrad.hip): every operand with the extent the kernel touches, the cores through the bond table the host
-// uploaded (the stand-in's device memory is host memory)
-static void check_input_grad(const InputGradParams &p, dim3 g, dim3 b, size_t shm) {
-  scan(&p, sizeof p, "InputGradParams");
-  if (p.b < 1 || p.b > p.b_pad || p.b_pad % 64 || p.x_bpad < p.b_pad) die("InputGradParams: b %d b_pad %d x_bpad %d", p.b, p.b_pad, p.x_bpad);
-  if (p.N < 2 || p.D < 2 || p.D > kMaxD || p.L < 1 || p.l_pos < 0 || p.l_pos >= p.N) die("InputGradParams: N %d D %d L %d l_pos %d", p.N, p.D, p.L, p.l_pos);
-  if (p.mb < 1 || p.mb > p.cap) die("InputGradParams: largest bond %d, capacity %d", p.mb, p.cap);
-  if (b.x != 256 || g.x != (unsigned)((p.b + 63) / 64) || g.y != 1 || g.z != 1) die("input_grad_kernel: grid %u block %u for b %d", g.x, b.x, p.b);
-  if (shm < input_grad_lds_bytes(p.mb, p.D, p.L, p.N)) die("input_grad_kernel: %zu bytes of LDS, %zu wanted (bond %d, D %d, L %d)", shm, input_grad_lds_bytes(p.mb, p.D, p.L, p.N), p.mb, p.D, p.L);
+// What InputGradParams and CoreGradParams share, as the view either kernel fills (grad_chain_device.h), under the name `blk` of the
+// block: the geometry, the extents of X, cot and cf and, for a launch of the two-pass chain (`kernel` names it;
+// nullptr: the reduction), its grid, block and LDS.
+static void check_grad_geometry(const GradChainView &p, const char *blk, const char *kernel, dim3 g, dim3 b, size_t shm) {
+  const std::string B(blk);
+  if (p.b < 1 || p.b > p.b_pad || p.b_pad % 64 || p.x_bpad < p.b_pad) die("%s: b %d b_pad %d x_bpad %d", blk, p.b, p.b_pad, p.x_bpad);
+  if (p.N < 2 || p.D < 2 || p.D > kMaxD || p.L < 1 || p.l_pos < 0 || p.l_pos >= p.N) die("%s: N %d D %d L %d l_pos %d", blk, p.N, p.D, p.L, p.l_pos);
+  if (p.mb < 1 || p.mb > p.cap) die("%s: largest bond %d, capacity %d", blk, p.mb, p.cap);
+  if (kernel) {
+    if (b.x != 256 || g.x != (unsigned)((p.b + 63) / 64) || g.y != 1 || g.z != 1) die("%s: grid %u block %u for b %d", kernel, g.x, b.x, p.b);
+    if (shm < grad_chain_lds_bytes(p.mb, p.D, p.L, p.N)) die("%s: %zu bytes of LDS, %zu wanted (bond %d, D %d, L %d)", kernel, shm, grad_chain_lds_bytes(p.mb, p.D, p.L, p.N), p.mb, p.D, p.L);
+  }
   const size_t bp = p.b_pad;
-  need(p.bond, (size_t)(p.N - 1) * 4, "InputGradParams.bond");
-  need(p.stack, (size_t)p.N * p.cap * bp * 4, "InputGradParams.stack");
-  need(p.X, (size_t)p.N * p.x_bpad * p.D * 4, "InputGradParams.X");
-  need(p.cot, (size_t)p.L * bp * 4, "InputGradParams.cot");
-  need(p.g, (size_t)p.b * p.N * p.D * 4, "InputGradParams.g");
-  opt(p.cf, (size_t)p.b * 4, "InputGradParams.cf");
+  need(p.X, (size_t)p.N * p.x_bpad * p.D * 4, (B + ".X").c_str());
+  need(p.cot, (size_t)p.L * bp * 4, (B + ".cot").c_str());
+  opt(p.cf, (size_t)p.b * 4, (B + ".cf").c_str());
+}
+// every site's bonds through the table the host uploaded (the stand-in's device memory is host memory; the caller has checked its
+// extent) and, for the two-pass chain, the extent of every core
+static void check_grad_sites(const GradChainView &p, const char *blk, bool chain) {
+  const std::string B(blk);
   for (int i = 0; i < p.N; ++i) {
     const int ml = i == 0 ? 1 : p.bond[i - 1], mr = i == p.N - 1 ? 1 : p.bond[i];
-    if (ml < 1 || ml > p.mb || mr < 1 || mr > p.mb) die("InputGradParams: site %d is %d x %d, largest bond %d", i, ml, mr, p.mb);
-    if (i == p.l_pos) need(p.labcore, (size_t)ml * p.D * mr * p.L * 4, "InputGradParams.labcore");
-    else need(p.cores + (size_t)i * p.core_stride, (size_t)ml * p.D * mr * 4, "InputGradParams.cores");
+    if (ml < 1 || ml > p.mb || mr < 1 || mr > p.mb) die("%s: site %d is %d x %d, largest bond %d", blk, i, ml, mr, p.mb);
+    if (!chain) continue;
+    if (i == p.l_pos) need(p.labcore, (size_t)ml * p.D * mr * p.L * 4, (B + ".labcore").c_str());
+    else need(p.cores + (size_t)i * p.core_stride, (size_t)ml * p.D * mr * 4, (B + ".cores").c_str());
   }
+}
+
+// input gradients (kernels_inputgrad.hip): every operand with the extent the kernel touches
+static void check_input_grad(const InputGradParams &p, dim3 g, dim3 b, size_t shm) {
+  scan(&p, sizeof p, "InputGradParams");
+  const GradChainView v{p.bond, p.cores, p.labcore, p.X, p.cot, p.stack, p.cf, p.core_stride, p.b, p.b_pad, p.x_bpad, p.N, p.D, p.L, p.l_pos, p.cap, p.mb};
+  check_grad_geometry(v, "InputGradParams", "input_grad_kernel", g, b, shm);
+  need(p.bond, (size_t)(p.N - 1) * 4, "InputGradParams.bond");
+  need(p.stack, (size_t)p.N * p.cap * p.b_pad * 4, "InputGradParams.stack");
+  need(p.g, (size_t)p.b * p.N * p.D * 4, "InputGradParams.g");
+  check_grad_sites(v, "InputGradParams", true);
 }
 
 // core gradients (kernels_coregrad.hip): one block for both kernels.  The chain kernel touches every core, X, cot, both stacks and cf;
 // the reduction both stacks, X, cot and every core's extent of G through the offset half of the table.
 static void check_core_grad(const CoreGradParams &p, dim3 g, dim3 b, size_t shm, bool reduce) {
   scan(&p, sizeof p, "CoreGradParams");
-  if (p.b < 1 || p.b > p.b_pad || p.b_pad % 64 || p.x_bpad < p.b_pad) die("CoreGradParams: b %d b_pad %d x_bpad %d", p.b, p.b_pad, p.x_bpad);
-  if (p.N < 2 || p.D < 2 || p.D > kMaxD || p.L < 1 || p.l_pos < 0 || p.l_pos >= p.N) die("CoreGradParams: N %d D %d L %d l_pos %d", p.N, p.D, p.L, p.l_pos);
-  if (p.mb < 1 || p.mb > p.cap) die("CoreGradParams: largest bond %d, capacity %d", p.mb, p.cap);
+  const GradChainView v{p.tab, p.cores, p.labcore, p.X, p.cot, p.stackP, p.cf, p.core_stride, p.b, p.b_pad, p.x_bpad, p.N, p.D, p.L, p.l_pos, p.cap, p.mb};
+  check_grad_geometry(v, "CoreGradParams", reduce ? nullptr : "core_grad_chain_kernel", g, b, shm);
   if (p.first != 0 && p.first != 1) die("CoreGradParams: first %d", p.first);
   const size_t bp = p.b_pad, tiles = (size_t)(p.b + 63) / 64 * 64;       // both kernels work on whole tiles of 64 samples
   if (tiles > bp) die("CoreGradParams: %zu samples in tiles, b_pad %zu", tiles, bp);
-  if (!reduce) {
-    if (b.x != 256 || g.x != (unsigned)((p.b + 63) / 64) || g.y != 1 || g.z != 1) die("core_grad_chain_kernel: grid %u block %u for b %d", g.x, b.x, p.b);
-    if (shm < core_grad_chain_lds_bytes(p.mb, p.D, p.L, p.N)) die("core_grad_chain_kernel: %zu bytes of LDS, %zu wanted", shm, core_grad_chain_lds_bytes(p.mb, p.D, p.L, p.N));
-  } else {
+  if (reduce) {
     if (b.x != 256 || g.x != (unsigned)p.N || g.y != (unsigned)core_grad_reduce_blocks(p.mb, p.D) || g.z != (unsigned)p.L)
       die("core_grad_reduce_kernel: grid (%u, %u, %u) block %u for N %d bond %d D %d L %d", g.x, g.y, g.z, b.x, p.N, p.mb, p.D, p.L);
     if (shm < core_grad_reduce_lds_bytes(p.mb, p.D)) die("core_grad_reduce_kernel: %zu bytes of LDS, %zu wanted", shm, core_grad_reduce_lds_bytes(p.mb, p.D));
@@ -256,20 +270,15 @@ static void check_core_grad(const CoreGradParams &p, dim3 g, dim3 b, size_t shm,
   need(p.tab, (size_t)2 * p.N * 4, "CoreGradParams.tab");
   need(p.stackP, (size_t)p.N * p.cap * bp * 4, "CoreGradParams.stackP");
   need(p.stackQ, (size_t)p.N * p.cap * bp * 4, "CoreGradParams.stackQ");
-  need(p.X, (size_t)p.N * p.x_bpad * p.D * 4, "CoreGradParams.X");
-  need(p.cot, (size_t)p.L * bp * 4, "CoreGradParams.cot");
-  opt(p.cf, (size_t)p.b * 4, "CoreGradParams.cf");
+  check_grad_sites(v, "CoreGradParams", !reduce);
   size_t off = 0;
   for (int i = 0; i < p.N; ++i) {
     const int ml = i == 0 ? 1 : p.tab[i - 1], mr = i == p.N - 1 ? 1 : p.tab[i];
-    if (ml < 1 || ml > p.mb || mr < 1 || mr > p.mb) die("CoreGradParams: site %d is %d x %d, largest bond %d", i, ml, mr, p.mb);
     // the reduction covers a site's output with ceil(ml D / 16) x ceil(ceil(mr / 16) / 2) wave pairs, four to a workgroup
     if (reduce && (size_t)((ml * p.D + 15) / 16) * (((mr + 15) / 16 + 1) / 2) > (size_t)4 * g.y) die("core_grad_reduce_kernel: site %d (%d x %d) is not covered by %u workgroups", i, ml, mr, g.y);
     const size_t ne = (size_t)ml * p.D * mr * (i == p.l_pos ? p.L : 1);
     if ((size_t)p.tab[p.N + i] != off) die("CoreGradParams: core %d at offset %d, the flat layout has it at %zu", i, p.tab[p.N + i], off);
     if (reduce) need(p.G + off, ne * 4, "CoreGradParams.G");
-    else if (i == p.l_pos) need(p.labcore, ne * 4, "CoreGradParams.labcore");
-    else need(p.cores + (size_t)i * p.core_stride, ne * 4, "CoreGradParams.cores");
     off += ne;
   }
 }

@@ -17,6 +17,7 @@
 #include "tnml_internal.h"
 #include "small_gemm_device.h"
 #include "wide_pipe_device.h"
+#include "grad_chain_device.h"
 
 using namespace tnml;
 
@@ -618,6 +619,15 @@ extern "C" int tnml_get_core_slots(tnml_ctx *c, float *slots, size_t slots_capac
   return TNML_OK;
 }
 
+// every core changed in place (same bonds, same l_pos): nothing computed from the cores is current any more
+static void cores_changed(tnml_ctx *c) {
+  c->envs_valid_L = c->envs_valid_R = false;
+  c->Ln_valid = c->Rn_valid = false;
+  c->f_current = false;
+  c->Bnew_valid = false;
+  drop_pregradients(c);
+}
+
 extern "C" int tnml_scale_cores(tnml_ctx *c, double factor) {
   if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
   if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
@@ -625,11 +635,7 @@ extern "C" int tnml_scale_cores(tnml_ctx *c, double factor) {
   launch_scale(c->cores, (size_t)c->N * c->core_stride, (float)factor, c->stream);
   launch_scale(c->lab[c->lab_cur], c->lab_elems, (float)factor, c->stream);
   HIP_TRY(hipGetLastError());
-  c->envs_valid_L = c->envs_valid_R = false;
-  c->Ln_valid = c->Rn_valid = false;
-  c->f_current = false;
-  c->Bnew_valid = false;
-  drop_pregradients(c);
+  cores_changed(c);
   return TNML_OK;
 }
 
@@ -960,6 +966,22 @@ static int pred_chain(tnml_ctx *c, int b) {
   return TNML_OK;
 }
 
+static int ds_gather(tnml_ctx *c, const int *idx_dev, int b, int b_pad, float *X_out, int *y_out);     // (with the dataset, below)
+
+// Samples off .. off + bc of a call into the prediction group, site-major in Xpred [N][pred_cap][D]: the dataset rows idx_dev[off ..)
+// with their labels to y_out (or nullptr), or, idx_dev == nullptr, X [..][N][D] of the host through Xpred_stage with y (or nullptr) to
+// ds_ypred
+static int load_chunk(tnml_ctx *c, const float *X, const int *idx_dev, const int32_t *y, int off, int bc, int *y_out) {
+  const int N = c->N, D = c->D;
+  if (idx_dev) return ds_gather(c, idx_dev + off, bc, c->pred_cap, c->Xpred, y_out);
+  HIP_TRY(hipMemcpyAsync(c->Xpred_stage, X + (size_t)off * N * D, (size_t)bc * N * D * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  if (y) HIP_TRY(hipMemcpyAsync(c->ds_ypred, y + off, (size_t)bc * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if (D != kD) launch_transpose_input_anyd(c->Xpred_stage, c->Xpred, bc, c->pred_cap, N, D, c->stream);
+  else launch_transpose_input(c->Xpred_stage, c->Xpred, bc, c->pred_cap, N, c->stream);
+  HIP_TRY(hipGetLastError());
+  return TNML_OK;
+}
+
 extern "C" int tnml_predict(tnml_ctx *c, const float *X, int b, float *f_out) {
   // Network.forward's output for a batch that is NOT made resident (validation, Network_class.py:339-346):
   // one chain towards the label site, no environment is stored, the training batch and its environments
@@ -969,18 +991,14 @@ extern "C" int tnml_predict(tnml_ctx *c, const float *X, int b, float *f_out) {
   int rc = pred_allowed(c);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  const int N = c->N, D = c->D, L = c->L;
   rc = pred_ensure_buffers(c, (b + 63) / 64 * 64);
   if (rc) return rc;
-  const int bpad = c->pred_cap;
-  HIP_TRY(hipMemcpyAsync(c->Xpred_stage, X, (size_t)b * N * D * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  if (D != kD) launch_transpose_input_anyd(c->Xpred_stage, c->Xpred, b, bpad, N, D, c->stream);
-  else launch_transpose_input(c->Xpred_stage, c->Xpred, b, bpad, N, c->stream);
+  if ((rc = load_chunk(c, X, nullptr, nullptr, 0, b, nullptr))) return rc;
   rc = pred_table(c);
   if (rc) return rc;
   if ((rc = pred_chain(c, b))) return rc;
-  HIP_TRY(hipMemcpy2DAsync(f_out, (size_t)b * sizeof(float), c->fpred, (size_t)bpad * sizeof(float), (size_t)b * sizeof(float),
-                           L, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpy2DAsync(f_out, (size_t)b * sizeof(float), c->fpred, (size_t)c->pred_cap * sizeof(float), (size_t)b * sizeof(float),
+                           c->L, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return TNML_OK;
 }
@@ -1188,11 +1206,10 @@ extern "C" int tnml_predict_indices(tnml_ctx *c, const int32_t *idx, int b, floa
   HIP_TRY(hipSetDevice(c->device));
   if ((rc = ds_upload_indices(c, idx, b))) return rc;
   if ((rc = pred_ensure_buffers(c, (b + 63) / 64 * 64))) return rc;
-  const int bpad = c->pred_cap;
-  if ((rc = ds_gather(c, c->ds_idx, b, bpad, c->Xpred, nullptr))) return rc;
+  if ((rc = load_chunk(c, nullptr, c->ds_idx, nullptr, 0, b, nullptr))) return rc;
   if ((rc = pred_table(c))) return rc;
   if ((rc = pred_chain(c, b))) return rc;
-  HIP_TRY(hipMemcpy2DAsync(f_out, (size_t)b * sizeof(float), c->fpred, (size_t)bpad * sizeof(float), (size_t)b * sizeof(float),
+  HIP_TRY(hipMemcpy2DAsync(f_out, (size_t)b * sizeof(float), c->fpred, (size_t)c->pred_cap * sizeof(float), (size_t)b * sizeof(float),
                            c->L, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return TNML_OK;
@@ -1225,7 +1242,7 @@ extern "C" int tnml_eval_indices(tnml_ctx *c, const int32_t *idx, int b, int act
   if ((rc = pred_table(c))) return rc;
   for (int off = 0; off < b; off += chunk) {
     const int bc = std::min(chunk, b - off);
-    if ((rc = ds_gather(c, c->ds_idx + off, bc, bpad, c->Xpred, c->ds_ypred))) return rc;
+    if ((rc = load_chunk(c, nullptr, c->ds_idx, nullptr, off, bc, c->ds_ypred))) return rc;
     if ((rc = pred_chain(c, bc))) return rc;
     if (!launch_dataset_metrics(c->fpred, c->ds_ypred, c->L, bc, bpad, act_fn, T, c->ds_part, off == 0, c->ds_acc, c->stream))
       return fail(TNML_ERR_ARG, "internal: metrics launch refused");
@@ -1283,11 +1300,42 @@ extern "C" int tnml_dataset_read(tnml_ctx *c, const int32_t *idx, int b, float *
 // ---------------------------------------------------------------------------------------------
 static constexpr size_t kIgStackBytes = (size_t)256 << 20;     // the default chunk keeps the stack of pass A within this
 
-// samples per pass: the caller's (rounded up to 64) or the largest multiple of 64 whose stack stays within kIgStackBytes, at least 64
-static int ig_chunk_samples(const tnml_ctx *c) {
-  if (c->ig_chunk > 0) return (c->ig_chunk + 63) / 64 * 64;
+// What the three gradient calls (input gradients, core gradients, gradient training) share: the chunk rule, the chain's LDS refusal,
+// the cotangent of a chunk; the chunk itself comes from load_chunk.
+// samples per pass: the caller's setting (ig_chunk or cg_chunk, rounded up to 64) or the largest multiple of 64 for which a stack
+// [N][Mmax][samples] stays within kIgStackBytes, at least 64
+static int grad_chunk_samples(const tnml_ctx *c, int setting) {
+  if (setting > 0) return (setting + 63) / 64 * 64;
   const size_t per_sample = (size_t)c->N * c->Mmax * sizeof(float);
   return (int)std::max<size_t>(64, kIgStackBytes / per_sample / 64 * 64);
+}
+
+static int largest_bond(const tnml_ctx *c) {
+  int mb = 1;
+  for (int v : c->bond) mb = std::max(mb, v);
+  return mb;
+}
+
+// the two-pass chain kernel stages a whole core and three tiles of the largest bond in LDS; `what` names the call in the refusal
+static int grad_chain_fits(const tnml_ctx *c, const char *what, int mb) {
+  const size_t lds = grad_chain_lds_bytes(mb, c->D, c->L, c->N);
+  if (lds > kLdsMax) return fail(TNML_ERR_ARG, "%s at D = %d, bond %d, L = %d: %zu bytes of LDS exceed 160 KB", what, c->D, mb, c->L, lds);
+  return TNML_OK;
+}
+
+// The cotangent of the loaded chunk in cot_dev [L][bp]: columns off .. off + bc of the caller's cot [L][b], or, cot == nullptr, the
+// predicted class: the prediction chain as it is, then the one-hot of its first maximum
+static int chunk_cotangent(tnml_ctx *c, const float *cot, int off, int b, int bc, float *cot_dev, int bp) {
+  if (cot) {
+    HIP_TRY(hipMemcpy2DAsync(cot_dev, (size_t)bp * sizeof(float), cot + off, (size_t)b * sizeof(float), (size_t)bc * sizeof(float), c->L,
+                             hipMemcpyHostToDevice, c->stream));
+    return TNML_OK;
+  }
+  int rc = pred_chain(c, bc);
+  if (rc) return rc;
+  if (!launch_input_grad_onehot(c->fpred, c->pred_cap, c->L, bc, cot_dev, bp, c->stream)) return fail(TNML_ERR_ARG, "internal: one-hot launch refused");
+  HIP_TRY(hipGetLastError());
+  return TNML_OK;
 }
 
 // Input-gradient group, grown to bp samples (a multiple of 64): everything the call sizes from its chunk, and the bond table.  The
@@ -1310,15 +1358,12 @@ static int ig_ensure_buffers(tnml_ctx *c, int bp) {
 static int input_grad_impl(tnml_ctx *c, const float *X, const int32_t *idx, int b, const float *cot, int wrt, float *grad_out, float *cf_out) {
   const int N = c->N, D = c->D, L = c->L;
   if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
-  int mb = 1;
-  for (int v : c->bond) mb = std::max(mb, v);
-  const size_t lds = input_grad_lds_bytes(mb, D, L, N);
-  if (lds > kLdsMax)
-    return fail(TNML_ERR_ARG, "input gradient at D = %d, bond %d, L = %d: %zu bytes of LDS exceed 160 KB", D, mb, L, lds);
+  const int mb = largest_bond(c);
+  int rc = grad_chain_fits(c, "input gradient", mb);
+  if (rc) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  int rc;
   if (idx && (rc = ds_upload_indices(c, idx, b))) return rc;    // refuses a bad index before anything is launched
-  const int chunk = std::min(ig_chunk_samples(c), (b + 63) / 64 * 64);
+  const int chunk = std::min(grad_chunk_samples(c, c->ig_chunk), (b + 63) / 64 * 64);
   if ((rc = pred_ensure_buffers(c, chunk))) return rc;
   if ((rc = ig_ensure_buffers(c, chunk))) return rc;
   const int bp = c->ig_cap, xbp = c->pred_cap;
@@ -1327,23 +1372,8 @@ static int input_grad_impl(tnml_ctx *c, const float *X, const int32_t *idx, int 
   const bool pixels = idx && wrt == TNML_WRT_PIXELS;
   for (int off = 0; off < b; off += chunk) {
     const int bc = std::min(chunk, b - off);
-    if (idx) {
-      if ((rc = ds_gather(c, c->ds_idx + off, bc, xbp, c->Xpred, nullptr))) return rc;
-    } else {
-      HIP_TRY(hipMemcpyAsync(c->Xpred_stage, X + (size_t)off * N * D, (size_t)bc * N * D * sizeof(float), hipMemcpyHostToDevice, c->stream));
-      if (D != kD) launch_transpose_input_anyd(c->Xpred_stage, c->Xpred, bc, xbp, N, D, c->stream);
-      else launch_transpose_input(c->Xpred_stage, c->Xpred, bc, xbp, N, c->stream);
-      HIP_TRY(hipGetLastError());
-    }
-    if (cot) {
-      HIP_TRY(hipMemcpy2DAsync(c->ig_cot, (size_t)bp * sizeof(float), cot + off, (size_t)b * sizeof(float), (size_t)bc * sizeof(float), L,
-                               hipMemcpyHostToDevice, c->stream));
-    } else {
-      // the predicted class: the prediction chain as it is, then the one-hot of its first maximum
-      if ((rc = pred_chain(c, bc))) return rc;
-      if (!launch_input_grad_onehot(c->fpred, xbp, L, bc, c->ig_cot, bp, c->stream)) return fail(TNML_ERR_ARG, "internal: one-hot launch refused");
-      HIP_TRY(hipGetLastError());
-    }
+    if ((rc = load_chunk(c, X, idx ? c->ds_idx : nullptr, nullptr, off, bc, nullptr))) return rc;
+    if ((rc = chunk_cotangent(c, cot, off, b, bc, c->ig_cot, bp))) return rc;
     InputGradParams p{};
     p.bond = c->ig_bond; p.cores = c->cores; p.labcore = c->lab[c->lab_cur]; p.X = c->Xpred; p.cot = c->ig_cot;
     p.stack = c->ig_stack; p.g = c->ig_g; p.cf = c->ig_cf; p.core_stride = c->core_stride;
@@ -1394,11 +1424,20 @@ extern "C" int tnml_set_input_grad_chunk(tnml_ctx *c, int samples) {
 // ---------------------------------------------------------------------------------------------
 // core gradients: G_i = d sum_s cf[s] / d A_i for every site (kernels_coregrad.hip)
 // ---------------------------------------------------------------------------------------------
-// samples per pass: the rule of ig_chunk_samples -- each of the two stacks stays within kIgStackBytes
-static int cg_chunk_samples(const tnml_ctx *c) {
-  if (c->cg_chunk > 0) return (c->cg_chunk + 63) / 64 * 64;
-  const size_t per_sample = (size_t)c->N * c->Mmax * sizeof(float);
-  return (int)std::max<size_t>(64, kIgStackBytes / per_sample / 64 * 64);
+// The table of CoreGradParams for the current cores: tab[0 .. N-2] the bonds, tab[N + i] the offset of core i in the flat layout of
+// tnml_get_cores; total: the floats of that layout, mb: the largest bond.  `what` names the call in the refusal.
+static int grad_table(const tnml_ctx *c, const char *what, std::vector<int> &tab, size_t &total, int &mb) {
+  const int N = c->N;
+  tab.assign(2 * (size_t)N, 0);
+  total = 0;
+  mb = largest_bond(c);
+  for (int i = 0; i < N; ++i) {
+    if (i < N - 1) tab[i] = c->bond[i];
+    if (total > (size_t)INT_MAX) return fail(TNML_ERR_ARG, "%s: %zu floats of cores are beyond the offset table", what, total);
+    tab[N + i] = (int)total;
+    total += core_elems(c, c->bond, i, c->l_pos);
+  }
+  return TNML_OK;
 }
 
 // Core-gradient group, grown to bp samples (a multiple of 64).  G and the table do not depend on bp; they are members all the same,
@@ -1418,61 +1457,44 @@ static int cg_ensure_buffers(tnml_ctx *c, int bp) {
   return TNML_OK;
 }
 
+// The chain and the reduction over the loaded chunk of bc samples with the cotangent in cg_cot: both stacks, cf, and G (first: the
+// accumulators start at zero, otherwise from G).  cg_tab holds the table of grad_table, mb is its largest bond.
+static int run_core_grad_chunk(tnml_ctx *c, int bc, bool first, int mb) {
+  const int bp = c->cg_cap;
+  CoreGradParams p{};
+  p.tab = c->cg_tab; p.cores = c->cores; p.labcore = c->lab[c->lab_cur]; p.X = c->Xpred; p.cot = c->cg_cot;
+  p.stackP = c->cg_stackP; p.stackQ = c->cg_stackQ; p.G = c->cg_G; p.cf = c->cg_cf; p.core_stride = c->core_stride;
+  p.b = bc; p.b_pad = bp; p.x_bpad = c->pred_cap; p.N = c->N; p.D = c->D; p.L = c->L; p.l_pos = c->l_pos; p.cap = c->Mmax; p.mb = mb;
+  p.first = first;
+  if (!launch_core_grad_chain(p, c->stream)) return fail(TNML_ERR_ARG, "internal: core-gradient chain launch refused (b %d, b_pad %d)", bc, bp);
+  HIP_TRY(hipGetLastError());
+  if (!launch_core_grad_reduce(p, c->stream)) return fail(TNML_ERR_ARG, "internal: core-gradient reduction launch refused (b %d, b_pad %d)", bc, bp);
+  HIP_TRY(hipGetLastError());
+  return TNML_OK;
+}
+
 // X [b][N][D] on the host, or the dataset rows idx[0..b) when X is NULL
 static int core_grad_impl(tnml_ctx *c, const float *X, const int32_t *idx, int b, const float *cot, float *grad_flat, size_t capacity, float *cf_out) {
-  const int N = c->N, D = c->D, L = c->L;
   if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
-  size_t total = 0;
-  std::vector<int> tab(2 * (size_t)N, 0);
-  int mb = 1;
-  for (int i = 0; i < N; ++i) {
-    if (i < N - 1) { tab[i] = c->bond[i]; mb = std::max(mb, c->bond[i]); }
-    if (total > (size_t)INT_MAX) return fail(TNML_ERR_ARG, "core gradient: %zu floats of cores are beyond the offset table", total);
-    tab[N + i] = (int)total;
-    total += core_elems(c, c->bond, i, c->l_pos);
-  }
+  size_t total;
+  std::vector<int> tab;
+  int mb, rc = grad_table(c, "core gradient", tab, total, mb);
+  if (rc) return rc;
   if (capacity < total) return fail(TNML_ERR_ARG, "capacity %zu < %zu floats", capacity, total);
-  const size_t lds = core_grad_chain_lds_bytes(mb, D, L, N);
-  if (lds > kLdsMax)
-    return fail(TNML_ERR_ARG, "core gradient at D = %d, bond %d, L = %d: %zu bytes of LDS exceed 160 KB", D, mb, L, lds);
+  if ((rc = grad_chain_fits(c, "core gradient", mb))) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  int rc;
   if (idx && (rc = ds_upload_indices(c, idx, b))) return rc;    // refuses a bad index before anything is launched
-  const int chunk = std::min(cg_chunk_samples(c), (b + 63) / 64 * 64);
+  const int chunk = std::min(grad_chunk_samples(c, c->cg_chunk), (b + 63) / 64 * 64);
   if ((rc = pred_ensure_buffers(c, chunk))) return rc;
   if ((rc = cg_ensure_buffers(c, chunk))) return rc;
-  const int bp = c->cg_cap, xbp = c->pred_cap;
   HIP_TRY(hipMemcpyAsync(c->cg_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));                     // (`tab` is a local: no return below leaves the copy reading it)
   if (!cot && (rc = pred_table(c))) return rc;
   for (int off = 0; off < b; off += chunk) {
     const int bc = std::min(chunk, b - off);
-    if (idx) {
-      if ((rc = ds_gather(c, c->ds_idx + off, bc, xbp, c->Xpred, nullptr))) return rc;
-    } else {
-      HIP_TRY(hipMemcpyAsync(c->Xpred_stage, X + (size_t)off * N * D, (size_t)bc * N * D * sizeof(float), hipMemcpyHostToDevice, c->stream));
-      if (D != kD) launch_transpose_input_anyd(c->Xpred_stage, c->Xpred, bc, xbp, N, D, c->stream);
-      else launch_transpose_input(c->Xpred_stage, c->Xpred, bc, xbp, N, c->stream);
-      HIP_TRY(hipGetLastError());
-    }
-    if (cot) {
-      HIP_TRY(hipMemcpy2DAsync(c->cg_cot, (size_t)bp * sizeof(float), cot + off, (size_t)b * sizeof(float), (size_t)bc * sizeof(float), L,
-                               hipMemcpyHostToDevice, c->stream));
-    } else {
-      // the predicted class: the prediction chain as it is, then the one-hot of its first maximum
-      if ((rc = pred_chain(c, bc))) return rc;
-      if (!launch_input_grad_onehot(c->fpred, xbp, L, bc, c->cg_cot, bp, c->stream)) return fail(TNML_ERR_ARG, "internal: one-hot launch refused");
-      HIP_TRY(hipGetLastError());
-    }
-    CoreGradParams p{};
-    p.tab = c->cg_tab; p.cores = c->cores; p.labcore = c->lab[c->lab_cur]; p.X = c->Xpred; p.cot = c->cg_cot;
-    p.stackP = c->cg_stackP; p.stackQ = c->cg_stackQ; p.G = c->cg_G; p.cf = c->cg_cf; p.core_stride = c->core_stride;
-    p.b = bc; p.b_pad = bp; p.x_bpad = xbp; p.N = N; p.D = D; p.L = L; p.l_pos = c->l_pos; p.cap = c->Mmax; p.mb = mb;
-    p.first = off == 0;
-    if (!launch_core_grad_chain(p, c->stream)) return fail(TNML_ERR_ARG, "internal: core-gradient chain launch refused (b %d, b_pad %d)", bc, bp);
-    HIP_TRY(hipGetLastError());
-    if (!launch_core_grad_reduce(p, c->stream)) return fail(TNML_ERR_ARG, "internal: core-gradient reduction launch refused (b %d, b_pad %d)", bc, bp);
-    HIP_TRY(hipGetLastError());
+    if ((rc = load_chunk(c, X, idx ? c->ds_idx : nullptr, nullptr, off, bc, nullptr))) return rc;
+    if ((rc = chunk_cotangent(c, cot, off, b, bc, c->cg_cot, c->cg_cap))) return rc;
+    if ((rc = run_core_grad_chunk(c, bc, off == 0, mb))) return rc;
     if (cf_out) HIP_TRY(hipMemcpyAsync(cf_out + off, c->cg_cf, (size_t)bc * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   }
   HIP_TRY(hipMemcpyAsync(grad_flat, c->cg_G, total * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -1558,7 +1580,7 @@ static int opt_ensure_metrics(tnml_ctx *c, int n_steps) {
 }
 
 // n_steps = ceil(n / batch) steps over X [n][N][D], y [n] on the host, or over the dataset rows idx[0..n) when X is NULL.  The
-// per-chunk body is core_grad_impl's with the loss derivative as the cotangent (a copy: that function's call sequence stays as it is).
+// per-chunk body is core_grad_impl's with the loss derivative as the cotangent.
 static int gd_impl(tnml_ctx *c, const float *X, const int32_t *y, const int32_t *idx, int n, int batch, float lr, float wd, int act_fn,
                    int loss_fn, float T, double *metrics_out) {
   const int N = c->N, D = c->D, L = c->L;
@@ -1567,19 +1589,11 @@ static int gd_impl(tnml_ctx *c, const float *X, const int32_t *y, const int32_t 
   if (y)
     for (int i = 0; i < n; ++i)
       if (y[i] < 0 || y[i] >= L) return fail(TNML_ERR_ARG, "label %d of sample %d outside [0, %d)", y[i], i, L);
-  size_t total = 0;
-  std::vector<int> &tab = c->opt_tab;
-  tab.assign(2 * (size_t)N, 0);
-  int mb = 1;
-  for (int i = 0; i < N; ++i) {
-    if (i < N - 1) { tab[i] = c->bond[i]; mb = std::max(mb, c->bond[i]); }
-    if (total > (size_t)INT_MAX) return fail(TNML_ERR_ARG, "gradient step: %zu floats of cores are beyond the offset table", total);
-    tab[N + i] = (int)total;
-    total += core_elems(c, c->bond, i, c->l_pos);
-  }
-  const size_t lds = core_grad_chain_lds_bytes(mb, D, L, N);
-  if (lds > kLdsMax)
-    return fail(TNML_ERR_ARG, "gradient step at D = %d, bond %d, L = %d: %zu bytes of LDS exceed 160 KB", D, mb, L, lds);
+  size_t total;
+  std::vector<int> &tab = c->opt_tab;                           // (a member: the upload below is not waited for)
+  int mb, rc = grad_table(c, "gradient step", tab, total, mb);
+  if (rc) return rc;
+  if ((rc = grad_chain_fits(c, "gradient step", mb))) return rc;
   if (dataset_metrics_lds_bytes(L) > 64 * 1024 || loss_cot_lds_bytes(L) > 64 * 1024)
     return fail(TNML_ERR_ARG, "metrics / loss-derivative kernel: %d labels exceed its LDS tile", L);
   const bool stateful = opt_stateful(c);
@@ -1587,10 +1601,9 @@ static int gd_impl(tnml_ctx *c, const float *X, const int32_t *y, const int32_t 
     return fail(TNML_ERR_STATE, "the optimiser state belongs to other bonds or another l_pos (l_pos %d then, %d now): call tnml_optim_reset",
                 c->opt.l_pos, c->l_pos);
   HIP_TRY(hipSetDevice(c->device));
-  int rc;
   if (idx && (rc = ds_upload_indices(c, idx, n))) return rc;    // refuses a bad index before anything is launched
   const int n_steps = (n + batch - 1) / batch;
-  const int chunk = std::min(cg_chunk_samples(c), (std::min(batch, n) + 63) / 64 * 64);
+  const int chunk = std::min(grad_chunk_samples(c, c->cg_chunk), (std::min(batch, n) + 63) / 64 * 64);
   if ((rc = pred_ensure_buffers(c, chunk))) return rc;
   if ((rc = cg_ensure_buffers(c, chunk))) return rc;
   if ((rc = ds_ensure_metrics(c, c->pred_cap))) return rc;
@@ -1599,25 +1612,12 @@ static int gd_impl(tnml_ctx *c, const float *X, const int32_t *y, const int32_t 
   const int bp = c->cg_cap, xbp = c->pred_cap;
   HIP_TRY(hipMemcpyAsync(c->cg_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
   if ((rc = pred_table(c))) return rc;
-  // the cores change from here on: what tnml_scale_cores leaves
-  c->envs_valid_L = c->envs_valid_R = false;
-  c->Ln_valid = c->Rn_valid = false;
-  c->f_current = false;
-  c->Bnew_valid = false;
-  drop_pregradients(c);
+  cores_changed(c);                                             // from here on
   for (int k = 0; k < n_steps; ++k) {
     const int s0 = k * batch, bk = std::min(batch, n - s0);
     for (int off = 0; off < bk; off += chunk) {
       const int bc = std::min(chunk, bk - off);
-      if (idx) {
-        if ((rc = ds_gather(c, c->ds_idx + s0 + off, bc, xbp, c->Xpred, c->ds_ypred))) return rc;
-      } else {
-        HIP_TRY(hipMemcpyAsync(c->Xpred_stage, X + (size_t)(s0 + off) * N * D, (size_t)bc * N * D * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->ds_ypred, y + s0 + off, (size_t)bc * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        if (D != kD) launch_transpose_input_anyd(c->Xpred_stage, c->Xpred, bc, xbp, N, D, c->stream);
-        else launch_transpose_input(c->Xpred_stage, c->Xpred, bc, xbp, N, c->stream);
-        HIP_TRY(hipGetLastError());
-      }
+      if ((rc = load_chunk(c, X, idx ? c->ds_idx : nullptr, y, s0 + off, bc, c->ds_ypred))) return rc;
       if ((rc = pred_chain(c, bc))) return rc;
       if (!launch_dataset_metrics(c->fpred, c->ds_ypred, L, bc, xbp, act_fn, T, c->ds_part, off == 0, c->ds_acc, c->stream))
         return fail(TNML_ERR_ARG, "internal: metrics launch refused");
@@ -1627,15 +1627,7 @@ static int gd_impl(tnml_ctx *c, const float *X, const int32_t *y, const int32_t 
       q.act_fn = act_fn; q.loss_fn = loss_fn; q.T = T;
       if (!launch_loss_cot(q, c->stream)) return fail(TNML_ERR_ARG, "internal: loss-derivative launch refused (b %d, b_pad %d)", bc, bp);
       HIP_TRY(hipGetLastError());
-      CoreGradParams p{};
-      p.tab = c->cg_tab; p.cores = c->cores; p.labcore = c->lab[c->lab_cur]; p.X = c->Xpred; p.cot = c->cg_cot;
-      p.stackP = c->cg_stackP; p.stackQ = c->cg_stackQ; p.G = c->cg_G; p.cf = c->cg_cf; p.core_stride = c->core_stride;
-      p.b = bc; p.b_pad = bp; p.x_bpad = xbp; p.N = N; p.D = D; p.L = L; p.l_pos = c->l_pos; p.cap = c->Mmax; p.mb = mb;
-      p.first = off == 0;
-      if (!launch_core_grad_chain(p, c->stream)) return fail(TNML_ERR_ARG, "internal: core-gradient chain launch refused (b %d, b_pad %d)", bc, bp);
-      HIP_TRY(hipGetLastError());
-      if (!launch_core_grad_reduce(p, c->stream)) return fail(TNML_ERR_ARG, "internal: core-gradient reduction launch refused (b %d, b_pad %d)", bc, bp);
-      HIP_TRY(hipGetLastError());
+      if ((rc = run_core_grad_chunk(c, bc, off == 0, mb))) return rc;
     }
     OptimStepParams o{};
     o.tab = c->cg_tab; o.cores = c->cores; o.labcore = c->lab[c->lab_cur]; o.G = c->cg_G;

@@ -278,7 +278,8 @@ size_t dataset_metrics_lds_bytes(int L);
 bool launch_dataset_metrics(const float *f, const int *y, int L, int b, int b_pad, int act_fn, float T, double *part, int reset, double *acc,
                             hipStream_t st);
 
-// Input gradients (kernels_inputgrad.hip): both chains of 64 samples per workgroup, see the head of that file.
+// Input gradients (kernels_inputgrad.hip): both chains of 64 samples per workgroup, the body of grad_chain_device.h (which also
+// has grad_chain_lds_bytes, the LDS of this kernel and of core_grad_chain_kernel).
 struct InputGradParams {
   const int *bond;         // [N-1] bond dimensions of the chain
   const float *cores;      // plain cores, core i at i * core_stride, [ml][D][mr]
@@ -293,7 +294,6 @@ struct InputGradParams {
   int cap;                 // rows of a stack slot: the context's bond capacity
   int mb;                  // largest bond of the chain: what the LDS tiles are sized for
 };
-size_t input_grad_lds_bytes(int mb, int D, int L, int N);
 // false: refused (geometry / LDS)
 bool launch_input_grad(const InputGradParams &p, hipStream_t st);
 // cot [L][b_pad] = one-hot of the first maximum of f [L][f_bpad] per sample, zero for samples b .. b_pad-1
@@ -325,7 +325,6 @@ struct CoreGradParams {
   int mb;                  // largest bond of the chain: what the LDS tiles are sized for
   int first;               // reduction: 1 = the accumulators start at zero, 0 = they start from G (a chunk after the first)
 };
-size_t core_grad_chain_lds_bytes(int mb, int D, int L, int N);
 size_t core_grad_reduce_lds_bytes(int mb, int D);
 // workgroups of the reduction along y: four waves, each with two 16 x 16 output tiles side by side, cover a site of bonds <= mb
 int core_grad_reduce_blocks(int mb, int D);

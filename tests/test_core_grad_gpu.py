@@ -6,7 +6,8 @@
                                 b in {1, 17, 70}, a dense random cotangent, for the (D, cap, L) rows below
   2  Euler identity             |sum(G_i A_i) - sum_s cf| for every site, on the device's own output, four rows
   3  tie to the input gradient  sum_{a,c} G_i[a][d][c] A_i[a][d][c] = sum_s x[s][i][d] g[s][i][d] for every site and d, G from
-                                core_grad and g from input_grad on the same X and cot
+                                core_grad and g from input_grad on the same X and cot; cf of the two calls bit-equal (one device
+                                body runs both chains)
   4  bit-equalities             chunk 64 against the default chunk (b = 70, 200); the same call twice; cot=None against the one-hot
                                 of predict's first maximum; core_grad_indices against core_grad on dataset_read; a capacity larger
                                 than needed leaves the floats behind the gradient alone
@@ -178,8 +179,9 @@ def test_tie_to_the_input_gradient(row):
         cores = cores_for(N, D, L, cap, l, rng, True)
         ctx.set_cores(cores, l)
         cot = rng.standard_normal((L, b)).astype(np.float32)
-        G, _ = ctx.core_grad(X, cot)
-        g, _ = ctx.input_grad(X, cot)
+        G, cf_core = ctx.core_grad(X, cot)
+        g, cf_input = ctx.input_grad(X, cot)
+        assert np.array_equal(cf_core, cf_input)                   # one device body computes both (csrc/grad_chain_device.h)
         terms = X.astype(np.float64) * g.astype(np.float64)                                      # (b, N, D)
         lhs = np.array([(G[i].astype(np.float64) * cores[i].astype(np.float64)).sum(axis=(0, 2, 3) if i == l else (0, 2)) for i in range(N)])
         worst = max(worst, np.abs(lhs - terms.sum(0)).max() / np.abs(terms).sum(0).max())
