@@ -317,6 +317,28 @@ int tnml_gd_train_indices(tnml_ctx *ctx, const int32_t *idx, int n, int batch, f
 int tnml_gd_step(tnml_ctx *ctx, const float *X, const int32_t *y, int b, float lr, float weight_dec, int act_fn, int loss_fn, float T,
                  double *metrics3);
 
+/* ---- range-safe chains ------------------------------------------------------------------------- */
+/* The chains of the prediction and gradient calls are float32 products over all sites.  A network whose f is of order 1 may still
+ * have partial products over a few hundred sites that leave float32 (after Adam, weight decay or a change of gauge moved the size
+ * of single cores); the calls then return inf, nan or a silent 0.  With this switch on every sample carries a power-of-two exponent
+ * along its chains: after the product of every site the sample's column is multiplied by exactly 2^-k, k = ilogb(max |.|) + 1
+ * (k = 0 where that maximum is 0 or not finite), and k joins the sample's int32 exponent.  The scaling is exact, so wherever the
+ * plain chain stays in range the results agree with it to rounding-order effects of the compiler only.
+ * on = 1: tnml_predict, tnml_predict_indices, tnml_eval_indices, tnml_input_grad(_indices), tnml_core_grad(_indices), tnml_gd_step
+ * and tnml_gd_train_indices (and the prediction behind a NULL cot) run scaled chains; their plain outputs receive
+ * ldexpf(mantissa, exponent) with IEEE saturation and flush, so an f that itself lies outside float32 still reads inf or 0 there:
+ * read such an f with tnml_predict_scaled.  The resident batch, its environments, the sweep, tnml_forward,
+ * tnml_forward_logabsmax and the orthogonalisation calls are untouched.  Default 0: every launch and buffer is what it was.
+ * on outside {0, 1}: TNML_ERR_ARG.  The refusals of the calls themselves (communicator, LDS limit) are unchanged. */
+int tnml_set_chain_scaling(tnml_ctx *ctx, int on);
+/* f of a batch that is NOT made resident, as mantissa and exponent: X [b][N][D] -> mant_out [L][b], expo_out [b] with
+ * f[l][s] = mant[l][s] * 2^expo[s] and 0.5 <= max_l |mant[l][s]| < 1 per sample.  Where every f[:, s] is 0 or one of them is not
+ * finite, expo[s] = 0 and mant holds the values as they are.  Works with the switch above on or off, at any label position
+ * tnml_predict accepts, and refuses what tnml_predict refuses (plus a shape beyond the 160 KB LDS limit of the kernel:
+ * TNML_ERR_ARG with the bytes).  This is how the output of an un-calibrated network (about 1e-66 at N = 784) is read and its
+ * argmax taken. */
+int tnml_predict_scaled(tnml_ctx *ctx, const float *X, int b, float *mant_out, int32_t *expo_out);
+
 /* Accuracy / speed of the in-kernel Jacobi SVD (no reference analogue: the reference calls LAPACK,
  * Network_class.py:887).  The iteration ends after a sweep in which every rotation had
  * g^2 <= stop2 * scale^2; the off-diagonals left behind are of relative size ~stop2.  Default 1e-6

@@ -136,6 +136,12 @@ class Network():
     (l_pos, left_dir, n_steps) of the segments of its last call; the direction of the last segment is pickled with the network
     (`seg_left`), so that a model saved mid-sweep goes on in the direction it was moving.
 
+    `scaled_chains` (default False, not pickled; not in the reference): when set, `predict`, `evaluate`, the input and core
+    gradients and `train_gradient` carry a power-of-two exponent per sample along their chains, so that a partial product that
+    leaves float32 -- after Adam, weight decay or a change of gauge moved the size of single cores -- no longer turns a
+    representable result into inf, nan or 0 (include/tnml.h, tnml_set_chain_scaling).  `forward`, the
+    resident batch and the sweep are untouched.  `predict_scaled(X)` returns f as (mantissa, exponent) whatever the switch says.
+
     D (2 <= D <= 8) is the local feature dimension (data_generator.psi(x, D) embeds pixels for it).  D != 2 runs the
     generic per-step device path (include/tnml.h).  Deviation from the reference: with normalize=True and no
     calibration_X the 16 random calibration samples are embedded with psi(u, D); the reference always embeds them
@@ -212,6 +218,8 @@ class Network():
         self._dataset = None          # DeviceDataset attached to self._ctx (attach_dataset); lives and dies with the context
         self._X_idx = None            # dataset indices of the resident batch when it was formed on the device
         self._any_position = False
+        self._scaled_chains = False   # what the user asked for; _scaled_applied: what the context was last told
+        self._scaled_applied = False
         self._seg_left = False        # direction of the last segment of train_resident(steps_per_batch=k) (pickled)
         self.segment_log = []         # (l_pos, left_dir, n_steps) of the segments of the last train_resident(steps_per_batch=k)
 
@@ -235,6 +243,14 @@ class Network():
         self._any_position = bool(on)
         if self._ctx is not None:
             self._ctx.set_any_position(self._any_position)
+
+    @property
+    def scaled_chains(self):
+        return self._scaled_chains
+
+    @scaled_chains.setter
+    def scaled_chains(self, on):
+        self._scaled_chains = bool(on)        # (reaches the context with the next device call: _sync_to_device)
 
     def _check_forward_position(self, lp):
         if lp != 0 and lp != self.N - 1 and not self._any_position:
@@ -291,6 +307,9 @@ class Network():
     def _sync_to_device(self, b=None):
         self._collect_user_edits()
         ctx = self._context(b if b is not None else max(self._b, 1))
+        if self._scaled_applied != self._scaled_chains:
+            ctx.set_chain_scaling(self._scaled_chains)
+            self._scaled_applied = self._scaled_chains
         if self._host_newer:
             ctx.set_cores(self._host_cores, self._l_pos)
             self._host_newer = False
@@ -400,6 +419,16 @@ class Network():
         self._check_forward_position(self.l_pos)
         ctx = self._sync_to_device(max(self._b, 1))
         return Tensor(elem=ctx.predict(X).astype(np.float64), axes_names=['l', 'b'])
+
+    def predict_scaled(self, X):
+        """predict(X) as (mant (L, b) float32, expo (b,) int32): f[l, s] = mant[l, s] * 2 ** expo[s] with
+        0.5 <= max_l |mant[l, s]| < 1 per sample, so that the output of a network whose f lies outside float32 (an un-calibrated
+        one is about 1e-66 at N = 784) can be read and its argmax taken: `mant.argmax(0)`.  Works with `scaled_chains` on or off.
+        Not in the reference."""
+        assert self.N == X.shape[1], "The 1 dimension of the input data must be the flattened number of pixels"
+        self._check_forward_position(self.l_pos)
+        ctx = self._sync_to_device(max(self._b, 1))
+        return ctx.predict_scaled(X)
 
     # ------------------------------------------------------------------------------------------
     # input gradients (not in the reference)

@@ -38,6 +38,7 @@ SYMBOLS = [
     'tnml_core_grad', 'tnml_core_grad_indices', 'tnml_set_core_grad_chunk',
     'tnml_optim_config', 'tnml_optim_reset', 'tnml_gd_train_indices', 'tnml_gd_step', 'tnml_get_core_slots',
     'tnml_orthogonalize', 'tnml_compress', 'tnml_bond_spectra',
+    'tnml_set_chain_scaling', 'tnml_predict_scaled',
 ]
 
 
@@ -137,6 +138,8 @@ def lib():
         L.tnml_orthogonalize.argtypes = [vp, C.c_double, i32p, f64p]
         L.tnml_compress.argtypes = [vp, C.c_int, C.c_double, C.c_double, i32p, f64p, f64p, f64p]
         L.tnml_bond_spectra.argtypes = [vp, C.c_double, i32p, f64p, f64p]
+        L.tnml_set_chain_scaling.argtypes = [vp, C.c_int]
+        L.tnml_predict_scaled.argtypes = [vp, f32p, C.c_int, f32p, i32p]
         _lib = L
     return _lib
 
@@ -485,6 +488,18 @@ class Context:
         _chk(lib().tnml_predict(self._h, _ptr(X, C.c_float), X.shape[0], _ptr(f, C.c_float)))
         return f
 
+    def predict_scaled(self, X):
+        """(mant (L, b) float32, expo (b,) int32) with f[l, s] = mant[l, s] * 2 ** expo[s] and 0.5 <= max_l |mant[l, s]| < 1: the
+        output of a batch that does not become resident, readable where f itself lies outside float32 (include/tnml.h).  A sample
+        whose f is all zero or not finite has expo 0 and the values as they are.  np.ldexp(mant.astype(np.float64), expo) is f."""
+        X = _f32(X)
+        assert X.ndim == 3 and X.shape[1] == self.N and X.shape[2] == self.D, \
+            "The 1 dimension of the input data must be the flattened number of pixels"
+        mant = np.empty((self.L, X.shape[0]), dtype=np.float32)
+        expo = np.empty(X.shape[0], dtype=np.int32)
+        _chk(lib().tnml_predict_scaled(self._h, _ptr(X, C.c_float), X.shape[0], _ptr(mant, C.c_float), _ptr(expo, C.c_int32)))
+        return mant, expo
+
     def forward_logabsmax(self):
         """log max|f| of the resident batch, exact even where f under/overflows float32."""
         v = C.c_double()
@@ -614,6 +629,12 @@ class Context:
         """True: forward / predict / predict_indices / eval_indices also run with the label at an intermediate site, and a
         forward there lets one sweep call start a segment in either direction (include/tnml.h); False (default): ends only."""
         _chk(lib().tnml_set_any_position(self._h, int(bool(on))))
+
+    def set_chain_scaling(self, on=True):
+        """True: predict / predict_indices / eval_indices, both gradient calls and the gradient-training calls carry a power-of-two
+        exponent per sample along their chains, so that partial products outside float32 no longer spoil a representable result
+        (include/tnml.h); False (default): the plain chains.  Anything but 0 / 1 is refused."""
+        _chk(lib().tnml_set_chain_scaling(self._h, int(on)))
 
     def set_narrow_path(self, force_large):
         """True: every step takes the large-tensor (HBM-resident) path; False: automatic."""

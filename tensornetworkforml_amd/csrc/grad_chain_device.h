@@ -43,10 +43,11 @@ struct GradChainView {
   int b, b_pad, x_bpad, N, D, L, l_pos, cap, mb;
 };
 
-inline size_t grad_chain_lds_bytes(int mb, int D, int L, int N) {
+// scaled: the two exponent rows of the range-safe form (below) behind the bond table
+inline size_t grad_chain_lds_bytes(int mb, int D, int L, int N, bool scaled = false) {
   const size_t ldA = (size_t)mb | 1, ldT = ((size_t)mb * D) | 1;
   return ((size_t)mb * D * ldA + 2 * (size_t)mb * kGcLd + (size_t)kGcTS * D + (size_t)L * kGcTS + (size_t)kGcTS * ldT) * sizeof(float) +
-         (size_t)(N + 1) * sizeof(int);
+         (size_t)(N + 1) * sizeof(int) + (scaled ? 2 * (size_t)kGcTS * sizeof(int) : 0);
 }
 
 // Two 16 x 16 output tiles that share their A operand, K in steps of 4 (operand and accumulator layout: anyd_mfma_tile of
@@ -70,14 +71,38 @@ __device__ inline void gc_mfma_pair(int K, int D, FA fa, FB0 fb0, FB1 fb1, gc_f4
   }
 }
 
+// The range-safe form: the column of sample s (the thread's, of the workgroup's 64; lane = (sample, quarter
+// `part` of the bond index)) of the tile E [m][kGcLd] is multiplied by exactly 2^-k, k = ilogb(max_a |E[a][s]|) + 1, and k is added
+// to the sample's exponent ex[s]; k = 0 where that maximum is 0 or not finite.  frexpf gives the same k (mx = v 2^k, 0.5 <= v < 1),
+// ldexpf is exact short of the subnormal range.  The four lanes of a sample are lanes r16, r16 + 16, r16 + 32, r16 + 48 of one wave.
+__device__ inline void gc_rescale(float *E, int m, int s, int part, int *ex) {
+  float mx = 0.f;
+  bool bad = false;
+  for (int a = part; a < m; a += 4) {
+    const float av = fabsf(E[a * kGcLd + s]);
+    bad |= !(av < INFINITY);
+    mx = fmaxf(mx, av);
+  }
+  if (bad) mx = INFINITY;
+  mx = fmaxf(mx, __shfl_xor(mx, 16));
+  mx = fmaxf(mx, __shfl_xor(mx, 32));
+  int k = 0;
+  if (mx > 0.f && mx < INFINITY) (void)frexpf(mx, &k);
+  if (k != 0) for (int a = part; a < m; a += 4) E[a * kGcLd + s] = ldexpf(E[a * kGcLd + s], -k);
+  if (part == 0) ex[s] += k;
+}
+
 // Both passes for the 64 samples of workgroup blockIdx.x, 256 threads.  The two places where the kernels differ:
 //   site_hook(i, ml, mr, sP, sQ, s0)   all 256 threads, pass B at the first label slice of site i, between the barrier that ends the
 //                                      products of site i + 1 and the one before those of site i: sQ [mr][kGcLd] holds Q_i, sP
 //                                      [mb][kGcLd] is free (P_i is not kept from pass A)
 //   t_hook(i, ml, s, Ts, sP, s0)       once T of site i is complete, before Q of site i - 1 replaces Q_i: the thread's sample s
 //                                      (of the workgroup's 64; lane = (sample, quarter of the bond index a)), its row Ts of T [ml D]
-template <class SiteHook, class THook>
-__device__ inline void grad_chain_body(const GradChainView &p, SiteHook site_hook, THook t_hook) {
+// SCALED: every P_{i+1} and every Q_{i-1} is rescaled per sample (gc_rescale) as soon as it is complete.  Pass A writes the cumulative
+// exponent eP_{i+1}[s] to estack [N][b_pad] beside the stack; pass B keeps eQ[s] in LDS.  Both hooks receive sEQ (the exponents of
+// the Q they see) as one more argument, and cf = ldexpf(Q_{-1}, eQ).  No expression of the unscaled form changes.
+template <bool SCALED = false, class SiteHook, class THook>
+__device__ inline void grad_chain_body(const GradChainView &p, SiteHook site_hook, THook t_hook, int *estack = nullptr) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int D = p.D, L = p.L, N = p.N, mb = p.mb, lp = p.l_pos;
   const int ldA = mb | 1, ldT = (mb * D) | 1;
@@ -88,8 +113,10 @@ __device__ inline void grad_chain_body(const GradChainView &p, SiteHook site_hoo
   float *sCot = sX + (size_t)kGcTS * D;                    // [L][64]
   float *sT = sCot + (size_t)L * kGcTS;                    // [64][ldT]
   int *sBond = (int *)(sT + (size_t)kGcTS * ldT);          // [N + 1]: 1, bond[0 .. N-2], 1 (a site's two bonds without a trip to memory)
+  int *sEP = sBond + (N + 1), *sEQ = sEP + kGcTS;          // SCALED: [64] exponents of P (pass A) and of Q (pass B)
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r16 = lane & 15, part = lane >> 4;
   const int s0 = blockIdx.x * kGcTS, sw = wave * 16;       // sw: this wave's samples
+  if constexpr (SCALED) { if (tid < 2 * kGcTS) sEP[tid] = 0; }
   for (int e = tid; e <= N; e += 256) sBond[e] = (e == 0 || e == N) ? 1 : p.bond[e - 1];
   auto stage = [&](int i, int sl, int ml, int mr) {
     const int n = ml * D * mr, qk = 256 / mr, qc = 256 % mr;
@@ -133,6 +160,11 @@ __device__ inline void grad_chain_body(const GradChainView &p, SiteHook site_hoo
       }
     }
     __syncthreads();
+    if constexpr (SCALED) {
+      gc_rescale(eout, mr, sw + r16, part, sEP);
+      __syncthreads();
+      if (tid < kGcTS) estack[(size_t)(i + 1) * p.b_pad + s0 + tid] = sEP[tid];
+    }
     float *dst = p.stack + (size_t)(i + 1) * p.cap * p.b_pad + s0;
     for (int e = tid; e < mr * kGcTS; e += 256) dst[(size_t)(e / kGcTS) * p.b_pad + e % kGcTS] = eout[(e / kGcTS) * kGcLd + e % kGcTS];
     float *t = ein; ein = eout; eout = t;
@@ -149,7 +181,8 @@ __device__ inline void grad_chain_body(const GradChainView &p, SiteHook site_hoo
       stage(i, sl, ml, mr);
       if (sl == 0) {
         load_x(i);
-        site_hook(i, ml, mr, sP, sQ, s0);
+        if constexpr (SCALED) site_hook(i, ml, mr, sP, sQ, s0, sEQ);
+        else site_hook(i, ml, mr, sP, sQ, s0);
       }
       __syncthreads();
       const float crv = i == lp ? sCot[sl * kGcTS + sw + r16] : 1.f, *qs = sQ + sw + r16;
@@ -170,16 +203,22 @@ __device__ inline void grad_chain_body(const GradChainView &p, SiteHook site_hoo
     // the small contractions of this wave's 16 samples: lane = (sample r16, quarter `part` of the bond index a)
     const int s = sw + r16;
     const float *Ts = sT + (size_t)s * ldT;
-    t_hook(i, ml, s, Ts, sP, s0);
+    if constexpr (SCALED) t_hook(i, ml, s, Ts, sP, s0, sEQ);
+    else t_hook(i, ml, s, Ts, sP, s0);
     // (a wave reads and writes only its own samples of Q, and its products with Q are behind it)
     for (int a = part; a < ml; a += 4) {
       float v = 0.f;
       for (int d = 0; d < D; ++d) v = fmaf(sX[s * D + d], Ts[a * D + d], v);
       sQ[a * kGcLd + s] = v;
     }
+    if constexpr (SCALED) gc_rescale(sQ, ml, s, part, sEQ);
   }
   __syncthreads();
-  if (p.cf && tid < kGcTS && s0 + tid < p.b) p.cf[s0 + tid] = sQ[tid];
+  if constexpr (SCALED) {
+    if (p.cf && tid < kGcTS && s0 + tid < p.b) p.cf[s0 + tid] = ldexpf(sQ[tid], sEQ[tid]);
+  } else {
+    if (p.cf && tid < kGcTS && s0 + tid < p.b) p.cf[s0 + tid] = sQ[tid];
+  }
 }
 
 }  // namespace tnml

@@ -50,9 +50,49 @@ __global__ __launch_bounds__(256) void core_grad_chain_kernel(CoreGradParams p) 
       [](int, int, int, const float *, const float *, int) {});
 }
 
+// The range-safe form: stackP keeps the mantissas of P_i, the second stack receives ldexpf(Q_i, eP_i + eQ_i), so
+// that the reduction kernel below, unchanged, sums the true P_i x_i Q_i wherever that is representable.
+__global__ __launch_bounds__(256) void core_grad_chain_scaled_kernel(CoreGradScaledParams ps) {
+  const CoreGradParams &p = ps.base;
+  const GradChainView v{p.tab, p.cores, p.labcore, p.X, p.cot, p.stackP, p.cf, p.core_stride, p.b, p.b_pad, p.x_bpad, p.N, p.D, p.L, p.l_pos, p.cap, p.mb};
+  const int tid = threadIdx.x;
+  grad_chain_body<true>(
+      v,
+      [&](int i, int ml, int mr, const float *, const float *sQ, int s0, const int *sEQ) {     // Q_i to the second stack
+        if (i == p.N - 1) {
+          // the reduction takes Q_{N-1} as the scalar 1 and not from the second stack: the last site's exponent goes into P_{N-1},
+          // which no later step of this kernel reads (this workgroup wrote the slot and the exponents in pass A)
+          float *slot = p.stackP + (size_t)i * p.cap * p.b_pad + s0;
+          const int *eP = ps.estack + (size_t)i * p.b_pad + s0;
+          for (int e = tid; e < ml * kGcTS; e += 256) {
+            float *v = slot + (size_t)(e / kGcTS) * p.b_pad + e % kGcTS;
+            *v = ldexpf(*v, eP[e % kGcTS]);
+          }
+        }
+        if (i < p.N - 1) {
+          float *dst = p.stackQ + (size_t)i * p.cap * p.b_pad + s0;
+          const int *eP = ps.estack + (size_t)i * p.b_pad + s0;
+          for (int e = tid; e < mr * kGcTS; e += 256) {
+            const int s = e % kGcTS;
+            dst[(size_t)(e / kGcTS) * p.b_pad + s] = ldexpf(sQ[(e / kGcTS) * kGcLd + s], (i == 0 ? 0 : eP[s]) + sEQ[s]);
+          }
+        }
+      },
+      [](int, int, int, const float *, const float *, int, const int *) {}, ps.estack);
+}
+
 static bool core_grad_geometry_ok(const CoreGradParams &p) {
   return p.b >= 1 && p.b <= p.b_pad && p.b_pad % kCgTS == 0 && p.x_bpad >= p.b_pad && p.mb >= 1 && p.mb <= p.cap && p.D >= 2 && p.D <= kMaxD &&
          p.N >= 2 && p.L >= 1 && p.l_pos >= 0 && p.l_pos < p.N;
+}
+
+bool launch_core_grad_chain_scaled(const CoreGradScaledParams &ps, hipStream_t st) {
+  const CoreGradParams &p = ps.base;
+  if (!core_grad_geometry_ok(p) || !ps.estack) return false;
+  const size_t lds = grad_chain_lds_bytes(p.mb, p.D, p.L, p.N, true);
+  if (lds > 160 * 1024) return false;
+  hipLaunchKernelGGL(core_grad_chain_scaled_kernel, dim3((p.b + kCgTS - 1) / kCgTS), dim3(256), lds, st, ps);
+  return true;
 }
 
 bool launch_core_grad_chain(const CoreGradParams &p, hipStream_t st) {

@@ -44,6 +44,46 @@ bool launch_input_grad(const InputGradParams &p, hipStream_t st) {
   return true;
 }
 
+// The range-safe form: P_i and Q_i are mantissas with the exponents eP_i (the exponent stack) and eQ_i (LDS),
+// and g = ldexpf(sum_a P T, eP_i + eQ_i).
+__global__ __launch_bounds__(256) void input_grad_scaled_kernel(InputGradScaledParams ps) {
+  const InputGradParams &p = ps.base;
+  const GradChainView v{p.bond, p.cores, p.labcore, p.X, p.cot, p.stack, p.cf, p.core_stride, p.b, p.b_pad, p.x_bpad, p.N, p.D, p.L, p.l_pos, p.cap, p.mb};
+  const int tid = threadIdx.x, part = (tid & 63) >> 4;
+  grad_chain_body<true>(
+      v,
+      [&](int i, int ml, int, float *sP, const float *, int s0, const int *) {          // P_i from the stack
+        if (i == 0) {
+          if (tid < kGcTS) sP[tid] = 1.f;
+        } else {
+          const float *src = p.stack + (size_t)i * p.cap * p.b_pad + s0;
+          for (int e = tid; e < ml * kGcTS; e += 256) sP[(e / kGcTS) * kGcLd + e % kGcTS] = src[(size_t)(e / kGcTS) * p.b_pad + e % kGcTS];
+        }
+      },
+      [&](int i, int ml, int s, const float *Ts, const float *sP, int s0, const int *sEQ) {   // g[i][:] of sample s
+        const int ex = (i == 0 ? 0 : ps.estack[(size_t)i * p.b_pad + s0 + s]) + sEQ[s];
+        for (int d = 0; d < p.D; ++d) {
+          float v = 0.f;
+          for (int a = part; a < ml; a += 4) v = fmaf(sP[a * kGcLd + s], Ts[a * p.D + d], v);
+          v += __shfl_xor(v, 16);
+          v += __shfl_xor(v, 32);
+          if (part == 0 && s0 + s < p.b) p.g[((size_t)(s0 + s) * p.N + i) * p.D + d] = ldexpf(v, ex);
+        }
+      },
+      ps.estack);
+}
+
+bool launch_input_grad_scaled(const InputGradScaledParams &ps, hipStream_t st) {
+  const InputGradParams &p = ps.base;
+  if (p.b < 1 || p.b > p.b_pad || p.b_pad % kGcTS || p.x_bpad < p.b_pad || p.mb < 1 || p.mb > p.cap || p.D < 2 || p.D > kMaxD ||
+      p.l_pos < 0 || p.l_pos >= p.N || !ps.estack)
+    return false;
+  const size_t lds = grad_chain_lds_bytes(p.mb, p.D, p.L, p.N, true);
+  if (lds > 160 * 1024) return false;
+  hipLaunchKernelGGL(input_grad_scaled_kernel, dim3((p.b + kGcTS - 1) / kGcTS), dim3(256), lds, st, ps);
+  return true;
+}
+
 // ------------------------------------------------------------------------------------------
 // cot[l'][s] = (l' == first maximum of f[:, s]) for s < b, 0 beyond: the rule of act_and_lossder (act_device.h)
 // ------------------------------------------------------------------------------------------

@@ -283,6 +283,45 @@ static void check_core_grad(const CoreGradParams &p, dim3 g, dim3 b, size_t shm,
   }
 }
 
+// range-safe chains.  The two scaled gradient kernels: the plain block with the scaled form's LDS, and the
+// exponent stack [N][b_pad] ints beside the stack of pass A.
+static void check_scaled_lds(const char *kernel, size_t shm, int mb, int D, int L, int N) {
+  const size_t want = grad_chain_lds_bytes(mb, D, L, N, true);
+  if (shm < want) die("%s: %zu bytes of LDS, %zu wanted (bond %d, D %d, L %d)", kernel, shm, want, mb, D, L);
+}
+static void check_input_grad_scaled(const InputGradScaledParams &ps, dim3 g, dim3 b, size_t shm) {
+  scan(&ps, sizeof ps, "InputGradScaledParams");
+  check_input_grad(ps.base, g, b, shm);
+  check_scaled_lds("input_grad_scaled_kernel", shm, ps.base.mb, ps.base.D, ps.base.L, ps.base.N);
+  need(ps.estack, (size_t)ps.base.N * ps.base.b_pad * 4, "InputGradScaledParams.estack");
+}
+static void check_core_grad_scaled(const CoreGradScaledParams &ps, dim3 g, dim3 b, size_t shm) {
+  scan(&ps, sizeof ps, "CoreGradScaledParams");
+  check_core_grad(ps.base, g, b, shm, false);
+  check_scaled_lds("core_grad_chain_scaled_kernel", shm, ps.base.mb, ps.base.D, ps.base.L, ps.base.N);
+  need(ps.estack, (size_t)ps.base.N * ps.base.b_pad * 4, "CoreGradScaledParams.estack");
+}
+// scaled_pred_kernel (kernels_scaled.hip): whole tiles of 64 samples of X, mant, expo and f; every core through the bond table
+static void check_scaled_pred(const ScaledPredParams &p, dim3 g, dim3 b, size_t shm) {
+  scan(&p, sizeof p, "ScaledPredParams");
+  if (p.b < 1 || p.b > p.b_pad || p.b_pad % 64) die("ScaledPredParams: b %d b_pad %d", p.b, p.b_pad);
+  if (p.N < 2 || p.D < 2 || p.D > kMaxD || p.L < 1 || p.l_pos < 0 || p.l_pos >= p.N || p.mb < 1) die("ScaledPredParams: N %d D %d L %d l_pos %d mb %d", p.N, p.D, p.L, p.l_pos, p.mb);
+  if (b.x != 256 || g.x != (unsigned)((p.b + 63) / 64) || g.y != 1 || g.z != 1) die("scaled_pred_kernel: grid %u block %u for b %d", g.x, b.x, p.b);
+  check_scaled_lds("scaled_pred_kernel", shm, p.mb, p.D, p.L, p.N);
+  const size_t bp = p.b_pad;
+  need(p.bond, (size_t)(p.N - 1) * 4, "ScaledPredParams.bond");
+  need(p.X, (size_t)p.N * bp * p.D * 4, "ScaledPredParams.X");
+  need(p.mant, (size_t)p.L * bp * 4, "ScaledPredParams.mant");
+  need(p.expo, bp * 4, "ScaledPredParams.expo");
+  need(p.f, (size_t)p.L * bp * 4, "ScaledPredParams.f");
+  for (int i = 0; i < p.N; ++i) {
+    const int ml = i == 0 ? 1 : p.bond[i - 1], mr = i == p.N - 1 ? 1 : p.bond[i];
+    if (ml < 1 || ml > p.mb || mr < 1 || mr > p.mb) die("ScaledPredParams: site %d is %d x %d, largest bond %d", i, ml, mr, p.mb);
+    if (i == p.l_pos) need(p.labcore, (size_t)ml * p.D * mr * p.L * 4, "ScaledPredParams.labcore");
+    else need(p.cores + (size_t)i * p.core_stride, (size_t)ml * p.D * mr * 4, "ScaledPredParams.cores");
+  }
+}
+
 // orthogonal form / compression / bond spectra (kernels_orth.hip): one parameter block for the load, chain and store kernels.  The
 // operation list is walked the way the chain kernel walks it: every decomposition hands its carried factor to the neighbouring site,
 // which the next operation must name; the list ends with the centre on the label site.  Every slot of the context, of the float64
@@ -438,6 +477,9 @@ static void tr_struct(const CoreGradParams &p) {
   P(tab) P(cores) P(labcore) P(X) P(cot) P(stackP) P(stackQ) P(G) P(cf) I(core_stride) I(b) I(b_pad) I(x_bpad) I(N) I(D) I(L) I(l_pos) I(cap)
   I(mb) I(first)
 }
+static void tr_struct(const InputGradScaledParams &p) { tr_struct(p.base); P(estack) }
+static void tr_struct(const CoreGradScaledParams &p) { tr_struct(p.base); P(estack) }
+static void tr_struct(const ScaledPredParams &p) { P(bond) P(cores) P(labcore) P(X) P(mant) P(expo) P(f) I(core_stride) I(b) I(b_pad) I(N) I(D) I(L) I(l_pos) I(mb) }
 static void tr_struct(const LossCotParams &p) { P(f) P(y) P(cot) I(L) I(b) I(b_pad) I(f_bpad) I(act_fn) I(loss_fn) R(T) }
 static void tr_struct(const OptimStepParams &p) {
   P(tab) P(cores) P(labcore) P(G) P(s0) P(s1) I(core_stride) I(N) I(D) I(L) I(l_pos) I(kind) I(clip) R(lr) R(wd) R(mu) R(beta1) R(beta2) R(eps)
@@ -474,6 +516,9 @@ static void tr_launch(const std::string &name, dim3 g, dim3 b, size_t shm, hipSt
     else if (is("WideParams")) tr_struct(*(const WideParams *)args[i]);
     else if (is("PrepParams")) tr_struct(*(const PrepParams *)args[i]);
     else if (is("MeetParams")) tr_struct(*(const MeetParams *)args[i]);
+    else if (is("InputGradScaledParams")) tr_struct(*(const InputGradScaledParams *)args[i]);
+    else if (is("CoreGradScaledParams")) tr_struct(*(const CoreGradScaledParams *)args[i]);
+    else if (is("ScaledPredParams")) tr_struct(*(const ScaledPredParams *)args[i]);
     else if (is("InputGradParams")) tr_struct(*(const InputGradParams *)args[i]);
     else if (is("CoreGradParams")) tr_struct(*(const CoreGradParams *)args[i]);
     else if (is("InputGradPixels")) tr_struct(*(const InputGradPixels *)args[i]);
@@ -545,6 +590,12 @@ hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t s
     if (g.x > 256) die("step_pipe_kernel: %u workgroups cannot be co-resident on 256 CUs", g.x);
   } else if (has("label_meet_kernel")) {
     check_meet(*(const MeetParams *)args[0], g, b, shm);
+  } else if (has("input_grad_scaled_kernel")) {
+    check_input_grad_scaled(*(const InputGradScaledParams *)args[0], g, b, shm);
+  } else if (has("core_grad_chain_scaled_kernel")) {
+    check_core_grad_scaled(*(const CoreGradScaledParams *)args[0], g, b, shm);
+  } else if (has("scaled_pred_kernel")) {
+    check_scaled_pred(*(const ScaledPredParams *)args[0], g, b, shm);
   } else if (has("input_grad_kernel")) {
     check_input_grad(*(const InputGradParams *)args[0], g, b, shm);
   } else if (has("core_grad_chain_kernel") || has("core_grad_reduce_kernel")) {

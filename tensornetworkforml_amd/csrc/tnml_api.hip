@@ -93,7 +93,7 @@ struct ZTicket {
 // undersized member, because every reader goes through that capacity field or one of those flags.
 struct Owner {
   enum Kind { kDev, kPinned, kEvent, kStream };
-  struct Member { void **slot; size_t arg; Kind kind; };       // arg: bytes (memory) or creation flags (event)
+  struct Member { void **slot; size_t arg; Kind kind; bool wanted = true; };   // arg: bytes (memory) or creation flags (event); !wanted: released, not created
   std::vector<std::pair<void *, Kind>> held;                   // by value: the slots may be locals or move (sweep_ev)
 
   Owner() = default;
@@ -118,6 +118,7 @@ struct Owner {
   hipError_t make(std::initializer_list<Member> group) {
     for (const Member &m : group) release(*m.slot);
     for (const Member &m : group) {
+      if (!m.wanted) continue;
       void *h = nullptr;
       hipError_t e = hipSuccess;
       switch (m.kind) {
@@ -137,6 +138,7 @@ struct Owner {
   }
 };
 template <class T> static Owner::Member own_dev(T *&p, size_t count) { return {(void **)&p, count * sizeof(T), Owner::kDev}; }
+template <class T> static Owner::Member own_dev_if(bool wanted, T *&p, size_t count) { return {(void **)&p, count * sizeof(T), Owner::kDev, wanted}; }
 template <class T> static Owner::Member own_pinned(T *&p, size_t count) { return {(void **)&p, count * sizeof(T), Owner::kPinned}; }
 static Owner::Member own_event(hipEvent_t &e, unsigned flags) { return {(void **)&e, flags, Owner::kEvent}; }
 static Owner::Member own_stream(hipStream_t &s) { return {(void **)&s, 0, Owner::kStream}; }
@@ -260,6 +262,12 @@ struct tnml_ctx {
   int num_cus = 256;
   float *Xpred_stage = nullptr, *Xpred = nullptr, *fpred = nullptr;   // tnml_predict's own batch (the resident one is untouched)
   int pred_cap = 0;
+  // range-safe chains (tnml_set_chain_scaling).  Members of the prediction group once a scaled prediction has
+  // been asked for: mantissas [L][pred_cap], exponents [pred_cap], the bond table [N] of scaled_pred_kernel.  The exponent stacks
+  // [N][cap] of pass A are members of the two gradient groups while the switch is on.
+  bool scaled = false;
+  float *pred_mant = nullptr;
+  int *pred_expo = nullptr, *pred_bond = nullptr, *ig_estack = nullptr, *cg_estack = nullptr;
   int slab_stride = 0, nblk_cap = 0, metrics_cap = 0;
   double *dbg = nullptr;
   size_t dbg_elems = 0;
@@ -918,14 +926,17 @@ extern "C" int tnml_forward(tnml_ctx *c, float *f_out) {
 // Prediction group, grown to bp samples: tnml_predict's own batch -- Xpred_stage [b][N][D] as uploaded, Xpred [N][pred_cap][D],
 // fpred [L][pred_cap] -- with the two environments next to an intermediate label site (predEnv) and the labels of the chunk
 // tnml_eval_indices is evaluating (ds_ypred)
-static int pred_ensure_buffers(tnml_ctx *c, int bp) {
-  if (bp <= c->pred_cap) return TNML_OK;
+static int pred_ensure_buffers(tnml_ctx *c, int bp, bool scaled_out = false) {
+  const bool sc = c->scaled || scaled_out || c->pred_mant;     // (once there, the scaled members stay members)
+  if (bp <= c->pred_cap && (!sc || c->pred_mant)) return TNML_OK;
+  bp = std::max(bp, c->pred_cap);                              // (the gradient groups were sized against this capacity)
   const int N = c->N, D = c->D, L = c->L;
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->pred_cap = 0;
   int rc = make_group(c, "the prediction buffers", {
       own_dev(c->Xpred_stage, (size_t)bp * N * D), own_dev(c->Xpred, (size_t)bp * N * D), own_dev(c->fpred, (size_t)bp * L),
-      own_dev(c->predEnv, (size_t)2 * c->Mmax * bp), own_dev(c->ds_ypred, (size_t)bp)});
+      own_dev(c->predEnv, (size_t)2 * c->Mmax * bp), own_dev(c->ds_ypred, (size_t)bp),
+      own_dev_if(sc, c->pred_mant, (size_t)bp * L), own_dev_if(sc, c->pred_expo, (size_t)bp), own_dev_if(sc, c->pred_bond, (size_t)N)});
   if (rc) return rc;
   // on the context's stream: a memset on the null stream is not ordered against this (non-blocking) stream and could land behind
   // the re-tiling kernel that follows
@@ -934,19 +945,48 @@ static int pred_ensure_buffers(tnml_ctx *c, int bp) {
   return TNML_OK;
 }
 
-// may a prediction run at this label position?
+// scaled_pred_kernel stages a whole core and three tiles of the largest bond in LDS, as the two-pass gradient chain does
+static int scaled_pred_fits(const tnml_ctx *c) {
+  const int mb = *std::max_element(c->bond.begin(), c->bond.end());
+  const size_t lds = scaled_pred_lds_bytes(mb, c->D, c->L, c->N);
+  if (lds > kLdsMax) return fail(TNML_ERR_ARG, "scaled prediction at D = %d, bond %d, L = %d: %zu bytes of LDS exceed 160 KB", c->D, mb, c->L, lds);
+  return TNML_OK;
+}
+
+// may a prediction run at this label position (and, with scaled chains, at these bonds)?
 static int pred_allowed(tnml_ctx *c) {
   if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
   if (label_inside(c) && !c->any_pos)
     return fail(TNML_ERR_STATE, "forward should not be called if l has an intermediate position (l_pos = %d)", c->l_pos);
-  return TNML_OK;
+  return c->scaled ? scaled_pred_fits(c) : TNML_OK;
 }
 
 // the chain table of a prediction: towards the label site, or the two half-chains
-static int pred_table(tnml_ctx *c) { return label_inside(c) ? upload_half_tables(c, false) : upload_chain_table(c); }
+// (scaled chains: the bond table of scaled_pred_kernel; c->bond is not written while a call is in flight)
+static int pred_table(tnml_ctx *c, bool scaled = false) {
+  if (c->scaled || scaled) {
+    HIP_TRY(hipMemcpyAsync(c->pred_bond, c->bond.data(), (size_t)(c->N - 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    return TNML_OK;
+  }
+  return label_inside(c) ? upload_half_tables(c, false) : upload_chain_table(c);
+}
+
+// scaled chains: both half-chains and the label site in one kernel over Xpred -> pred_mant, pred_expo, fpred
+static int pred_chain_scaled(tnml_ctx *c, int b) {
+  if (int rc = scaled_pred_fits(c)) return rc;
+  const int mb = *std::max_element(c->bond.begin(), c->bond.end());
+  ScaledPredParams p{};
+  p.bond = c->pred_bond; p.cores = c->cores; p.labcore = c->lab[c->lab_cur]; p.X = c->Xpred;
+  p.mant = c->pred_mant; p.expo = c->pred_expo; p.f = c->fpred; p.core_stride = c->core_stride;
+  p.b = b; p.b_pad = c->pred_cap; p.N = c->N; p.D = c->D; p.L = c->L; p.l_pos = c->l_pos; p.mb = mb;
+  if (!launch_scaled_pred(p, c->stream)) return fail(TNML_ERR_ARG, "internal: scaled prediction launch refused (b %d, b_pad %d)", b, c->pred_cap);
+  HIP_TRY(hipGetLastError());
+  return TNML_OK;
+}
 
 // one chain towards the label site over Xpred -> fpred, no environment stored (the chain table must be uploaded)
 static int pred_chain(tnml_ctx *c, int b) {
+  if (c->scaled) return pred_chain_scaled(c, b);
   const int N = c->N, D = c->D, L = c->L, bpad = c->pred_cap;
   if (label_inside(c)) {
     float *EL = c->predEnv, *ER = c->predEnv + (size_t)c->Mmax * c->pred_cap;
@@ -1000,6 +1040,32 @@ extern "C" int tnml_predict(tnml_ctx *c, const float *X, int b, float *f_out) {
   HIP_TRY(hipMemcpy2DAsync(f_out, (size_t)b * sizeof(float), c->fpred, (size_t)c->pred_cap * sizeof(float), (size_t)b * sizeof(float),
                            c->L, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return TNML_OK;
+}
+
+extern "C" int tnml_predict_scaled(tnml_ctx *c, const float *X, int b, float *mant_out, int32_t *expo_out) {
+  if (!c || !X || !mant_out || !expo_out) return fail(TNML_ERR_ARG, "NULL argument");
+  if (b < 1) return fail(TNML_ERR_ARG, "empty batch");
+  int rc = pred_allowed(c);
+  if (!rc) rc = scaled_pred_fits(c);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  rc = pred_ensure_buffers(c, (b + 63) / 64 * 64, true);
+  if (rc) return rc;
+  if ((rc = load_chunk(c, X, nullptr, nullptr, 0, b, nullptr))) return rc;
+  if ((rc = pred_table(c, true))) return rc;
+  if ((rc = pred_chain_scaled(c, b))) return rc;
+  HIP_TRY(hipMemcpy2DAsync(mant_out, (size_t)b * sizeof(float), c->pred_mant, (size_t)c->pred_cap * sizeof(float), (size_t)b * sizeof(float),
+                           c->L, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(expo_out, c->pred_expo, (size_t)b * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return TNML_OK;
+}
+
+extern "C" int tnml_set_chain_scaling(tnml_ctx *c, int on) {
+  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
+  if (on != 0 && on != 1) return fail(TNML_ERR_ARG, "chain scaling %d is neither 0 nor 1", on);
+  c->scaled = on != 0;
   return TNML_OK;
 }
 
@@ -1318,7 +1384,7 @@ static int largest_bond(const tnml_ctx *c) {
 
 // the two-pass chain kernel stages a whole core and three tiles of the largest bond in LDS; `what` names the call in the refusal
 static int grad_chain_fits(const tnml_ctx *c, const char *what, int mb) {
-  const size_t lds = grad_chain_lds_bytes(mb, c->D, c->L, c->N);
+  const size_t lds = grad_chain_lds_bytes(mb, c->D, c->L, c->N, c->scaled);
   if (lds > kLdsMax) return fail(TNML_ERR_ARG, "%s at D = %d, bond %d, L = %d: %zu bytes of LDS exceed 160 KB", what, c->D, mb, c->L, lds);
   return TNML_OK;
 }
@@ -1341,13 +1407,15 @@ static int chunk_cotangent(tnml_ctx *c, const float *cot, int off, int b, int bc
 // Input-gradient group, grown to bp samples (a multiple of 64): everything the call sizes from its chunk, and the bond table.  The
 // chunk's site-major X, its staging buffer and (cot == NULL) its f are the prediction group's.
 static int ig_ensure_buffers(tnml_ctx *c, int bp) {
-  if (bp <= c->ig_cap) return TNML_OK;
+  if (bp <= c->ig_cap && (!c->scaled || c->ig_estack)) return TNML_OK;
+  bp = std::max(bp, c->ig_cap);
   const size_t N = c->N, D = c->D, L = c->L;
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->ig_cap = 0;
   int rc = make_group(c, "the input-gradient buffers", {
       own_dev(c->ig_stack, N * c->Mmax * bp), own_dev(c->ig_cot, L * bp), own_dev(c->ig_g, (size_t)bp * N * D),
-      own_dev(c->ig_gpix, (size_t)bp * N), own_dev(c->ig_cf, (size_t)bp), own_dev(c->ig_bond, N)});
+      own_dev(c->ig_gpix, (size_t)bp * N), own_dev(c->ig_cf, (size_t)bp), own_dev(c->ig_bond, N),
+      own_dev_if(c->scaled || c->ig_estack, c->ig_estack, N * bp)});
   if (rc) return rc;
   HIP_TRY(hipMemsetAsync(c->ig_cot, 0, L * bp * sizeof(float), c->stream));     // the columns behind a chunk's samples stay finite
   c->ig_cap = bp;
@@ -1378,6 +1446,10 @@ static int input_grad_impl(tnml_ctx *c, const float *X, const int32_t *idx, int 
     p.bond = c->ig_bond; p.cores = c->cores; p.labcore = c->lab[c->lab_cur]; p.X = c->Xpred; p.cot = c->ig_cot;
     p.stack = c->ig_stack; p.g = c->ig_g; p.cf = c->ig_cf; p.core_stride = c->core_stride;
     p.b = bc; p.b_pad = bp; p.x_bpad = xbp; p.N = N; p.D = D; p.L = L; p.l_pos = c->l_pos; p.cap = c->Mmax; p.mb = mb;
+    if (c->scaled) {
+      const InputGradScaledParams ps{p, c->ig_estack};
+      if (!launch_input_grad_scaled(ps, c->stream)) return fail(TNML_ERR_ARG, "internal: scaled input-gradient launch refused (b %d, b_pad %d)", bc, bp);
+    } else
     if (!launch_input_grad(p, c->stream)) return fail(TNML_ERR_ARG, "internal: input-gradient launch refused (b %d, b_pad %d)", bc, bp);
     HIP_TRY(hipGetLastError());
     if (pixels) {
@@ -1444,13 +1516,15 @@ static int grad_table(const tnml_ctx *c, const char *what, std::vector<int> &tab
 // so that a failed growth leaves nothing behind.  The chunk's site-major X, its staging buffer and (cot == NULL) its f are the
 // prediction group's.
 static int cg_ensure_buffers(tnml_ctx *c, int bp) {
-  if (bp <= c->cg_cap) return TNML_OK;
+  if (bp <= c->cg_cap && (!c->scaled || c->cg_estack)) return TNML_OK;
+  bp = std::max(bp, c->cg_cap);
   const size_t N = c->N, L = c->L;
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->cg_cap = 0;
   int rc = make_group(c, "the core-gradient buffers", {
       own_dev(c->cg_stackP, N * c->Mmax * bp), own_dev(c->cg_stackQ, N * c->Mmax * bp), own_dev(c->cg_cot, L * bp),
-      own_dev(c->cg_cf, (size_t)bp), own_dev(c->cg_tab, 2 * N), own_dev(c->cg_G, N * c->core_stride + c->lab_elems)});
+      own_dev(c->cg_cf, (size_t)bp), own_dev(c->cg_tab, 2 * N), own_dev(c->cg_G, N * c->core_stride + c->lab_elems),
+      own_dev_if(c->scaled || c->cg_estack, c->cg_estack, N * bp)});
   if (rc) return rc;
   HIP_TRY(hipMemsetAsync(c->cg_cot, 0, L * bp * sizeof(float), c->stream));     // the columns behind a chunk's samples stay finite
   c->cg_cap = bp;
@@ -1466,6 +1540,10 @@ static int run_core_grad_chunk(tnml_ctx *c, int bc, bool first, int mb) {
   p.stackP = c->cg_stackP; p.stackQ = c->cg_stackQ; p.G = c->cg_G; p.cf = c->cg_cf; p.core_stride = c->core_stride;
   p.b = bc; p.b_pad = bp; p.x_bpad = c->pred_cap; p.N = c->N; p.D = c->D; p.L = c->L; p.l_pos = c->l_pos; p.cap = c->Mmax; p.mb = mb;
   p.first = first;
+  if (c->scaled) {
+    const CoreGradScaledParams ps{p, c->cg_estack};
+    if (!launch_core_grad_chain_scaled(ps, c->stream)) return fail(TNML_ERR_ARG, "internal: scaled core-gradient chain launch refused (b %d, b_pad %d)", bc, bp);
+  } else
   if (!launch_core_grad_chain(p, c->stream)) return fail(TNML_ERR_ARG, "internal: core-gradient chain launch refused (b %d, b_pad %d)", bc, bp);
   HIP_TRY(hipGetLastError());
   if (!launch_core_grad_reduce(p, c->stream)) return fail(TNML_ERR_ARG, "internal: core-gradient reduction launch refused (b %d, b_pad %d)", bc, bp);

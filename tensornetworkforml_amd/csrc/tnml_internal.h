@@ -332,6 +332,37 @@ int core_grad_reduce_blocks(int mb, int D);
 bool launch_core_grad_chain(const CoreGradParams &p, hipStream_t st);
 bool launch_core_grad_reduce(const CoreGradParams &p, hipStream_t st);
 
+// Range-safe chains: the gradient kernels with a power-of-two exponent per sample carried along both passes.
+// The blocks wrap the plain ones, whose fields and order stay what the stand-in runtime and the traces read.
+struct InputGradScaledParams {
+  InputGradParams base;
+  int *estack;             // [N][b_pad]: row i receives the exponent of P_i in base.stack, i = 1 .. N-1
+};
+struct CoreGradScaledParams {
+  CoreGradParams base;     // stackQ receives ldexpf(Q_i, eP_i + eQ_i): the reduction kernel runs on it as it is
+  int *estack;             // [N][b_pad]: row i receives the exponent of P_i in base.stackP, i = 1 .. N-1
+};
+bool launch_input_grad_scaled(const InputGradScaledParams &p, hipStream_t st);
+bool launch_core_grad_chain_scaled(const CoreGradScaledParams &p, hipStream_t st);
+// Prediction with per-sample exponents (kernels_scaled.hip): both half-chains towards the label site and the label site itself in
+// one kernel, 64 samples per workgroup, no environment stored.  f[l][s] = mant[l][s] 2^expo[s], 0.5 <= max_l |mant[l][s]| < 1
+// (expo = 0 and the plain values where every f[:, s] is 0 or one is not finite); f receives ldexpf(mant, expo).
+struct ScaledPredParams {
+  const int *bond;         // [N-1] bond dimensions of the chain
+  const float *cores;      // plain cores, core i at i * core_stride, [ml][D][mr]
+  const float *labcore;    // [ml][D][mr][L] of site l_pos
+  const float *X;          // [N][b_pad][D]; samples b .. b_pad-1 are zero
+  float *mant;             // [L][b_pad]
+  int *expo;               // [b_pad]
+  float *f;                // [L][b_pad]
+  size_t core_stride;
+  int b, b_pad, N, D, L, l_pos;
+  int mb;                  // largest bond of the chain: what the LDS tiles are sized for
+};
+size_t scaled_pred_lds_bytes(int mb, int D, int L, int N);
+// false: refused (geometry / LDS)
+bool launch_scaled_pred(const ScaledPredParams &p, hipStream_t st);
+
 // Gradient training (kernels_optim.hip): the loss derivative of a chunk as the cotangent of the core gradients, and one optimiser
 // step over all cores.
 struct LossCotParams {

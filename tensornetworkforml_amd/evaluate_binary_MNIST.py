@@ -34,11 +34,14 @@ def main(argv=None):
     ap.add_argument('--saliency', metavar='OUT.npy', default=None, help='write d f[predicted class] / d pixel of every test digit, (n, h, w)')
     ap.add_argument('--spectra', metavar='OUT.npy', default=None,
                     help='write the normalised Schmidt spectrum of every bond, (N - 1, largest rank), zero-padded (Network.bond_spectra)')
+    ap.add_argument('--scaled-chains', dest='scaled_chains', action='store_true',
+                    help='carry a power-of-two exponent per sample along the chains (Network.scaled_chains): for a model whose partial products leave float32')
     args = ap.parse_args(argv)
 
     with open(args.filename, 'rb') as fh:
         net = pickle.load(fh)
     net.any_position = True        # a model saved mid-sweep carries its label inside the chain
+    net.scaled_chains = args.scaled_chains
     _, _, data, labels = gen.get_MNIST_dataset(args.data_dir)
     while data[0].size > net.N and min(data.shape[1:]) >= 2:
         data = pooling(data)

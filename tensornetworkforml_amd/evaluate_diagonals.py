@@ -39,11 +39,14 @@ def main(argv=None):
     ap.add_argument('--features', action='store_true', help='upload host-embedded features instead of pixels')
     ap.add_argument('--spectra', metavar='OUT.npy', default=None,
                     help='write the normalised Schmidt spectrum of every bond, (N - 1, largest rank), zero-padded (Network.bond_spectra)')
+    ap.add_argument('--scaled-chains', dest='scaled_chains', action='store_true',
+                    help='carry a power-of-two exponent per sample along the chains (Network.scaled_chains): for a model whose partial products leave float32')
     args = ap.parse_args(argv)
 
     with open(args.filename, 'rb') as fh:
         net = pickle.load(fh)
     net.any_position = True        # a model saved mid-sweep carries its label inside the chain
+    net.scaled_chains = args.scaled_chains
     linear_dim = int(round(np.sqrt(net.N)))
     if linear_dim * linear_dim != net.N:
         raise SystemExit('the network has N = %d sites, which is not a square image' % net.N)

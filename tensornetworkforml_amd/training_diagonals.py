@@ -41,12 +41,16 @@ def main(argv=None):
                     help='gradient descent over all cores at fixed bonds instead of sweeps (Network.train_gradient; needs --resident)')
     ap.add_argument('--compress', type=int, default=None, metavar='M',
                     help='after training, cut every bond to M on its Schmidt decomposition (Network.compress; needs --resident)')
+    ap.add_argument('--scaled-chains', dest='scaled_chains', action='store_true',
+                    help='gradient training on range-safe chains (Network.scaled_chains; needs --resident --optimizer)')
     ap.add_argument('--out', type=str, default='trained_diag_model.dat')
     args = ap.parse_args(argv)
     if args.compress is not None and not args.resident:
         ap.error('--compress needs --resident')
     if args.optimizer is not None and not args.resident:
         ap.error('--optimizer needs --resident')
+    if args.scaled_chains and args.optimizer is None:
+        ap.error('--scaled-chains needs --resident --optimizer')
     if args.steps_per_batch is not None and not args.resident:
         ap.error('--steps-per-batch needs --resident')
 
@@ -65,6 +69,7 @@ def main(argv=None):
     if args.resident:
         _, train_idx, val_idx, _ = gen.prepare_device_dataset(net, data, label, 1, 0.2, train_batch, 128, 128, D=args.D)
         if args.optimizer is not None:
+            net.scaled_chains = args.scaled_chains
             val_acc, var_hist = net.train_gradient(train_idx, val_idx, lr=args.lr, n_epochs=args.n_epochs, weight_dec=args.L2_decay,
                                                    optimizer=args.optimizer)
         else:
