@@ -365,6 +365,13 @@ int tnml_set_step_pipeline(tnml_ctx *ctx, int on);
  *                     keeps them from meeting: the bounded waits then time out and tnml_sweep fails with TNML_ERR_STATE
  *   on = 0            one launch per step everywhere */
 int tnml_set_persistent(tnml_ctx *ctx, int on);
+/* The one-launch persistent sweep (tnml_set_persistent 1) is also compiled for the step shapes of its table (bond 10 and 20 at two
+ * labels, D = 2): a step whose behind, ahead, shared and kept bond all equal that bond runs a body with the shape as compile-time
+ * constants, every other step (the bond ramps at the chain ends, any other bond or label count) the generic body.  Same results, bit
+ * for bit.  on = 1 (default) / 0: mark such steps or run the generic body everywhere. */
+int tnml_set_shape_kernels(tnml_ctx *ctx, int on);
+/* *n_steps = steps of the last persistent sweep that ran a body compiled for their shape (0: none, switch off, or mode 2) */
+int tnml_fixed_shape_steps(tnml_ctx *ctx, int *n_steps);
 
 /* tnml_sweep enqueues every launch of its n_steps steps without waiting (2 - 14 launches per step).  A profiler that
  * intercepts dispatches (rocprofv3 --pmc serialises them and keeps per-dispatch state) can be overrun by tens of

@@ -39,6 +39,7 @@ SYMBOLS = [
     'tnml_optim_config', 'tnml_optim_reset', 'tnml_gd_train_indices', 'tnml_gd_step', 'tnml_get_core_slots',
     'tnml_orthogonalize', 'tnml_compress', 'tnml_bond_spectra',
     'tnml_set_chain_scaling', 'tnml_predict_scaled',
+    'tnml_set_shape_kernels', 'tnml_fixed_shape_steps',
 ]
 
 
@@ -96,6 +97,8 @@ def lib():
         L.tnml_svd_stats.argtypes = [vp, C.c_int, f64p]
         L.tnml_svd_stats_ex.argtypes = [vp, C.c_int, f64p, C.c_int]
         L.tnml_set_persistent.argtypes = [vp, C.c_int]
+        L.tnml_set_shape_kernels.argtypes = [vp, C.c_int]
+        L.tnml_fixed_shape_steps.argtypes = [vp, C.POINTER(C.c_int)]
         L.tnml_trunc_rank.argtypes = [C.c_int] * 9
         L.tnml_update_B.argtypes = [vp, f32p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float,
                                     f64p, C.c_size_t, f32p]
@@ -601,6 +604,16 @@ class Context:
     def set_persistent(self, on=True):
         """1 / True (default): a full sweep as ONE persistent launch; 2: one launch per role on three streams; 0 / False: one launch per step."""
         _chk(lib().tnml_set_persistent(self._h, int(on)))
+
+    def set_shape_kernels(self, on=True):
+        """True (default): steps of a persistent sweep whose shape is in the compiled table run the body compiled for it; False: the generic body everywhere."""
+        _chk(lib().tnml_set_shape_kernels(self._h, int(bool(on))))
+
+    def fixed_shape_steps(self):
+        """Steps of the last persistent sweep that ran a body compiled for their shape."""
+        v = C.c_int()
+        _chk(lib().tnml_fixed_shape_steps(self._h, C.byref(v)))
+        return v.value
 
     def set_sync_interval(self, n_steps):
         """Drain the stream every n_steps sweep steps (0: never); for runs under a dispatch-intercepting profiler."""

@@ -197,9 +197,24 @@ __device__ __forceinline__ RecField<T> rec_field(const T *field) { return RecFie
 // before the launch (persist_record_ok), since a field that is a constant here would be ignored silently.  z_first, z_rows, red,
 // lab, pl and Ng ARE planned (the helper and batch-side records are built from them), but under persist the update role never
 // reads them: its operands are the helpers' projections.
-struct PersistArgs {
-  // -- by value: geometry, the front of the step (one batch of scalar loads, one wait), what the Jacobi rounds read
-  int L, h, g, s, m, bsize, l2_flag;
+//
+// The geometry of the step is a type of its own, the base of PersistArgs:
+//   DynShape             the six integers of the record, by value (any step)
+//   FixedShape<H, LBL>   (wide_pipe_device.h) the same names as compile-time constants, for a step in the uniform middle of the chain
+//                        (h = g = s = m = H, L = LBL): everything narrow_body derives from them -- r, c, n, ne, np, len, RW, the LDS
+//                        carve, the wave roles of the Jacobi rounds, the tile deals and k-loops of the products -- folds, and the
+//                        six values leave the scalar registers.  sweep_persist (tnml_api.hip) marks the records a shape fits.
+struct DynShape {
+  static constexpr int id = 0;
+  int L, h, g, s, m, bsize;
+  __device__ __forceinline__ void load_shape(const __attribute__((address_space(4))) NarrowParams *r) {
+    L = r->L; h = r->h; g = r->g; s = r->s; m = r->m; bsize = r->bsize;
+  }
+};
+template <class Shape>
+struct PersistArgs : Shape {
+  // -- by value: the front of the step (one batch of scalar loads, one wait), what the Jacobi rounds read
+  int l2_flag;
   float lr, wd;
   const double *Nh;
   int persist_off, Mcap;
@@ -241,7 +256,7 @@ struct PersistArgs {
         metrics(rec_field(&rec->metrics)), counters(rec_field(&rec->counters)), status(rec_field(&rec->status)),
         aflag(rec_field(&rec->aflag)), coreflag(rec_field(&rec->coreflag)), coretoken(rec_field(&rec->coretoken)) {
     const auto *r = (const __attribute__((address_space(4))) NarrowParams *)rec;
-    L = r->L; h = r->h; g = r->g; s = r->s; m = r->m; bsize = r->bsize; l2_flag = r->l2_flag;
+    this->load_shape(r); l2_flag = r->l2_flag;
     lr = r->lr; wd = r->wd; Nh = r->Nh; persist_off = r->persist_off; Mcap = r->Mcap;
     pready = r->pready; pwant = r->pwant; abort_flag = r->abort_flag; zred = r->zred; zsize = r->zsize;
     prepRaw = r->prepRaw; prepB = r->prepB; prepG = r->prepG; Bnew = r->Bnew; flag = r->flag; token = r->token;
@@ -250,7 +265,7 @@ struct PersistArgs {
 };
 
 // returns true when a wait of a persistent sweep timed out (the caller leaves its step loop)
-// NP: StepArgs (per-step launches) or PersistArgs (persistent sweep), above
+// NP: StepArgs (per-step launches) or PersistArgs<Shape> (persistent sweep), above
 template <class NP>
 __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw) {
   // value ranges the launcher guarantees (narrow_lds_bytes / narrow_path): with them the compiler turns the index products into
@@ -633,23 +648,28 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
       while (t >= rowlen) { t -= rowlen; ++ti; --rowlen; }
       const int tj = ti + t;
       const int i0 = ti << 4, j0 = tj << 4;
-      const bool va = i0 + rr < n, vb = j0 + rr < n;
-      const float *pa = Wb + min(i0 + rr, n - 1) * rs, *pb = Wb + min(j0 + rr, n - 1) * rs;
-      const int k_lo = ks * kchunk, k_hi = min(len, k_lo + kchunk);
+      // rows / columns past n read row n - 1 (clamped): they only reach accumulator entries that are stored as the padding zero
+      // or not at all, so the operands need no select (mm_lds does the same); 24-bit multiplies: LDS element offsets
+      const float *pa = Wb + __mul24(min(i0 + rr, n - 1), rs), *pb = Wb + __mul24(min(j0 + rr, n - 1), rs);
+      // the slice as (start, length): where the long index divides evenly, the length is kchunk for every slice -- said outright, so
+      // that with a constant shape the k-loop unrolls into its MFMAs, the clamp and the k predicate of each step decided
+      const bool even_k = gsplit * kchunk == len;
+      const int k_lo = ks * kchunk, klen = even_k ? kchunk : min(len - k_lo, kchunk);
+      const float *pak = pa + __mul24(k_lo, cs), *pbk = pb + __mul24(k_lo, cs);
       dvec4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
-      for (int k0 = k_lo; k0 < k_hi; k0 += 16) {           // up to four k-steps per trip, all LDS reads issued first
+      for (int k0 = 0; k0 < klen; k0 += 16) {              // up to four k-steps per trip, all LDS reads issued first
         float fa[4], fb[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          const int kc = min(k0 + 4 * u + qq, k_hi - 1) * cs;
-          fa[u] = pa[kc];
-          fb[u] = pb[kc];
+          const int kc = __mul24(min(k0 + 4 * u + qq, klen - 1), cs);
+          fa[u] = pak[kc];
+          fb[u] = pbk[kc];
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          const bool vk = k0 + 4 * u + qq < k_hi;
-          const double av = (va && vk) ? (double)fa[u] : 0.0, bv = (vb && vk) ? (double)fb[u] : 0.0;
-          if (k0 + 4 * u < k_hi) {
+          const bool vk = k0 + 4 * u + qq < klen;
+          const double av = vk ? (double)fa[u] : 0.0, bv = vk ? (double)fb[u] : 0.0;
+          if (k0 + 4 * u < klen) {
             if (u & 1) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc1, 0, 0, 0);
             else acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc0, 0, 0, 0);
           }
@@ -657,11 +677,11 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
       }
       const dvec4 acc = acc0 + acc1;
       const int j = j0 + rr;
-      double *Pk = P0 + (size_t)ks * ne * ne;              // the four ne x ne buffers are contiguous
+      double *Pk = P0 + (size_t)ks * ne * ne + (__mul24(i0 + qq, ne) + j);      // the four ne x ne buffers are contiguous
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
         const int i = i0 + qq + 4 * reg;
-        if (i < ne && j < ne) Pk[i * ne + j] = (i < n && j < n) ? acc[reg] : 0.0;     // padding row / column = 0
+        if (i < ne && j < ne) Pk[4 * reg * ne] = (i < n && j < n) ? acc[reg] : 0.0;     // padding row / column = 0
       }
     }
     lds_barrier();
@@ -739,7 +759,8 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
 #pragma unroll
   for (int u = 0; u < MAXI; ++u) {
     const int it = gtid + u * NW;
-    itValid[u] = wrank >= NVW && gtid < NW && it < nG;
+    // (u * NW < nG: a thread's u-th item is number gtid + u * NW >= u * NW -- where the shape is a constant, a pass without items folds away)
+    itValid[u] = u * NW < nG && wrank >= NVW && gtid < NW && it < nG;
     int P = 0, Q = 0;
     if (itValid[u]) {                         // it-th pair (P <= Q) in row-major order of the upper triangle
       int rem = it;
@@ -899,7 +920,8 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
     if (r.level >= 2) k.sFlag[6 + (applied & 1)] = applied + 1;
   };
   int round_idx = 0, last_big1 = 0;          // rounds applied so far; 1 + index of the last round with a big rotation
-  auto jacobi_round = [&]() {
+  // returns true once ne - 1 consecutive rounds applied no big rotation (see the loop below)
+  auto jacobi_round = [&]() -> bool {
         const double *csc = k.dCS + cur * np * 4;
         const int big_slot = k.sFlag[6 + (round_idx & 1)];      // consumed after this round's barrier
         if (isParam) {
@@ -934,7 +956,8 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
           const float h1 = ra ? fmaf(sA, q0y, cA * q1y) : fmaf(cA, q0y, -sA * q1y);
           const float ng = rb ? fmaf(sB, h0, cB * h1) : fmaf(cB, h0, -sB * h1);
           const RotT r = jacobi_rot_f32(na, nb, ng, fmaxf((float)kept2, kept_lo), (float)abs2, (float)p.svd_stop2);
-          publish(k.dCS + ((cur ^ 1) * np + tid) * 4, r, round_idx + 1);
+          // (the other slot's offset by a scalar select: with a constant np the product became a 64-bit multiply-add on this chain)
+          publish(k.dCS + ((cur ? 0 : 4 * np) + 4 * tid), r, round_idx + 1);
         }
         if (isVwave) {                                    // whole waves: every lane runs the shifts
           const double2 tc = *reinterpret_cast<const double2 *>(csc + 4 * (vLaneOk ? vQ : 0));     // (t, c0) of pair Q
@@ -980,11 +1003,17 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
           if (!itDiag[u]) Gn[itD21[u]] = n21;                   // (n21 of a diagonal block is n12's mirror)
           Gn[itD22[u]] = n22;
         }
+        // the exit test's operand in FRONT of the barrier (the flag word arrived with this round's operands): block-uniform, and told
+        // so -- the word comes out of LDS (a vector register), and a loop exit the compiler has to treat as divergent wraps every
+        // round in EXEC-mask bookkeeping.  Behind the barrier only the branch is left on the chain.
+        last_big1 = max(last_big1, big_slot);
+        const int last_big_s = __builtin_amdgcn_readfirstlane(last_big1);
+        const bool done = round_idx + 1 - last_big_s >= ne - 1;
         lds_barrier();
         double *tsw = Gc; Gc = Gn; Gn = tsw;
         cur ^= 1;
-        last_big1 = max(last_big1, big_slot);
         ++round_idx;
+        return done;
   };
   if (n > 1) {
     kept2 = kept_scale(Gc);
@@ -1000,12 +1029,10 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
     // applied no big rotation: quadratic convergence then leaves off-diagonals of relative size ~svd_stop2, exactly the
     // guarantee of "a whole sweep without a big rotation", but the window need not start at a sweep boundary (it saves
     // about a third of a sweep per decomposition once the chain has settled).
+    // (measured: one flat loop over the rounds instead of this nest costs the generic body 60 cycles per round)
     for (; sweeps < kJacobiMaxSweeps && !converged; ++sweeps) {
       for (int rnd = 0; rnd < ne - 1; ++rnd) {
-        jacobi_round();
-        // block-uniform, and told so: the flag word comes out of LDS (a vector register), and a loop exit the compiler has
-        // to treat as divergent wraps every round in EXEC-mask bookkeeping
-        if (round_idx - __builtin_amdgcn_readfirstlane(last_big1) >= ne - 1) { converged = 1; break; }
+        if (jacobi_round()) { converged = 1; break; }
       }
       if (!converged) kept2 = kept_scale(Gc);
     }
@@ -1128,7 +1155,7 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
   // (short_rows), the first product of the next behind norm environment, T2 = Nh . Cb, needs nothing the long-side product
   // writes: the two run back to back without a barrier, their tiles dealt to the waves as one list.
   const int DM = D * mk;
-  auto store_T2 = [&](int, int i, int j, double v) { k.dT2[i * DM + j] = v; };
+  auto store_T2 = [&](int, int i, int j, double v) { k.dT2[__mul24(i, DM) + j] = v; };
   if (short_rows) {
     // long index = ahead group x = (dk1, g_, l) = qq * L + l: the label is the batch, rows are qq = (dk1, g_)
     // (persistent sweep: the next step forms its merged tensor from T_{k+1} and this step's behind core, so the new label core
@@ -1186,8 +1213,8 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
     // Nh_new[s', s''] = sum_{(h_, d)} Cb[(h_, d), s'] T2[(h_, d), s'']
     mm_lds(1, mk, mk, h * D, k.sCb, 0, 1, mk, k.dT2, 0, mk, 1,
            [&](int, int i, int j, double v) {
-             Nh_new[i * mk + j] = v;
-             if (p.persist) PL.Nh[i * mk + j] = v;
+             Nh_new[__mul24(i, mk) + j] = v;
+             if (p.persist) PL.Nh[__mul24(i, mk) + j] = v;
            });
     if (p.persist) {                      // the helpers' copy: 16-byte stores from the LDS copy, the last double padded where mk is odd
       lds_barrier();
@@ -1388,7 +1415,9 @@ __device__ __forceinline__ bool persist_helper_block(const HP &t, int hid, int n
   // after the previous step ends), A' / 1 / sigma (after the previous step's cores), Nh (the previous step's last act).  The first
   // product level needs A' and 1 / sigma only and runs beside the update workgroup's norm environment; Nh is waited for in front of
   // the third product, and only with the L2 term.
-  const int cw = (RW + nH - 1) / nH, c0 = min(RW, hid * cw), nc = min(RW, c0 + cw) - c0;
+  // (0 <= hid < nH; where the columns divide evenly, every slice is cw wide: said outright, so that a constant shape gives a constant nc)
+  const bool even_split = RW % nH == 0;
+  const int cw = (RW + nH - 1) / nH, c0 = even_split ? hid * cw : min(RW, hid * cw), nc = even_split ? cw : min(RW, c0 + cw) - c0;
   const int cw2 = 2 * cw;
   // (sA | sIv | sNh mirror the published block, persist_pub_off: 16-byte loads land where they are used)
   double *sA = (double *)smem_raw;                           // [zr][h]  A' (float64)
@@ -1442,12 +1471,12 @@ __device__ __forceinline__ bool persist_helper_block(const HP &t, int hid, int n
     // [h][cw] = Af^T Z with the core as stored, on the float32 matrix pipe (the per-step path's contraction, number for number), and
     // [h][2 cw] = A'^T (T | TN) with the unrounded core; independent, their tiles dealt as one list
     // (results into LDS staging tiles: they leave as 16-byte stores once the workgroup has met)
-    mm_lds_f32(h, nc, zr, sAff, 1, h, sZf, cw, 1, [&](int i, int j, float v) { sOut[i * cw + j] = v; });
+    mm_lds_f32(h, nc, zr, sAff, 1, h, sZf, cw, 1, [&](int i, int j, float v) { sOut[__mul24(i, cw) + j] = v; });
     const int slot = (((h + 15) >> 4) * ((nc + 15) >> 4)) & ((NT >> 6) - 1);
     mm_lds(1, h, t.l2_flag ? 2 * cw : cw, zr, sA, 0, 1, h, sS, 0, cw2, 1,
            [&](int, int i, int j, double v) {
-             if (j < cw) { if (j < nc) sOut[(h + i) * cw + j] = (float)(v * sIv[i]); }
-             else sP2[i * cw + (j - cw)] = v * sIv[i];
+             if (j < cw) { if (j < nc) sOut[__mul24(h + i, cw) + j] = (float)(v * sIv[i]); }
+             else sP2[__mul24(i, cw) + (j - cw)] = v * sIv[i];
            }, false, slot);
   }
   if (t.l2_flag) {
@@ -1478,7 +1507,7 @@ __device__ __forceinline__ bool persist_helper_block(const HP &t, int hid, int n
   if (t.l2_flag) {
     if (nc > 0) {
       // (Ln.B.Rn)[e_, c] = sum_a Nh[a, e_] P2[a, c]   (staged where T | TN were)
-      mm_lds(1, h, nc, h, sNh, 0, 1, h, sP2, 0, cw, 1, [&](int, int i, int j, double v) { sS[i * cw + j] = v; });
+      mm_lds(1, h, nc, h, sNh, 0, 1, h, sP2, 0, cw, 1, [&](int, int i, int j, double v) { sS[__mul24(i, cw) + j] = v; });
     }
     lds_barrier();
     st_sc1_rows(t.prepG, sS, h, cw, RW, c0, nc);
@@ -1491,6 +1520,18 @@ __device__ __forceinline__ bool persist_helper_block(const HP &t, int hid, int n
   return false;
 }
 
+// Shape: DynShape (every step runs the generic bodies: the kernel as it was), or an entry of kPersistShapes (wide_pipe_device.h): the
+// update role and part 2 of the helper role then have a second body compiled for that shape, taken for the records whose `shape`
+// field names it -- a scalar branch on a scalar load, the same for the whole workgroup.  Part 1 of the helpers and the batch side run
+// beside the SVD and have one body.
+template <class Shape>
+struct HelperArgs : PersistHelperParams {      // the helper's record with the geometry of Shape as constants (the names hide the base's)
+  static constexpr int zr = Shape::zr, s = Shape::s, g = Shape::g, L = Shape::L, h = Shape::h;
+  __device__ __forceinline__ explicit HelperArgs(const PersistHelperParams &q) : PersistHelperParams(q) {}
+};
+__device__ __forceinline__ int rec_shape(const PersistStep *rec) { return *(const __attribute__((address_space(4))) int *)&rec->shape; }
+
+template <class Shape>
 __global__ __launch_bounds__(kNarrowThreads) void sweep_persist_kernel(const PersistStep *__restrict__ steps_g, int n_steps, int nH) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   // the host wrote the records before the launch and nothing in the kernel writes them: constant address space -> scalar loads.
@@ -1498,8 +1539,15 @@ __global__ __launch_bounds__(kNarrowThreads) void sweep_persist_kernel(const Per
   const int blk = blockIdx.x;
   if (blk == 0) {
 #pragma nounroll
-    for (int k = 0; k < n_steps; ++k)
-      if (narrow_body(PersistArgs(&steps_g[k].n), smem_raw)) break;
+    for (int k = 0; k < n_steps; ++k) {
+      if constexpr (Shape::id != 0) {
+        if (rec_shape(&steps_g[k]) == Shape::id) {
+          if (narrow_body(PersistArgs<Shape>(&steps_g[k].n), smem_raw)) break;
+          continue;
+        }
+      }
+      if (narrow_body(PersistArgs<DynShape>(&steps_g[k].n), smem_raw)) break;
+    }
   } else if (blk <= nH) {
     // T_0; then per step: the projections of step k, and T_{k+1} once B_new(k) is there -- one call site (the body is inlined once)
 #pragma nounroll
@@ -1507,6 +1555,13 @@ __global__ __launch_bounds__(kNarrowThreads) void sweep_persist_kernel(const Per
       PersistHelperParams t;
       __builtin_memcpy(&t, &steps_g[ph >> 1].t, sizeof t);
       lds_barrier();
+      if constexpr (Shape::id != 0) {
+        // (a marked record: nH == kPersistHelpers, checked by sweep_persist)
+        if ((ph & 1) && rec_shape(&steps_g[ph >> 1]) == Shape::id) {
+          if (persist_helper_block(HelperArgs<Shape>(t), blk - 1, kPersistHelpers, smem_raw, true)) break;
+          continue;
+        }
+      }
       if (persist_helper_block(t, blk - 1, nH, smem_raw, (ph & 1) != 0)) break;
     }
   } else {
@@ -1521,8 +1576,18 @@ __global__ __launch_bounds__(kNarrowThreads) void sweep_persist_kernel(const Per
   }
 }
 
-void launch_sweep_persist(const PersistStep *steps_dev, int n_steps, int n_helpers, int grid, size_t lds_bytes, hipStream_t st) {
-  hipLaunchKernelGGL(sweep_persist_kernel, dim3(grid), dim3(kNarrowThreads), lds_bytes, st, steps_dev, n_steps, n_helpers);
+// shape: 0 or 1 + index into kPersistShapes: the instantiation whose fixed bodies the marked records of the sweep take
+template <int I>
+using TableShape = FixedShape<kPersistShapes[I].H, kPersistShapes[I].L, I + 1>;
+static_assert(kNumPersistShapes == 2, "one case below per entry of kPersistShapes");
+bool launch_sweep_persist(const PersistStep *steps_dev, int n_steps, int n_helpers, int grid, size_t lds_bytes, hipStream_t st, int shape) {
+  const dim3 gr(grid), bl(kNarrowThreads);
+  switch (shape) {
+    case 0: hipLaunchKernelGGL(sweep_persist_kernel<DynShape>, gr, bl, lds_bytes, st, steps_dev, n_steps, n_helpers); return true;
+    case 1: hipLaunchKernelGGL(sweep_persist_kernel<TableShape<0>>, gr, bl, lds_bytes, st, steps_dev, n_steps, n_helpers); return true;
+    case 2: hipLaunchKernelGGL(sweep_persist_kernel<TableShape<1>>, gr, bl, lds_bytes, st, steps_dev, n_steps, n_helpers); return true;
+  }
+  return false;               // a shape this build has no kernel for: an error, never another kernel in its place
 }
 
 // The same sweep as THREE launches, one per role, on three streams: the roles then get their own register allocation (inside one
@@ -1535,7 +1600,7 @@ __global__ __launch_bounds__(kNarrowThreads) void persist_update_kernel(const Pe
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
 #pragma nounroll
   for (int k = 0; k < n_steps; ++k)
-    if (narrow_body(PersistArgs(&steps_g[k].n), smem_raw)) break;
+    if (narrow_body(PersistArgs<DynShape>(&steps_g[k].n), smem_raw)) break;
 }
 __global__ __launch_bounds__(kNarrowThreads) void persist_helper_kernel(const PersistStep *__restrict__ steps_g, int n_steps, int nH) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];

@@ -42,6 +42,8 @@ static std::map<std::string, long> &launch_map() { static auto *m = new std::map
 #define g_kernels kernel_map()
 #define g_launches launch_map()
 static long g_checked_ptrs = 0, g_allreduces = 0;
+static const PersistStep *g_last_persist = nullptr;      // records and step count of the last persistent launch (san_stub_last_persist)
+static int g_last_persist_n = 0;
 // injected failure: the allocation call (hipMalloc / hipHostMalloc) with this number returns hipErrorOutOfMemory, once (0: none)
 static long g_alloc_calls = 0, g_fail_call = 0;
 static bool alloc_fails() {
@@ -467,7 +469,7 @@ static void tr_struct(const PersistHelperParams &p) {
   I(zr) I(s) I(g) I(L) I(h) I(l2_flag) P(W) V(lab) V(pl) P(Ng) P(T) P(TN) P(Z) P(prepRaw) P(prepB) P(prepG) P(Apub) P(flag) I(want)
   P(aflag) P(nflag) I(awant) P(zready) I(zwant) P(tcnt) P(pcnt) P(abort_flag) P(status) P(stamps)
 }
-static void tr_struct(const PersistStep &p) { tr(" n:"); tr_struct(p.n); tr(" w:"); tr_struct(p.w); tr(" t:"); tr_struct(p.t); }
+static void tr_struct(const PersistStep &p) { tr(" n:"); tr_struct(p.n); tr(" w:"); tr_struct(p.w); tr(" t:"); tr_struct(p.t); tr(" shape=%d", p.shape); }
 static void tr_struct(const PrepParams &p) { V(lab) V(pl) P(Nh) P(Ng) I(h) I(g) I(s) I(L) I(l2_flag) P(prepB) P(prepG) I(nparts) }
 static void tr_struct(const MeetParams &p) { P(Lenv) P(Renv) P(x) P(core) P(f) I(b) I(b_pad) I(ml) I(mr) I(D) I(L) I(rows_per_chunk) }
 static void tr_struct(const InputGradParams &p) {
@@ -582,6 +584,10 @@ hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t s
     need(st, (size_t)(n + 1) * sizeof(PersistStep), "persistent step records");
     for (int k = 0; k < n; ++k) { check_narrow(st[k].n); check_pipe(st[k].w); scan(&st[k].t, sizeof st[k].t, "PersistHelperParams"); }
     check_pipe(st[n].w);                 // the prologue of the batch side
+    for (int k = 0; k <= n; ++k)         // a marked record needs a kernel compiled for its shape: the launched one
+      if (st[k].shape && (st[k].shape < 1 || st[k].shape > kNumPersistShapes || k == n || !has("sweep_persist_kernel<") || has("DynShape")))
+        die("record %d carries shape %d in a launch of %s", k, st[k].shape, name.c_str());
+    g_last_persist = st; g_last_persist_n = n;
   } else if (has("step_pipe_kernel")) {
     const NarrowParams &n = *(const NarrowParams *)args[0];
     const WidePipeParams &w = *(const WidePipeParams *)args[1];
@@ -826,4 +832,6 @@ long san_stub_alloc_calls(void) { return g_alloc_calls; }
 void san_stub_fail_alloc(long nth) { g_fail_call = nth > 0 ? g_alloc_calls + nth : 0; }
 int san_stub_fail_pending(void) { return g_fail_call != 0; }
 void san_stub_poke_int(void *dev, int v) { need(dev, 4, "poke"); memcpy(dev, &v, 4); }
+// the records of the last persistent launch as the "device" holds them (n steps; record n is the batch side's prologue)
+const void *san_stub_last_persist(int *n_steps) { *n_steps = g_last_persist_n; return g_last_persist; }
 }

@@ -252,6 +252,8 @@ struct tnml_ctx {
   // persistent sweep (sweep_persist_kernel): per-step records (device + two pinned host staging buffers), second buffers of the
   // reduced pre-gradient, T_k buffers, per-step arrival counters, the flag words of the launch
   bool persist_enabled = true;               // tnml_set_persistent
+  bool shape_kernels = true;                 // tnml_set_shape_kernels: persistent sweeps may run the bodies compiled for a step shape
+  int fixed_steps = 0;                       // steps of the last persistent sweep that did (tnml_fixed_shape_steps)
   PersistStep *pst_dev = nullptr, *pst_host[2] = {nullptr, nullptr};
   hipEvent_t pst_ev[2] = {nullptr, nullptr};
   int pst_cur = 0;
@@ -2427,6 +2429,18 @@ static int sweep_persist(tnml_ctx *c, const SweepCall &sc) {
   if (lds > kLdsMax || lds_wide > kLdsMax || lds_help > kLdsMax) return give_up();
   const int persist_off = (int)((lds - pbytes) & ~(size_t)15);
   for (int k = 0; k < n_steps; ++k) st[k].n.persist_off = persist_off;
+  // ---- the steps a compiled shape fits (kPersistShapes): every constant of the shape against the update AND the helper record.  One
+  // launch has the bodies of one shape: the first one met (a chain has one uniform bond); mode 2 has the generic kernels only.
+  int shape = 0, n_fixed = 0;
+  if (c->shape_kernels && c->persist_mode < 2)
+    for (int k = 0; k < n_steps; ++k) {
+      const NarrowParams &n = st[k].n;
+      const PersistHelperParams &t = st[k].t;
+      const int id = persist_step_shape(n.h, n.g, n.s, n.m, n.L, n.z_rows, n.bsize, nH);
+      if (!id || (shape && id != shape) || n.D != kD) continue;
+      if (persist_step_shape(t.h, t.g, t.s, n.m, t.L, t.zr, n.bsize, nH) != id) continue;
+      shape = id; st[k].shape = id; ++n_fixed;
+    }
   // ---- enqueue: records, zeroed flags and counters, one launch
   HIP_TRY(hipMemcpyAsync(c->pst_dev, st, (size_t)(n_steps + 1) * sizeof(PersistStep), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipEventRecord(c->pst_ev[buf], c->stream));
@@ -2446,9 +2460,11 @@ static int sweep_persist(tnml_ctx *c, const SweepCall &sc) {
     HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_p2, 0));
     HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_p3, 0));
   } else {
-    launch_sweep_persist(c->pst_dev, n_steps, nH, 1 + nH + nwide, lds, c->stream);
+    if (!launch_sweep_persist(c->pst_dev, n_steps, nH, 1 + nH + nwide, lds, c->stream, shape))
+      return fail(TNML_ERR_STATE, "no persistent sweep kernel for step shape %d", shape);
     HIP_TRY(hipGetLastError());
   }
+  c->fixed_steps = n_fixed;
   c->cnt_steps += n_steps; c->cnt_bytes += bytes; c->cnt_flops += flops;
   c->sweep_launches += 1; c->step_launches += n_steps; c->persist_sweeps += 1;
   c->Bnew_valid = true; c->f_current = true; drop_pregradients(c);
@@ -3184,6 +3200,18 @@ extern "C" int tnml_set_step_pipeline(tnml_ctx *c, int on) {
   c->bigpipe.enabled = on != 0;
   c->pipe.tiles = on >= 2 ? on : (on == 1 ? 2 : 1);
   drop_pregradients(c);
+  return TNML_OK;
+}
+
+extern "C" int tnml_set_shape_kernels(tnml_ctx *c, int on) {
+  if (!c) return TNML_ERR_ARG;
+  c->shape_kernels = on != 0;
+  return TNML_OK;
+}
+
+extern "C" int tnml_fixed_shape_steps(tnml_ctx *c, int *n_steps) {
+  if (!c || !n_steps) return TNML_ERR_ARG;
+  *n_steps = c->fixed_steps;
   return TNML_OK;
 }
 

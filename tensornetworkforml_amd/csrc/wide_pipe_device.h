@@ -188,8 +188,39 @@ struct PersistHelperParams {
   int *status;
   double *stamps;            // diagnostics (helper 0 of the stamped step): 100 MHz real-time stamps of part 2
 };
-struct PersistStep { NarrowParams n; WidePipeParams w; PersistHelperParams t; };
+// shape: 0, or 1 + index into kPersistShapes of the shape whose compiled bodies run this step (behind the three role records, whose
+// layout stays what it was)
+struct PersistStep { NarrowParams n; WidePipeParams w; PersistHelperParams t; int shape; int pad_; };
 constexpr int kPersistHelpers = 8;
+// The step shapes sweep_persist_kernel is also compiled for: behind = ahead = shared = kept bond H, L labels -- the uniform middle
+// of a chain at bond H.  The one table: launch_sweep_persist (kernels_narrow.hip) has one kernel per entry, persist_step_shape below
+// marks the records.
+struct PersistShape { int H, L; };
+constexpr PersistShape kPersistShapes[] = {{10, 2}, {20, 2}};
+constexpr int kNumPersistShapes = (int)(sizeof(kPersistShapes) / sizeof(kPersistShapes[0]));
+// the constants the fixed bodies are compiled with (kernels_narrow.hip: PersistArgs<Shape>, HelperArgs<Shape>); zr = z_rows of the record
+template <int H, int LBL, int ID>
+struct FixedShape {
+  static constexpr int id = ID;
+  static constexpr int h = H, g = H, s = H, m = H, L = LBL, bsize = H * kD * kD * H * LBL, zr = kD * H, nH = kPersistHelpers;
+  static_assert(H >= 1 && H <= 64 && kD * H <= 64 && ((kD * H) & 1) == 0 && bsize <= 8192, "beyond the in-LDS persistent step");
+  template <class R> __device__ __forceinline__ void load_shape(const R *) {}
+  // every constant above against the numbers of a planned step
+  static constexpr bool fits(int h_, int g_, int s_, int m_, int L_, int z_rows_, int bsize_, int nH_) {
+    return h_ == h && g_ == g && s_ == s && m_ == m && L_ == L && z_rows_ == zr && bsize_ == bsize && nH_ == nH;
+  }
+};
+// 1 + index of the table entry whose constants ALL equal the step's numbers, or 0: a step that differs in one of them runs the generic
+// body (a constant that disagreed with its record would be used silently)
+template <int I = 0>
+constexpr int persist_step_shape(int h, int g, int s, int m, int L, int z_rows, int bsize, int nH) {
+  if constexpr (I < kNumPersistShapes) {
+    return FixedShape<kPersistShapes[I].H, kPersistShapes[I].L, I + 1>::fits(h, g, s, m, L, z_rows, bsize, nH)
+               ? I + 1 : persist_step_shape<I + 1>(h, g, s, m, L, z_rows, bsize, nH);
+  } else {
+    return 0;
+  }
+}
 // The block the update workgroup publishes for the helpers (Apub), in doubles: A' [na] at 0, 1 / sigma [h] at na rounded up to even,
 // Nh [h][h] at the returned offset; each part starts on a 16-byte boundary and is padded to an even count (16-byte transport).
 __host__ __device__ inline int persist_pub_off(int na, int h) { return ((na + 1) & ~1) + ((h + 1) & ~1); }
@@ -209,7 +240,8 @@ inline size_t persist_helper_lds_bytes(int zr, int s, int g, int L, int h, int n
   return (p1 > p2 ? p1 : p2) + 64;
 }
 // steps_dev: n_steps + 1 records, the last one carrying the prologue of the batch side in its `w`
-void launch_sweep_persist(const PersistStep *steps_dev, int n_steps, int n_helpers, int grid, size_t lds_bytes, hipStream_t st);
+// shape: 0 (generic bodies only) or the value the marked records carry; false: no kernel for it
+bool launch_sweep_persist(const PersistStep *steps_dev, int n_steps, int n_helpers, int grid, size_t lds_bytes, hipStream_t st, int shape);
 // one launch per role on three streams (kernels_narrow.hip)
 void launch_sweep_persist_split(const PersistStep *steps_dev, int n_steps, int n_helpers, int n_wide, size_t lds_update, size_t lds_helper,
                                 size_t lds_wide, hipStream_t st_update, hipStream_t st_helper, hipStream_t st_wide);

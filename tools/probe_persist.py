@@ -12,6 +12,8 @@ hp = (1e-3, 1e-3, True, 'softmax', 'full_cross_ent', 0.1, 'fixed')
 for persistent in (True, False):
     ctx = _hip.Context(N, D, L, M, b)
     ctx.set_persistent(persistent)
+    if hasattr(ctx, 'set_shape_kernels'):
+        ctx.set_shape_kernels(os.environ.get('SHAPE', '1') != '0')      # SHAPE=0: the generic bodies everywhere
     batches = [bench.synth(N, b, L, 1234 + 97 * k) for k in range(4)]
     for k, (X, y) in enumerate(batches):
         ctx.stage_batch(k, X, y)
