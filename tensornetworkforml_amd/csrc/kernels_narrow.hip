@@ -325,9 +325,11 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
   const bool fast0 = p.pipe && !p.persist && (size_t)p.z_rows * RWz + (size_t)p.z_rows * h <= (size_t)((float *)k.sOrd - k.fBp) &&
                      Bs <= 8 * NT && p.z_rows * RWz <= 16 * NT && p.z_rows * h <= 4 * NT && h * h <= 2 * NT && g * g <= 2 * NT;
   // ---- persistent sweep: merged tensor, L2 term and raw gradient of this step are projections with the previous step's behind core,
-  //   B_k = diag(1 / sigma) A'^T . T_k,   (Ln.B.Rn)_k = Nh^T . diag(1 / sigma) A'^T . (T_k . Ng),   dB_raw_k = A'^T . Z_k,
+  //   B_k = diag(1 / sigma) A'^T . T_k,   P2_k = diag(1 / sigma) A'^T . (T_k . Ng),   dB_raw_k = A'^T . Z_k,
   // formed by the helper workgroups of the launch (persist_helper_block), each for a slice of the columns, from operands they
-  // prepared beside the previous SVD; this workgroup waits for their arrival counter and loads the three results.
+  // prepared beside the previous SVD; this workgroup waits for their arrival counter and loads the three results.  The L2 term is
+  // (Ln.B.Rn)_k = Nh^T . P2_k: Nh is this workgroup's own product of one step earlier, still in its LDS (PL.Nh), so the last factor
+  // is applied here (phases 2-3) and the helpers never wait for the end of the previous step.
   const PersistLds PL = persist_lds(smem_raw + p.persist_off, p.Mcap);
   float *sRaw = k.fBp;                          // raw gradient [h][RW] (float): dead before phase 5 rewrites fBp
   if (p.persist) {
@@ -350,7 +352,8 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
 #pragma unroll
     for (int u = 0; u < 2; ++u) { const int e = 4 * (tid + u * NT); if (e < Bs) { *reinterpret_cast<tn_uvec4 *>(sRaw + e) = qr[u]; *reinterpret_cast<tn_uvec4 *>(k.fB + e) = qb[u]; } }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) { const int e = 2 * (tid + u * NT); if (p.l2_flag && e < Bs) *reinterpret_cast<tn_uvec4 *>(k.dG + e) = qg[u]; }
+    // (the prepG slot holds P2 = diag(1 / sigma) A'^T (T . Ng): its last factor, Nh^T, is applied below from this workgroup's own copy)
+    for (int u = 0; u < 4; ++u) { const int e = 2 * (tid + u * NT); if (p.l2_flag && e < Bs) *reinterpret_cast<tn_uvec4 *>(k.dT + e) = qg[u]; }
   }
   float *sZ = k.fBp, *sZc = sZ + (size_t)p.z_rows * RWz;
   if (fast0) {
@@ -516,6 +519,12 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
     // G = T . Ng over the ahead bond: rows i = (e_, dk, dk1), columns f_, the label is the batch
     mm_lds(L, Bs / (g * L), g, g, k.dT, 1, g * L, L, k.dNg, 0, g, 1,
            [&](int l, int i, int j, double v) { k.dG[(i * g + j) * L + l] = v; });
+    lds_barrier();
+  }
+  if (p.l2_flag && p.persist) {
+    // the helpers' P2 (in dT) times the behind norm environment this workgroup formed one step earlier and still holds:
+    // (Ln.B.Rn)[e_, c] = sum_a Nh[a, e_] P2[a, c] -- the call shape of the first product above
+    mm_lds(1, h, RW, h, k.dNh, 0, 1, h, k.dT, 0, RW, 1, [&](int, int i, int j, double v) { k.dG[__mul24(i, RW) + j] = v; });
     lds_barrier();
   }
   TNML_STAMP(2);
@@ -1189,7 +1198,7 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
     // and raises the token: no meeting of the workgroup, the other waves are in phase 10 meanwhile (the last wave: the norm
     // environment's few tiles are dealt from wave 0).
     if (wave_u == (NT >> 6) - 1) {
-      // (layout of the block: persist_pub_off; r * mk is even, 1 / sigma ends in a padded double where mk is odd; two doubles per
+      // (layout of the block: persist_pub_doubles; r * mk is even, 1 / sigma ends in a padded double where mk is odd; two doubles per
       // lane and store, from the LDS copies)
       const int ln = tid & 63;
       const __amdgpu_buffer_rsrc_t rP = sc1_rsrc(p.Apub);
@@ -1214,15 +1223,8 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
     mm_lds(1, mk, mk, h * D, k.sCb, 0, 1, mk, k.dT2, 0, mk, 1,
            [&](int, int i, int j, double v) {
              Nh_new[__mul24(i, mk) + j] = v;
-             if (p.persist) PL.Nh[__mul24(i, mk) + j] = v;
+             if (p.persist) PL.Nh[__mul24(i, mk) + j] = v;      // the next step's front reads it from here: nobody else needs it
            });
-    if (p.persist) {                      // the helpers' copy: 16-byte stores from the LDS copy, the last double padded where mk is odd
-      lds_barrier();
-      const __amdgpu_buffer_rsrc_t rP = sc1_rsrc(p.Apub);
-      const int oN = persist_pub_off(r * mk, mk), nn2 = mk * mk;
-      for (int e = tid; e < (nn2 + 1) >> 1; e += NT)
-        st_sc1_b128(rP, (unsigned)(oN + 2 * e) * 8u, pack_d2(PL.Nh[2 * e], 2 * e + 1 < nn2 ? PL.Nh[2 * e + 1] : 0.0));
-    }
   }
 
   if (p.stamps && tid == 0) {
@@ -1316,11 +1318,11 @@ void launch_step_pipe_update(const NarrowParams &p, const WidePipeParams &w, siz
 //         T_k[i, d, (d', g), l]  = sum_s W[i, d, s, l] A_{k+1}(s, (d', g))       W = B_new(k-1) as [(h, d_{k-1}), d_k, s, l]; the label core at k == 0
 //         TN_k[i, d, d', g', l]  = sum_g T_k[i, d, d', g, l] Ng[g, g']
 //       in float64 (exact sums of float32 products), written to memory for everybody;
-//   (2) [once the update workgroup has published A' = U sqrt(S), 1 / sigma and Nh of step k-1, every helper has finished (1) and the
+//   (2) [once the update workgroup has published A' = U sqrt(S) and 1 / sigma of step k-1, every helper has finished (1) and the
 //       pre-gradient Z_k is reduced]  its COLUMN slice of
-//         dB_raw = A'^T Z_k,   B_k = diag(1 / sigma) A'^T T_k,   (Ln.B.Rn)_k = Nh^T diag(1 / sigma) A'^T TN_k
-//       -> prepRaw / prepB / prepG, then its arrival.
-// (2) of step k is the only part on the critical path of the sweep: three 2 x 2-tile products and one more, on LDS operands.
+//         dB_raw = A'^T Z_k,   B_k = diag(1 / sigma) A'^T T_k,   P2_k = diag(1 / sigma) A'^T TN_k
+//       -> prepRaw / prepB / prepG, then its arrival.  (The L2 term is Nh^T P2_k: the update workgroup holds Nh and applies it.)
+// (2) of step k is the only part on the critical path of the sweep: three 2 x 2-tile products on LDS operands, one level.
 // Columns [c0, c0 + nc) of `rows` rows of a row-major [rows][RW] array, from an LDS tile with row stride `srs`, as agent-scope stores:
 // 16 bytes wherever a whole aligned group of the row lies inside the slice, single elements for the head and the tail of each row
 // (at most 16 / sizeof(T) - 1 each: neither the slice width nor a row's start need to sit on the 16-byte grid).
@@ -1412,25 +1414,22 @@ __device__ __forceinline__ bool persist_helper_block(const HP &t, int hid, int n
   }
   // ---------------- part 2: columns [c0, c0 + nc) of the RW columns ----------------
   // Order of the waits = order in which the operands become final: T_k / TN_k (beside the previous SVD), Z_k (shortly before or
-  // after the previous step ends), A' / 1 / sigma (after the previous step's cores), Nh (the previous step's last act).  The first
-  // product level needs A' and 1 / sigma only and runs beside the update workgroup's norm environment; Nh is waited for in front of
-  // the third product, and only with the L2 term.
+  // after the previous step ends), A' / 1 / sigma (after the previous step's cores).  The one product level needs A' and 1 / sigma
+  // only and runs beside the update workgroup's norm environment; the L2 term's last factor Nh^T is applied by the update workgroup,
+  // which holds Nh in LDS, so nothing here waits for the end of the previous step.
   // (0 <= hid < nH; where the columns divide evenly, every slice is cw wide: said outright, so that a constant shape gives a constant nc)
   const bool even_split = RW % nH == 0;
   const int cw = (RW + nH - 1) / nH, c0 = even_split ? hid * cw : min(RW, hid * cw), nc = even_split ? cw : min(RW, c0 + cw) - c0;
   const int cw2 = 2 * cw;
-  // (sA | sIv | sNh mirror the published block, persist_pub_off: 16-byte loads land where they are used)
+  // (sA | sIv mirror the published block, persist_pub_doubles: 16-byte loads land where they are used)
   double *sA = (double *)smem_raw;                           // [zr][h]  A' (float64)
   double *sIv = sA + (((size_t)zr * h + 1) & ~(size_t)1);    // [h]      1 / sigma
-  double *sNh = sIv + ((h + 1) & ~1);                        // [h][h]
-  double *sS = sNh + (((size_t)h * h + 1) & ~(size_t)1);     // [zr][2 cw]  (T | TN) columns of this slice; dead after the first product
-                                                             // level: then [h][cw] staging tile of prepG
-  float *sOut = (float *)(sS + persist_helper_ss_doubles(zr, h, cw));   // [2][h][cw] staging tiles of prepRaw and prepB
-  double *sP2 = (double *)sOut + (size_t)h * cw;             // [h][cw]  diag(1 / sigma) A'^T TN
+  double *sS = sIv + ((h + 1) & ~1);                         // [zr][2 cw]  (T | TN) columns of this slice
+  float *sOut = (float *)(sS + persist_helper_ss_doubles(zr, cw));   // [2][h][cw] staging tiles of prepRaw and prepB
+  double *sP2 = (double *)sOut + (size_t)h * cw;             // [h][cw]  diag(1 / sigma) A'^T TN: staging tile of prepG
   float *sZf = (float *)(sP2 + (size_t)h * cw);              // [zr][cw] Z columns of this slice
   float *sAff = sZf + (size_t)zr * cw;                       // [zr][h]  A' as stored (float32)
   double *hst = (t.stamps && hid == 0 && tid == 0) ? t.stamps : nullptr;
-  double *hst2 = (t.stamps && hid == 0) ? t.stamps : nullptr;   // (the last wave's stamps around the second wait)
   auto rt = []() { return (double)(__builtin_amdgcn_s_memrealtime() & ((1ull << 40) - 1)); };
   if (tid == 0) { if (hst) hst[22] = rt(); give_up(spin_wait_ge(t.tcnt, (unsigned)nH, t.abort_flag)); if (hst) hst[30] = rt(); }
   lds_barrier();
@@ -1456,14 +1455,14 @@ __device__ __forceinline__ bool persist_helper_block(const HP &t, int hid, int n
   if (t.awant) {
     // A' and 1 / sigma: one run of 16-byte agent-scope loads (zr * h is even past k == 0; the padded double of 1 / sigma comes along)
     const __amdgpu_buffer_rsrc_t rP = sc1_rsrc(t.Apub);
-    const int n1 = persist_pub_off(zr * h, h) >> 1, nA = (zr * h) >> 1;
+    const int n1 = persist_pub_doubles(zr * h, h) >> 1, nA = (zr * h) >> 1;
     for (int e = tid; e < n1; e += NT) {
       const tn_uvec4 q = ld_sc1_b128(rP, (unsigned)e * 16u);
       *reinterpret_cast<tn_uvec4 *>(sA + 2 * e) = q;
       if (e < nA) { const dvec2_t a = __builtin_bit_cast(dvec2_t, q); sAff[2 * e] = (float)a[0]; sAff[2 * e + 1] = (float)a[1]; }
     }
   } else if (tid == 0) {                                     // k == 0: zr == h == 1, the identity
-    sA[0] = 1.0; sAff[0] = 1.f; sIv[0] = 1.0; sNh[0] = 1.0;
+    sA[0] = 1.0; sAff[0] = 1.f; sIv[0] = 1.0;
   }
   lds_barrier();
   if (hst) hst[25] = rt();
@@ -1479,39 +1478,12 @@ __device__ __forceinline__ bool persist_helper_block(const HP &t, int hid, int n
              else sP2[__mul24(i, cw) + (j - cw)] = v * sIv[i];
            }, false, slot);
   }
-  if (t.l2_flag) {
-    // The last wave, its tiles done, waits for the end of step k-1 and fetches Nh on its own; the others meet it at the barrier the
-    // third product needs anyway (every helper takes this path, also one without columns: the give-up is decided for the workgroup)
-    if (t.awant && (tid >> 6) == (NT >> 6) - 1) {
-      const int ln = tid & 63;
-      int bad = 0;
-      if (ln == 0) { if (hst2) hst2[31] = rt(); bad = spin_wait_ge(t.nflag, t.awant, t.abort_flag); give_up(bad); if (hst2) hst2[21] = rt(); }
-      if (!__builtin_amdgcn_readfirstlane(bad)) {
-        // 16-byte loads, four per lane in flight (h * h odd: the padded double comes along)
-        const __amdgpu_buffer_rsrc_t rP = sc1_rsrc(t.Apub);
-        const int oN = persist_pub_off(zr * h, h), nq = (h * h + 1) >> 1;
-        for (int e0 = ln; e0 < nq; e0 += 4 * 64) {
-          tn_uvec4 q[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) if (e0 + 64 * u < nq) q[u] = ld_sc1_b128(rP, (unsigned)(oN + 2 * (e0 + 64 * u)) * 8u);
-#pragma unroll
-          for (int u = 0; u < 4; ++u) if (e0 + 64 * u < nq) *reinterpret_cast<tn_uvec4 *>(sNh + 2 * (e0 + 64 * u)) = q[u];
-        }
-      }
-    }
-  }
   lds_barrier();
-  if (t.l2_flag && sBad) return true;
+  if (hst) hst[31] = rt();
+  // the three slices leave together (P2 in the slot of prepG: the update workgroup multiplies it by Nh^T)
   st_sc1_rows(t.prepRaw, sOut, h, cw, RW, c0, nc);
   st_sc1_rows(t.prepB, sOut + (size_t)h * cw, h, cw, RW, c0, nc);
-  if (t.l2_flag) {
-    if (nc > 0) {
-      // (Ln.B.Rn)[e_, c] = sum_a Nh[a, e_] P2[a, c]   (staged where T | TN were)
-      mm_lds(1, h, nc, h, sNh, 0, 1, h, sP2, 0, cw, 1, [&](int, int i, int j, double v) { sS[__mul24(i, cw) + j] = v; });
-    }
-    lds_barrier();
-    st_sc1_rows(t.prepG, sS, h, cw, RW, c0, nc);
-  }
+  if (t.l2_flag) st_sc1_rows(t.prepG, sP2, h, cw, RW, c0, nc);
   if (hst) hst[26] = rt();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   lds_barrier();

@@ -467,7 +467,7 @@ static void tr_struct(const WidePipeParams &p) {
 }
 static void tr_struct(const PersistHelperParams &p) {
   I(zr) I(s) I(g) I(L) I(h) I(l2_flag) P(W) V(lab) V(pl) P(Ng) P(T) P(TN) P(Z) P(prepRaw) P(prepB) P(prepG) P(Apub) P(flag) I(want)
-  P(aflag) P(nflag) I(awant) P(zready) I(zwant) P(tcnt) P(pcnt) P(abort_flag) P(status) P(stamps)
+  P(aflag) I(awant) P(zready) I(zwant) P(tcnt) P(pcnt) P(abort_flag) P(status) P(stamps)
 }
 static void tr_struct(const PersistStep &p) { tr(" n:"); tr_struct(p.n); tr(" w:"); tr_struct(p.w); tr(" t:"); tr_struct(p.t); tr(" shape=%d", p.shape); }
 static void tr_struct(const PrepParams &p) { V(lab) V(pl) P(Nh) P(Ng) I(h) I(g) I(s) I(L) I(l2_flag) P(prepB) P(prepG) I(nparts) }

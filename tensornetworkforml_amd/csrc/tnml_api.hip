@@ -2351,7 +2351,7 @@ static int sweep_persist(tnml_ctx *c, const SweepCall &sc) {
   if (1 + nH + nwide > c->num_cus) return 0;                 // every workgroup of the launch must be resident
   const int Mcap = c->Mmax;
   const size_t pbytes = persist_lds_bytes(Mcap);
-  unsigned *fl = c->pst_flags;                               // [0] B_new token, [2] Z ready, [3] end of step: behind core / Nh stored, [4] abort, [5] A' / 1 / sigma stored
+  unsigned *fl = c->pst_flags;                               // [0] B_new token, [2] Z ready, [3] end of step: behind core stored, [4] abort, [5] A' / 1 / sigma stored
   float *zr2[2] = {c->zred, c->zred2};
   size_t lds_narrow = 0, lds_wide = 0, lds_help = 0;
   // prologue: Z_0 from forward's f
@@ -2415,7 +2415,7 @@ static int sweep_persist(tnml_ctx *c, const SweepCall &sc) {
     t.lab = n.lab; t.pl = n.pl; t.Ng = n.Ng;
     t.T = c->Tbuf[k & 1]; t.TN = c->TNbuf[k & 1]; t.Z = zr2[k & 1];
     t.prepRaw = c->prepRaw; t.prepB = c->prepB; t.prepG = c->prepG; t.Apub = c->Apub;
-    t.flag = fl + 0; t.want = (unsigned)k; t.aflag = fl + 5; t.nflag = fl + 3; t.awant = (unsigned)k; t.zready = fl + 2; t.zwant = (unsigned)k + 1;
+    t.flag = fl + 0; t.want = (unsigned)k; t.aflag = fl + 5; t.awant = (unsigned)k; t.zready = fl + 2; t.zwant = (unsigned)k + 1;
     t.tcnt = c->pst_cnt + (size_t)k * 32 + 20; t.pcnt = c->pst_cnt + (size_t)k * 32 + 21;
     t.abort_flag = fl + 4; t.status = c->status; t.stamps = n.stamps;
     lds_help = std::max(lds_help, persist_helper_lds_bytes(zr, s, g, L, h, nH));

@@ -174,12 +174,11 @@ struct PersistHelperParams {
   double *T, *TN;            // T_k, T_k . Ng   [zr][D][D][g][L] float64
   const float *Z;            // reduced pre-gradient Z_k [zr][RW]
   float *prepRaw, *prepB;    // out [h][RW]
-  double *prepG;
-  const double *Apub;        // A' [zr][h], 1 / sigma [h], Nh [h][h] of step k-1 (update workgroup)
+  double *prepG;             // out [h][RW]: P2 = diag(1 / sigma) A'^T TN_k (the update workgroup applies Nh^T)
+  const double *Apub;        // A' [zr][h], 1 / sigma [h] of step k-1 (update workgroup)
   const unsigned *flag;      // >= want: B_new(k-1) is stored (want == 0: nothing to wait for)
   unsigned want;
   const unsigned *aflag;     // >= awant: A' and 1 / sigma of Apub are stored (awant == 0 at k == 0: the identity)
-  const unsigned *nflag;     // >= awant: Nh of Apub is stored as well (end of step k-1); waited for only where l2_flag is set
   unsigned awant;
   const unsigned *zready;    // >= zwant: Z_k is reduced
   unsigned zwant;
@@ -221,21 +220,18 @@ constexpr int persist_step_shape(int h, int g, int s, int m, int L, int z_rows, 
     return 0;
   }
 }
-// The block the update workgroup publishes for the helpers (Apub), in doubles: A' [na] at 0, 1 / sigma [h] at na rounded up to even,
-// Nh [h][h] at the returned offset; each part starts on a 16-byte boundary and is padded to an even count (16-byte transport).
-__host__ __device__ inline int persist_pub_off(int na, int h) { return ((na + 1) & ~1) + ((h + 1) & ~1); }
-__host__ __device__ inline size_t persist_pub_doubles(int na, int h) { return (size_t)persist_pub_off(na, h) + (((size_t)h * h + 1) & ~(size_t)1); }
-// helper part 2: doubles of the (T | TN) tile [zr][2 cw], which later stages the [h][cw] slice of prepG
-__host__ __device__ inline size_t persist_helper_ss_doubles(int zr, int h, int cw) {
-  const size_t a = 2 * (size_t)zr * cw, b = (size_t)h * cw;
-  return ((a > b ? a : b) + 1) & ~(size_t)1;
-}
+// The block the update workgroup publishes for the helpers (Apub), in doubles: A' [na] at 0, 1 / sigma [h] at na rounded up to even;
+// each part starts on a 16-byte boundary and is padded to an even count (16-byte transport).  (The behind norm environment is not
+// in it: its only reader is the update workgroup itself, which keeps it in LDS.)
+__host__ __device__ inline int persist_pub_doubles(int na, int h) { return ((na + 1) & ~1) + ((h + 1) & ~1); }
+// helper part 2: doubles of the (T | TN) tile [zr][2 cw]
+__host__ __device__ inline size_t persist_helper_ss_doubles(int zr, int cw) { return 2 * (size_t)zr * cw; }
 inline size_t persist_helper_lds_bytes(int zr, int s, int g, int L, int h, int nH) {
   const size_t DG = (size_t)kD * g, RW = kD * DG * L;
   const size_t per = ((size_t)zr * kD + nH - 1) / nH, cw = (RW + nH - 1) / nH;
   const size_t p1 = (((per * s * L + 3) & ~(size_t)3) + (((size_t)s * DG + 3) & ~(size_t)3)) * sizeof(float) +
                     ((((size_t)g * g + 1) & ~(size_t)1) + 2 * per * DG * L) * sizeof(double);
-  const size_t p2 = (persist_pub_doubles(zr * h, h) + persist_helper_ss_doubles(zr, h, (int)cw) + 2 * (size_t)h * cw) * sizeof(double) +
+  const size_t p2 = ((size_t)persist_pub_doubles(zr * h, h) + persist_helper_ss_doubles(zr, cw) + 2 * (size_t)h * cw) * sizeof(double) +
                     ((size_t)zr * cw + (size_t)zr * h) * sizeof(float);
   return (p1 > p2 ? p1 : p2) + 64;
 }

@@ -8,7 +8,8 @@ import bench
 from tensornetworkforml_amd import _hip
 
 N, M, b, L, D = 784, int(os.environ.get('M', '20')), int(os.environ.get('B', '5000')), 2, 2
-hp = (1e-3, 1e-3, True, 'softmax', 'full_cross_ent', 0.1, 'fixed')
+L2 = os.environ.get('L2', '1') != '0'                                       # L2=0: bench.py --no-l2
+hp = (1e-3, 1e-3, L2, 'softmax', 'full_cross_ent', 0.1, 'fixed')
 for persistent in (True, False):
     ctx = _hip.Context(N, D, L, M, b)
     ctx.set_persistent(persistent)
@@ -38,8 +39,9 @@ for persistent in (True, False):
     if persistent:
         print('   helper 0, part 2 of that step, us relative to the update workgroup starting the step: enter %.2f | core token (A\', 1 / sigma) seen %.2f | T seen %.2f | Z seen %.2f | operands in LDS %.2f | products issued %.2f | arrived %.2f | update workgroup saw all arrivals %.2f'
               % tuple((st[i] - st[28]) / 100.0 for i in (22, 23, 30, 24, 25, 26, 27, 29)))
-        print('   helper 0, the second wait of that step (L2 term), same clock: first product level done %.2f | end-of-step token of the previous step (Nh stored) seen %.2f, i.e. %.2f us waited: the first level ran beside the norm environment for the %.2f us before'
-              % ((st[31] - st[28]) / 100.0, (st[21] - st[28]) / 100.0, (st[21] - st[31]) / 100.0, (st[31] - st[23]) / 100.0))
+        # (the helpers wait once: no stamp of an end-of-step token any more; the L2 term's last factor is the update workgroup's)
+        print('   helper 0, same clock: product level done %.2f, %.2f us after the core token | update workgroup: Nh^T . P2 (the "L2" cycles above) %.0f cycles'
+              % ((st[31] - st[28]) / 100.0, (st[31] - st[23]) / 100.0, st[11]))
         print('   batch-side workgroup 0 in the iteration of that step (f of step k, Z of step k+1), same clock: enter %.2f | core flag seen %.2f | B_new flag seen %.2f | tiles done %.2f | partial stored + ticket %.2f | reduced Z published (last arriver) %.2f'
               % tuple((st[i] - st[28]) / 100.0 for i in (32, 33, 34, 35, 36, 37)))
     ctx.close()
