@@ -481,6 +481,32 @@ int tnml_compress(tnml_ctx *ctx, int m_max, double threshold, double rank_tol, i
                   double *discarded_out, double *log_norm_out);
 int tnml_bond_spectra(tnml_ctx *ctx, double rank_tol, int32_t *rank_out, double *sigma_out, double *log_norm_out);
 
+/* ---- inner products and linear combinations of two MPS --------------- */
+/* W is the context's chain, V a second chain with the same N, D, L and the same label position, handed in as other_flat / other_bond
+ * in the layout of tnml_get_cores; its bonds are free.  With a symmetric float64 metric S_i per site (metric NULL: the identity;
+ * metric_sites 1: one [D][D] for all sites; metric_sites N: [N][D][D]; the label axis is always contracted with the identity)
+ *   <W|V>_S = sum W[d_0 .. d_{N-1}, l'] V[d'_0 .. d'_{N-1}, l'] prod_i S_i[d_i, d'_i],
+ * computed in float64 from the float32 cores by two transfer half-chains that meet on the label site.  After every site the transfer
+ * matrix is multiplied by an exact power of two that joins an integer exponent, so nothing leaves the range at N = 784 whatever the
+ * cores' scale.  out6 = {sign, log|.|} of <W|W>, <V|V>, <W|V>; a zero product gives (0, -inf).  other_flat NULL: only <W|W> (the
+ * other four entries 0 and -inf).  The three products run the same instructions in the same order: a V bit-equal to W gives three
+ * bit-equal pairs, and two calls on the same cores are bit-equal.  tnml_inner changes nothing on the device (bit for bit, as
+ * tnml_bond_spectra); no forward is needed afterwards.
+ * tnml_axpby: W <- alpha W + beta V as the direct sum: every bond becomes mW_i + mV_i (bond_out [N-1]), interior cores are
+ * block-diagonal per d (and per l' on the label site), site 0 is a row concatenation, site N-1 a column stack; alpha and beta multiply
+ * the label-site blocks only, in float64 with one rounding per element.  It commits as tnml_compress does: the state
+ * tnml_scale_cores leaves, every slot float behind the new core zero, the optimiser state unbound.
+ * A call that fails leaves cores, bonds and l_pos as they were; all of these happen before anything is launched:
+ * TNML_ERR_ARG (NULL output; n_floats not what the bonds imply; a bond < 1; other_l_pos != l_pos; metric_sites not 1 or N; a
+ * non-finite alpha or beta; for tnml_axpby a NULL other_flat or a summed bond above the context's bond capacity), TNML_ERR_STATE
+ * (cores never set; a communicator attached), TNML_ERR_SHAPE (the transfer matrix of the two largest bonds does not fit the
+ * kernel's LDS; the message names the bytes).  TNML_ERR_NONFINITE: a core element that is not finite (tnml_inner), a result element
+ * that is not a finite float32 (tnml_axpby). */
+int tnml_inner(tnml_ctx *ctx, const float *other_flat, size_t n_floats, const int32_t *other_bond, int other_l_pos,
+               const double *metric, int metric_sites, double *out6);
+int tnml_axpby(tnml_ctx *ctx, double alpha, double beta, const float *other_flat, size_t n_floats,
+               const int32_t *other_bond, int other_l_pos, int32_t *bond_out);
+
 /* Host-side planning helper, exported so that CPU tests can check the bond bookkeeping without a
  * GPU: truncation rank kept by tensor_svd (Network_class.py:894-945) for a step on sites
  * (p, p+1).  Returns m >= 1, or TNML_ERR_SHAPE where the reference itself raises. */

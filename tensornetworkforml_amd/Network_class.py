@@ -20,11 +20,14 @@ Differences from the reference, all opt-in or unavoidable:
   * `update_B`, `tensor_svd` and `compute_L2_reg` are fused into one kernel per sweep step; the
     methods of that name run the same device code on the operands they are given.
 """
+import math
+
 import numpy as np
 
 from Tensor_class import Tensor
 from custom_linalg_tools import contract, partial_trace  # noqa: F401  (re-exported like the reference)
 from data_generator import psi as _psi
+from data_generator import psi_gram as _psi_gram
 
 try:
     from tensornetworkforml_amd import _hip
@@ -694,6 +697,73 @@ class Network():
         ranks, sigma, log_norm = ctx.bond_spectra(rank_tol)
         return [sigma[i, :int(r)].copy() for i, r in enumerate(ranks)], log_norm
 
+    # ------------------------------------------------------------------------------------------
+    # inner products, distances and linear combinations of two MPS (not in the reference)
+    # ------------------------------------------------------------------------------------------
+    def _algebra_operand(self, other):
+        """(cores, l_pos) of the second network, checked against this one"""
+        if not isinstance(other, Network):
+            raise TypeError('the second operand must be a Network, got %s' % type(other).__name__)
+        if (other.N, other.D, other.L) != (self.N, self.D, self.L):
+            raise ValueError('the networks differ in (N, D, L): %s and %s' % ((self.N, self.D, self.L), (other.N, other.D, other.L)))
+        other._sync_to_host()
+        if other._l_pos != self.l_pos:
+            raise ValueError('the label sits on site %d of this network and on site %d of the other: move one of them first'
+                             % (self.l_pos, other._l_pos))
+        return other._host_cores, other._l_pos
+
+    def _metric(self, metric):
+        if isinstance(metric, str):
+            if metric != 'uniform':
+                raise ValueError("metric must be None, an array (D, D) or (N, D, D), or 'uniform'")
+            return _psi_gram(self.D)
+        return metric
+
+    def inner(self, other=None, metric=None):
+        """[(sign, log|.|) of <W|W>, of <V|V>, of <W|V>] for this network W and `other` V (same N, D, L and label position; any
+        bonds), in float64 on the device; other None: <W|W> alone, the other two pairs (0, -inf).  metric: None (Euclidean),
+        a symmetric (D, D) array for every site or (N, D, D) per site, or 'uniform' -- data_generator.psi_gram(D), with which
+        <W|V> is the L2 inner product of the two models as functions of uniformly distributed pixels.  The products are
+        returned as logarithms because they leave float64 at N = 784.  Nothing on the device changes."""
+        ctx = self._sync_to_device(max(self._b, 1))
+        if other is None:
+            out = ctx.inner(None, 0, self._metric(metric))
+        else:
+            cores, lp = self._algebra_operand(other)
+            out = ctx.inner(cores, lp, self._metric(metric))
+        return [(float(s), float(v)) for s, v in out]
+
+    def cosine(self, other, metric=None):
+        """<W|V> / (|W| |V|); exactly 1.0 for a network with the same float32 cores."""
+        (_, lww), (_, lvv), (s, lwv) = self.inner(other, metric)
+        return s * math.exp(lwv - 0.5 * (lww + lvv)) if s != 0 else 0.0
+
+    def distance(self, other, metric=None, relative=True):
+        """|W - V| / |W| (relative) or |W - V|, from the three inner products: sqrt(max(0, 1 + <V|V>/<W|W> - 2 <W|V>/<W|W>)).
+        The three terms cancel in float64: a relative distance below about 1e-6 is not resolved (it may come out as 0 or as
+        noise of that size); exactly 0.0 for a network with the same float32 cores.  The absolute distance is returned as a
+        float and overflows where |W| does."""
+        (_, lww), (_, lvv), (s, lwv) = self.inner(other, metric)
+        d2 = 1.0 + math.exp(lvv - lww) - 2.0 * s * (math.exp(lwv - lww) if s != 0 else 0.0)
+        d = math.sqrt(max(0.0, d2))
+        return d if relative else d * math.exp(0.5 * lww)
+
+    def add(self, other, alpha=1.0, beta=1.0):
+        """In place W <- alpha W + beta V as the direct sum: every bond becomes the sum of the two bonds, f becomes
+        alpha f_W + beta f_V.  The network's M must hold the summed bonds (ValueError naming the M needed otherwise); compress
+        brings them down again.  A forward is needed before the next sweep, configure_optimizer before the next stateful
+        gradient_step (as after compress).  Returns the new bonds."""
+        cores, lp = self._algebra_operand(other)
+        ctx = self._sync_to_device(max(self._b, 1))
+        _, mine, _ = ctx.get_cores()
+        need = max(int(a) + int(c.shape[2]) for a, c in zip(mine, cores[:-1]))
+        if need > ctx.bond_capacity:
+            raise ValueError('the sum needs bonds up to %d, this network holds %d: create it with M >= %d or compress first'
+                             % (need, ctx.bond_capacity, need))
+        bonds = ctx.axpby(alpha, beta, cores, lp)
+        self._after_device_update()
+        return [int(v) for v in bonds]
+
     def configure_optimizer(self, optimizer='sgd', momentum=0.0, betas=(0.9, 0.999), eps=1e-8, clip=True):
         """The optimiser of gradient_step / train_gradient: 'sgd' (momentum, the reference's clip per core) or 'adam' (decoupled
         weight decay, no clip).  Resets the optimiser state."""
@@ -1055,6 +1125,63 @@ class DeviceDataset:
 
     def __repr__(self):
         return 'DeviceDataset(n=%d, N=%d, D=%d, %s)' % (self.n, self.N, self.D, 'pixels' if self.pixels else 'features')
+
+
+_COMPRESS_MAX_BOND = 96      # the largest bond tnml_compress takes (the LDS of its one workgroup, include/tnml.h)
+
+
+def combine(nets, coeffs=None, max_bond=None, threshold=None):
+    """A new Network holding sum_k coeffs[k] W_k (default: the mean) of networks with the same N, D, L and label position: the
+    direct sum on the device in a temporary context (Context.axpby per network), then compress(max_bond, threshold).  Where the
+    next sum would exceed the bond compress accepts (96), the partial sum is compressed first with the same arguments.  The
+    result has M = max_bond (the largest bond of the sum where max_bond is None) and the first network's T, activation, loss and
+    truncation policy."""
+    nets = list(nets)
+    if not nets:
+        raise ValueError('combine needs at least one network')
+    coeffs = [1.0 / len(nets)] * len(nets) if coeffs is None else [float(v) for v in coeffs]
+    if len(coeffs) != len(nets):
+        raise ValueError('%d coefficients for %d networks' % (len(coeffs), len(nets)))
+    first = nets[0]
+    first._sync_to_host()
+    lp = first._l_pos
+    operands = [(first._host_cores, lp)] + [first._algebra_operand(n) for n in nets[1:]]
+    widths = [max([int(c.shape[2]) for c in cores[:-1]]) for cores, _ in operands]
+    cap = min(sum(widths), _COMPRESS_MAX_BOND)
+    if max(widths) > cap:
+        raise ValueError('a network has bond %d, compress takes %d at the most' % (max(widths), cap))
+    ctx = _hip.Context(first.N, first.D, first.L, cap, 1, first._device)
+    try:
+        cores0 = [np.asarray(c, dtype=np.float32) for c in operands[0][0]]
+        ctx.set_cores(cores0, lp)
+        cur = widths[0]
+        m_arg = ctx.bond_capacity if max_bond is None else int(max_bond)
+        thr = 1.0 if threshold is None else threshold
+        for k in range(1, len(nets)):
+            if cur + widths[k] > ctx.bond_capacity:
+                if max_bond is None and threshold is None:
+                    raise ValueError('the sum reaches bond %d, beyond %d: combine needs max_bond or threshold to compress on the way'
+                                     % (cur + widths[k], ctx.bond_capacity))
+                cur = int(max(ctx.compress(m_arg, thr)[0]))
+                if cur + widths[k] > ctx.bond_capacity:
+                    raise ValueError('the compressed partial sum (bond %d) and the next network (bond %d) exceed bond %d'
+                                     % (cur, widths[k], ctx.bond_capacity))
+            # the first coefficient rides on the first sum (alpha multiplies the label core once)
+            cur = int(max(ctx.axpby(coeffs[0] if k == 1 else 1.0, coeffs[k], operands[k][0], lp)))
+        if len(nets) == 1 and coeffs[0] != 1.0:
+            cores0[lp] = (coeffs[0] * cores0[lp].astype(np.float64)).astype(np.float32)
+            ctx.set_cores(cores0, lp)
+        if max_bond is not None or threshold is not None:
+            cur = int(max(ctx.compress(m_arg, thr)[0]))
+        cores, _, lp_out = ctx.get_cores()
+    finally:
+        ctx.close()
+    out = Network(first.N, int(max_bond) if max_bond is not None else max(cur, 1), D=first.D, L=first.L, T=first.T, act_fn=first.act_fn,
+                  loss_fn=first.loss_fn, trunc=first.trunc, device=first._device)
+    out._host_cores = [c.astype(np.float64) for c in cores]
+    out._l_pos = lp_out
+    out._host_newer = True
+    return out
 
 
 def _unpack_batch(data):

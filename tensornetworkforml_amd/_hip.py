@@ -40,6 +40,7 @@ SYMBOLS = [
     'tnml_orthogonalize', 'tnml_compress', 'tnml_bond_spectra',
     'tnml_set_chain_scaling', 'tnml_predict_scaled',
     'tnml_set_shape_kernels', 'tnml_fixed_shape_steps',
+    'tnml_inner', 'tnml_axpby',
 ]
 
 
@@ -143,6 +144,8 @@ def lib():
         L.tnml_bond_spectra.argtypes = [vp, C.c_double, i32p, f64p, f64p]
         L.tnml_set_chain_scaling.argtypes = [vp, C.c_int]
         L.tnml_predict_scaled.argtypes = [vp, f32p, C.c_int, f32p, i32p]
+        L.tnml_inner.argtypes = [vp, f32p, C.c_size_t, i32p, C.c_int, f64p, C.c_int, f64p]
+        L.tnml_axpby.argtypes = [vp, C.c_double, C.c_double, f32p, C.c_size_t, i32p, C.c_int, i32p]
         _lib = L
     return _lib
 
@@ -271,6 +274,44 @@ class Context:
         logn = C.c_double()
         _chk(lib().tnml_bond_spectra(self._h, float(rank_tol), _ptr(rank, C.c_int32), _ptr(sigma, C.c_double), C.byref(logn)))
         return rank, sigma, logn.value
+
+    # ---- inner products and linear combinations of two MPS
+    def _other(self, cores):
+        if len(cores) != self.N:
+            raise TnmlError(-1, 'the second chain has %d cores, this context %d sites' % (len(cores), self.N))
+        bond = np.array([cores[i].shape[2] for i in range(self.N - 1)], dtype=np.int32)
+        flat = _f32(np.concatenate([np.asarray(c, dtype=np.float32).ravel() for c in cores]))
+        return flat, bond
+
+    def inner(self, cores=None, l_pos=0, metric=None):
+        """-> float64 (3, 2): (sign, log|.|) of <W|W>, <V|V>, <W|V> for the second chain V = `cores` (canonical arrays, label on
+        l_pos); cores None: <W|W> alone, the other rows (0, -inf).  metric: None, (D, D) or (N, D, D) float64, symmetric.  Nothing
+        on the device changes."""
+        out = np.zeros(6, dtype=np.float64)
+        mp, ms = None, 0
+        if metric is not None:
+            metric = np.ascontiguousarray(metric, dtype=np.float64)
+            if metric.shape == (self.D, self.D):
+                ms = 1
+            elif metric.shape == (self.N, self.D, self.D):
+                ms = self.N
+            else:
+                raise TnmlError(-1, 'the metric has shape %s, neither (D, D) nor (N, D, D)' % (metric.shape,))
+            mp = _ptr(metric, C.c_double)
+        if cores is None:
+            _chk(lib().tnml_inner(self._h, None, 0, None, 0, mp, ms, _ptr(out, C.c_double)))
+        else:
+            flat, bond = self._other(cores)
+            _chk(lib().tnml_inner(self._h, _ptr(flat, C.c_float), flat.size, _ptr(bond, C.c_int32), int(l_pos), mp, ms, _ptr(out, C.c_double)))
+        return out.reshape(3, 2)
+
+    def axpby(self, alpha, beta, cores, l_pos):
+        """W <- alpha W + beta V as the direct sum (every bond becomes the sum of the two) -> the new bonds (N-1,)"""
+        flat, bond = self._other(cores)
+        out = np.empty(self.N - 1, dtype=np.int32)
+        _chk(lib().tnml_axpby(self._h, float(alpha), float(beta), _ptr(flat, C.c_float), flat.size, _ptr(bond, C.c_int32), int(l_pos),
+                              _ptr(out, C.c_int32)))
+        return out
 
     # ---- batch
     def set_input(self, X, y=None):

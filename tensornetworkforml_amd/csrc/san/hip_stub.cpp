@@ -378,6 +378,60 @@ static void check_orth(const OrthParams &p, dim3 g, dim3 b, size_t shm, int whic
   need(p.status, 4, "OrthParams.status");
 }
 
+// inner products and linear combinations (kernels_algebra.hip): one parameter block for the chain, meet and place kernels.  Both bond
+// tables and both offset tables are read here as the kernels read them; every core of either chain, the staging areas and half
+// results of the workgroups of the launch, the outputs and (place kernel) the float32 result with the summed cores inside their slots.
+static void check_algebra(const AlgebraParams &p, dim3 g, dim3 b, size_t shm, int which) {  // which: 0 chain, 1 meet, 2 place
+  scan(&p, sizeof p, "AlgebraParams");
+  if (p.N < 2 || p.D < 2 || p.D > kMaxD || p.L < 1 || p.l_pos < 0 || p.l_pos >= p.N) die("AlgebraParams: N %d D %d L %d l_pos %d", p.N, p.D, p.L, p.l_pos);
+  if (p.n_prod != 1 && p.n_prod != 3) die("AlgebraParams: %d products", p.n_prod);
+  const int chains = (which == 2 || p.n_prod == 3) ? 2 : 1;
+  if (which == 2 && p.n_prod != 3) die("sum_place_kernel without a second chain");
+  need(p.bond, (size_t)chains * (p.N - 1) * 4, "AlgebraParams.bond");
+  need(p.off, (size_t)(chains - 1) * p.N * 8 + (size_t)p.N * 8, "AlgebraParams.off");
+  int mb = 1;
+  for (int ch = 0; ch < chains; ++ch) {
+    const int *bond = p.bond + (size_t)ch * (p.N - 1);
+    const long long *off = p.off + (size_t)ch * p.N;
+    const float *plain = ch ? p.v_plain : p.w_plain, *lab = ch ? p.v_lab : p.w_lab;
+    for (int i = 0; i < p.N; ++i) {
+      const int ml = i == 0 ? 1 : bond[i - 1], mr = i == p.N - 1 ? 1 : bond[i];
+      if (ml < 1 || mr < 1) die("AlgebraParams: chain %d site %d is %d x %d", ch, i, ml, mr);
+      mb = mb > mr ? mb : mr;
+      const size_t ne = (size_t)ml * p.D * mr * (i == p.l_pos ? p.L : 1);
+      if (i == p.l_pos) need(lab, ne * 4, ch ? "AlgebraParams.v_lab" : "AlgebraParams.w_lab");
+      else {
+        if (off[i] < 0) die("AlgebraParams: chain %d core %d at offset %lld", ch, i, off[i]);
+        need(plain + off[i], ne * 4, ch ? "AlgebraParams.v_plain" : "AlgebraParams.w_plain");
+      }
+    }
+  }
+  need(p.status, 4, "AlgebraParams.status");
+  if (which == 2) {
+    if (g.x != (unsigned)p.N || g.y != 1 || g.z != 1 || b.x != 256) die("sum_place_kernel: grid %u block %u for N %d", g.x, b.x, p.N);
+    if (!(p.alpha == p.alpha && p.beta == p.beta)) die("AlgebraParams: alpha %g beta %g", p.alpha, p.beta);
+    need(p.out_cores, (size_t)p.N * p.core_stride * 4, "AlgebraParams.out_cores");
+    need(p.out_lab, p.lab_elems * 4, "AlgebraParams.out_lab");
+    for (int i = 0; i < p.N; ++i) {
+      const int ml = i == 0 ? 1 : p.bond[i - 1] + p.bond[p.N - 1 + i - 1], mr = i == p.N - 1 ? 1 : p.bond[i] + p.bond[p.N - 1 + i];
+      const size_t ne = (size_t)ml * p.D * mr * (i == p.l_pos ? p.L : 1);
+      if (ne > (i == p.l_pos ? p.lab_elems : p.core_stride)) die("AlgebraParams: summed core %d of %zu floats beyond its slot", i, ne);
+    }
+    return;
+  }
+  const size_t m2 = (size_t)mb * mb;
+  if ((size_t)p.lds_m2 < m2 || p.half_stride < m2 || p.stage_stride < m2 * p.D) die("AlgebraParams: lds_m2 %d half_stride %zu stage_stride %zu for bond %d", p.lds_m2, p.half_stride, p.stage_stride, mb);
+  if (b.x != 1024 || g.x != (unsigned)p.n_prod || g.y != (which == 0 ? 2u : 1u) || g.z != 1) die("inner kernel %d: grid (%u, %u) block %u for %d products", which, g.x, g.y, b.x, p.n_prod);
+  if (which == 0 && (shm < ((size_t)2 * p.lds_m2 + 32) * 8 || (size_t)p.lds_m2 > 10 * 1024)) die("inner_chain_kernel: %zu bytes of LDS for bond %d", shm, mb);
+  if (which == 1 && shm < ((size_t)p.lds_m2 + 1024) * 8) die("inner_meet_kernel: %zu bytes of LDS for bond %d", shm, mb);
+  if (p.metric_sites != 0 && p.metric_sites != 1 && p.metric_sites != p.N) die("AlgebraParams: metric_sites %d", p.metric_sites);
+  if (p.metric_sites) need(p.metric, (size_t)p.metric_sites * p.D * p.D * 8, "AlgebraParams.metric");
+  need(p.stage, (size_t)p.n_prod * 2 * 2 * p.stage_stride * 8, "AlgebraParams.stage");
+  need(p.half_E, (size_t)p.n_prod * 2 * p.half_stride * 8, "AlgebraParams.half_E");
+  need(p.half_expo, (size_t)p.n_prod * 2 * 4, "AlgebraParams.half_expo");
+  need(p.out, (size_t)p.n_prod * 2 * 8, "AlgebraParams.out");
+}
+
 // gradient training (kernels_optim.hip).  loss_cot_kernel: f and cot at their own strides, the labels of the chunk, one thread per
 // column of cot.  optim_step_kernel: one workgroup per site; every core's slot and its part of G, vel / m / v through the table.
 static void check_loss_cot(const LossCotParams &p, dim3 g, dim3 b, size_t shm) {
@@ -487,6 +541,10 @@ static void tr_struct(const OptimStepParams &p) {
   P(tab) P(cores) P(labcore) P(G) P(s0) P(s1) I(core_stride) I(N) I(D) I(L) I(l_pos) I(kind) I(clip) R(lr) R(wd) R(mu) R(beta1) R(beta2) R(eps)
   R(corr1) R(corr2)
 }
+static void tr_struct(const AlgebraParams &p) {
+  I(N) I(D) I(L) I(l_pos) I(n_prod) I(metric_sites) I(lds_m2) P(bond) P(off) P(w_plain) P(w_lab) P(v_plain) P(v_lab) P(metric) P(stage) I(stage_stride)
+  P(half_E) I(half_stride) P(half_expo) P(out) P(status) R(alpha) R(beta) P(out_cores) P(out_lab) I(core_stride) I(lab_elems)
+}
 static void tr_struct(const InputGradPixels &p) { P(g) P(data) P(idx) P(out) I(b) I(N) I(D) }
 static void tr_struct(const BigExtArgs &p) { P(Eprev) P(x_km1) P(x_k) V(A) I(b_pad) P(Ecur) P(Pk) }
 static void tr_struct(const ChainSite &p) { I(core_off) I(is_label) I(n_in) I(n_out) I(s_in) I(s_d) I(s_out) I(x_site) I(env_out_off) }
@@ -527,6 +585,7 @@ static void tr_launch(const std::string &name, dim3 g, dim3 b, size_t shm, hipSt
     else if (is("LossCotParams")) tr_struct(*(const LossCotParams *)args[i]);
     else if (is("OptimStepParams")) tr_struct(*(const OptimStepParams *)args[i]);
     else if (is("BigExtArgs")) tr_struct(*(const BigExtArgs *)args[i]);
+    else if (is("AlgebraParams")) tr_struct(*(const AlgebraParams *)args[i]);
     else if (is("CoreView")) { const CoreView &v = *(const CoreView *)args[i]; tr(" [%s %d %d %d %d %d]", dp(v.base).c_str(), v.n_in, v.n_out, v.s_in, v.s_d, v.s_out); }
     else if (is("BigFrontTiles")) tr(" %d %d", ((int *)args[i])[0], ((int *)args[i])[1]);
     else if (is("float")) tr(" %.9g", *(float *)args[i]);
@@ -612,6 +671,8 @@ hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t s
     check_optim_step(*(const OptimStepParams *)args[0], g, b);
   } else if (has("orth_load_kernel") || has("orth_chain_kernel") || has("orth_store_kernel")) {
     check_orth(*(const OrthParams *)args[0], g, b, shm, has("orth_chain_kernel") ? 1 : has("orth_store_kernel") ? 2 : 0);
+  } else if (has("inner_chain_kernel") || has("inner_meet_kernel") || has("sum_place_kernel")) {
+    check_algebra(*(const AlgebraParams *)args[0], g, b, shm, has("inner_chain_kernel") ? 0 : has("inner_meet_kernel") ? 1 : 2);
   } else if (has("input_grad_onehot_kernel")) {   // (f, f_bpad, L, b, cot, b_pad)
     const int fbp = *(int *)args[1], L = *(int *)args[2], bb = *(int *)args[3], bp = *(int *)args[5];
     if (bb < 1 || bb > bp || bp > fbp || (size_t)g.x * b.x < (size_t)bp) die("input_grad_onehot_kernel: b %d b_pad %d f_bpad %d grid %u x %u", bb, bp, fbp, g.x, b.x);

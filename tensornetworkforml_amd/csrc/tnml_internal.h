@@ -427,4 +427,35 @@ size_t orth_chain_lds_bytes(int mb);
 // load, chain and store kernel of one call; mb: largest bond of the chain.  false: refused (geometry / LDS)
 bool launch_orth(const OrthParams &p, int mb, hipStream_t st);
 
+// Inner products and linear combinations of two MPS (kernels_algebra.hip): one parameter block for the three
+// kernels.  Chain 0 is W, the context's (plain cores in their slots, the label core in its buffer), chain 1 is V in the flat layout of
+// tnml_get_cores; products 0, 1, 2 are <W|W>, <V|V>, <W|V>, and workgroup (product, half) of the chain kernel has the number
+// 2 * product + half (half 0: sites 0 .. l_pos-1, half 1: sites N-1 .. l_pos+1).
+struct AlgebraParams {
+  int N, D, L, l_pos;
+  int n_prod;              // 1: <W|W> alone (chain 1 is not read), 3: all three
+  int metric_sites;        // 0: identity, 1: one [D][D] for all sites, N: [N][D][D]
+  int lds_m2;              // LDS geometry: the square of the largest bond of either chain (launch_inner fills it)
+  const int *bond;         // [2][N-1] bond dimensions of W, then of V
+  const long long *off;    // [2][N] float offset of core i from w_plain / v_plain (not read for the label site)
+  const float *w_plain, *w_lab, *v_plain, *v_lab;
+  const double *metric;
+  double *stage;           // [6][2][stage_stride] the two cores of the site a workgroup is on, as doubles
+  size_t stage_stride;
+  double *half_E;          // [6][half_stride] what each half-chain hands to the meet kernel, with half_expo [6]: E 2^expo is the half's product
+  size_t half_stride;
+  int *half_expo;
+  double *out;             // [6] {sign, log|.|} per product
+  int *status;             // [0]: 1 a non-finite input or result
+  // sum_place_kernel: the float32 scratch copy of the slots of alpha W + beta V, zero behind each core
+  double alpha, beta;
+  float *out_cores, *out_lab;
+  size_t core_stride, lab_elems;
+};
+size_t algebra_chain_lds_bytes(int mb_w, int mb_v);
+size_t algebra_meet_lds_bytes(int mb_w, int mb_v);
+// chain and meet kernel of one tnml_inner call; mb_w, mb_v: largest bond of either chain.  false: refused (geometry / LDS)
+bool launch_inner(const AlgebraParams &p, int mb_w, int mb_v, hipStream_t st);
+bool launch_sum_place(const AlgebraParams &p, hipStream_t st);
+
 }  // namespace tnml

@@ -129,6 +129,17 @@ def psi(x, D=2):
     return np.stack(comps, axis=-1)
 
 
+def psi_gram(D=2, points=64):
+    """The Gram matrix int_0^1 psi(x) psi(x)^T dx of the feature map, (D, D) float64, by Gauss-Legendre quadrature on the host.
+    The components of psi are not orthonormal on [0, 1]: with this matrix as the metric of every site, Network.inner is the L2
+    inner product of the two models as functions of uniform pixels."""
+    t, w = np.polynomial.legendre.leggauss(int(points))
+    x = 0.5 * (t + 1.0)
+    p = psi(x[None, :], D)[0]                                    # (points, D)
+    G = np.einsum('q,qa,qb->ab', 0.5 * w, p, p)
+    return 0.5 * (G + G.T)
+
+
 def prepare_dataset(data, label, train_perc, val_perc, train_batch_size, val_batch_size, test_batch_size, D=2):
     """Embed, split and wrap in loaders (data_generator.py:125-192).  As in the reference the
     pixels go through psi un-normalised: pass data in [0, 1].  D: components of the feature map (psi)."""

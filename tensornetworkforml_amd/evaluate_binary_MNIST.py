@@ -34,6 +34,8 @@ def main(argv=None):
     ap.add_argument('--saliency', metavar='OUT.npy', default=None, help='write d f[predicted class] / d pixel of every test digit, (n, h, w)')
     ap.add_argument('--spectra', metavar='OUT.npy', default=None,
                     help='write the normalised Schmidt spectrum of every bond, (N - 1, largest rank), zero-padded (Network.bond_spectra)')
+    ap.add_argument('--compare', metavar='OTHER.dat', default=None,
+                    help='print the cosine and the relative distance between this model and another pickled one (same N, D, L and label position)')
     ap.add_argument('--scaled-chains', dest='scaled_chains', action='store_true',
                     help='carry a power-of-two exponent per sample along the chains (Network.scaled_chains): for a model whose partial products leave float32')
     args = ap.parse_args(argv)
@@ -59,6 +61,9 @@ def main(argv=None):
     if args.spectra:
         from tensornetworkforml_amd.evaluate_diagonals import write_spectra
         write_spectra(net, args.spectra)
+    if args.compare:
+        from tensornetworkforml_amd.evaluate_diagonals import compare_models
+        compare_models(net, args.compare)
     if args.saliency:
         import numpy as np
         if args.features:

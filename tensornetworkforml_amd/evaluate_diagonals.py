@@ -30,6 +30,15 @@ def write_spectra(net, path):
           % (log_norm, max(entropy), int(np.argmax(entropy)), path))
 
 
+def compare_models(net, path):
+    """cosine and relative distance between the loaded network and the pickled network at `path` (Network.cosine / distance)"""
+    with open(path, 'rb') as fh:
+        other = pickle.load(fh)
+    cos, dist = net.cosine(other), net.distance(other)
+    print('\tAgainst %s: cosine %.9f, relative distance |W - V| / |W| %.6g' % (path, cos, dist))
+    return cos, dist
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Evaluate a trained Tensor Network on a generated dataset of diagonals')
     ap.add_argument('--filename', type=str, default='trained_diag_model.dat', help='Pickled network to load')
@@ -39,6 +48,8 @@ def main(argv=None):
     ap.add_argument('--features', action='store_true', help='upload host-embedded features instead of pixels')
     ap.add_argument('--spectra', metavar='OUT.npy', default=None,
                     help='write the normalised Schmidt spectrum of every bond, (N - 1, largest rank), zero-padded (Network.bond_spectra)')
+    ap.add_argument('--compare', metavar='OTHER.dat', default=None,
+                    help='print the cosine and the relative distance between this model and another pickled one (same N, D, L and label position)')
     ap.add_argument('--scaled-chains', dest='scaled_chains', action='store_true',
                     help='carry a power-of-two exponent per sample along the chains (Network.scaled_chains): for a model whose partial products leave float32')
     args = ap.parse_args(argv)
@@ -56,6 +67,8 @@ def main(argv=None):
     acc, mae = net.evaluate(test_loader)
     if args.spectra:
         write_spectra(net, args.spectra)
+    if args.compare:
+        compare_models(net, args.compare)
     print('\tAccuracy:            ', acc)
     print('\tMean Absolute Error: ', mae)
     return acc, mae

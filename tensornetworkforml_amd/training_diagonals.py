@@ -77,10 +77,13 @@ def main(argv=None):
                                                    steps_per_batch=args.steps_per_batch)
         if args.compress is not None:
             before = np.mean([net._ctx.eval_indices(idx, net.act_fn, net.T)[0] / len(idx) for idx in val_idx])
+            uncompressed = pickle.loads(pickle.dumps(net))          # a host copy of the chain before the cut
             bonds, discarded = net.compress(max_bond=args.compress)
             after = np.mean([net._ctx.eval_indices(idx, net.act_fn, net.T)[0] / len(idx) for idx in val_idx])
             print('compressed to bond %d (largest bond now %d, discarded weight %.3g): validation accuracy %.4f -> %.4f'
                   % (args.compress, max(bonds), float(np.sum(discarded)), before, after))
+            print('relative distance |W - W_c| / |W| between the model before and after the compression: %.6g'
+                  % uncompressed.distance(net))
     else:
         val_acc, var_hist = net.train(train_loader, val_loader, lr=args.lr, n_epochs=args.n_epochs,
                                       weight_dec=args.L2_decay)
