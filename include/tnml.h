@@ -507,6 +507,32 @@ int tnml_inner(tnml_ctx *ctx, const float *other_flat, size_t n_floats, const in
 int tnml_axpby(tnml_ctx *ctx, double alpha, double beta, const float *other_flat, size_t n_floats,
                const int32_t *other_bond, int other_l_pos, int32_t *bond_out);
 
+/* ---- samples and log-likelihoods of the Born distribution ------------- */
+/* Over a pixel grid of K levels (2 <= K <= 256) with feature vectors phi [K][D] and positive weights w [K] the chain defines
+ *   p(k_0 .. k_{N-1}, l) = prod_i w[k_i] f_l(phi[k_0], .., phi[k_{N-1}])^2 / Z,     Z = <W|W>_S,  S = sum_k w_k phi_k phi_k^T.
+ * tnml_sample draws n exact samples from it in one pass over the chain, without rejection, in float64 from the float32 cores:
+ * metric environments R_i from the right (one stack per class a call conditions on, one with the label summed; each multiplied
+ * by an exact power of two per site), then per sample and site the K densities w_k phi_k^T Q phi_k, their running sums c_k and
+ * the smallest k with c_k > u_i c_{K-1} (the last k of positive density if there is none).
+ * classes [n]: -1 draws the label on the label site from P(l | levels before it), by u[N] and the same rule, and its log joins
+ * logp; a class c conditions on it: the sample comes from p(. | c) and no label term enters logp.  classes NULL: all -1.
+ * given [n][n_given]: the first n_given sites are clamped to these levels instead of drawn.  u [n][N+1] in [0, 1): the uniforms
+ * (column N for the label); u NULL: the device generates u[s][j] as SplitMix64 of seed + (s (N+1) + j + 1) 0x9E3779B97F4A7C15,
+ * top 53 bits times 2^-53, so that a seeded call can be repeated anywhere.
+ * levels_out [n][N], labels_out [n] (the given class where there is one), logp_out [n][2]: [0] the log-probability of all levels
+ * [and the drawn label] [given the class], [1] the sum of the terms of the clamped sites alone -- with the label site outside
+ * the prefix, or a given class, [0] - [1] is the log-density of the completion given the prefix.  n_given = N is a likelihood
+ * call: nothing but a label is drawn.  Masks other than a prefix are not supported.
+ * Every sum runs in a fixed order: two calls with the same arguments are bit-equal.  Nothing else on the device changes (cores,
+ * bonds, l_pos, the resident batch, f, the environments and the optimiser binding stay bit for bit); no forward is needed afterwards.
+ * Refused before anything is launched: TNML_ERR_ARG (n < 1; K outside [2, 256]; a class outside [-1, L); a given level outside
+ * [0, K); n_given outside [0, N]; a weight that is not positive and finite, a non-finite phi, a u outside [0, 1); a NULL phi, w or
+ * output, a NULL given with n_given > 0), TNML_ERR_STATE (cores never set; a communicator attached), TNML_ERR_SHAPE (a bond above
+ * 64, or LDS: the message names the bytes).  After the run: TNML_ERR_NONFINITE (a core element that is not finite), TNML_ERR_ARG
+ * naming the sample and its class when a sample is conditioned on a class or a prefix of zero weight. */
+int tnml_sample(tnml_ctx *ctx, int n, int K, const double *phi, const double *w, const int32_t *classes, const int32_t *given,
+                int n_given, const double *u, uint64_t seed, int32_t *levels_out, int32_t *labels_out, double *logp_out);
+
 /* Host-side planning helper, exported so that CPU tests can check the bond bookkeeping without a
  * GPU: truncation rank kept by tensor_svd (Network_class.py:894-945) for a step on sites
  * (p, p+1).  Returns m >= 1, or TNML_ERR_SHAPE where the reference itself raises. */

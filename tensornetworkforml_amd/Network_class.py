@@ -764,6 +764,95 @@ class Network():
         self._after_device_update()
         return [int(v) for v in bonds]
 
+    # ------------------------------------------------------------------------------------------
+    # samples and log-likelihoods of the Born distribution |f|^2 (not in the reference)
+    # ------------------------------------------------------------------------------------------
+    def _pixel_grid(self, levels, grid, weights):
+        """(x (K,), phi (K, D), w (K,)) float64: `grid` (pixel values, default k / (K - 1) for K = levels) through psi, `weights`
+        normalised to sum 1 (default 1 / K)"""
+        x = np.arange(int(levels), dtype=np.float64) / (int(levels) - 1) if grid is None else np.asarray(grid, dtype=np.float64).ravel()
+        K = len(x)
+        w = np.full(K, 1.0 / K) if weights is None else np.asarray(weights, dtype=np.float64).ravel()
+        if w.shape != (K,):
+            raise ValueError('%d weights for a grid of %d levels' % (len(w), K))
+        if not (np.all(np.isfinite(w)) and np.all(w > 0)):
+            raise ValueError('the weights must be positive and finite')
+        return x, np.ascontiguousarray(_psi(x[None, :], self.D)[0], dtype=np.float64), w / w.sum()
+
+    @staticmethod
+    def _levels_of(values, x, what):
+        """integer levels as they are; pixel values -> the level of the grid point each one equals (ValueError otherwise)"""
+        values = np.asarray(values)
+        if values.ndim != 2:
+            raise ValueError('%s must have shape (n, sites), got %s' % (what, values.shape))
+        if np.issubdtype(values.dtype, np.integer):
+            return np.ascontiguousarray(values, dtype=np.int32)
+        order = np.argsort(x)
+        pos = np.clip(np.searchsorted(x[order], values), 1, len(x) - 1)
+        lo, hi = x[order][pos - 1], x[order][pos]
+        near = np.where(np.abs(values - lo) <= np.abs(hi - values), pos - 1, pos)
+        lev = order[near]
+        if not np.all(np.abs(x[lev] - values) <= 1e-12 * np.maximum(1.0, np.abs(values))):
+            raise ValueError('%s holds pixel values that are not on the grid' % what)
+        return np.ascontiguousarray(lev, dtype=np.int32)
+
+    def _classes_of(self, classes, n):
+        if classes is None:
+            return None
+        c = np.asarray(classes)
+        if c.ndim == 0:
+            c = np.full(n, int(c))
+        return np.ascontiguousarray(c, dtype=np.int32)
+
+    def sample(self, n, classes=None, levels=256, grid=None, weights=None, given=None, seed=0, u=None):
+        """n exact samples of p(x, l) = prod_i w(x_i) f_l(psi(x))^2 / Z over the pixel grid, in one pass over the chain on the
+        device -> (X (n, N) pixel values, labels (n,), logp (n, 2), levels (n, N)).  classes: None draws the label with the
+        image; an int or an array (n,) conditions on it (-1 in the array: draw it), and the sample comes from p(x | class).
+        given: (n, n_given) pixel values on the grid or integer levels of the FIRST n_given sites, which are kept; only a
+        prefix can be given.  logp[:, 0] is the log-probability of the whole sample [given the class], logp[:, 1] the part of
+        the given sites.  seed: the device generates the uniforms by a counter hash (repeatable); u (n, N + 1) overrides them."""
+        x, phi, w = self._pixel_grid(levels, grid, weights)
+        n = int(n)
+        g = None if given is None else self._levels_of(given, x, 'given')
+        ctx = self._sync_to_device(max(self._b, 1))
+        lev, labels, logp = ctx.sample(n, phi, w, self._classes_of(classes, n), g, u, seed)
+        return x[lev], labels, logp, lev
+
+    def log_prob(self, X_or_levels, classes=None, levels=256, grid=None, weights=None, joint=False, seed=0, u=None):
+        """log-probabilities of images (n, N) (pixel values on the grid, or integer levels) -> (logp (n,), labels (n,)).
+        classes None: the label is drawn from P(l | x) and logp is log p(x, that label).  classes given (int or (n,)):
+        log p(x | class); with joint=True log p(x, class) = log p(x | class) + log P(class), the class weights by class_log_weights."""
+        x, phi, w = self._pixel_grid(levels, grid, weights)
+        lev = self._levels_of(X_or_levels, x, 'X_or_levels')
+        if lev.shape[1] != self.N:
+            raise ValueError('images of %d sites for a network of %d' % (lev.shape[1], self.N))
+        n = len(lev)
+        cls = self._classes_of(classes, n)
+        ctx = self._sync_to_device(max(self._b, 1))
+        _, labels, logp = ctx.sample(n, phi, w, cls, lev, u, seed)
+        out = logp[:, 0].copy()
+        if joint:
+            if cls is None or np.any(cls < 0):
+                raise ValueError('joint=True needs a class for every image')
+            out += self.class_log_weights(levels, grid, weights)[cls]
+        return out, labels
+
+    def class_log_weights(self, levels=256, grid=None, weights=None):
+        """log P(l) of the joint distribution, (L,): <W_l|W_l>_S / <W|W>_S by Network.inner under the grid's metric S, W_l the
+        chain with every label slice but l zeroed"""
+        _, phi, w = self._pixel_grid(levels, grid, weights)
+        S = np.einsum('k,kd,ke->de', w, phi, phi)
+        ctx = self._sync_to_device(max(self._b, 1))
+        cores, _, lp = ctx.get_cores()
+        out = np.empty(self.L)
+        for c in range(self.L):
+            V = list(cores)
+            V[lp] = np.zeros_like(cores[lp])
+            V[lp][..., c] = cores[lp][..., c]
+            t = ctx.inner(V, lp, S)
+            out[c] = t[1, 1] - t[0, 1] if t[1, 0] != 0 else -np.inf
+        return out
+
     def configure_optimizer(self, optimizer='sgd', momentum=0.0, betas=(0.9, 0.999), eps=1e-8, clip=True):
         """The optimiser of gradient_step / train_gradient: 'sgd' (momentum, the reference's clip per core) or 'adam' (decoupled
         weight decay, no clip).  Resets the optimiser state."""

@@ -41,6 +41,7 @@ SYMBOLS = [
     'tnml_set_chain_scaling', 'tnml_predict_scaled',
     'tnml_set_shape_kernels', 'tnml_fixed_shape_steps',
     'tnml_inner', 'tnml_axpby',
+    'tnml_sample',
 ]
 
 
@@ -146,6 +147,7 @@ def lib():
         L.tnml_predict_scaled.argtypes = [vp, f32p, C.c_int, f32p, i32p]
         L.tnml_inner.argtypes = [vp, f32p, C.c_size_t, i32p, C.c_int, f64p, C.c_int, f64p]
         L.tnml_axpby.argtypes = [vp, C.c_double, C.c_double, f32p, C.c_size_t, i32p, C.c_int, i32p]
+        L.tnml_sample.argtypes = [vp, C.c_int, C.c_int, f64p, f64p, i32p, i32p, C.c_int, f64p, C.c_uint64, i32p, i32p, f64p]
         _lib = L
     return _lib
 
@@ -312,6 +314,41 @@ class Context:
         _chk(lib().tnml_axpby(self._h, float(alpha), float(beta), _ptr(flat, C.c_float), flat.size, _ptr(bond, C.c_int32), int(l_pos),
                               _ptr(out, C.c_int32)))
         return out
+
+    # ---- samples and log-likelihoods of the Born distribution
+    def sample(self, n, phi, w, classes=None, given=None, u=None, seed=0):
+        """-> (levels (n, N) int32, labels (n,) int32, logp (n, 2) float64).  phi (K, D), w (K,) float64: the grid; classes (n,) with
+        -1 = draw the label (None: all -1); given (n, n_given) levels of the first sites; u (n, N + 1) uniforms in [0, 1), or None:
+        the device's counter hash of (seed, sample, site).  Nothing else on the device changes."""
+        n = int(n)
+        phi = np.ascontiguousarray(phi, dtype=np.float64)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if phi.ndim != 2 or phi.shape[1] != self.D or w.shape != (phi.shape[0],):
+            raise TnmlError(-1, 'the grid has phi %s and w %s, not (K, %d) and (K,)' % (phi.shape, w.shape, self.D))
+        cp = gp = up = None
+        n_given = 0
+        if classes is not None:
+            classes = np.ascontiguousarray(classes, dtype=np.int32)
+            if classes.shape != (n,):
+                raise TnmlError(-1, 'classes has shape %s, not (%d,)' % (classes.shape, n))
+            cp = _ptr(classes, C.c_int32)
+        if given is not None:
+            given = np.ascontiguousarray(given, dtype=np.int32)
+            if given.ndim != 2 or given.shape[0] != n:
+                raise TnmlError(-1, 'given has shape %s, not (%d, n_given)' % (given.shape, n))
+            n_given = given.shape[1]
+            gp = _ptr(given, C.c_int32) if n_given else None
+        if u is not None:
+            u = np.ascontiguousarray(u, dtype=np.float64)
+            if u.shape != (n, self.N + 1):
+                raise TnmlError(-1, 'u has shape %s, not (%d, %d)' % (u.shape, n, self.N + 1))
+            up = _ptr(u, C.c_double)
+        levels = np.empty((max(n, 0), self.N), dtype=np.int32)
+        labels = np.empty(max(n, 0), dtype=np.int32)
+        logp = np.empty((max(n, 0), 2), dtype=np.float64)
+        _chk(lib().tnml_sample(self._h, n, phi.shape[0], _ptr(phi, C.c_double), _ptr(w, C.c_double), cp, gp, n_given, up,
+                               int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(levels, C.c_int32), _ptr(labels, C.c_int32), _ptr(logp, C.c_double)))
+        return levels, labels, logp
 
     # ---- batch
     def set_input(self, X, y=None):

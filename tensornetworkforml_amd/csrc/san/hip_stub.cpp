@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <sys/mman.h>
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -432,6 +433,75 @@ static void check_algebra(const AlgebraParams &p, dim3 g, dim3 b, size_t shm, in
   need(p.out, (size_t)p.n_prod * 2 * 8, "AlgebraParams.out");
 }
 
+// samples and log-likelihoods (kernels_sample.hip): one parameter block for the two environment launches and the walk.  The bond,
+// slot and tile tables, the classes and the given levels are read here as the kernels read them: every core, every environment a
+// workgroup of the launch stores or reads, the staging areas, the grid, the uniforms and the outputs with their extents; every
+// sample in exactly one tile, and that tile of its class.
+static void check_sample(const SampleParams &p, dim3 g, dim3 b, size_t shm, bool walk) {
+  scan(&p, sizeof p, "SampleParams");
+  if (p.N < 2 || p.D < 2 || p.D > kMaxD || p.L < 1 || p.l_pos < 0 || p.l_pos >= p.N) die("SampleParams: N %d D %d L %d l_pos %d", p.N, p.D, p.L, p.l_pos);
+  if (p.K < 2 || p.K > kSmpMaxK || p.n < 1 || p.n_given < 0 || p.n_given > p.N) die("SampleParams: K %d n %d n_given %d", p.K, p.n, p.n_given);
+  if (p.n_slots < 1 || p.n_slots > p.L + 1 || p.n_tiles < 1) die("SampleParams: %d slots %d tiles", p.n_slots, p.n_tiles);
+  need(p.bond, (size_t)(p.N - 1) * 4, "SampleParams.bond");
+  int mb = 1;
+  for (int i = 0; i < p.N; ++i) {
+    const int ml = i == 0 ? 1 : p.bond[i - 1], mr = i == p.N - 1 ? 1 : p.bond[i];
+    if (ml < 1 || mr < 1) die("SampleParams: site %d is %d x %d", i, ml, mr);
+    mb = mb > mr ? mb : mr;
+    const size_t ne = (size_t)ml * p.D * mr * (i == p.l_pos ? p.L : 1);
+    if (i == p.l_pos) need(p.lab, ne * 4, "SampleParams.lab");
+    else need(p.cores + (size_t)i * p.core_stride, ne * 4, "SampleParams.cores");
+  }
+  const size_t m2 = (size_t)mb * mb;
+  if (p.lds_m != mb || mb > kSmpMaxBond || p.env_stride < m2 || p.stage_stride < m2 * p.D) die("SampleParams: lds_m %d env_stride %zu stage_stride %zu for bond %d", p.lds_m, p.env_stride, p.stage_stride, mb);
+  need(p.S, (size_t)p.D * p.D * 8, "SampleParams.S");
+  need(p.slot_class, (size_t)p.n_slots * 4, "SampleParams.slot_class");
+  for (int j = 0; j < p.n_slots; ++j)
+    if (p.slot_class[j] < -1 || p.slot_class[j] >= p.L || (j && p.slot_class[j] <= p.slot_class[j - 1])) die("SampleParams: slot %d is class %d", j, p.slot_class[j]);
+  need(p.env_shared, (size_t)(p.N + 1) * p.env_stride * 8, "SampleParams.env_shared");
+  if (p.l_pos >= 1) need(p.env_slots, (size_t)p.n_slots * (p.l_pos + 1) * p.env_stride * 8, "SampleParams.env_slots");
+  need(p.status, 2 * 4, "SampleParams.status");
+  if (p.status[0] != 0 || p.status[1] != INT_MAX) die("SampleParams: status words %d %d at launch", p.status[0], p.status[1]);
+  if (!walk) {
+    if (p.phase != 1 && p.phase != 2) die("sample_env_kernel: phase %d", p.phase);
+    if (p.phase == 2 && p.l_pos < 1) die("sample_env_kernel: phase 2 with the label on site 0");
+    const unsigned want = p.phase == 1 ? 1u : (unsigned)p.n_slots;
+    if (g.x != want || g.y != 1 || g.z != 1 || b.x != 1024) die("sample_env_kernel phase %d: grid %u block %u for %d slots", p.phase, g.x, b.x, p.n_slots);
+    if (shm < sample_env_lds_bytes(mb, p.D) || m2 > 4 * 1024) die("sample_env_kernel: %zu bytes of LDS for bond %d", shm, mb);
+    need(p.stage, (size_t)want * p.stage_stride * 8, "SampleParams.stage");
+    return;
+  }
+  if (p.phase != 0) die("sample_walk_kernel: phase %d", p.phase);
+  if (g.x != (unsigned)p.n_tiles || g.y != 1 || g.z != 1 || b.x != 512) die("sample_walk_kernel: grid %u block %u for %d tiles", g.x, b.x, p.n_tiles);
+  if (shm < sample_walk_lds_bytes(mb, p.D, p.L, p.K)) die("sample_walk_kernel: %zu bytes of LDS for bond %d", shm, mb);
+  need(p.phi, (size_t)p.K * p.D * 8, "SampleParams.phi");
+  need(p.w, (size_t)p.K * 8, "SampleParams.w");
+  need(p.tile_slot, (size_t)p.n_tiles * 4, "SampleParams.tile_slot");
+  need(p.tile_samples, (size_t)p.n_tiles * kSmpTile * 4, "SampleParams.tile_samples");
+  need(p.classes, (size_t)p.n * 4, "SampleParams.classes");
+  if (p.n_given) need(p.given, (size_t)p.n * p.n_given * 4, "SampleParams.given");
+  if (p.u) need(p.u, (size_t)p.n * (p.N + 1) * 8, "SampleParams.u");
+  need(p.levels, (size_t)p.n * p.N * 4, "SampleParams.levels");
+  need(p.labels, (size_t)p.n * 4, "SampleParams.labels");
+  need(p.logp, (size_t)p.n * 2 * 8, "SampleParams.logp");
+  std::vector<char> seen((size_t)p.n, 0);
+  for (int t = 0; t < p.n_tiles; ++t) {
+    const int slot = p.tile_slot[t];
+    if (slot < 0 || slot >= p.n_slots) die("SampleParams: tile %d of slot %d", t, slot);
+    for (int k = 0; k < kSmpTile; ++k) {
+      const int smp = p.tile_samples[t * kSmpTile + k];
+      if (smp == -1) continue;
+      if (smp < 0 || smp >= p.n || seen[smp]) die("SampleParams: tile %d holds sample %d", t, smp);
+      seen[smp] = 1;
+      if (p.classes[smp] != p.slot_class[slot]) die("SampleParams: sample %d of class %d in a tile of class %d", smp, p.classes[smp], p.slot_class[slot]);
+      for (int i = 0; i < p.n_given; ++i)
+        if (p.given[(size_t)smp * p.n_given + i] < 0 || p.given[(size_t)smp * p.n_given + i] >= p.K) die("SampleParams: given level of sample %d site %d", smp, i);
+    }
+  }
+  for (int smp = 0; smp < p.n; ++smp)
+    if (!seen[smp]) die("SampleParams: sample %d is in no tile", smp);
+}
+
 // gradient training (kernels_optim.hip).  loss_cot_kernel: f and cot at their own strides, the labels of the chunk, one thread per
 // column of cot.  optim_step_kernel: one workgroup per site; every core's slot and its part of G, vel / m / v through the table.
 static void check_loss_cot(const LossCotParams &p, dim3 g, dim3 b, size_t shm) {
@@ -545,6 +615,10 @@ static void tr_struct(const AlgebraParams &p) {
   I(N) I(D) I(L) I(l_pos) I(n_prod) I(metric_sites) I(lds_m2) P(bond) P(off) P(w_plain) P(w_lab) P(v_plain) P(v_lab) P(metric) P(stage) I(stage_stride)
   P(half_E) I(half_stride) P(half_expo) P(out) P(status) R(alpha) R(beta) P(out_cores) P(out_lab) I(core_stride) I(lab_elems)
 }
+static void tr_struct(const SampleParams &p) {
+  I(N) I(D) I(L) I(l_pos) I(K) I(n) I(n_given) I(n_tiles) I(n_slots) I(phase) I(lds_m) P(bond) P(cores) P(lab) I(core_stride) P(S) P(phi) P(w) P(slot_class)
+  P(env_shared) P(env_slots) I(env_stride) P(stage) I(stage_stride) P(tile_slot) P(tile_samples) P(classes) P(given) P(u) I(seed) P(levels) P(labels) P(logp) P(status)
+}
 static void tr_struct(const InputGradPixels &p) { P(g) P(data) P(idx) P(out) I(b) I(N) I(D) }
 static void tr_struct(const BigExtArgs &p) { P(Eprev) P(x_km1) P(x_k) V(A) I(b_pad) P(Ecur) P(Pk) }
 static void tr_struct(const ChainSite &p) { I(core_off) I(is_label) I(n_in) I(n_out) I(s_in) I(s_d) I(s_out) I(x_site) I(env_out_off) }
@@ -586,6 +660,7 @@ static void tr_launch(const std::string &name, dim3 g, dim3 b, size_t shm, hipSt
     else if (is("OptimStepParams")) tr_struct(*(const OptimStepParams *)args[i]);
     else if (is("BigExtArgs")) tr_struct(*(const BigExtArgs *)args[i]);
     else if (is("AlgebraParams")) tr_struct(*(const AlgebraParams *)args[i]);
+    else if (is("SampleParams")) tr_struct(*(const SampleParams *)args[i]);
     else if (is("CoreView")) { const CoreView &v = *(const CoreView *)args[i]; tr(" [%s %d %d %d %d %d]", dp(v.base).c_str(), v.n_in, v.n_out, v.s_in, v.s_d, v.s_out); }
     else if (is("BigFrontTiles")) tr(" %d %d", ((int *)args[i])[0], ((int *)args[i])[1]);
     else if (is("float")) tr(" %.9g", *(float *)args[i]);
@@ -673,6 +748,8 @@ hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t s
     check_orth(*(const OrthParams *)args[0], g, b, shm, has("orth_chain_kernel") ? 1 : has("orth_store_kernel") ? 2 : 0);
   } else if (has("inner_chain_kernel") || has("inner_meet_kernel") || has("sum_place_kernel")) {
     check_algebra(*(const AlgebraParams *)args[0], g, b, shm, has("inner_chain_kernel") ? 0 : has("inner_meet_kernel") ? 1 : 2);
+  } else if (has("sample_env_kernel") || has("sample_walk_kernel")) {
+    check_sample(*(const SampleParams *)args[0], g, b, shm, has("sample_walk_kernel"));
   } else if (has("input_grad_onehot_kernel")) {   // (f, f_bpad, L, b, cot, b_pad)
     const int fbp = *(int *)args[1], L = *(int *)args[2], bb = *(int *)args[3], bp = *(int *)args[5];
     if (bb < 1 || bb > bp || bp > fbp || (size_t)g.x * b.x < (size_t)bp) die("input_grad_onehot_kernel: b %d b_pad %d f_bpad %d grid %u x %u", bb, bp, fbp, g.x, b.x);

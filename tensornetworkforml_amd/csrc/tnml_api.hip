@@ -339,6 +339,19 @@ struct tnml_ctx {
     std::vector<int> bond_host;              // host copies of the two tables for the call in flight (they outlive the asynchronous upload)
     std::vector<long long> off_host;
   } alg;
+  // samples and log-likelihoods.  One group, regrown when a call needs more of any member: the tables of the
+  // call (bonds, slots, tiles, classes, given levels), the grid and its metric, the uniforms (u_cap doubles, 1 when they are hashed),
+  // the environment stacks (shared part and env_slots per-slot parts of lpos_cap sites each, env_stride doubles a site), the
+  // staging areas of the environment workgroups, the outputs and the status words.
+  struct {
+    int *bond = nullptr, *slot_class = nullptr, *tile_slot = nullptr, *tile_samples = nullptr, *classes = nullptr, *given = nullptr;
+    int *levels = nullptr, *labels = nullptr, *status = nullptr;
+    double *S = nullptr, *phi = nullptr, *w = nullptr, *u = nullptr, *env_shared = nullptr, *env_slots = nullptr, *stage = nullptr, *logp = nullptr;
+    size_t n_cap = 0, given_cap = 0, u_cap = 0, tiles_cap = 0, slots_cap = 0, slot_sites_cap = 0;
+    int m_cap = 0;
+    std::vector<int> host;                   // host copies of the tables for the call in flight (they outlive the asynchronous upload)
+    std::vector<double> hostd;
+  } smp;
   // multi-GPU
   ncclComm_t comm = nullptr;
   int rank = 0, nranks = 1;
@@ -2055,6 +2068,152 @@ extern "C" int tnml_axpby(tnml_ctx *c, double alpha, double beta, const float *o
   for (int i = 0; i < N - 1; ++i) bond_out[i] = nb[i];
   cores_changed(c);
   if (c->opt_s0) c->opt.l_pos = -1;                            // vel / m / v refer to the old cores: unbound until tnml_optim_reset
+  return TNML_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// samples and log-likelihoods of the Born distribution (kernels_sample.hip)
+// ---------------------------------------------------------------------------------------------
+// The group of the call, (re)sized when any member is too small: all of it or none
+static int smp_ensure(tnml_ctx *c, size_t n, size_t given, size_t u, size_t tiles, size_t slots, size_t slot_sites, int mb) {
+  auto &g = c->smp;
+  if (g.m_cap > 0 && g.n_cap >= n && g.given_cap >= given && g.u_cap >= u && g.tiles_cap >= tiles && g.slots_cap >= slots &&
+      g.slot_sites_cap >= slot_sites && g.m_cap >= mb)
+    return TNML_OK;
+  const size_t N = (size_t)c->N, D = (size_t)c->D;
+  const size_t n_cap = std::max(g.n_cap, n), given_cap = std::max(std::max(g.given_cap, given), (size_t)1), u_cap = std::max(std::max(g.u_cap, u), (size_t)1);
+  const size_t tiles_cap = std::max(g.tiles_cap, tiles), slots_cap = std::max(g.slots_cap, slots);
+  const size_t slot_sites_cap = std::max(std::max(g.slot_sites_cap, slot_sites), (size_t)1);
+  const int m_cap = std::max(g.m_cap, mb);
+  g.n_cap = g.given_cap = g.u_cap = g.tiles_cap = g.slots_cap = g.slot_sites_cap = 0;
+  g.m_cap = 0;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const size_t m2 = (size_t)m_cap * m_cap;
+  int rc = make_group(c, "the scratch of the sampler", {
+      own_dev(g.bond, N), own_dev(g.slot_class, slots_cap), own_dev(g.tile_slot, tiles_cap), own_dev(g.tile_samples, tiles_cap * kSmpTile),
+      own_dev(g.classes, n_cap), own_dev(g.given, given_cap), own_dev(g.S, D * D), own_dev(g.phi, (size_t)kSmpMaxK * D),
+      own_dev(g.w, (size_t)kSmpMaxK), own_dev(g.u, u_cap), own_dev(g.env_shared, (N + 1) * m2), own_dev(g.env_slots, slot_sites_cap * m2),
+      own_dev(g.stage, slots_cap * m2 * D), own_dev(g.levels, n_cap * N), own_dev(g.labels, n_cap), own_dev(g.logp, 2 * n_cap),
+      own_dev(g.status, 2)});
+  if (rc) return rc;
+  g.n_cap = n_cap; g.given_cap = given_cap; g.u_cap = u_cap; g.tiles_cap = tiles_cap; g.slots_cap = slots_cap;
+  g.slot_sites_cap = slot_sites_cap; g.m_cap = m_cap;
+  return TNML_OK;
+}
+
+extern "C" int tnml_sample(tnml_ctx *c, int n, int K, const double *phi, const double *w, const int32_t *classes, const int32_t *given,
+                           int n_given, const double *u, uint64_t seed, int32_t *levels_out, int32_t *labels_out, double *logp_out) {
+  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
+  if (!levels_out || !labels_out || !logp_out) return fail(TNML_ERR_ARG, "tnml_sample: an output is NULL");
+  if (!phi || !w) return fail(TNML_ERR_ARG, "tnml_sample: %s is NULL", phi ? "w" : "phi");
+  if (n < 1) return fail(TNML_ERR_ARG, "tnml_sample: n = %d < 1", n);
+  if (K < 2 || K > kSmpMaxK) return fail(TNML_ERR_ARG, "tnml_sample: K = %d outside [2, %d]", K, kSmpMaxK);
+  const int N = c->N, D = c->D, L = c->L;
+  if (n_given < 0 || n_given > N) return fail(TNML_ERR_ARG, "tnml_sample: n_given = %d outside [0, %d]", n_given, N);
+  if (n_given > 0 && !given) return fail(TNML_ERR_ARG, "tnml_sample: given is NULL with n_given = %d", n_given);
+  for (int k = 0; k < K; ++k) {
+    if (!(w[k] > 0.0) || !std::isfinite(w[k])) return fail(TNML_ERR_ARG, "tnml_sample: weight %d is %g (weights are positive and finite)", k, w[k]);
+    for (int d = 0; d < D; ++d)
+      if (!std::isfinite(phi[(size_t)k * D + d])) return fail(TNML_ERR_ARG, "tnml_sample: phi[%d][%d] is not finite", k, d);
+  }
+  if (classes)
+    for (int s = 0; s < n; ++s)
+      if (classes[s] < -1 || classes[s] >= L) return fail(TNML_ERR_ARG, "tnml_sample: class %d of sample %d outside [-1, %d)", (int)classes[s], s, L);
+  for (size_t e = 0; e < (size_t)n * n_given; ++e)
+    if (given[e] < 0 || given[e] >= K)
+      return fail(TNML_ERR_ARG, "tnml_sample: given level %d of sample %zu, site %zu outside [0, %d)", (int)given[e], e / n_given, e % n_given, K);
+  if (u)
+    for (size_t e = 0; e < (size_t)n * (N + 1); ++e)
+      if (!(u[e] >= 0.0 && u[e] < 1.0)) return fail(TNML_ERR_ARG, "tnml_sample: u[%zu][%zu] = %g outside [0, 1)", e / (N + 1), e % (N + 1), u[e]);
+  if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
+  if (c->comm) return fail(TNML_ERR_STATE, "tnml_sample runs on one GPU: this context has a communicator attached");
+  int mb = 1;
+  for (int i = 0; i < N - 1; ++i) mb = std::max(mb, c->bond[i]);
+  const size_t lds = std::max(sample_env_lds_bytes(mb, D), sample_walk_lds_bytes(mb, D, L, K));
+  if (lds > kLdsMax || mb > kSmpMaxBond)
+    return fail(TNML_ERR_SHAPE, "tnml_sample at bond %d, D = %d, L = %d, K = %d: the core, the environment and the tile of %d samples take %zu bytes of LDS "
+                "(160 KB and bonds up to %d fit)", mb, D, L, K, kSmpTile, lds, kSmpMaxBond);
+  // slots in the order -1, 0 .. L-1 of those the call uses; tiles of one slot each
+  auto &g = c->smp;
+  std::vector<int> slot_of((size_t)L + 1, -1), count((size_t)L + 1, 0);
+  for (int s = 0; s < n; ++s) count[(classes ? classes[s] : -1) + 1]++;
+  int n_slots = 0, n_tiles = 0;
+  for (int q = 0; q <= L; ++q)
+    if (count[q]) { slot_of[q] = n_slots++; n_tiles += (count[q] + kSmpTile - 1) / kSmpTile; }
+  // host tables: bond [N] | slot_class [n_slots] | tile_slot [n_tiles] | tile_samples [n_tiles][16] | classes [n]
+  const size_t o_slot = (size_t)N, o_tslot = o_slot + n_slots, o_tsmp = o_tslot + n_tiles, o_cls = o_tsmp + (size_t)n_tiles * kSmpTile;
+  g.host.assign(o_cls + n, -1);
+  for (int i = 0; i < N - 1; ++i) g.host[i] = c->bond[i];
+  g.host[N - 1] = 1;
+  {
+    std::vector<int> next((size_t)L + 1, 0);
+    int t = 0;
+    for (int q = 0; q <= L; ++q)
+      if (count[q]) {
+        g.host[o_slot + slot_of[q]] = q - 1;
+        next[q] = t * kSmpTile;
+        const int nt = (count[q] + kSmpTile - 1) / kSmpTile;
+        for (int k = 0; k < nt; ++k) g.host[o_tslot + t + k] = slot_of[q];
+        t += nt;
+      }
+    for (int s = 0; s < n; ++s) {
+      const int q = (classes ? classes[s] : -1) + 1;
+      g.host[o_tsmp + next[q]++] = s;
+      g.host[o_cls + s] = q - 1;
+    }
+  }
+  // the grid's metric S = sum_k w_k phi_k phi_k^T, in this order
+  g.hostd.assign((size_t)D * D, 0.0);
+  for (int k = 0; k < K; ++k)
+    for (int d = 0; d < D; ++d)
+      for (int e = 0; e < D; ++e) g.hostd[(size_t)d * D + e] += w[k] * phi[(size_t)k * D + d] * phi[(size_t)k * D + e];
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = smp_ensure(c, (size_t)n, (size_t)n * n_given, u ? (size_t)n * (N + 1) : 0, (size_t)n_tiles, (size_t)n_slots,
+                      (size_t)n_slots * (c->l_pos + 1), mb);
+  if (rc) return rc;
+  const int init_status[2] = {0, INT_MAX};
+  HIP_TRY(hipMemcpyAsync(g.bond, g.host.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(g.slot_class, g.host.data() + o_slot, (size_t)n_slots * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(g.tile_slot, g.host.data() + o_tslot, (size_t)n_tiles * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(g.tile_samples, g.host.data() + o_tsmp, (size_t)n_tiles * kSmpTile * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(g.classes, g.host.data() + o_cls, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(g.S, g.hostd.data(), (size_t)D * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(g.phi, phi, (size_t)K * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(g.w, w, (size_t)K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(g.status, init_status, sizeof init_status, hipMemcpyHostToDevice, c->stream));
+  if (n_given) HIP_TRY(hipMemcpyAsync(g.given, given, (size_t)n * n_given * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if (u) HIP_TRY(hipMemcpyAsync(g.u, u, (size_t)n * (N + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  SampleParams p{};
+  p.N = N; p.D = D; p.L = L; p.l_pos = c->l_pos; p.K = K;
+  p.n = n; p.n_given = n_given; p.n_tiles = n_tiles; p.n_slots = n_slots;
+  p.bond = g.bond; p.cores = c->cores; p.lab = c->lab[c->lab_cur]; p.core_stride = c->core_stride;
+  p.S = g.S; p.phi = g.phi; p.w = g.w; p.slot_class = g.slot_class;
+  const size_t m2 = (size_t)g.m_cap * g.m_cap;
+  p.env_shared = g.env_shared; p.env_slots = g.env_slots; p.env_stride = m2;
+  p.stage = g.stage; p.stage_stride = m2 * D;
+  p.tile_slot = g.tile_slot; p.tile_samples = g.tile_samples; p.classes = g.classes; p.given = n_given ? g.given : nullptr;
+  p.u = u ? g.u : nullptr; p.seed = seed;
+  p.levels = g.levels; p.labels = g.labels; p.logp = g.logp; p.status = g.status;
+  if (!launch_sample(p, mb, c->stream)) {
+    (void)hipStreamSynchronize(c->stream);                       // (the uploads read the caller's memory)
+    return fail(TNML_ERR_SHAPE, "tnml_sample: the launch was refused (bond %d)", mb);
+  }
+  HIP_TRY(hipGetLastError());
+  int st[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(st, g.status, sizeof st, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (st[0] & 1) return fail(TNML_ERR_NONFINITE, "tnml_sample: a core element is not finite");
+  if (st[0] & 2) {
+    const int s = st[1] >= 0 && st[1] < n ? st[1] : 0, cls = classes ? classes[s] : -1;
+    if (cls >= 0)
+      return fail(TNML_ERR_ARG, "tnml_sample: sample %d is conditioned on class %d%s, which the model gives zero weight", s, cls,
+                  n_given ? " and on its given levels" : "");
+    return fail(TNML_ERR_ARG, "tnml_sample: sample %d (class -1) is conditioned on given levels of zero weight, or the model is zero", s);
+  }
+  HIP_TRY(hipMemcpyAsync(levels_out, g.levels, (size_t)n * N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(labels_out, g.labels, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(logp_out, g.logp, (size_t)2 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return TNML_OK;
 }
 

@@ -458,4 +458,43 @@ size_t algebra_meet_lds_bytes(int mb_w, int mb_v);
 bool launch_inner(const AlgebraParams &p, int mb_w, int mb_v, hipStream_t st);
 bool launch_sum_place(const AlgebraParams &p, hipStream_t st);
 
+// Samples and log-likelihoods of the Born distribution (kernels_sample.hip): one parameter block for the
+// environment kernel (phase 1: the sites all class slots share, phase 2: one workgroup per slot) and the walk kernel (one workgroup
+// per tile of kSmpTile samples of ONE slot).  A slot is a class the call conditions on, or -1 for the label summed; the call's slots
+// are numbered 0 .. n_slots-1 in slot_class.
+constexpr int kSmpTile = 16;
+constexpr int kSmpMaxK = 256;
+constexpr int kSmpMaxBond = 64;
+struct SampleParams {
+  int N, D, L, l_pos, K;
+  int n, n_given, n_tiles, n_slots;
+  int phase;               // environment kernel: 1 or 2 (launch_sample fills it)
+  int lds_m;               // LDS geometry: the largest bond (launch_sample fills it)
+  const int *bond;         // [N-1]
+  const float *cores, *lab;
+  size_t core_stride;
+  const double *S;         // [D][D] sum_k w_k phi_k phi_k^T
+  const double *phi, *w;   // [K][D], [K]
+  const int *slot_class;   // [n_slots]
+  double *env_shared;      // [N+1][env_stride]: R_i for i > l_pos (R_N = 1)
+  double *env_slots;       // [n_slots][l_pos+1][env_stride]: R_i for 1 <= i <= l_pos
+  size_t env_stride;
+  double *stage;           // [n_slots][stage_stride] the metric-folded core of the site a workgroup is on
+  size_t stage_stride;
+  const int *tile_slot;    // [n_tiles]
+  const int *tile_samples; // [n_tiles][kSmpTile] sample numbers, -1 behind the last of a slot
+  const int *classes;      // [n]
+  const int *given;        // [n][n_given] (not read when n_given is 0)
+  const double *u;         // [n][N+1], or null: the counter hash of (seed, sample, site)
+  unsigned long long seed;
+  int *levels;             // [n][N]
+  int *labels;             // [n]
+  double *logp;            // [n][2]
+  int *status;             // [0] bit 1 non-finite, bit 2 a sample of zero weight; [1] the smallest such sample
+};
+size_t sample_env_lds_bytes(int mb, int D);
+size_t sample_walk_lds_bytes(int mb, int D, int L, int K);
+// the two environment launches and the walk of one tnml_sample call; mb: largest bond.  false: refused (geometry / LDS)
+bool launch_sample(const SampleParams &p, int mb, hipStream_t st);
+
 }  // namespace tnml

@@ -38,6 +38,8 @@ def main(argv=None):
                     help='print the cosine and the relative distance between this model and another pickled one (same N, D, L and label position)')
     ap.add_argument('--scaled-chains', dest='scaled_chains', action='store_true',
                     help='carry a power-of-two exponent per sample along the chains (Network.scaled_chains): for a model whose partial products leave float32')
+    from tensornetworkforml_amd.evaluate_diagonals import add_sample_arguments
+    add_sample_arguments(ap)
     args = ap.parse_args(argv)
 
     with open(args.filename, 'rb') as fh:
@@ -64,6 +66,12 @@ def main(argv=None):
     if args.compare:
         from tensornetworkforml_amd.evaluate_diagonals import compare_models
         compare_models(net, args.compare)
+    if args.sample:
+        from tensornetworkforml_amd.evaluate_diagonals import write_samples
+        write_samples(net, args.sample, args.sample_n, args.sample_class, args.seed)
+    if args.log_prob:
+        from tensornetworkforml_amd.evaluate_diagonals import print_log_prob
+        print_log_prob(net, data01, labels01)
     if args.saliency:
         import numpy as np
         if args.features:

@@ -39,6 +39,39 @@ def compare_models(net, path):
     return cos, dist
 
 
+def write_samples(net, path, n, cls, seed):
+    """n images drawn from the model's own distribution |f|^2 over 8-bit pixels (Network.sample), (n, h, w) where N is a square;
+    cls None draws the label with the image.  Prints the mean log-probability per class."""
+    X, labels, logp, _ = net.sample(n, classes=cls, seed=seed)
+    side = int(round(np.sqrt(net.N)))
+    np.save(path, X.reshape(n, side, side) if side * side == net.N else X)
+    for c in sorted(set(int(v) for v in labels)):
+        sel = labels == c
+        print('\tSamples of class %d: %d, mean log p(x%s) %.4f' % (c, int(sel.sum()), ', l' if cls is None else ' | l', float(logp[sel, 0].mean())))
+    print('\tSamples written to   ', path, X.shape)
+    return X, labels, logp
+
+
+def add_sample_arguments(ap):
+    ap.add_argument('--sample', metavar='OUT.npy', default=None, help="write images drawn from the model's distribution |f|^2 over 8-bit pixels (Network.sample)")
+    ap.add_argument('--sample-n', dest='sample_n', type=int, default=64, help='number of images of --sample')
+    ap.add_argument('--sample-class', dest='sample_class', type=int, default=None, help='condition the images on this class (default: draw the label too)')
+    ap.add_argument('--seed', type=int, default=0, help='seed of the uniforms of --sample')
+    ap.add_argument('--log-prob', dest='log_prob', action='store_true',
+                    help='print the mean log p(x, y) of the test set under the model, pixels rounded to 8 bits (Network.log_prob)')
+
+
+def print_log_prob(net, pixels, labels, chunk=4096):
+    """mean log p(x, y) over a data set: integer pixels are levels 0 .. 255, pixels in [0, 1] are rounded to the nearest of 256 levels"""
+    pixels = np.asarray(pixels).reshape(len(pixels), -1)
+    lev = pixels if np.issubdtype(pixels.dtype, np.integer) else np.rint(np.clip(pixels, 0.0, 1.0) * 255.0)
+    lev = lev.astype(np.int32)
+    labels = np.asarray(labels)
+    lp = np.concatenate([net.log_prob(lev[i:i + chunk], classes=labels[i:i + chunk], joint=True)[0] for i in range(0, len(lev), chunk)])
+    print('\tMean log p(x, y):     %.4f over %d samples (%.4f per pixel)' % (float(lp.mean()), len(lp), float(lp.mean()) / net.N))
+    return lp
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Evaluate a trained Tensor Network on a generated dataset of diagonals')
     ap.add_argument('--filename', type=str, default='trained_diag_model.dat', help='Pickled network to load')
@@ -52,6 +85,7 @@ def main(argv=None):
                     help='print the cosine and the relative distance between this model and another pickled one (same N, D, L and label position)')
     ap.add_argument('--scaled-chains', dest='scaled_chains', action='store_true',
                     help='carry a power-of-two exponent per sample along the chains (Network.scaled_chains): for a model whose partial products leave float32')
+    add_sample_arguments(ap)
     args = ap.parse_args(argv)
 
     with open(args.filename, 'rb') as fh:
@@ -69,6 +103,10 @@ def main(argv=None):
         write_spectra(net, args.spectra)
     if args.compare:
         compare_models(net, args.compare)
+    if args.sample:
+        write_samples(net, args.sample, args.sample_n, args.sample_class, args.seed)
+    if args.log_prob:
+        print_log_prob(net, data, label)
     print('\tAccuracy:            ', acc)
     print('\tMean Absolute Error: ', mae)
     return acc, mae
