@@ -312,7 +312,7 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
   const bool short_rows = (r <= c);
   const int n = short_rows ? r : c, ne = n + (n & 1), len = short_rows ? c : r;
 
-  unsigned long long t_c0 = 0, t_r0 = 0, t_c1 = 0, t_c2 = 0, t_c2b = 0, t_c2c = 0;
+  unsigned long long t_c0 = 0, t_r0 = 0, t_c1 = 0, t_c2 = 0, t_c2b = 0;
   unsigned long long t_p[5] = {0, 0, 0, 0, 0};
 #define TNML_STAMP(i) if (p.stamps && tid == 0) t_p[i] = __builtin_amdgcn_s_memtime()
   if (p.stamps && tid == 0) { t_c0 = __builtin_amdgcn_s_memtime(); t_r0 = __builtin_amdgcn_s_memrealtime(); }
@@ -1102,7 +1102,7 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
   }
   lds_barrier();
 
-  if (p.stamps && tid == 0) t_c2b = __builtin_amdgcn_s_memtime();
+  if (p.stamps && tid == 0) { t_c2b = __builtin_amdgcn_s_memtime(); p.stamps[6] = (double)(t_c2b - t_c2); }
   // ---- adaptive truncation (not reference behaviour: the reference computes this index and never uses it,
   // Network_class.py:889-891): keep the fewest singular values whose cumulative share exceeds the threshold
   // (the output pointers and strides as locals: the epilogues of the products below run per element)
@@ -1160,6 +1160,41 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
     }
    }
   lds_barrier();
+  // The next step's projections are formed by the helper workgroups: they get the behind core before its rounding to float32
+  // (the projection divides by sigma: rounding errors of A' would come back multiplied by sigma_max / sigma_j) and 1 / sigma, so that
+  // the stores travel while the norm environment is formed; the batch-side workgroups extend their environments with the float32
+  // core in its slot.  The two are all that the helpers' first product level needs, so they get a token of their own and the
+  // projections start beside the norm environment.  ONE wave stores them (agent scope), drains its own counter and raises the
+  // token: no meeting of the workgroup, the other waves go on meanwhile.
+  auto publish_core = [&]() {
+    if (wave_u == (NT >> 6) - 1) {
+      // (layout of the block: persist_pub_doubles; r * mk is even, 1 / sigma ends in a padded double where mk is odd; two doubles per
+      // lane and store, from the LDS copies)
+      const int ln = tid & 63;
+      const __amdgpu_buffer_rsrc_t rP = sc1_rsrc(p.Apub);
+      for (int e = ln; e < (r * mk) >> 1; e += 64) st_sc1_b128(rP, (unsigned)e * 16u, pack_d2(PL.Ad[2 * e], PL.Ad[2 * e + 1]));
+      for (int e = ln; e < (mk + 1) >> 1; e += 64) {
+        const double i0 = k.dSq[ne + 2 * e], i1 = 2 * e + 1 < mk ? k.dSq[ne + 2 * e + 1] : 0.0;
+        st_sc1_b128(rP, (unsigned)(r * mk + 2 * e) * 8u, pack_d2(i0 * i0, i1 * i1));
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (ln == 0) { unsigned *const aflag = p.aflag; __hip_atomic_store(aflag, (unsigned)p.coretoken, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    }
+  };
+  // Where the short side is the behind core (every uniform step of a sweep), A' (PL.Ad) and 1 / sigma (dSq[ne + .]) are complete at
+  // the barrier above, so the token goes out HERE, in front of T2 = Nh . Cb: T2 is the first product of the next norm environment,
+  // which no helper reads, and everything in front of the token is on the step's chain (the helpers' part 2 starts at the token and
+  // the next step's front waits for their arrivals), while what follows it runs beside them.  Safe without a further barrier: the
+  // publishing wave only READS PL.Ad and dSq, which nothing writes again before the next step's front; T2 reads dNh and sCb and
+  // writes dT2, the long-side product (last step of a launch only) reads fB and dVs and writes memory; the helpers read only the
+  // published block, whose previous content they finished with before their arrivals of this step, which the front has seen.
+  // T2's tiles are dealt from wave 0 (6 tiles at bond 20), so the publishing wave, the last one, has none of them (but at the last
+  // step of a launch, where the ahead core's tiles come first).  Its drain is longer than T2: the workgroup waits for it at the
+  // barrier below, 1.2 k cycles at bond 20, which the helpers' chain hides.
+  if (p.persist && short_rows) {
+    publish_core();
+    if (p.stamps && tid == 0) { const unsigned long long now = __builtin_amdgcn_s_memtime(); p.stamps[7] = (double)(now - t_c2b); t_c2b = now; }
+  }
   // long-side factor: W (q_j / sigma_j^(1/2)); columns s', inner index the short one.  When the short side is the behind core
   // (short_rows), the first product of the next behind norm environment, T2 = Nh . Cb, needs nothing the long-side product
   // writes: the two run back to back without a barrier, their tiles dealt to the waves as one list.
@@ -1188,31 +1223,19 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
              st_behind(__mul24(h_, ob_s_h) + dk * ob_s_d + __mul24(sp, ob_s_m), v);
            });
   }
-  lds_barrier();
-  if (p.persist) {
-    // The next step's projections are formed by the helper workgroups: they get the behind core before its rounding to float32
-    // (the projection divides by sigma: rounding errors of A' would come back multiplied by sigma_max / sigma_j) and 1 / sigma, now,
-    // so that the stores travel while the norm environment is formed; the batch-side workgroups extend their environments with
-    // the float32 core in its slot.  The two are all that the helpers' first product level needs, so they get a token of their own
-    // here and the projections start beside the norm environment below.  ONE wave stores them (agent scope), drains its own counter
-    // and raises the token: no meeting of the workgroup, the other waves are in phase 10 meanwhile (the last wave: the norm
-    // environment's few tiles are dealt from wave 0).
-    if (wave_u == (NT >> 6) - 1) {
-      // (layout of the block: persist_pub_doubles; r * mk is even, 1 / sigma ends in a padded double where mk is odd; two doubles per
-      // lane and store, from the LDS copies)
-      const int ln = tid & 63;
-      const __amdgpu_buffer_rsrc_t rP = sc1_rsrc(p.Apub);
-      for (int e = ln; e < (r * mk) >> 1; e += 64) st_sc1_b128(rP, (unsigned)e * 16u, pack_d2(PL.Ad[2 * e], PL.Ad[2 * e + 1]));
-      for (int e = ln; e < (mk + 1) >> 1; e += 64) {
-        const double i0 = k.dSq[ne + 2 * e], i1 = 2 * e + 1 < mk ? k.dSq[ne + 2 * e + 1] : 0.0;
-        st_sc1_b128(rP, (unsigned)(r * mk + 2 * e) * 8u, pack_d2(i0 * i0, i1 * i1));
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (ln == 0) { unsigned *const aflag = p.aflag; __hip_atomic_store(aflag, (unsigned)p.coretoken, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    }
-  }
+  lds_barrier();                            // (stays where the token went first: phase 10 reads dT2)
+  // chain-end steps (the behind core comes out of the long-side product, PL.Ad is written in its epilogue): the token goes out
+  // here, beside phase 10 (the last wave: the norm environment's few tiles are dealt from wave 0)
+  if (p.persist && !short_rows) publish_core();
 
-  if (p.stamps && tid == 0) t_c2c = __builtin_amdgcn_s_memtime();
+  if (p.stamps && tid == 0) {
+    // [7]: sort to "core token issued"; [38]: from there to "T2 done" where the token went in front of T2, else 0 (T2 is then
+    // part of phase 10, or of the cores on the per-step path); t_c2b from here on: start of phase 10
+    const unsigned long long now = __builtin_amdgcn_s_memtime();
+    if (p.persist && short_rows) p.stamps[38] = (double)(now - t_c2b);
+    else { p.stamps[7] = (double)(now - t_c2b); p.stamps[38] = 0.0; }
+    t_c2b = now;
+  }
   // ---- phase 10: behind norm environment of the next step ------------------------------------------
   if (Nh_new) {
     if (!short_rows) {
@@ -1236,7 +1259,7 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
     p.stamps[3] = (double)(t_r3 - t_r0); p.stamps[4] = (double)sweeps; p.stamps[5] = (double)n;
     p.stamps[50] = (double)round_idx;                 // rounds actually run (the sliding window stops inside a sweep)
     for (int i = 0; i < 5; ++i) p.stamps[9 + i] = (double)(t_p[i] - (i ? t_p[i - 1] : t_c0));
-    p.stamps[6] = (double)(t_c2b - t_c2); p.stamps[7] = (double)(t_c2c - t_c2b); p.stamps[8] = (double)(t_c3 - t_c2c);
+    p.stamps[8] = (double)(t_c3 - t_c2b);      // ([7], [38]: written in phase 9)
   }
 
   // ---- phase 11: metrics of this step (var_hist, Network_class.py:739-750) --------------------------

@@ -127,7 +127,7 @@ struct NarrowParams {
   const unsigned *pready;  // >= pwant: every helper workgroup has stored its slice of the three
   unsigned pwant;
   double *Apub;            // out: behind core before rounding [D h][m], 1 / sigma [m], next behind norm environment [m][m]
-  unsigned *aflag;         // set to coretoken once the behind core before rounding and 1 / sigma are stored (right after phase 9): the
+  unsigned *aflag;         // set to coretoken once the behind core before rounding and 1 / sigma are stored (in phase 9, as soon as both are complete): the
                            // helpers start the projections that do not need the norm environment
   unsigned *coreflag;      // set to coretoken at the end of the step: the norm environment in Apub and the float32 behind core are stored
                            // (helpers: the L2 projection; batch side: extends)
