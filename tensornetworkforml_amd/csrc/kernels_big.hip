@@ -669,8 +669,13 @@ __global__ __launch_bounds__(1024) void big_jacobi_kernel(BigJacobiArgs a) {
             const double b11 = fma(-tq[u].x, a12, a11), b12 = fma(tq[u].x, a11, a12);
             const double b21 = fma(-tq[u].x, a22, a21), b22 = fma(tq[u].x, a21, a22);
             const double c00 = tp[u].y * tq[u].y, corr = rot_corr(tp[u].x, tp[u].y) * rot_corr(tq[u].x, tq[u].y);
+            // The annihilated element of a diagonal block keeps its computed value.  t is a float32 number formed from float32
+            // predictions of the pair, so the rotation -- orthogonal to float64 accuracy -- leaves ~1e-7 of the old element; an exact
+            // zero written instead is no similarity transform: it moved every small eigenvalue by ~2e-8 lambda_max (singular values
+            // below 1e-4 sigma_max came out wrong, exact zeros as 1.5e-4 sigma_max: tests/test_svd_split_gpu.py,
+            // tests/emulation/jacobi_annihilated_element_emulation.py).  The next sweep sees the remainder like any other element.
+            // (The in-LDS kernel still writes the zero: DESIGN.md 5.3, "Constructed spectra".)
             n11[u] = (b11 * c00) * corr; n12[u] = (b12 * c00) * corr; n21[u] = (b21 * c00) * corr; n22[u] = (b22 * c00) * corr;
-            if (itDiag[u] && tq[u].x != 0.0) { n12[u] = 0.0; n21[u] = 0.0; }
           }
 #pragma unroll
           for (int u = 0; u < K; ++u) {

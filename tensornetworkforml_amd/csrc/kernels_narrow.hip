@@ -1007,6 +1007,8 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
           const double b21 = fma(-tq.x, a22, a21), b22 = fma(tq.x, a21, a22);
           const double c00 = tp.y * tq.y, corr = rot_corr(tp.x, tp.y) * rot_corr(tq.x, tq.y);
           double n11 = (b11 * c00) * corr, n12 = (b12 * c00) * corr, n21 = (b21 * c00) * corr, n22 = (b22 * c00) * corr;
+          // (Known defect, DESIGN.md 5.3 "Constructed spectra": t is a float32 number, so the rotation leaves ~1e-7 of the element, and
+          // the exact zero written here discards it -- no similarity transform: every small eigenvalue moves by ~2e-8 lambda_max.)
           if (itDiag[u] && tq.x != 0.0) { n12 = 0.0; n21 = 0.0; }   // the annihilated element, exactly
           Gn[itD11[u]] = n11; Gn[itD12[u]] = n12;
           if (!itDiag[u]) Gn[itD21[u]] = n21;                   // (n21 of a diagonal block is n12's mirror)
@@ -1068,8 +1070,15 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
   if (use_chol) {
     // back from the eigenvectors u of G' = L^T L to those of G: v = L u / sqrt(lambda) (columns stay at their positions)
     for (int j = tid; j < n; j += NT) {                  // 1 / sqrt(lambda_j) once per column (dSq is free until phase 9)
+      // (trace ~ 1 here.  An eigenvalue at kJacobiAbs is what the factorisation made of the rounding noise a rank-deficient G leaves
+      // on its diagonal -- float32 noise of B anyway: L u / sqrt(lambda) of it is a unit vector in no particular direction, and as a
+      // kept column it put entries of 1e-2 .. 1e-1 sqrt(sigma_max) where zeros belong.  Such columns are zero; nothing else changes.
+      // The floor as a numerator of 1.0 or 0.0 chosen by the high word of lambda against that of kJacobiAbs: measured on C3,
+      // `ls > kJacobiAbs ? 1.0 / sqrt(ls) : 0.0` costs 1.1 % of the step rate and a float compare 0.4 %, this form nothing.)
+      constexpr int kAbsHi = (int)(__builtin_bit_cast(unsigned long long, kJacobiAbs) >> 32);
+      static_assert(kAbsHi == 0x3CD203AF, "high word of kJacobiAbs = 1e-15");
       const double ls = Gc[j * ne + j];
-      k.dSq[j] = ls > 1e-300 ? 1.0 / sqrt(ls) : 0.0;
+      k.dSq[j] = ls > 1e-300 ? __hiloint2double(__double2hiint(ls) > kAbsHi ? 0x3FF00000 : 0, 0) / sqrt(ls) : 0.0;
     }
     lds_barrier();
     mm_lds(1, n, n, n, Lm, 0, 1, ne, V, 0, ne, 1, [&](int, int i, int j, double v) { Gn[i * ne + j] = v * k.dSq[j]; });
