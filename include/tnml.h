@@ -522,7 +522,7 @@ int tnml_axpby(tnml_ctx *ctx, double alpha, double beta, const float *other_flat
  * levels_out [n][N], labels_out [n] (the given class where there is one), logp_out [n][2]: [0] the log-probability of all levels
  * [and the drawn label] [given the class], [1] the sum of the terms of the clamped sites alone -- with the label site outside
  * the prefix, or a given class, [0] - [1] is the log-density of the completion given the prefix.  n_given = N is a likelihood
- * call: nothing but a label is drawn.  Masks other than a prefix are not supported.
+ * call: nothing but a label is drawn.  For known sites other than a prefix see tnml_sample_masked below.
  * Every sum runs in a fixed order: two calls with the same arguments are bit-equal.  Nothing else on the device changes (cores,
  * bonds, l_pos, the resident batch, f, the environments and the optimiser binding stay bit for bit); no forward is needed afterwards.
  * Refused before anything is launched: TNML_ERR_ARG (n < 1; K outside [2, 256]; a class outside [-1, L); a given level outside
@@ -532,6 +532,32 @@ int tnml_axpby(tnml_ctx *ctx, double alpha, double beta, const float *other_flat
  * naming the sample and its class when a sample is conditioned on a class or a prefix of zero weight. */
 int tnml_sample(tnml_ctx *ctx, int n, int K, const double *phi, const double *w, const int32_t *classes, const int32_t *given,
                 int n_given, const double *u, uint64_t seed, int32_t *levels_out, int32_t *labels_out, double *logp_out);
+
+/* ---- the same given ANY set of known pixels ---------------------------- */
+/* mask [mask_rows][N] (mask_rows 1: shared by all samples, or n): site i of sample s is KNOWN where it is non-zero, and its level is
+ * known [n][N] there (entries at other sites are ignored, whatever they hold; known may be NULL when no mask bit is set).  Every
+ * sample has metric environments of its own from the right, with w_k phi_k phi_k^T in place of S on its known sites, each multiplied
+ * by a power of two per site whose exponents are summed: E_s = log R_{s,0} + ln2 sum.  The same kernel computes, as one more row
+ * with the empty mask, the normaliser of every class slot the call needs.
+ * draw = 1: the walk of tnml_sample with the sample's own environments; nothing is drawn on a known site.  levels_out [n][N] holds
+ * the known levels as given and the drawn ones elsewhere, labels_out [n] the given class or the drawn label, logp_out [n][2]:
+ *   [0] log p(drawn levels [, drawn label] | known levels [, class]),
+ *   [1] log p(known levels [| class])   (class -1: the marginal over the label; exactly 0 for an empty mask).
+ * draw = 0: only the environments run; [1] as above, [0] = 0, labels_out (if not NULL) the given classes, levels_out may be NULL.
+ * class_logw_out [L] or NULL: log P(c), -inf for a class of zero weight.  u, seed: as tnml_sample (the hash takes the call's sample
+ * number).  The stack of environments, (N + 1) m^2 doubles a sample at largest bond m, is filled in chunks of whole tiles that stay
+ * within tnml_set_sample_stack_bytes (default 1 GiB); no result depends on the chunking, on the tile size or on the other samples
+ * of the call.  Every sum runs in a fixed order.  Nothing else on the device changes, as for tnml_sample.
+ * Refused before anything is launched: the list of tnml_sample, and TNML_ERR_ARG for mask_rows neither 1 nor n, a NULL mask, a NULL
+ * known with a mask bit set, a known level outside [0, K) at a masked site, draw with a NULL levels_out or labels_out, a NULL
+ * logp_out, a stack budget below one tile's need; TNML_ERR_STATE (cores never set; a communicator attached); TNML_ERR_SHAPE (a bond
+ * above 64, or LDS: the message names the bytes).  After the run: TNML_ERR_NONFINITE as tnml_sample; TNML_ERR_ARG naming the smallest
+ * sample, and its class, whose known pixels (or class) have zero weight. */
+int tnml_sample_masked(tnml_ctx *ctx, int n, int K, const double *phi, const double *w, const int32_t *classes, const uint8_t *mask,
+                       int mask_rows, const int32_t *known, const double *u, uint64_t seed, int draw, int32_t *levels_out,
+                       int32_t *labels_out, double *logp_out, double *class_logw_out);
+/* bytes of the environment stack a chunk of tnml_sample_masked may take (0: TNML_ERR_ARG) */
+int tnml_set_sample_stack_bytes(tnml_ctx *ctx, size_t bytes);
 
 /* Host-side planning helper, exported so that CPU tests can check the bond bookkeeping without a
  * GPU: truncation rank kept by tensor_svd (Network_class.py:894-945) for a step on sites

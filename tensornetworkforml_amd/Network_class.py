@@ -804,15 +804,23 @@ class Network():
             c = np.full(n, int(c))
         return np.ascontiguousarray(c, dtype=np.int32)
 
-    def sample(self, n, classes=None, levels=256, grid=None, weights=None, given=None, seed=0, u=None):
+    def sample(self, n, classes=None, levels=256, grid=None, weights=None, given=None, seed=0, u=None, mask=None):
         """n exact samples of p(x, l) = prod_i w(x_i) f_l(psi(x))^2 / Z over the pixel grid, in one pass over the chain on the
         device -> (X (n, N) pixel values, labels (n,), logp (n, 2), levels (n, N)).  classes: None draws the label with the
         image; an int or an array (n,) conditions on it (-1 in the array: draw it), and the sample comes from p(x | class).
         given: (n, n_given) pixel values on the grid or integer levels of the FIRST n_given sites, which are kept; only a
         prefix can be given.  logp[:, 0] is the log-probability of the whole sample [given the class], logp[:, 1] the part of
-        the given sites.  seed: the device generates the uniforms by a counter hash (repeatable); u (n, N + 1) overrides them."""
+        the given sites.  seed: the device generates the uniforms by a counter hash (repeatable); u (n, N + 1) overrides them.
+        mask: (N,) or (n, N) bool with given (n, N) -- pixel values on the grid or integer levels, read where the mask is set:
+        ANY set of known sites (section 23 of DESIGN.md).  Known sites come back as given; logp[:, 0] is then
+        log p(drawn pixels [, drawn label] | known pixels [, class]) and logp[:, 1] is log p(known pixels [| class])."""
         x, phi, w = self._pixel_grid(levels, grid, weights)
         n = int(n)
+        if mask is not None:
+            m, lev = self._masked_levels(given, mask, x, n)
+            ctx = self._sync_to_device(max(self._b, 1))
+            lev, labels, logp = ctx.sample_masked(n, phi, w, m, lev, self._classes_of(classes, n), u, seed)
+            return x[lev], labels, logp, lev
         g = None if given is None else self._levels_of(given, x, 'given')
         ctx = self._sync_to_device(max(self._b, 1))
         lev, labels, logp = ctx.sample(n, phi, w, self._classes_of(classes, n), g, u, seed)
@@ -836,6 +844,55 @@ class Network():
                 raise ValueError('joint=True needs a class for every image')
             out += self.class_log_weights(levels, grid, weights)[cls]
         return out, labels
+
+    def _masked_levels(self, X, mask, x, n):
+        """(mask (N,) or (n, N) bool, levels (n, N) int32): _levels_of applied where the mask is set, 0 elsewhere"""
+        m = np.asarray(mask) != 0
+        if m.shape not in ((self.N,), (n, self.N)):
+            raise ValueError('mask has shape %s, neither (%d,) nor (%d, %d)' % (m.shape, self.N, n, self.N))
+        if X is None:
+            if m.any():
+                raise ValueError('a mask with known sites needs their values')
+            return m, None
+        X = np.asarray(X)
+        if X.shape != (n, self.N):
+            raise ValueError('the known values have shape %s, not (%d, %d)' % (X.shape, n, self.N))
+        mm = np.broadcast_to(m, X.shape)
+        if np.issubdtype(X.dtype, np.integer):
+            return m, np.ascontiguousarray(np.where(mm, X, 0), dtype=np.int32)
+        return m, self._levels_of(np.where(mm, X, x[0]), x, 'given') * mm.astype(np.int32)
+
+    def log_prob_masked(self, X, mask, classes=None, levels=256, grid=None, weights=None, joint=False):
+        """log-probabilities of partially observed images -> (n,).  X (n, N) pixel values on the grid or integer levels, read where
+        mask ((N,) or (n, N) bool) is set; the other pixels are summed out by the model.  classes None: log p(x_G), the marginal
+        over the label too; classes given (int or (n,)): log p(x_G | c), with joint=True log p(x_G, c)."""
+        x, phi, w = self._pixel_grid(levels, grid, weights)
+        n = len(X)
+        m, lev = self._masked_levels(X, mask, x, n)
+        cls = self._classes_of(classes, n)
+        if joint and (cls is None or np.any(cls < 0)):
+            raise ValueError('joint=True needs a class for every image')
+        ctx = self._sync_to_device(max(self._b, 1))
+        res = ctx.sample_masked(n, phi, w, m, lev, cls, draw=False, class_logw=joint)
+        return res[2][:, 1] + res[3][cls] if joint else res[2][:, 1].copy()
+
+    def classify_masked(self, X, mask, levels=256, grid=None, weights=None):
+        """Classify partially observed images with the hidden pixels summed out -> (pred (n,), log_post (n, L)):
+        log P(c | x_G) = log p(x_G | c) + log P(c), normalised over c; pred is its first maximum.  One device call over the n L
+        rows (sample, class)."""
+        x, phi, w = self._pixel_grid(levels, grid, weights)
+        n, L = len(X), self.L
+        m, lev = self._masked_levels(X, mask, x, n)
+        ctx = self._sync_to_device(max(self._b, 1))
+        rows_m = m if m.ndim == 1 else np.repeat(m, L, axis=0)
+        rows_lev = None if lev is None else np.repeat(lev, L, axis=0)
+        cls = np.tile(np.arange(L, dtype=np.int32), n)
+        _, _, logp, clw = ctx.sample_masked(n * L, phi, w, rows_m, rows_lev, cls, draw=False, class_logw=True)
+        with np.errstate(invalid='ignore'):
+            lp = logp[:, 1].reshape(n, L) + clw[None, :]
+        top = lp.max(axis=1, keepdims=True)
+        log_post = lp - (top + np.log(np.exp(lp - top).sum(axis=1, keepdims=True)))
+        return log_post.argmax(axis=1), log_post
 
     def class_log_weights(self, levels=256, grid=None, weights=None):
         """log P(l) of the joint distribution, (L,): <W_l|W_l>_S / <W|W>_S by Network.inner under the grid's metric S, W_l the

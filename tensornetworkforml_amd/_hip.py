@@ -41,7 +41,7 @@ SYMBOLS = [
     'tnml_set_chain_scaling', 'tnml_predict_scaled',
     'tnml_set_shape_kernels', 'tnml_fixed_shape_steps',
     'tnml_inner', 'tnml_axpby',
-    'tnml_sample',
+    'tnml_sample', 'tnml_sample_masked', 'tnml_set_sample_stack_bytes',
 ]
 
 
@@ -148,6 +148,9 @@ def lib():
         L.tnml_inner.argtypes = [vp, f32p, C.c_size_t, i32p, C.c_int, f64p, C.c_int, f64p]
         L.tnml_axpby.argtypes = [vp, C.c_double, C.c_double, f32p, C.c_size_t, i32p, C.c_int, i32p]
         L.tnml_sample.argtypes = [vp, C.c_int, C.c_int, f64p, f64p, i32p, i32p, C.c_int, f64p, C.c_uint64, i32p, i32p, f64p]
+        L.tnml_sample_masked.argtypes = [vp, C.c_int, C.c_int, f64p, f64p, i32p, C.POINTER(C.c_uint8), C.c_int, i32p, f64p, C.c_uint64, C.c_int,
+                                         i32p, i32p, f64p, f64p]
+        L.tnml_set_sample_stack_bytes.argtypes = [vp, C.c_size_t]
         _lib = L
     return _lib
 
@@ -349,6 +352,52 @@ class Context:
         _chk(lib().tnml_sample(self._h, n, phi.shape[0], _ptr(phi, C.c_double), _ptr(w, C.c_double), cp, gp, n_given, up,
                                int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(levels, C.c_int32), _ptr(labels, C.c_int32), _ptr(logp, C.c_double)))
         return levels, labels, logp
+
+    # ---- the same given any set of known pixels
+    def sample_masked(self, n, phi, w, mask, known, classes=None, u=None, seed=0, draw=True, class_logw=False):
+        """-> (levels (n, N) int32 or None, labels (n,) int32, logp (n, 2) float64[, class_logw (L,)]).  mask (N,) or (n, N): the
+        known sites; known (n, N) levels, read where the mask is set (None with an empty mask).  draw: levels hold the known levels
+        as given and drawn ones elsewhere, logp[:, 0] = log p(drawn | known [, class]); draw=False: only logp[:, 1] =
+        log p(known [| class]), logp[:, 0] = 0, levels None.  class_logw: log P(c) as a fourth result."""
+        n = int(n)
+        phi = np.ascontiguousarray(phi, dtype=np.float64)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if phi.ndim != 2 or phi.shape[1] != self.D or w.shape != (phi.shape[0],):
+            raise TnmlError(-1, 'the grid has phi %s and w %s, not (K, %d) and (K,)' % (phi.shape, w.shape, self.D))
+        if mask is None:
+            raise TnmlError(-1, 'mask is None')
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if mask.shape not in ((self.N,), (n, self.N)):
+            raise TnmlError(-1, 'mask has shape %s, neither (%d,) nor (%d, %d)' % (mask.shape, self.N, n, self.N))
+        mask_rows = 1 if mask.ndim == 1 else n
+        cp = kp = up = None
+        if classes is not None:
+            classes = np.ascontiguousarray(classes, dtype=np.int32)
+            if classes.shape != (n,):
+                raise TnmlError(-1, 'classes has shape %s, not (%d,)' % (classes.shape, n))
+            cp = _ptr(classes, C.c_int32)
+        if known is not None:
+            known = np.ascontiguousarray(known, dtype=np.int32)
+            if known.shape != (n, self.N):
+                raise TnmlError(-1, 'known has shape %s, not (%d, %d)' % (known.shape, n, self.N))
+            kp = _ptr(known, C.c_int32)
+        if u is not None:
+            u = np.ascontiguousarray(u, dtype=np.float64)
+            if u.shape != (n, self.N + 1):
+                raise TnmlError(-1, 'u has shape %s, not (%d, %d)' % (u.shape, n, self.N + 1))
+            up = _ptr(u, C.c_double)
+        levels = np.empty((max(n, 0), self.N), dtype=np.int32) if draw else None
+        labels = np.empty(max(n, 0), dtype=np.int32)
+        logp = np.empty((max(n, 0), 2), dtype=np.float64)
+        clw = np.empty(self.L, dtype=np.float64) if class_logw else None
+        _chk(lib().tnml_sample_masked(self._h, n, phi.shape[0], _ptr(phi, C.c_double), _ptr(w, C.c_double), cp, _ptr(mask, C.c_uint8), mask_rows,
+                                      kp, up, int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if draw else 0, None if levels is None else _ptr(levels, C.c_int32),
+                                      _ptr(labels, C.c_int32), _ptr(logp, C.c_double), None if clw is None else _ptr(clw, C.c_double)))
+        return (levels, labels, logp, clw) if class_logw else (levels, labels, logp)
+
+    def set_sample_stack_bytes(self, nbytes):
+        """the bytes of environment stack one chunk of sample_masked may take (default 1 GiB)"""
+        _chk(lib().tnml_set_sample_stack_bytes(self._h, int(nbytes)))
 
     # ---- batch
     def set_input(self, X, y=None):

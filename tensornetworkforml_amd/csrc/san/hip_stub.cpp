@@ -502,6 +502,66 @@ static void check_sample(const SampleParams &p, dim3 g, dim3 b, size_t shm, bool
     if (!seen[smp]) die("SampleParams: sample %d is in no tile", smp);
 }
 
+// the same given any set of known pixels (kernels_sample_masked.hip): one parameter block for the environment launch and the walk of
+// one chunk of tiles.  The bond, tile and row tables, the mask and the known levels are read here as the kernels read them: every
+// core, the stack slots and E of every row of the launch, the grid, the uniforms and the outputs with their extents; T the one the
+// host derives for both kernels; no sample twice in a launch.  The (sample, class) pairs of the launches since the last
+// san_stub_masked_reset are kept for san_stub_masked_check: every sample of a call in exactly one tile, and that tile of its class.
+static std::vector<std::pair<int, int>> g_masked_rows[2];        // [0] environment launches, [1] walk launches
+static void check_sample_masked(const SampleMaskedParams &p, dim3 g, dim3 b, size_t shm, bool walk) {
+  scan(&p, sizeof p, "SampleMaskedParams");
+  if (p.N < 2 || p.D < 2 || p.D > kMaxD || p.L < 1 || p.l_pos < 0 || p.l_pos >= p.N) die("SampleMaskedParams: N %d D %d L %d l_pos %d", p.N, p.D, p.L, p.l_pos);
+  if (p.K < 2 || p.K > kSmpMaxK || p.n < 1 || p.n_tiles < 1 || (p.mask_rows != 1 && p.mask_rows != p.n)) die("SampleMaskedParams: K %d n %d tiles %d mask_rows %d", p.K, p.n, p.n_tiles, p.mask_rows);
+  need(p.bond, (size_t)(p.N - 1) * 4, "SampleMaskedParams.bond");
+  int mb = 1;
+  for (int i = 0; i < p.N; ++i) {
+    const int ml = i == 0 ? 1 : p.bond[i - 1], mr = i == p.N - 1 ? 1 : p.bond[i];
+    if (ml < 1 || mr < 1) die("SampleMaskedParams: site %d is %d x %d", i, ml, mr);
+    mb = mb > mr ? mb : mr;
+    const size_t ne = (size_t)ml * p.D * mr * (i == p.l_pos ? p.L : 1);
+    if (i == p.l_pos) need(p.lab, ne * 4, "SampleMaskedParams.lab");
+    else need(p.cores + (size_t)i * p.core_stride, ne * 4, "SampleMaskedParams.cores");
+  }
+  const size_t m2 = (size_t)mb * mb, rows = (size_t)p.n_tiles * p.T;
+  if (p.lds_m != mb || mb > kSmpMaxBond || p.env_stride < m2) die("SampleMaskedParams: lds_m %d env_stride %zu for bond %d", p.lds_m, p.env_stride, mb);
+  if (p.T < 1 || p.T != sample_masked_tile(mb, p.D, p.L, p.K)) die("SampleMaskedParams: tiles of %d rows, %d fit at bond %d", p.T, sample_masked_tile(mb, p.D, p.L, p.K), mb);
+  need(p.S, (size_t)p.D * p.D * 8, "SampleMaskedParams.S");
+  need(p.phi, (size_t)p.K * p.D * 8, "SampleMaskedParams.phi");
+  need(p.w, (size_t)p.K * 8, "SampleMaskedParams.w");
+  need(p.tile_class, (size_t)p.n_tiles * 4, "SampleMaskedParams.tile_class");
+  need(p.tile_rows, rows * 4, "SampleMaskedParams.tile_rows");
+  need(p.mask, (size_t)p.mask_rows * p.N, "SampleMaskedParams.mask");
+  need(p.known, (size_t)p.n * p.N * 4, "SampleMaskedParams.known");
+  need(p.stack, rows * (p.N + 1) * p.env_stride * 8, "SampleMaskedParams.stack");
+  need(p.E, rows * 8, "SampleMaskedParams.E");
+  need(p.status, 2 * 4, "SampleMaskedParams.status");
+  if (p.status[0] != 0 || p.status[1] != INT_MAX) die("SampleMaskedParams: status words %d %d at launch", p.status[0], p.status[1]);
+  const char *kn = walk ? "sample_walk_masked_kernel" : "sample_env_masked_kernel";
+  if (g.x != (unsigned)p.n_tiles || g.y != 1 || g.z != 1 || b.x != 512) die("%s: grid %u block %u for %d tiles", kn, g.x, b.x, p.n_tiles);
+  if (shm < (walk ? sample_masked_walk_lds_bytes(mb, p.D, p.L, p.K, p.T) : sample_masked_env_lds_bytes(mb, p.D, p.T))) die("%s: %zu bytes of LDS for bond %d, T %d", kn, shm, mb, p.T);
+  if (walk) {
+    if (p.u) need(p.u, (size_t)p.n * (p.N + 1) * 8, "SampleMaskedParams.u");
+    need(p.levels, (size_t)p.n * p.N * 4, "SampleMaskedParams.levels");
+    need(p.labels, (size_t)p.n * 4, "SampleMaskedParams.labels");
+    need(p.logp0, (size_t)p.n * 8, "SampleMaskedParams.logp0");
+  }
+  std::vector<char> seen((size_t)p.n, 0);
+  for (int t = 0; t < p.n_tiles; ++t) {
+    const int cls = p.tile_class[t];
+    if (cls < -1 || cls >= p.L) die("SampleMaskedParams: tile %d of class %d", t, cls);
+    for (int k = 0; k < p.T; ++k) {
+      const int smp = p.tile_rows[(size_t)t * p.T + k];
+      if (smp == -1) continue;
+      if (smp < 0 || smp >= p.n || seen[smp]) die("SampleMaskedParams: tile %d holds sample %d", t, smp);
+      seen[smp] = 1;
+      g_masked_rows[walk].emplace_back(smp, cls);
+      const unsigned char *ms = p.mask + (size_t)(p.mask_rows == 1 ? 0 : smp) * p.N;
+      for (int i = 0; i < p.N; ++i)
+        if (ms[i] && (p.known[(size_t)smp * p.N + i] < 0 || p.known[(size_t)smp * p.N + i] >= p.K)) die("SampleMaskedParams: known level of sample %d site %d", smp, i);
+    }
+  }
+}
+
 // gradient training (kernels_optim.hip).  loss_cot_kernel: f and cot at their own strides, the labels of the chunk, one thread per
 // column of cot.  optim_step_kernel: one workgroup per site; every core's slot and its part of G, vel / m / v through the table.
 static void check_loss_cot(const LossCotParams &p, dim3 g, dim3 b, size_t shm) {
@@ -619,6 +679,10 @@ static void tr_struct(const SampleParams &p) {
   I(N) I(D) I(L) I(l_pos) I(K) I(n) I(n_given) I(n_tiles) I(n_slots) I(phase) I(lds_m) P(bond) P(cores) P(lab) I(core_stride) P(S) P(phi) P(w) P(slot_class)
   P(env_shared) P(env_slots) I(env_stride) P(stage) I(stage_stride) P(tile_slot) P(tile_samples) P(classes) P(given) P(u) I(seed) P(levels) P(labels) P(logp) P(status)
 }
+static void tr_struct(const SampleMaskedParams &p) {
+  I(N) I(D) I(L) I(l_pos) I(K) I(n) I(T) I(n_tiles) I(lds_m) I(mask_rows) P(bond) P(cores) P(lab) I(core_stride) P(S) P(phi) P(w) P(tile_class) P(tile_rows)
+  P(mask) P(known) P(stack) I(env_stride) P(E) P(u) I(seed) P(levels) P(labels) P(logp0) P(status)
+}
 static void tr_struct(const InputGradPixels &p) { P(g) P(data) P(idx) P(out) I(b) I(N) I(D) }
 static void tr_struct(const BigExtArgs &p) { P(Eprev) P(x_km1) P(x_k) V(A) I(b_pad) P(Ecur) P(Pk) }
 static void tr_struct(const ChainSite &p) { I(core_off) I(is_label) I(n_in) I(n_out) I(s_in) I(s_d) I(s_out) I(x_site) I(env_out_off) }
@@ -661,6 +725,7 @@ static void tr_launch(const std::string &name, dim3 g, dim3 b, size_t shm, hipSt
     else if (is("BigExtArgs")) tr_struct(*(const BigExtArgs *)args[i]);
     else if (is("AlgebraParams")) tr_struct(*(const AlgebraParams *)args[i]);
     else if (is("SampleParams")) tr_struct(*(const SampleParams *)args[i]);
+    else if (is("SampleMaskedParams")) tr_struct(*(const SampleMaskedParams *)args[i]);
     else if (is("CoreView")) { const CoreView &v = *(const CoreView *)args[i]; tr(" [%s %d %d %d %d %d]", dp(v.base).c_str(), v.n_in, v.n_out, v.s_in, v.s_d, v.s_out); }
     else if (is("BigFrontTiles")) tr(" %d %d", ((int *)args[i])[0], ((int *)args[i])[1]);
     else if (is("float")) tr(" %.9g", *(float *)args[i]);
@@ -750,6 +815,8 @@ hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t s
     check_algebra(*(const AlgebraParams *)args[0], g, b, shm, has("inner_chain_kernel") ? 0 : has("inner_meet_kernel") ? 1 : 2);
   } else if (has("sample_env_kernel") || has("sample_walk_kernel")) {
     check_sample(*(const SampleParams *)args[0], g, b, shm, has("sample_walk_kernel"));
+  } else if (has("sample_env_masked_kernel") || has("sample_walk_masked_kernel")) {
+    check_sample_masked(*(const SampleMaskedParams *)args[0], g, b, shm, has("sample_walk_masked_kernel"));
   } else if (has("input_grad_onehot_kernel")) {   // (f, f_bpad, L, b, cot, b_pad)
     const int fbp = *(int *)args[1], L = *(int *)args[2], bb = *(int *)args[3], bp = *(int *)args[5];
     if (bb < 1 || bb > bp || bp > fbp || (size_t)g.x * b.x < (size_t)bp) die("input_grad_onehot_kernel: b %d b_pad %d f_bpad %d grid %u x %u", bb, bp, fbp, g.x, b.x);
@@ -970,6 +1037,18 @@ long san_stub_alloc_calls(void) { return g_alloc_calls; }
 void san_stub_fail_alloc(long nth) { g_fail_call = nth > 0 ? g_alloc_calls + nth : 0; }
 int san_stub_fail_pending(void) { return g_fail_call != 0; }
 void san_stub_poke_int(void *dev, int v) { need(dev, 4, "poke"); memcpy(dev, &v, 4); }
+// tnml_sample_masked: forget the rows seen so far; every sample of a call of n samples in exactly one tile of the launches since, and
+// that tile of its class (walk: the walk launches)
+void san_stub_masked_reset(void) { g_masked_rows[0].clear(); g_masked_rows[1].clear(); }
+void san_stub_masked_check(int walk, int n, const int32_t *classes) {
+  std::vector<int> cls((size_t)n, INT_MIN);
+  for (auto &r : g_masked_rows[walk ? 1 : 0]) {
+    if (r.first >= n || cls[r.first] != INT_MIN) die("tnml_sample_masked: sample %d is in two tiles of the %s launches", r.first, walk ? "walk" : "environment");
+    cls[r.first] = r.second;
+  }
+  for (int s = 0; s < n; ++s)
+    if (cls[s] != (classes ? classes[s] : -1)) die("tnml_sample_masked: sample %d of class %d is in %s", s, classes ? classes[s] : -1, cls[s] == INT_MIN ? "no tile" : "a tile of another class");
+}
 // the records of the last persistent launch as the "device" holds them (n steps; record n is the batch side's prologue)
 const void *san_stub_last_persist(int *n_steps) { *n_steps = g_last_persist_n; return g_last_persist; }
 }

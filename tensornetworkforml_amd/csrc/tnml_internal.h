@@ -497,4 +497,40 @@ size_t sample_walk_lds_bytes(int mb, int D, int L, int K);
 // the two environment launches and the walk of one tnml_sample call; mb: largest bond.  false: refused (geometry / LDS)
 bool launch_sample(const SampleParams &p, int mb, hipStream_t st);
 
+// The same given any set of known pixels (kernels_sample_masked.hip): one parameter block for the environment
+// kernel and the walk kernel of one chunk of tiles.  A row is a sample of the call or an empty mask (tile_rows -1: the normaliser of
+// its class slot, or padding); a tile holds T rows of one class slot, and row r of the launch owns stack slots [r][0 .. N].
+constexpr int kSmkMaxTile = 16;
+struct SampleMaskedParams {
+  int N, D, L, l_pos, K;
+  int n;                   // samples of the CALL (the extent of mask, known, u and the outputs)
+  int T, n_tiles;          // rows per tile (16, 8, 4, 2 or 1), tiles of this launch
+  int lds_m;               // LDS geometry: the largest bond (launch_sample_masked fills it)
+  int mask_rows;           // 1 or n
+  const int *bond;         // [N-1]
+  const float *cores, *lab;
+  size_t core_stride;
+  const double *S;         // [D][D] sum_k w_k phi_k phi_k^T
+  const double *phi, *w;   // [K][D], [K]
+  const int *tile_class;   // [n_tiles]
+  const int *tile_rows;    // [n_tiles][T] sample numbers of the call, -1: the empty mask
+  const unsigned char *mask;   // [mask_rows][N]
+  const int *known;        // [n][N], read where the mask is set
+  double *stack;           // [n_tiles T][N+1][env_stride]: R_{s,i}, R_{s,N} = 1
+  size_t env_stride;
+  double *E;               // [n_tiles T] log R_{s,0} + ln2 sum of the exponents
+  const double *u;         // [n][N+1], or null: the counter hash of (seed, sample, site)
+  unsigned long long seed;
+  int *levels;             // [n][N]
+  int *labels;             // [n]
+  double *logp0;           // [n]
+  int *status;             // [0] bit 1 non-finite, bit 2 a sample whose densities sum to nothing; [1] the smallest such sample
+};
+size_t sample_masked_env_lds_bytes(int mb, int D, int T);
+size_t sample_masked_walk_lds_bytes(int mb, int D, int L, int K, int T);
+// the largest T of 16, 8, 4, 2, 1 at which both kernels fit 160 KB of LDS; 0: none does
+int sample_masked_tile(int mb, int D, int L, int K);
+// the environment launch and (walk) the walk launch of one chunk; mb: largest bond.  false: refused (geometry / LDS)
+bool launch_sample_masked(const SampleMaskedParams &p, int mb, bool walk, hipStream_t st);
+
 }  // namespace tnml

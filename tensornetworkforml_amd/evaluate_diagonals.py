@@ -52,6 +52,63 @@ def write_samples(net, path, n, cls, seed):
     return X, labels, logp
 
 
+def _levels8(pixels):
+    """(n, N) int32 levels 0 .. 255: integer pixels as they are, pixels in [0, 1] rounded to the nearest of 256 levels"""
+    pixels = np.asarray(pixels).reshape(len(pixels), -1)
+    lev = pixels if np.issubdtype(pixels.dtype, np.integer) else np.rint(np.clip(pixels, 0.0, 1.0) * 255.0)
+    return lev.astype(np.int32)
+
+
+def known_half(which, side):
+    """(side * side,) bool: the pixels --inpaint keeps"""
+    r, c = np.divmod(np.arange(side * side), side)
+    return {'top': r < side // 2, 'bottom': r >= side // 2, 'left': c < side // 2, 'right': c >= side // 2,
+            'checker': (r + c) % 2 == 0}[which]
+
+
+def write_inpainted(net, path, pixels, labels, n, which, seed):
+    """The first n test images rounded to 8 bits, one half kept (`which`), the rest and the label drawn by the model given the kept
+    pixels (Network.sample with a mask) -> (n, h, w).  Prints the mean log p(completion | known) and the share of drawn labels
+    that equal the true ones."""
+    lev = _levels8(pixels)[:n]
+    n = len(lev)
+    side = int(round(np.sqrt(net.N)))
+    if side * side != net.N:
+        raise SystemExit('--inpaint needs a square image, the network has N = %d sites' % net.N)
+    mask = known_half(which, side)
+    X, drawn, logp, _ = net.sample(n, given=lev, mask=mask, seed=seed)
+    np.save(path, X.reshape(n, side, side))
+    hit = float((drawn == np.asarray(labels)[:n]).mean())
+    print('\tInpainted %d images, %s known: mean log p(completion | known) %.4f, drawn labels equal to the true ones %.4f'
+          % (n, which, float(logp[:, 0].mean()), hit))
+    print('\tInpainted images written to', path, (n, side, side))
+    return X, drawn, logp
+
+
+def print_occluded(net, pixels, labels, fraction, seed, chunk=1024):
+    """Hides a seeded random `fraction` of every test image's pixels and prints the accuracy of Network.classify_masked (hidden
+    pixels summed out by the model) next to the accuracy of Network.predict on the same images with the hidden pixels set to 0."""
+    if not 0.0 <= fraction < 1.0:
+        raise SystemExit('--occluded takes a fraction in [0, 1)')
+    lev = _levels8(pixels)
+    labels = np.asarray(labels)
+    known = np.random.default_rng(seed).random(lev.shape) >= fraction
+    pred = np.concatenate([net.classify_masked(lev[i:i + chunk], known[i:i + chunk])[0] for i in range(0, len(lev), chunk)])
+    zeroed = np.where(known, lev, 0) / 255.0
+    f = np.concatenate([net.predict(gen.psi(zeroed[i:i + chunk], net.D)).elem for i in range(0, len(lev), chunk)], axis=1)
+    acc_m, acc_z = float((pred == labels).mean()), float((f.argmax(axis=0) == labels).mean())
+    print('\tOccluded %.2f of the pixels of %d images: accuracy with hidden pixels summed out %.4f, with hidden pixels set to 0 %.4f'
+          % (fraction, len(lev), acc_m, acc_z))
+    return acc_m, acc_z
+
+
+def run_masked_arguments(net, args, pixels, labels):
+    if args.inpaint:
+        write_inpainted(net, args.inpaint, pixels, labels, args.sample_n, args.inpaint_known, args.seed)
+    if args.occluded is not None:
+        print_occluded(net, pixels, labels, args.occluded, args.seed)
+
+
 def add_sample_arguments(ap):
     ap.add_argument('--sample', metavar='OUT.npy', default=None, help="write images drawn from the model's distribution |f|^2 over 8-bit pixels (Network.sample)")
     ap.add_argument('--sample-n', dest='sample_n', type=int, default=64, help='number of images of --sample')
@@ -59,13 +116,18 @@ def add_sample_arguments(ap):
     ap.add_argument('--seed', type=int, default=0, help='seed of the uniforms of --sample')
     ap.add_argument('--log-prob', dest='log_prob', action='store_true',
                     help='print the mean log p(x, y) of the test set under the model, pixels rounded to 8 bits (Network.log_prob)')
+    ap.add_argument('--inpaint', metavar='OUT.npy', default=None,
+                    help='keep one half of the first --sample-n test images (8-bit pixels) and let the model draw the rest and the label')
+    ap.add_argument('--inpaint-known', dest='inpaint_known', choices=['top', 'bottom', 'left', 'right', 'checker'], default='top',
+                    help='the pixels --inpaint keeps')
+    ap.add_argument('--occluded', metavar='FRACTION', type=float, default=None,
+                    help='hide a seeded random FRACTION of every test image and print the accuracy of Network.classify_masked next to '
+                         'that of the classifier on the same images with the hidden pixels set to 0')
 
 
 def print_log_prob(net, pixels, labels, chunk=4096):
     """mean log p(x, y) over a data set: integer pixels are levels 0 .. 255, pixels in [0, 1] are rounded to the nearest of 256 levels"""
-    pixels = np.asarray(pixels).reshape(len(pixels), -1)
-    lev = pixels if np.issubdtype(pixels.dtype, np.integer) else np.rint(np.clip(pixels, 0.0, 1.0) * 255.0)
-    lev = lev.astype(np.int32)
+    lev = _levels8(pixels)
     labels = np.asarray(labels)
     lp = np.concatenate([net.log_prob(lev[i:i + chunk], classes=labels[i:i + chunk], joint=True)[0] for i in range(0, len(lev), chunk)])
     print('\tMean log p(x, y):     %.4f over %d samples (%.4f per pixel)' % (float(lp.mean()), len(lp), float(lp.mean()) / net.N))
@@ -107,6 +169,7 @@ def main(argv=None):
         write_samples(net, args.sample, args.sample_n, args.sample_class, args.seed)
     if args.log_prob:
         print_log_prob(net, data, label)
+    run_masked_arguments(net, args, data, label)
     print('\tAccuracy:            ', acc)
     print('\tMean Absolute Error: ', mae)
     return acc, mae
