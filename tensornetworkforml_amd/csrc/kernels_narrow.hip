@@ -759,43 +759,8 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
   const bool isVwave = wrank >= 0 && wrank < NVW;
   const int vP0 = (wrank * gpw + vgrp) * vr;
   const bool vLaneOk = isVwave && vgrp < gpw;
-  // G items: the np(np+1)/2 blocks P <= Q of the symmetric G (only entries with row <= column are kept
-  // up to date); at most 2 per worker thread (np <= 32: 528 items on >= 448 threads)
-  constexpr int MAXI = 2;
-  const int nG = np * (np + 1) / 2;
-  bool itValid[MAXI], itDiag[MAXI];
-  int itSrc[MAXI], itCsQ[MAXI], itCsP[MAXI], itD11[MAXI], itD12[MAXI], itD21[MAXI], itD22[MAXI];
-#pragma unroll
-  for (int u = 0; u < MAXI; ++u) {
-    const int it = gtid + u * NW;
-    // (u * NW < nG: a thread's u-th item is number gtid + u * NW >= u * NW -- where the shape is a constant, a pass without items folds away)
-    itValid[u] = u * NW < nG && wrank >= NVW && gtid < NW && it < nG;
-    int P = 0, Q = 0;
-    if (itValid[u]) {                         // it-th pair (P <= Q) in row-major order of the upper triangle
-      int rem = it;
-      while (rem >= np - P) { rem -= np - P; ++P; }
-      Q = P + rem;
-    }
-    const int c1 = k.sPi[2 * Q], c2 = k.sPi[2 * Q + 1];
-    const int o1 = k.sPi[2 * P], o2 = k.sPi[2 * P + 1];
-    itSrc[u] = (2 * P) * ne + 2 * Q;
-    itCsQ[u] = 4 * Q; itCsP[u] = 4 * P;
-    itDiag[u] = P == Q;
-    // every element lands at (min, max) of its new position
-    itD11[u] = min(o1, c1) * ne + max(o1, c1); itD12[u] = min(o1, c2) * ne + max(o1, c2);
-    itD21[u] = min(o2, c1) * ne + max(o2, c1); itD22[u] = min(o2, c2) * ne + max(o2, c2);
-  }
   const double abs2 = kJacobiAbs * kJacobiAbs;      // trace is ~1 after scaling
-  // parameter-thread constants
-  const bool isParam = tid < np;
-  int pa = 0, pb = 1;
-  if (isParam) { pa = k.sPiInv[2 * tid]; pb = k.sPiInv[2 * tid + 1]; }
-  const int pA = pa >> 1, ra = pa & 1, pB = pb >> 1, rb = pb & 1;
-  // element offsets of the parameter thread's reads, formed once: left inline they are eight 32-bit multiplies per round on
-  // the critical chain of the parameter wave (v_mul_lo_u32 issues at quarter rate)
-  const int oAd = (2 * pA) * ne + 2 * pA, oAb = (2 * pA + 1) * ne + 2 * pA + 1;
-  const int oBd = (2 * pB) * ne + 2 * pB, oBb = (2 * pB + 1) * ne + 2 * pB + 1;
-  const int oR0 = pA <= pB ? (2 * pA) * ne + 2 * pB : (2 * pB) * ne + 2 * pA, oR1 = oR0 + ne;   // stored block (min, max)
+  const bool isParam = tid < np;                    // parameter threads
 
   if (p.stamps && tid == 0) t_c1 = __builtin_amdgcn_s_memtime();
   // ---- phase 6b: one pivoted-Cholesky step when G is far from diagonal ------------------------------------------
@@ -887,17 +852,12 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
   // (piInv(2k), piInv(2k+1)) in today's positions, its new diagonal follows from today's diagonal
   // blocks (alpha' = alpha - t gamma, beta' = beta + t gamma) and its new off-diagonal element from
   // one element of the updated block (A, B), which the thread recomputes itself.
-  // Thread roles.  wave 0: parameter threads (tid < np).  waves 1..NVW: V.  The rest: G items.
+  // Wave roles.  wave 0: parameter threads (tid < np).  waves 1..NVW: V.  The next nGw: G items.  The rest: idle (they keep the
+  // barriers).  Each role runs a round loop of its own that holds only its section and the skeleton (`one_round` below).
   //   V never touches LDS during the iteration: a thread keeps kVR 2x2 blocks (row pairs P0..P0+kVR-1,
   //   column pair Q = its lane within a group of np lanes) in registers; the column rotation is local and
   //   the tournament move (top element of pair Q -> pair Q+1, bottom element -> pair Q-1) is a one-lane
   //   wave shift (DPP wave_shr / wave_shl, tools/ubench/dpp_wave_shift.hip).
-  double vb[kVR][4];                                     // {v11, v12, v21, v22} per block
-#pragma unroll
-  for (int r = 0; r < kVR; ++r) {
-    const double one = (vP0 + r == vQ) ? 1.0 : 0.0;      // V = I
-    vb[r][0] = one; vb[r][1] = 0.0; vb[r][2] = 0.0; vb[r][3] = one;
-  }
   int sweeps = 0, converged = 0;
   double *Gc = G0, *Gn = G1;
   auto kept_scale = [&](const double *G) -> double {
@@ -914,7 +874,6 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
     return lm * lm;
   };
 
-  int cur = 0;
   double kept2 = 0.0;
   // Rotation slot of pair k in dCS (4 doubles): [0] t, [1] c0 as doubles (float32-exact values), [2] the same two as a
   // float2 for the look-ahead chain.  See jacobi_rot_f32 (jacobi_device.h) for the arithmetic.
@@ -923,32 +882,119 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
   // round index + 1 in slot applied & 1 of sFlag[6..7]: every thread reads that slot at the top of round `applied` (the
   // barrier of the previous round completed the writes; the slot is next written two rounds later), so all threads know
   // the last round that applied a big rotation without any reduction.
-  auto publish = [&](double *o, const RotT &r, int applied) {
+  auto publish = [&](double *o, const RotT &r, int *flag_slot, int applied) {
     *reinterpret_cast<double2 *>(o) = make_double2((double)r.t, (double)r.c0);
     *reinterpret_cast<float2 *>(o + 2) = make_float2(r.t, r.c0);
-    if (r.level >= 2) k.sFlag[6 + (applied & 1)] = applied + 1;
+    if (r.level >= 2) *flag_slot = applied + 1;
   };
   int round_idx = 0, last_big1 = 0;          // rounds applied so far; 1 + index of the last round with a big rotation
-  // returns true once ne - 1 consecutive rounds applied no big rotation (see the loop below)
-  auto jacobi_round = [&]() -> bool {
-        const double *csc = k.dCS + cur * np * 4;
-        const int big_slot = k.sFlag[6 + (round_idx & 1)];      // consumed after this round's barrier
+  // Everything that alternates from round to round -- the G buffer read and the one written, the rotation slots, the flag slot -- is
+  // a function of the round's parity alone.  A round's work is therefore written against explicit operands (Gr: G read, Gw: G written,
+  // csr / csw: rotation slots read / written, fw: flag slot a big rotation of the NEXT round is announced in), and the loop over the
+  // rounds of a sweep is unrolled by two with the operands exchanged between the halves: nothing is swapped or re-addressed per round.
+  // The sections of the parameter, V and G waves stand inside their role's branch below; an idle wave has none:
+  auto idle_work = [&](const double *, double *, const double *, double *, int *) __attribute__((always_inline)) {};
+  // One round of one role: the skeleton, written once.  `fr` is the flag slot of this round (its word arrived with this round's
+  // operands and is consumed after the barrier).  The exit decision is complete in FRONT of the barrier: block-uniform, and told so
+  // -- the word comes out of LDS (a vector register), and a loop exit the compiler has to treat as divergent wraps every round in
+  // EXEC-mask bookkeeping.  The empty asm pins the finished difference to a scalar register there (left alone, the compiler sinks the
+  // readfirstlane and the arithmetic behind the barrier); behind the barrier only the sign test of that register and the branch are left.
+  // Returns true once ne - 1 consecutive rounds applied no big rotation (see the loop below).
+  auto one_round = [&](auto &work, const double *Gr, double *Gw, const double *csr, double *csw, const int *fr, int *fw)
+                       __attribute__((always_inline)) -> bool {
+    const int big_slot = *fr;
+    work(Gr, Gw, csr, csw, fw);
+    last_big1 = max(last_big1, big_slot);
+    const int last_big_s = __builtin_amdgcn_readfirstlane(last_big1);
+    int over = round_idx + 1 - last_big_s - (ne - 1);      // >= 0: ne - 1 rounds without a big rotation
+    asm volatile("" : "+s"(over));
+    lds_barrier();
+    ++round_idx;
+    return over >= 0;
+  };
+  // The ne - 1 rounds of a sweep for one role (ne - 1 is odd: pairs of rounds, then one round whose operands are those of the first
+  // half; the next sweep starts on the other parity).  Every role runs the same number of rounds: the trip count depends on ne and on
+  // `done` alone, and `done` derives in every wave from the same flag words, read behind the same barrier.
+  auto role_sweep = [&](auto &work) __attribute__((always_inline)) -> bool {
+    const int par = round_idx & 1;
+    double *Ga = par ? G1 : G0, *Gb = par ? G0 : G1;                               // read in the first / the second half
+    double *csa = k.dCS + (par ? 4 * np : 0), *csb = k.dCS + (par ? 0 : 4 * np);   // (scalar selects, once per sweep)
+    int *fa = k.sFlag + 6 + par, *fb = k.sFlag + 6 + (par ^ 1);
+    for (int rnd = 0; rnd < ne - 2; rnd += 2) {
+      if (one_round(work, Ga, Gb, csa, csb, fa, fb)) return true;
+      if (one_round(work, Gb, Ga, csb, csa, fb, fa)) return true;
+    }
+    return one_round(work, Ga, Gb, csa, csb, fa, fb);
+  };
+  // The whole nest of one role: sweeps of ne - 1 rounds, the kept scale between them.  (Measured: one flat loop over the rounds
+  // instead of this nest costs the generic body 60 cycles per round.)
+  auto run_role = [&](auto &work) __attribute__((always_inline)) {
+    for (; sweeps < kJacobiMaxSweeps && !converged; ++sweeps) {
+      converged = role_sweep(work);
+      if (!converged) kept2 = kept_scale((round_idx & 1) ? G1 : G0);
+    }
+  };
+  // the eigenvectors leave the registers: V[row][column position], as phase 9 reads them
+  double *V = V0;
+  auto store_v = [&](const double (&vb)[kVR][4]) __attribute__((always_inline)) {
+    if (vLaneOk) {
+#pragma unroll
+      for (int r = 0; r < kVR; ++r) {
+        const int P = vP0 + r;
+        if (r < vr && P < np) {
+          *reinterpret_cast<double2 *>(V + (2 * P) * ne + 2 * vQ) = make_double2(vb[r][0], vb[r][1]);
+          *reinterpret_cast<double2 *>(V + (2 * P + 1) * ne + 2 * vQ) = make_double2(vb[r][2], vb[r][3]);
+        }
+      }
+    }
+  };
+  // The role is a function of the wave index alone: one scalar value, branched on ONCE per decomposition.  What a role keeps in
+  // registers -- its offsets, the V blocks -- is formed inside its branch and lives only there.
+  enum { kRoleParam, kRoleV, kRoleG, kRoleIdle };
+  const int role = __builtin_amdgcn_readfirstlane(wave_u == 0 ? kRoleParam : wrank < NVW ? kRoleV : wrank < NVW + nGw ? kRoleG : kRoleIdle);
+  if (n > 1) {
+    kept2 = kept_scale(Gc);
+    if (tid == 0) { k.sFlag[6] = 0; k.sFlag[7] = 0; }
+    if (isParam) {                                   // rotations of the very first round
+      const double2 top = *reinterpret_cast<const double2 *>(Gc + (2 * tid) * ne + 2 * tid);
+      const RotT r = jacobi_rot_f32((float)top.x, (float)Gc[(2 * tid + 1) * ne + 2 * tid + 1], (float)top.y,
+                                    fmaxf((float)kept2, kept_lo), (float)abs2, (float)p.svd_stop2);
+      publish(k.dCS + tid * 4, r, k.sFlag + 6, 0);
+    }
+    lds_barrier();
+    // The iteration ends as soon as ne - 1 consecutive rounds -- any such window is a complete sweep over all pairs --
+    // applied no big rotation: quadratic convergence then leaves off-diagonals of relative size ~svd_stop2, exactly the
+    // guarantee of "a whole sweep without a big rotation", but the window need not start at a sweep boundary (it saves
+    // about a third of a sweep per decomposition once the chain has settled).
+    if (role == kRoleParam) {
+      // parameter-thread constants
+      int pa = 0, pb = 1;
+      if (isParam) { pa = k.sPiInv[2 * tid]; pb = k.sPiInv[2 * tid + 1]; }
+      const int pA = pa >> 1, ra = pa & 1, pB = pb >> 1, rb = pb & 1;
+      // element offsets of the parameter thread's reads, formed once: left inline they are eight 32-bit multiplies per round on
+      // the critical chain of the parameter wave (v_mul_lo_u32 issues at quarter rate)
+      const int oAd = (2 * pA) * ne + 2 * pA, oAb = (2 * pA + 1) * ne + 2 * pA + 1;
+      const int oBd = (2 * pB) * ne + 2 * pB, oBb = (2 * pB + 1) * ne + 2 * pB + 1;
+      const int oR0 = pA <= pB ? (2 * pA) * ne + 2 * pB : (2 * pB) * ne + 2 * pA, oR1 = oR0 + ne;   // stored block (min, max)
+
+      // -- parameter wave (wave 0, lanes < np) --
+      auto param_work = [&](const double *Gr, double *, const double *csr, double *csw, int *fw) __attribute__((always_inline)) {
         if (isParam) {
           // look-ahead: pair `tid` of the NEXT round is (a, b) in today's positions; its three elements after today's
           // rotations, in float32 (the inputs are read as float64 and converted)
-          const float2 fA = *reinterpret_cast<const float2 *>(csc + 4 * pA + 2);     // (t, c0) of pair A
-          const float2 fB = *reinterpret_cast<const float2 *>(csc + 4 * pB + 2);
-          const double2 dA = *reinterpret_cast<const double2 *>(Gc + oAd);
-          const double bA = Gc[oAb];
-          const double2 dB = *reinterpret_cast<const double2 *>(Gc + oBd);
-          const double bB = Gc[oBb];
+          const float2 fA = *reinterpret_cast<const float2 *>(csr + 4 * pA + 2);     // (t, c0) of pair A
+          const float2 fB = *reinterpret_cast<const float2 *>(csr + 4 * pB + 2);
+          const double2 dA = *reinterpret_cast<const double2 *>(Gr + oAd);
+          const double bA = Gr[oAb];
+          const double2 dB = *reinterpret_cast<const double2 *>(Gr + oBd);
+          const double bB = Gr[oBb];
           double2 r0, r1;                                       // rows of block (A, B)
           if (pA < pB) {
-            r0 = *reinterpret_cast<const double2 *>(Gc + oR0);
-            r1 = *reinterpret_cast<const double2 *>(Gc + oR1);
+            r0 = *reinterpret_cast<const double2 *>(Gr + oR0);
+            r1 = *reinterpret_cast<const double2 *>(Gr + oR1);
           } else if (pA > pB) {                                 // stored as (B, A): transpose
-            const double2 s0 = *reinterpret_cast<const double2 *>(Gc + oR0);
-            const double2 s1 = *reinterpret_cast<const double2 *>(Gc + oR1);
+            const double2 s0 = *reinterpret_cast<const double2 *>(Gr + oR0);
+            const double2 s1 = *reinterpret_cast<const double2 *>(Gr + oR1);
             r0 = make_double2(s0.x, s1.x);
             r1 = make_double2(s0.y, s1.y);
           } else {                                              // n == 2: the pair meets itself again
@@ -965,37 +1011,77 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
           const float h1 = ra ? fmaf(sA, q0y, cA * q1y) : fmaf(cA, q0y, -sA * q1y);
           const float ng = rb ? fmaf(sB, h0, cB * h1) : fmaf(cB, h0, -sB * h1);
           const RotT r = jacobi_rot_f32(na, nb, ng, fmaxf((float)kept2, kept_lo), (float)abs2, (float)p.svd_stop2);
-          // (the other slot's offset by a scalar select: with a constant np the product became a 64-bit multiply-add on this chain)
-          publish(k.dCS + ((cur ? 0 : 4 * np) + 4 * tid), r, round_idx + 1);
+          publish(csw + 4 * tid, r, fw, round_idx + 1);
         }
-        if (isVwave) {                                    // whole waves: every lane runs the shifts
-          const double2 tc = *reinterpret_cast<const double2 *>(csc + 4 * (vLaneOk ? vQ : 0));     // (t, c0) of pair Q
-          const double cq = tc.y * rot_corr(tc.x, tc.y);
+      };
+      run_role(param_work);
+    } else if (role == kRoleV) {
+      double vb[kVR][4];                                     // {v11, v12, v21, v22} per block
 #pragma unroll
-          for (int r = 0; r < kVR; ++r) {
-            if (r >= vr) break;                                 // wave-uniform
-            // columns by R_Q: (v1, v2) -> c (v1 - t v2), c (t v1 + v2)
-            const double n11 = cq * fma(-tc.x, vb[r][1], vb[r][0]), n12 = cq * fma(tc.x, vb[r][0], vb[r][1]);
-            const double n21 = cq * fma(-tc.x, vb[r][3], vb[r][2]), n22 = cq * fma(tc.x, vb[r][2], vb[r][3]);
-            if (np > 1) {
-              const double t1 = dpp_f64<0x138>(n11), t2 = dpp_f64<0x138>(n21);      // top column of pair Q-1
-              const double b1 = dpp_f64<0x138>(n12), b2 = dpp_f64<0x138>(n22);      // bottom column of pair Q-1
-              const double c1 = dpp_f64<0x130>(n12), c2 = dpp_f64<0x130>(n22);      // bottom column of pair Q+1
-              vb[r][0] = vQ == 0 ? n11 : (vQ == 1 ? b1 : t1);
-              vb[r][2] = vQ == 0 ? n21 : (vQ == 1 ? b2 : t2);
-              vb[r][1] = vQ == np - 1 ? n11 : c1;
-              vb[r][3] = vQ == np - 1 ? n21 : c2;
-            } else {
-              vb[r][0] = n11; vb[r][1] = n12; vb[r][2] = n21; vb[r][3] = n22;
-            }
+      for (int r = 0; r < kVR; ++r) {
+        const double one = (vP0 + r == vQ) ? 1.0 : 0.0;      // V = I
+        vb[r][0] = one; vb[r][1] = 0.0; vb[r][2] = 0.0; vb[r][3] = one;
+      }
+      // -- V waves (whole waves: every lane runs the shifts) --
+      auto v_work = [&](const double *, double *, const double *csr, double *, int *) __attribute__((always_inline)) {
+        const double2 tc = *reinterpret_cast<const double2 *>(csr + 4 * (vLaneOk ? vQ : 0));     // (t, c0) of pair Q
+        const double cq = tc.y * rot_corr(tc.x, tc.y);
+#pragma unroll
+        for (int r = 0; r < kVR; ++r) {
+          if (r >= vr) break;                                 // wave-uniform
+          // columns by R_Q: (v1, v2) -> c (v1 - t v2), c (t v1 + v2)
+          const double n11 = cq * fma(-tc.x, vb[r][1], vb[r][0]), n12 = cq * fma(tc.x, vb[r][0], vb[r][1]);
+          const double n21 = cq * fma(-tc.x, vb[r][3], vb[r][2]), n22 = cq * fma(tc.x, vb[r][2], vb[r][3]);
+          if (np > 1) {
+            const double t1 = dpp_f64<0x138>(n11), t2 = dpp_f64<0x138>(n21);      // top column of pair Q-1
+            const double b1 = dpp_f64<0x138>(n12), b2 = dpp_f64<0x138>(n22);      // bottom column of pair Q-1
+            const double c1 = dpp_f64<0x130>(n12), c2 = dpp_f64<0x130>(n22);      // bottom column of pair Q+1
+            vb[r][0] = vQ == 0 ? n11 : (vQ == 1 ? b1 : t1);
+            vb[r][2] = vQ == 0 ? n21 : (vQ == 1 ? b2 : t2);
+            vb[r][1] = vQ == np - 1 ? n11 : c1;
+            vb[r][3] = vQ == np - 1 ? n21 : c2;
+          } else {
+            vb[r][0] = n11; vb[r][1] = n12; vb[r][2] = n21; vb[r][3] = n22;
           }
         }
+      };
+      run_role(v_work);
+      store_v(vb);
+    } else if (role == kRoleG) {
+      // G items: the np(np+1)/2 blocks P <= Q of the symmetric G (only entries with row <= column are kept
+      // up to date); at most 2 per worker thread (np <= 32: 528 items on >= 448 threads)
+      constexpr int MAXI = 2;
+      const int nG = np * (np + 1) / 2;
+      bool itValid[MAXI], itDiag[MAXI];
+      int itSrc[MAXI], itCsQ[MAXI], itCsP[MAXI], itD11[MAXI], itD12[MAXI], itD21[MAXI], itD22[MAXI];
+#pragma unroll
+      for (int u = 0; u < MAXI; ++u) {
+        const int it = gtid + u * NW;
+        // (u * NW < nG: a thread's u-th item is number gtid + u * NW >= u * NW -- where the shape is a constant, a pass without items folds away)
+        itValid[u] = u * NW < nG && wrank >= NVW && gtid < NW && it < nG;
+        int P = 0, Q = 0;
+        if (itValid[u]) {                         // it-th pair (P <= Q) in row-major order of the upper triangle
+          int rem = it;
+          while (rem >= np - P) { rem -= np - P; ++P; }
+          Q = P + rem;
+        }
+        const int c1 = k.sPi[2 * Q], c2 = k.sPi[2 * Q + 1];
+        const int o1 = k.sPi[2 * P], o2 = k.sPi[2 * P + 1];
+        itSrc[u] = (2 * P) * ne + 2 * Q;
+        itCsQ[u] = 4 * Q; itCsP[u] = 4 * P;
+        itDiag[u] = P == Q;
+        // every element lands at (min, max) of its new position
+        itD11[u] = min(o1, c1) * ne + max(o1, c1); itD12[u] = min(o1, c2) * ne + max(o1, c2);
+        itD21[u] = min(o2, c1) * ne + max(o2, c1); itD22[u] = min(o2, c2) * ne + max(o2, c2);
+      }
+      // -- G waves --
+      auto g_work = [&](const double *Gr, double *Gw, const double *csr, double *, int *) __attribute__((always_inline)) {
 #pragma unroll
         for (int u = 0; u < MAXI; ++u) {
           if (!itValid[u]) continue;
-          const double2 tq = *reinterpret_cast<const double2 *>(csc + itCsQ[u]);      // (t, c0) of the column pair
-          const double2 tp = *reinterpret_cast<const double2 *>(csc + itCsP[u]);      // ... of the row pair
-          const double *src = Gc + itSrc[u];
+          const double2 tq = *reinterpret_cast<const double2 *>(csr + itCsQ[u]);      // (t, c0) of the column pair
+          const double2 tp = *reinterpret_cast<const double2 *>(csr + itCsP[u]);      // ... of the row pair
+          const double *src = Gr + itSrc[u];
           const double2 r0 = *reinterpret_cast<const double2 *>(src);
           double2 r1 = *reinterpret_cast<const double2 *>(src + ne);
           if (itDiag[u]) r1.x = r0.y;                           // lower element of a diagonal block = its mirror
@@ -1010,56 +1096,26 @@ __device__ __forceinline__ bool narrow_body(const NP &p, unsigned char *smem_raw
           // (Known defect, DESIGN.md 5.3 "Constructed spectra": t is a float32 number, so the rotation leaves ~1e-7 of the element, and
           // the exact zero written here discards it -- no similarity transform: every small eigenvalue moves by ~2e-8 lambda_max.)
           if (itDiag[u] && tq.x != 0.0) { n12 = 0.0; n21 = 0.0; }   // the annihilated element, exactly
-          Gn[itD11[u]] = n11; Gn[itD12[u]] = n12;
-          if (!itDiag[u]) Gn[itD21[u]] = n21;                   // (n21 of a diagonal block is n12's mirror)
-          Gn[itD22[u]] = n22;
+          Gw[itD11[u]] = n11; Gw[itD12[u]] = n12;
+          if (!itDiag[u]) Gw[itD21[u]] = n21;                   // (n21 of a diagonal block is n12's mirror)
+          Gw[itD22[u]] = n22;
         }
-        // the exit test's operand in FRONT of the barrier (the flag word arrived with this round's operands): block-uniform, and told
-        // so -- the word comes out of LDS (a vector register), and a loop exit the compiler has to treat as divergent wraps every
-        // round in EXEC-mask bookkeeping.  Behind the barrier only the branch is left on the chain.
-        last_big1 = max(last_big1, big_slot);
-        const int last_big_s = __builtin_amdgcn_readfirstlane(last_big1);
-        const bool done = round_idx + 1 - last_big_s >= ne - 1;
-        lds_barrier();
-        double *tsw = Gc; Gc = Gn; Gn = tsw;
-        cur ^= 1;
-        ++round_idx;
-        return done;
-  };
-  if (n > 1) {
-    kept2 = kept_scale(Gc);
-    if (tid == 0) { k.sFlag[6] = 0; k.sFlag[7] = 0; }
-    if (isParam) {                                   // rotations of the very first round
-      const double2 top = *reinterpret_cast<const double2 *>(Gc + (2 * tid) * ne + 2 * tid);
-      const RotT r = jacobi_rot_f32((float)top.x, (float)Gc[(2 * tid + 1) * ne + 2 * tid + 1], (float)top.y,
-                                    fmaxf((float)kept2, kept_lo), (float)abs2, (float)p.svd_stop2);
-      publish(k.dCS + (cur * np + tid) * 4, r, 0);
+      };
+      run_role(g_work);
+    } else {
+      run_role(idle_work);
     }
-    lds_barrier();
-    // The iteration ends as soon as ne - 1 consecutive rounds -- any such window is a complete sweep over all pairs --
-    // applied no big rotation: quadratic convergence then leaves off-diagonals of relative size ~svd_stop2, exactly the
-    // guarantee of "a whole sweep without a big rotation", but the window need not start at a sweep boundary (it saves
-    // about a third of a sweep per decomposition once the chain has settled).
-    // (measured: one flat loop over the rounds instead of this nest costs the generic body 60 cycles per round)
-    for (; sweeps < kJacobiMaxSweeps && !converged; ++sweeps) {
-      for (int rnd = 0; rnd < ne - 1; ++rnd) {
-        if (jacobi_round()) { converged = 1; break; }
-      }
-      if (!converged) kept2 = kept_scale(Gc);
-    }
+    if (round_idx & 1) { Gc = G1; Gn = G0; }         // the buffer the last round wrote holds G
   } else {
     converged = 1;
-  }
-  // the eigenvectors leave the registers: V[row][column position], as phase 9 reads them
-  double *V = V0;
-  if (vLaneOk) {
+    if (role == kRoleV) {                            // V = I
+      double vb[kVR][4];                                     // {v11, v12, v21, v22} per block
 #pragma unroll
-    for (int r = 0; r < kVR; ++r) {
-      const int P = vP0 + r;
-      if (r < vr && P < np) {
-        *reinterpret_cast<double2 *>(V + (2 * P) * ne + 2 * vQ) = make_double2(vb[r][0], vb[r][1]);
-        *reinterpret_cast<double2 *>(V + (2 * P + 1) * ne + 2 * vQ) = make_double2(vb[r][2], vb[r][3]);
+      for (int r = 0; r < kVR; ++r) {
+        const double one = (vP0 + r == vQ) ? 1.0 : 0.0;      // V = I
+        vb[r][0] = one; vb[r][1] = 0.0; vb[r][2] = 0.0; vb[r][3] = one;
       }
+      store_v(vb);
     }
   }
   if (p.stamps && tid == 0) t_c2 = __builtin_amdgcn_s_memtime();
