@@ -372,6 +372,16 @@ int tnml_set_persistent(tnml_ctx *ctx, int on);
 int tnml_set_shape_kernels(tnml_ctx *ctx, int on);
 /* *n_steps = steps of the last persistent sweep that ran a body compiled for their shape (0: none, switch off, or mode 2) */
 int tnml_fixed_shape_steps(tnml_ctx *ctx, int *n_steps);
+/* How the batch-side workgroups of a persistent sweep (both modes) sum their partial pre-gradients where one workgroup's LDS does not
+ * hold sixteen of them (bond 20 at two labels: 6400 floats per partial):
+ *   mode = 1 (default)  in slices: every workgroup counts its arrival, the first R workgroups each sum runs of 16 16-byte elements
+ *                       over all partials and count themselves done, the helper workgroups wait for R
+ *   mode = 0            by last arrivers: the last of each group of sixteen sums its group, the last group sums the group sums
+ * Same summation tree, same results bit for bit.  Smaller pre-gradients take one level through one workgroup's LDS either way, and
+ * per-step launches always reduce by last arrivers. */
+int tnml_set_persist_reduce(tnml_ctx *ctx, int mode);
+/* *n_steps = batch-side iterations of the last persistent sweep that reduced in slices (0: none, or mode 0) */
+int tnml_slice_reduce_steps(tnml_ctx *ctx, int *n_steps);
 
 /* tnml_sweep enqueues every launch of its n_steps steps without waiting (2 - 14 launches per step).  A profiler that
  * intercepts dispatches (rocprofv3 --pmc serialises them and keeps per-dispatch state) can be overrun by tens of

@@ -39,7 +39,7 @@ SYMBOLS = [
     'tnml_optim_config', 'tnml_optim_reset', 'tnml_gd_train_indices', 'tnml_gd_step', 'tnml_get_core_slots',
     'tnml_orthogonalize', 'tnml_compress', 'tnml_bond_spectra',
     'tnml_set_chain_scaling', 'tnml_predict_scaled',
-    'tnml_set_shape_kernels', 'tnml_fixed_shape_steps',
+    'tnml_set_shape_kernels', 'tnml_fixed_shape_steps', 'tnml_set_persist_reduce', 'tnml_slice_reduce_steps',
     'tnml_inner', 'tnml_axpby',
     'tnml_sample', 'tnml_sample_masked', 'tnml_set_sample_stack_bytes',
 ]
@@ -101,6 +101,8 @@ def lib():
         L.tnml_set_persistent.argtypes = [vp, C.c_int]
         L.tnml_set_shape_kernels.argtypes = [vp, C.c_int]
         L.tnml_fixed_shape_steps.argtypes = [vp, C.POINTER(C.c_int)]
+        L.tnml_set_persist_reduce.argtypes = [vp, C.c_int]
+        L.tnml_slice_reduce_steps.argtypes = [vp, C.POINTER(C.c_int)]
         L.tnml_trunc_rank.argtypes = [C.c_int] * 9
         L.tnml_update_B.argtypes = [vp, f32p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float,
                                     f64p, C.c_size_t, f32p]
@@ -740,6 +742,16 @@ class Context:
         """Steps of the last persistent sweep that ran a body compiled for their shape."""
         v = C.c_int()
         _chk(lib().tnml_fixed_shape_steps(self._h, C.byref(v)))
+        return v.value
+
+    def set_persist_reduce(self, mode=1):
+        """1 (default): a persistent sweep reduces pre-gradients beyond one level in slices, by many workgroups; 0: by last arrivers."""
+        _chk(lib().tnml_set_persist_reduce(self._h, int(mode)))
+
+    def slice_reduce_steps(self):
+        """Batch-side iterations of the last persistent sweep that reduced in slices."""
+        v = C.c_int()
+        _chk(lib().tnml_slice_reduce_steps(self._h, C.byref(v)))
         return v.value
 
     def set_sync_interval(self, n_steps):

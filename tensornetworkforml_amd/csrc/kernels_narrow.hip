@@ -1629,9 +1629,10 @@ __global__ __launch_bounds__(kNarrowThreads) void sweep_persist_kernel(const Per
 #pragma nounroll
     for (int it = 0; it <= n_steps; ++it) {
       WidePipeParams w;
-      __builtin_memcpy(&w, &steps_g[it == 0 ? n_steps : it - 1].w, sizeof w);
+      const WidePipeParams *rec = &steps_g[it == 0 ? n_steps : it - 1].w;
+      __builtin_memcpy(&w, rec, sizeof w);
       lds_barrier();                                       // the previous iteration's LDS arrays are dead
-      if (wide_pipe_block(WidePipeArgs<1>(w), (float *)smem_raw)) break;
+      if (wide_pipe_block(WidePipeArgs<1>(w, rec), (float *)smem_raw)) break;
     }
   }
 }
@@ -1677,10 +1678,11 @@ __global__ __launch_bounds__(kNarrowThreads) void persist_batch_kernel(const Per
 #pragma nounroll
   for (int it = 0; it <= n_steps; ++it) {
     WidePipeParams w;
-    __builtin_memcpy(&w, &steps_g[it == 0 ? n_steps : it - 1].w, sizeof w);
+    const WidePipeParams *rec = &steps_g[it == 0 ? n_steps : it - 1].w;
+    __builtin_memcpy(&w, rec, sizeof w);
     w.wg0 = 0;                                             // this grid holds batch-side workgroups only
     lds_barrier();
-    if (wide_pipe_block(WidePipeArgs<1>(w), (float *)smem_raw)) break;
+    if (wide_pipe_block(WidePipeArgs<1>(w, rec), (float *)smem_raw)) break;
   }
 }
 void launch_sweep_persist_split(const PersistStep *steps_dev, int n_steps, int n_helpers, int n_wide, size_t lds_update, size_t lds_helper,

@@ -181,7 +181,22 @@ static void check_pipe(const WidePipeParams &w) {
     if (w.zsize != nI * kD * kD * w.gn * w.L) die("WidePipeParams.zsize %d != nI D D gn L (%d %d %d)", w.zsize, nI, w.gn, w.L);
     if (w.slab_stride < w.zsize + kMetricSlots) die("WidePipeParams.slab_stride %d < zsize + tail", w.slab_stride);
     need(w.slabs, (size_t)w.nwide * w.slab_stride * 4, "WidePipeParams.slabs");
-    if (!w.one_level) need(w.gslabs, (size_t)w.ngroups * w.slab_stride * 4, "WidePipeParams.gslabs");
+    if (!w.one_level && !w.slice_red) need(w.gslabs, (size_t)w.ngroups * w.slab_stride * 4, "WidePipeParams.gslabs");
+    if (w.slice_red) {
+      // the slice plan of a persistent record: whole 128-byte lines per run, every 16-byte element in exactly one run, no more
+      // reducers than workgroups, the group sums of a run inside the workgroup's LDS, both words inside the step's counter block
+      const int n4 = (w.zsize + kMetricSlots + 3) / 4;
+      if (!w.persist || w.one_level) die("WidePipeParams: slice reduction on a record with persist %d one_level %d", w.persist, w.one_level);
+      if (w.slice_S < 8 || w.slice_S % 8) die("WidePipeParams.slice_S %d is no multiple of 8", w.slice_S);
+      if (w.slice_R < 1 || w.slice_R > w.nwide || w.slice_R > (n4 + w.slice_S - 1) / w.slice_S) die("WidePipeParams.slice_R %d for %d workgroups, %d elements", w.slice_R, w.nwide, n4);
+      if (w.slice_R < w.nwide && w.slice_R * w.slice_S < n4) die("WidePipeParams: %d reducers x %d elements < %d and not capped", w.slice_R, w.slice_S, n4);
+      if (w.ngroups < 1 || w.ngroups > kPipeGroupMax || w.gsz * w.ngroups < w.nwide) die("WidePipeParams: %d groups of %d for %d workgroups", w.ngroups, w.gsz, w.nwide);
+      if ((size_t)w.ngroups * w.slice_S * 16 > wide_pipe_lds_bytes(w) - 16) die("WidePipeParams: group sums of a run beyond the workgroup's LDS");
+      if ((size_t)w.nwide * w.slab_stride * 4 >= ((size_t)1 << 31)) die("WidePipeParams: the partials of %d workgroups beyond a 31-bit offset", w.nwide);
+      if ((size_t)n4 * 4 > (size_t)w.slab_stride) die("WidePipeParams: %d 16-byte elements beyond the slab stride %d", n4, w.slab_stride);
+      need(w.sarrive, 4, "WidePipeParams.sarrive"); need(w.sdone, 4, "WidePipeParams.sdone");
+      if (w.sarrive != w.gcnt + kPstArriveWord || w.sdone != w.gcnt + kPstDoneWord) die("WidePipeParams: slice words outside the step's counter block");
+    }
     need(w.zred, (size_t)(w.zsize + kMetricSlots) * 4, "WidePipeParams.zred");
     need(w.gcnt, (size_t)(w.ngroups > 0 ? w.ngroups : 1) * 4, "WidePipeParams.gcnt"); need(w.tcnt, 4, "WidePipeParams.tcnt");
     if (w.nwide * w.tiles_per_wg < w.ntiles) die("WidePipeParams: %d workgroups x %d tiles < %d tiles", w.nwide, w.tiles_per_wg, w.ntiles);
@@ -646,7 +661,7 @@ static void tr_struct(const WideParams &p) {
 static void tr_struct(const WidePipeParams &p) {
   I(b) I(b_pad) I(L) I(hj) I(gj) I(gn) I(hprev) I(first) I(do_ext) I(first_ext) I(do_f) I(wait_flag) I(do_z) I(act_fn) I(loss_fn) R(T)
   P(x_jm1) P(x_j) P(x_jp1) P(x_jp2) P(Eprev) P(Ecur) V(ext_core) P(Gj) P(Gn) P(Bnew) P(y) P(f) I(zsize) I(slab_stride) P(slabs) P(gslabs)
-  P(zred) P(gcnt) P(tcnt) I(nwide) I(gsz) I(ngroups) I(one_level) I(wg0) I(tiles_per_wg) I(ntiles) P(flag) I(token) P(status) I(persist)
+  P(zred) P(gcnt) P(tcnt) I(nwide) I(gsz) I(ngroups) I(one_level) I(slice_red) I(slice_S) I(slice_R) P(sarrive) P(sdone) I(wg0) I(tiles_per_wg) I(ntiles) P(flag) I(token) P(status) I(persist)
   P(coreflag) I(corewant) P(zready) I(zpublish) P(abort_flag) P(stamps)
 }
 static void tr_struct(const PersistHelperParams &p) {

@@ -254,6 +254,8 @@ struct tnml_ctx {
   bool persist_enabled = true;               // tnml_set_persistent
   bool shape_kernels = true;                 // tnml_set_shape_kernels: persistent sweeps may run the bodies compiled for a step shape
   int fixed_steps = 0;                       // steps of the last persistent sweep that did (tnml_fixed_shape_steps)
+  bool persist_slices = true;                // tnml_set_persist_reduce: pre-gradients beyond one level are reduced in slices by many workgroups
+  int slice_steps = 0;                       // records of the last persistent sweep that were (tnml_slice_reduce_steps)
   PersistStep *pst_dev = nullptr, *pst_host[2] = {nullptr, nullptr};
   hipEvent_t pst_ev[2] = {nullptr, nullptr};
   int pst_cur = 0;
@@ -2584,6 +2586,19 @@ static void pipe_try_one_level(WidePipeParams &w) {
   }
 }
 
+// Persistent sweep, a record that would take two levels (`blk`: the step's own 32-word counter block, zeroed before the launch): the
+// first R batch-side workgroups reduce runs of S 16-byte elements straight from the partials (wide_pipe_block).  R = ceil(n4 / S),
+// capped at the workgroups there are (a reducer then loops over runs `R` apart).  Left as it is where the group sums of a run do not
+// fit the workgroup's LDS.
+static void pipe_plan_slices(WidePipeParams &w, unsigned *blk) {
+  if (!w.persist || !w.do_z || w.one_level) return;
+  const int S = kPipeSliceLen, n4 = (w.zsize + kMetricSlots + 3) / 4;
+  if ((size_t)w.ngroups * S * 4 * sizeof(float) > wide_pipe_lds_bytes(w) - 16 || w.ngroups > kPipeGroupMax) return;
+  if ((size_t)w.nwide * w.slab_stride * sizeof(float) >= ((size_t)1 << 31)) return;      // the reducers address all partials from one base
+  w.slice_red = 1; w.slice_S = S; w.slice_R = std::min((n4 + S - 1) / S, w.nwide);
+  w.sarrive = blk + kPstArriveWord; w.sdone = blk + kPstDoneWord;
+}
+
 // `tpw` sample tiles per batch-side workgroup: the workgroups and reduction groups of the launch
 static void set_pipe_tiles(WidePipeParams &w, int tpw) {
   w.tiles_per_wg = tpw; w.nwide = (w.ntiles + tpw - 1) / tpw;
@@ -2894,6 +2909,8 @@ static int sweep_persist(tnml_ctx *c, const SweepCall &sc) {
   pro.gcnt = c->pst_cnt + (size_t)n_steps * 32; pro.tcnt = pro.gcnt + 16;
   if (!wide_pipe_fits(c, pro)) return give_up();
   pipe_try_one_level(pro);
+  if (c->persist_slices) pipe_plan_slices(pro, pro.gcnt);
+  int n_slice = pro.slice_red;
   lds_wide = wide_pipe_lds_bytes(pro);
   double bytes = 0, flops = 0;
   for (int k = 0; k < n_steps; ++k) {
@@ -2939,6 +2956,8 @@ static int sweep_persist(tnml_ctx *c, const SweepCall &sc) {
     wp.stamps = n.stamps;
     if (!wide_pipe_fits(c, wp)) return give_up();
     pipe_try_one_level(wp);
+    if (c->persist_slices) pipe_plan_slices(wp, wp.gcnt);
+    n_slice += wp.slice_red;
     lds_wide = std::max(lds_wide, wide_pipe_lds_bytes(wp));
     // ---- helper workgroups: T_k, T_k . Ng beside the SVD of step k-1; the three projections once its behind core is published
     PersistHelperParams &t = ps.t;
@@ -2950,6 +2969,10 @@ static int sweep_persist(tnml_ctx *c, const SweepCall &sc) {
     t.flag = fl + 0; t.want = (unsigned)k; t.aflag = fl + 5; t.awant = (unsigned)k; t.zready = fl + 2; t.zwant = (unsigned)k + 1;
     t.tcnt = c->pst_cnt + (size_t)k * 32 + 20; t.pcnt = c->pst_cnt + (size_t)k * 32 + 21;
     t.abort_flag = fl + 4; t.status = c->status; t.stamps = n.stamps;
+    // Z_k reduced in slices: its reducers count themselves done in their step's block, and all of them is what the helpers wait for
+    // (no last finisher, no flag hop); otherwise the single writer stores k + 1 into the launch's Z word
+    const WidePipeParams &zsrc = k == 0 ? pro : st[k - 1].w;
+    if (zsrc.slice_red) { t.zready = zsrc.sdone; t.zwant = (unsigned)zsrc.slice_R; }
     lds_help = std::max(lds_help, persist_helper_lds_bytes(zr, s, g, L, h, nH));
     if ((size_t)zr * D * D * g * L + kMetricSlots > (size_t)c->zstride) return give_up();
     // ---- the bookkeeping of the per-step path (the capture block belongs to the stamped step, if there is one)
@@ -2996,7 +3019,7 @@ static int sweep_persist(tnml_ctx *c, const SweepCall &sc) {
       return fail(TNML_ERR_STATE, "no persistent sweep kernel for step shape %d", shape);
     HIP_TRY(hipGetLastError());
   }
-  c->fixed_steps = n_fixed;
+  c->fixed_steps = n_fixed; c->slice_steps = n_slice;
   c->cnt_steps += n_steps; c->cnt_bytes += bytes; c->cnt_flops += flops;
   c->sweep_launches += 1; c->step_launches += n_steps; c->persist_sweeps += 1;
   c->Bnew_valid = true; c->f_current = true; drop_pregradients(c);
@@ -3744,6 +3767,19 @@ extern "C" int tnml_set_shape_kernels(tnml_ctx *c, int on) {
 extern "C" int tnml_fixed_shape_steps(tnml_ctx *c, int *n_steps) {
   if (!c || !n_steps) return TNML_ERR_ARG;
   *n_steps = c->fixed_steps;
+  return TNML_OK;
+}
+
+extern "C" int tnml_set_persist_reduce(tnml_ctx *c, int mode) {
+  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
+  if (mode < 0 || mode > 1) return fail(TNML_ERR_ARG, "mode %d outside [0, 1]", mode);
+  c->persist_slices = mode == 1;
+  return TNML_OK;
+}
+
+extern "C" int tnml_slice_reduce_steps(tnml_ctx *c, int *n_steps) {
+  if (!c || !n_steps) return TNML_ERR_ARG;
+  *n_steps = c->slice_steps;
   return TNML_OK;
 }
 

@@ -12,7 +12,8 @@
 // environments that exist already -- not the new core A_k.  So the workgroups of this file run inside the launch of
 // step k, next to the workgroup that performs the SVD: they extend E_k (with A_{k-1}, a product of the previous
 // launch), wait for B_new(k) on a flag, form f, activation, loss derivative and metrics, accumulate Z_{k+1} over their
-// samples and reduce the partial tensors in two fixed-order levels (last arriver of a group, then last group); the next
+// samples and reduce the partial tensors in two fixed-order levels (last arriver of a group, then last group; in a persistent
+// sweep the same tree in slices, by many workgroups at once: the slice reduction at the end of wide_pipe_block); the next
 // launch starts from the reduced Z and contracts it with A_k (2 h x h doubles of work).  The batch-sized work is off the
 // critical path as long as it is shorter than the SVD.
 //
@@ -31,6 +32,10 @@ typedef float fvec4 __attribute__((ext_vector_type(4)));
 constexpr int kPipeThreads = 1024;      // the launch is shared with the narrow workgroup
 constexpr int kPTSP = kTS + 1;          // sample stride of the LDS operand arrays (bank spread)
 constexpr int kPipeGroupMax = 16;       // members of a reduction group (and number of groups): up to 256 batch-side workgroups
+// slice reduction of the persistent sweep: 16-byte elements per run (a multiple of 8: whole 128-byte lines), and the two words it
+// takes of a step's 32-word counter block ([0..15] group tickets, [16] top ticket, [20] / [21] the helpers' arrivals)
+constexpr int kPipeSliceLen = 16;
+constexpr int kPstArriveWord = 22, kPstDoneWord = 23;
 
 __host__ __device__ inline int upm(int x, int m) { return (x + m - 1) / m * m; }
 
@@ -71,6 +76,11 @@ struct WidePipeParams {
   unsigned *tcnt;        // top-level arrival counter
   int nwide, gsz, ngroups;
   int one_level;         // small pre-gradient: the last arriver of the single group sums all partials through its LDS (host checked the room)
+  // persistent sweep, where the record would take two levels: the first slice_R workgroups each reduce runs of slice_S 16-byte
+  // elements straight from the partials (pipe_plan_slices below); no ticket, no group sums
+  int slice_red, slice_S, slice_R;
+  unsigned *sarrive;     // arrival word of the step's counter block: +1 per workgroup once its partial is stored and drained
+  unsigned *sdone;       // done word of the same block: +1 per reducer once its part of zred is stored and drained
   int wg0;               // blockIdx of the first batch-side workgroup
   int tiles_per_wg;      // sample tiles (kTS samples) a workgroup accumulates before it writes its partial tensor
   int ntiles;            // b_pad / kTS
@@ -251,8 +261,13 @@ void launch_sweep_persist_split(const PersistStep *steps_dev, int n_steps, int n
 // code of its own mode only.
 template <int PERSIST>
 struct WidePipeArgs : WidePipeParams {
-  __device__ __forceinline__ WidePipeArgs(const WidePipeParams &q) : WidePipeParams(q) {}
+  // rec: the record in memory the host wrote before the launch (persistent kernels).  What only the reduction at the end of the
+  // iteration reads -- the slice plan -- is a scalar load from it where it is used, not a value held across the whole iteration
+  // (the batch side is short of SGPRs, and in the one-kernel form the roles share one allocation)
+  __device__ __forceinline__ WidePipeArgs(const WidePipeParams &q, const WidePipeParams *rec_ = nullptr) : WidePipeParams(q), rec(rec_) {}
   static constexpr int persist = PERSIST;
+  const WidePipeParams *rec;
+  template <class T> __device__ __forceinline__ T late(const T WidePipeParams::*f) const { return *(const __attribute__((address_space(4))) T *)&(rec->*f); }
 };
 // returns true when the workgroup gave up (persistent sweep: a wait timed out here or elsewhere)
 template <class WP>
@@ -547,6 +562,69 @@ __device__ __forceinline__ bool wide_pipe_block(const WP &p, float *smem) {
   __shared__ unsigned sTicket;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   lds_barrier();
+  if (p.persist && p.late(&WidePipeParams::slice_red)) {
+    // ---- slice reduction (persistent sweep, pre-gradients beyond one level).  Every workgroup counts its arrival; the first
+    // slice_R workgroups then each sum runs of slice_S 16-byte elements over ALL partials, many CUs at once, and count themselves
+    // done; the helpers wait for slice_R on the done word.  First row of the hand-off table on both hops: sc1 stores, drained,
+    // barrier, one lane adds; one lane polls with sc1 loads, barrier, sc1 loads only -- no acquire.  The sums are sum_slabs' tree:
+    // the members of a group in slab order from +0, then the group sums in group order from +0.  The counter block belongs to
+    // this step alone (zeroed before the launch, never reset under its pollers).
+    unsigned *const sarrive = p.late(&WidePipeParams::sarrive);
+    const int R = p.late(&WidePipeParams::slice_R);
+    if (tid == 0) __hip_atomic_fetch_add(sarrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (bst) bst[36] = rt();
+    if (wg >= R) return false;
+    if (tid == 0) {                                                // (a reducer has arrived itself before it polls)
+      const int bad = spin_wait_ge(sarrive, (unsigned)p.nwide, p.abort_flag);
+      if (bad == 1) { atomicOr(p.status, 8); __hip_atomic_store(p.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+      sGiveUp = bad;
+    }
+    lds_barrier();
+    if (sGiveUp) return true;
+    if (bst) bst[39] = rt();
+    const int n4 = (n + 3) / 4, S = p.late(&WidePipeParams::slice_S), work = p.ngroups * S;
+    float4 *part = reinterpret_cast<float4 *>(smem);               // [ngroups][S] group sums (the staged partial has left: drained above)
+    // (ONE descriptor for all partials, the group in the offset: a descriptor per group is a per-lane one, which the compiler serves
+    // with a loop over the groups of a wave -- measured 4.2 us for a run of 16 elements where this form takes 2.2; the host keeps
+    // the partials inside a 31-bit offset)
+    const __amdgpu_buffer_rsrc_t rZ = sc1_rsrc(p.zred), rS = sc1_rsrc(p.slabs);
+    for (int run = wg; run * S < n4; run += R) {           // more than one run only where slice_R was capped at nwide
+      const int e0 = run * S, ne = min(S, n4 - e0);
+      if (run != wg) lds_barrier();                                // the previous run's group sums are dead
+      for (int idx = tid; idx < work; idx += NT) {
+        const int c = idx / S, el = idx - c * S;
+        if (el >= ne) continue;
+        const int k_lo = c * p.gsz, cnt = min(p.gsz, p.nwide - k_lo);
+        tn_uvec4 v[kPipeGroupMax];
+#pragma unroll
+        for (int k = 0; k < kPipeGroupMax; ++k)                    // all of the element's summands of this group in flight
+          v[k] = k < cnt ? ld_sc1_b128(rS, (unsigned)(((size_t)(k_lo + k) * p.slab_stride + 4 * (size_t)(e0 + el)) * sizeof(float))) : tn_uvec4{0u, 0u, 0u, 0u};
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int k = 0; k < kPipeGroupMax; ++k) {
+          a.x += __uint_as_float(v[k].x); a.y += __uint_as_float(v[k].y); a.z += __uint_as_float(v[k].z); a.w += __uint_as_float(v[k].w);
+        }
+        part[idx] = a;
+      }
+      lds_barrier();
+      for (int el = tid; el < ne; el += NT) {
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int c = 0; c < kPipeGroupMax; ++c) {                  // group order; the groups beyond ngroups are sum_slabs' padded zeros
+          const float4 g4 = c < p.ngroups ? part[c * S + el] : make_float4(0.f, 0.f, 0.f, 0.f);
+          a.x += g4.x; a.y += g4.y; a.z += g4.z; a.w += g4.w;
+        }
+        tn_uvec4 o; o.x = __float_as_uint(a.x); o.y = __float_as_uint(a.y); o.z = __float_as_uint(a.z); o.w = __float_as_uint(a.w);
+        st_sc1_b128(rZ, (unsigned)(16 * (e0 + el)), o);
+      }
+    }
+    if (bst) bst[40] = rt();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lds_barrier();
+    if (tid == 0) __hip_atomic_fetch_add(p.late(&WidePipeParams::sdone), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (bst) bst[41] = rt();
+    return false;
+  }
   const int grp = wg / p.gsz;
   const int g_lo = grp * p.gsz, g_n = min(p.gsz, p.nwide - g_lo);
   if (tid == 0) sTicket = __hip_atomic_fetch_add(p.gcnt + grp, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -13,6 +13,8 @@ hp = (1e-3, 1e-3, L2, 'softmax', 'full_cross_ent', 0.1, 'fixed')
 for persistent in (True, False):
     ctx = _hip.Context(N, D, L, M, b)
     ctx.set_persistent(persistent)
+    if hasattr(ctx, 'set_persist_reduce'):
+        ctx.set_persist_reduce(int(os.environ.get('REDUCE', '1')))          # REDUCE=0: the last-arriver reduction
     if hasattr(ctx, 'set_shape_kernels'):
         ctx.set_shape_kernels(os.environ.get('SHAPE', '1') != '0')      # SHAPE=0: the generic bodies everywhere
     batches = [bench.synth(N, b, L, 1234 + 97 * k) for k in range(4)]
@@ -42,6 +44,13 @@ for persistent in (True, False):
         # (the helpers wait once: no stamp of an end-of-step token any more; the L2 term's last factor is the update workgroup's)
         print('   helper 0, same clock: product level done %.2f, %.2f us after the core token | update workgroup: Nh^T . P2 (the "L2" cycles above) %.0f cycles'
               % ((st[31] - st[28]) / 100.0, (st[31] - st[23]) / 100.0, st[11]))
-        print('   batch-side workgroup 0 in the iteration of that step (f of step k, Z of step k+1), same clock: enter %.2f | core flag seen %.2f | B_new flag seen %.2f | tiles done %.2f | partial stored + ticket %.2f | reduced Z published (last arriver) %.2f'
-              % tuple((st[i] - st[28]) / 100.0 for i in (32, 33, 34, 35, 36, 37)))
+        sliced = hasattr(ctx, 'slice_reduce_steps') and ctx.slice_reduce_steps() > 0
+        if sliced:
+            # (slices: workgroup 0 is a reducer; Z is there for the helpers once every reducer is counted -- "Z seen" above, one step on)
+            print('   batch-side workgroup 0 in the iteration of that step (f of step k, Z of step k+1), same clock: enter %.2f | core flag seen %.2f | B_new flag seen %.2f | tiles done %.2f | partial stored + arrival %.2f | arrivals seen %.2f | slice summed %.2f | done counted %.2f'
+                  % tuple((st[i] - st[28]) / 100.0 for i in (32, 33, 34, 35, 36, 39, 40, 41)))
+            print('   slice reduction: %d batch-side iterations of the sweep' % ctx.slice_reduce_steps())
+        else:
+            print('   batch-side workgroup 0 in the iteration of that step (f of step k, Z of step k+1), same clock: enter %.2f | core flag seen %.2f | B_new flag seen %.2f | tiles done %.2f | partial stored + ticket %.2f | reduced Z published (last arriver) %.2f'
+                  % tuple((st[i] - st[28]) / 100.0 for i in (32, 33, 34, 35, 36, 37)))
     ctx.close()
