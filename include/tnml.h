@@ -111,6 +111,8 @@ int tnml_set_cores(tnml_ctx *ctx, const float *cores_flat, size_t n_floats, cons
                    int l_pos);
 int tnml_cores_size(tnml_ctx *ctx, size_t *n_floats);
 int tnml_get_cores(tnml_ctx *ctx, float *cores_flat, size_t capacity, int32_t *bond, int *l_pos);
+/* bond [N-1] and l_pos (or NULL) alone: host bookkeeping, nothing is copied from the device */
+int tnml_get_bonds(tnml_ctx *ctx, int32_t *bond, int *l_pos);
 /* every core *= factor: the calibration loop of Network.__init__ (Network_class.py:175-176) */
 int tnml_scale_cores(tnml_ctx *ctx, double factor);
 /* Tests and diagnostics: the core slots as the device holds them, padding included -- slots [N][core_stride] with
@@ -568,6 +570,44 @@ int tnml_sample_masked(tnml_ctx *ctx, int n, int K, const double *phi, const dou
                        int32_t *labels_out, double *logp_out, double *class_logw_out);
 /* bytes of the environment stack a chunk of tnml_sample_masked may take (0: TNML_ERR_ARG) */
 int tnml_set_sample_stack_bytes(tnml_ctx *ctx, size_t bytes);
+
+/* ---- the gradient of the log-norm ------------------------------------ */
+/* grad_flat receives Gz_i = d log|<W|W>_S| / d A_i for every core, in the layout of tnml_get_cores (capacity in floats, at least
+ * tnml_cores_size; floats behind the gradient are left alone), and sign_log2 [2] = {sign of <W|W>_S, log|<W|W>_S|}, the pair
+ * tnml_inner returns (for an indefinite metric the sign may be -1; the gradient is that of log|.| either way).  S: NULL for the
+ * Euclidean product, else a symmetric float64 metric, [D][D] for every site (per_site 0) or [N][D][D] (per_site 1); the label axis
+ * is contracted with the identity.  With S = sum_k w_k phi_k phi_k^T of a pixel grid <W|W>_S is the normaliser Z of tnml_sample,
+ * and Gz is the model term of every likelihood gradient.
+ * Computed in float64 from the float32 cores: both metric environments of every site, each multiplied by an exact power of two
+ * after every site and stored with its running exponent, then per site L_i . (S A_i) . R_{i+1} scaled by 2 / <W|W>_S, the power of two
+ * applied by ldexp, one rounding to float32 per element.  sum(Gz_i A_i) = 2 at every site, and Gz is of order 1 / |A_i|: it is a
+ * float32 for the un-calibrated 784-site chain whose <W|W> is about 1e-132.  No float atomic, every sum in a fixed order: two calls
+ * on the same cores are bit-equal.  Nothing on the device changes but the call's own buffers; no forward is needed afterwards.
+ * Refused before anything is launched: TNML_ERR_ARG (a NULL output; per_site neither 0 nor 1; capacity too small; a metric entry
+ * that is not finite, or S[d][e] and S[e][d] further apart than 1e-12 of their size; a bond above 64 or environments beyond 160 KB of LDS: the message names the bytes),
+ * TNML_ERR_STATE (cores never set; a communicator attached).  After the run: TNML_ERR_NONFINITE (a core element or an environment
+ * that is not finite; <W|W>_S == 0, sign_log2 then holds (0, -inf); a gradient element beyond float32): grad_flat is not written. */
+int tnml_log_norm_grad(tnml_ctx *ctx, const double *S, int per_site, float *grad_flat, size_t capacity, double *sign_log2);
+
+/* The negative log-likelihood of a batch under p(x, l) = prod_i w(x_i) f_l(x)^2 / Z, Z = <W|W>_S, and its gradient over all cores.
+ * X [b][N][D] are the features phi[level] of the pixels on the grid whose Gram matrix is S [D][D] (NULL: the identity); y [b], or
+ * NULL for -log p(x) with the label summed.  out3 = { -mean_s(log f_y^2 [or log sum_l f_l^2] - log Z), log Z, samples whose
+ * cotangent is not finite }; the term -mean_s sum_i log w(x_{s,i}) does not depend on the model and is the caller's to add.
+ * grad_flat (layout and capacity of tnml_core_grad) receives the DESCENT direction G = Gd - Gz: cores + lr G lowers the value.  Gd
+ * is tnml_core_grad's gradient with the cotangent 2 delta(l', y_s) / (b f_y[s]) (or 2 f_l'[s] / (b sum_l f_l[s]^2)), in the chunks
+ * and with the kernels of that call (tnml_set_core_grad_chunk, tnml_set_chain_scaling apply); Gz is tnml_log_norm_grad's, subtracted
+ * on the device.  sum(G_i A_i) = 0 at every site.  The gradient does not depend on the chunk size, nor does the value.
+ * The cotangent is a float32, so f itself must be representable: a calibrated network.  Samples with f_y == 0 or a non-finite f are
+ * counted; if there are any the call returns TNML_ERR_NONFINITE naming the count, with out3 written and grad_flat not.
+ * _indices: the rows idx of the attached dataset (its features must lie on the grid), with the dataset's labels (use_labels != 0) or
+ * without.  tnml_nll_eval / tnml_nll_eval_indices: the value alone, without a gradient launch.
+ * Refusals: those of tnml_core_grad(_indices) and of tnml_log_norm_grad (per_site 0), and TNML_ERR_ARG for a label outside [0, L).
+ * Nothing on the device changes but the calls' own buffers. */
+int tnml_nll_grad(tnml_ctx *ctx, const float *X, const int32_t *y, int b, const double *S, float *grad_flat, size_t capacity, double *out3);
+int tnml_nll_grad_indices(tnml_ctx *ctx, const int32_t *idx, int b, int use_labels, const double *S, float *grad_flat, size_t capacity,
+                          double *out3);
+int tnml_nll_eval(tnml_ctx *ctx, const float *X, const int32_t *y, int b, const double *S, double *out3);
+int tnml_nll_eval_indices(tnml_ctx *ctx, const int32_t *idx, int n, int use_labels, const double *S, double *out3);
 
 /* Host-side planning helper, exported so that CPU tests can check the bond bookkeeping without a
  * GPU: truncation rank kept by tensor_svd (Network_class.py:894-945) for a step on sites

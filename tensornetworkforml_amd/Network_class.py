@@ -765,6 +765,83 @@ class Network():
         return [int(v) for v in bonds]
 
     # ------------------------------------------------------------------------------------------
+    # the gradient of the log-norm (not in the reference)
+    # ------------------------------------------------------------------------------------------
+    def _checked_metric(self, metric):
+        """None, or the metric as a float64 array (D, D) or (N, D, D), symmetric and finite (ValueError otherwise)"""
+        metric = self._metric(metric)
+        if metric is None:
+            return None
+        metric = np.ascontiguousarray(metric, dtype=np.float64)
+        if metric.shape not in ((self.D, self.D), (self.N, self.D, self.D)):
+            raise ValueError('the metric has shape %s, neither (D, D) = %s nor (N, D, D) = %s'
+                             % (metric.shape, (self.D, self.D), (self.N, self.D, self.D)))
+        if not np.isfinite(metric).all():
+            raise ValueError('the metric has an entry that is not finite')
+        mt = np.swapaxes(metric, -1, -2)
+        if not (np.abs(metric - mt) <= 1e-12 * (np.abs(metric) + np.abs(mt))).all():
+            raise ValueError('the metric is not symmetric')
+        return metric
+
+    def log_norm_gradient(self, metric=None):
+        """(G, (sign, log|Z|)) with Z = <W|W>_S: G a list of N float32 arrays in the canonical core shapes (ml, D, mr[, L]),
+        G[i] = d log|Z| / d A_i, formed in float64 on the device from both metric environments of every site and rounded once.
+        metric as for inner, 'uniform' included; with the Gram matrix of a pixel grid Z is the normaliser of sample / log_prob and
+        G the model term of every likelihood gradient.  sum(G[i] * A_i) = 2 at every site; a step A_i += lr G[i] raises the norm.
+        Bonds up to 64.  Nothing on the device changes."""
+        metric = self._checked_metric(metric)
+        ctx = self._sync_to_device(max(self._b, 1))
+        return ctx.log_norm_grad(metric)
+
+    def _likelihood_batch(self, X, y, levels, grid, weights):
+        """(features (b, N, D) float32, labels (b,) int32 or None, S (D, D), -mean_s sum_i log w(x_si)) of images on the grid"""
+        x, phi, w = self._pixel_grid(levels, grid, weights)
+        lev = self._levels_of(X, x, 'X')
+        if lev.shape[1] != self.N:
+            raise ValueError('images of %d sites for a network of %d' % (lev.shape[1], self.N))
+        if lev.min() < 0 or lev.max() >= len(x):
+            raise ValueError('X holds levels outside [0, %d)' % len(x))
+        if y is not None:
+            y = np.ascontiguousarray(y, dtype=np.int32)
+            if y.shape != (len(lev),):
+                raise ValueError('%d images and labels of shape %s' % (len(lev), y.shape))
+            if y.min() < 0 or y.max() >= self.L:
+                raise ValueError('y holds labels outside [0, %d)' % self.L)
+        S = np.einsum('k,kd,ke->de', w, phi, phi)
+        return phi[lev].astype(np.float32), y, S, -float(np.log(w)[lev].sum(axis=1).mean())
+
+    def nll_gradient(self, X, y=None, levels=256, grid=None, weights=None):
+        """(G, nll) of a batch of images X (b, N) (pixel values on the grid, or integer levels) under the model's own distribution
+        p(x, l) = prod_i w(x_i) f_l(psi(x))^2 / Z: nll = -mean(log p(x, y)), or -mean(log p(x)) with y None (the label summed), equal
+        to -mean(log_prob(X, y, joint=True)[0]); G the DESCENT direction over all cores in the canonical shapes, A_i += lr G[i]
+        lowers nll.  sum(G[i] * A_i) = 0 at every site: the likelihood does not see the scale of a core.  The network must be
+        calibrated (f a float32; a sample with f_y == 0 raises).  Bonds up to 64.  Nothing on the device changes."""
+        feats, y, S, logw = self._likelihood_batch(X, y, levels, grid, weights)
+        ctx = self._sync_to_device(max(self._b, 1))
+        G, out = ctx.nll_grad(feats, y, S)
+        return G, float(out[0]) + logw
+
+    def nll_gradient_indices(self, idx, labels=True, levels=256, grid=None, weights=None):
+        """The same for the samples idx of the attached dataset, with its labels or (labels=False) without.  The caller sees to it
+        that the dataset's pixels lie on the grid; the returned value leaves out the term -mean(sum_i log w(x_i)), which does not
+        depend on the model."""
+        _, phi, w = self._pixel_grid(levels, grid, weights)
+        ctx = self._sync_to_device(max(self._b, 1))
+        G, out = ctx.nll_grad_indices(idx, labels, np.einsum('k,kd,ke->de', w, phi, phi))
+        return G, float(out[0])
+
+    def nll(self, indices_or_X, y=None, labels=True, levels=256, grid=None, weights=None):
+        """The value alone, without a gradient launch: images X (b, N) with y or None, as nll_gradient; or a one-dimensional list
+        of dataset indices with `labels`, as nll_gradient_indices (the value then leaves out the sum log w term)."""
+        if np.ndim(indices_or_X) == 1:
+            _, phi, w = self._pixel_grid(levels, grid, weights)
+            ctx = self._sync_to_device(max(self._b, 1))
+            return float(ctx.nll_eval_indices(indices_or_X, labels, np.einsum('k,kd,ke->de', w, phi, phi))[0])
+        feats, y, S, logw = self._likelihood_batch(indices_or_X, y, levels, grid, weights)
+        ctx = self._sync_to_device(max(self._b, 1))
+        return float(ctx.nll_eval(feats, y, S)[0]) + logw
+
+    # ------------------------------------------------------------------------------------------
     # samples and log-likelihoods of the Born distribution |f|^2 (not in the reference; DESIGN.md section 22)
     # ------------------------------------------------------------------------------------------
     def _pixel_grid(self, levels, grid, weights):

@@ -42,6 +42,7 @@ SYMBOLS = [
     'tnml_set_shape_kernels', 'tnml_fixed_shape_steps', 'tnml_set_persist_reduce', 'tnml_slice_reduce_steps',
     'tnml_inner', 'tnml_axpby',
     'tnml_sample', 'tnml_sample_masked', 'tnml_set_sample_stack_bytes',
+    'tnml_get_bonds', 'tnml_log_norm_grad', 'tnml_nll_grad', 'tnml_nll_grad_indices', 'tnml_nll_eval', 'tnml_nll_eval_indices',
 ]
 
 
@@ -153,6 +154,12 @@ def lib():
         L.tnml_sample_masked.argtypes = [vp, C.c_int, C.c_int, f64p, f64p, i32p, C.POINTER(C.c_uint8), C.c_int, i32p, f64p, C.c_uint64, C.c_int,
                                          i32p, i32p, f64p, f64p]
         L.tnml_set_sample_stack_bytes.argtypes = [vp, C.c_size_t]
+        L.tnml_get_bonds.argtypes = [vp, i32p, C.POINTER(C.c_int)]
+        L.tnml_log_norm_grad.argtypes = [vp, f64p, C.c_int, f32p, C.c_size_t, f64p]
+        L.tnml_nll_grad.argtypes = [vp, f32p, i32p, C.c_int, f64p, f32p, C.c_size_t, f64p]
+        L.tnml_nll_grad_indices.argtypes = [vp, i32p, C.c_int, C.c_int, f64p, f32p, C.c_size_t, f64p]
+        L.tnml_nll_eval.argtypes = [vp, f32p, i32p, C.c_int, f64p, f64p]
+        L.tnml_nll_eval_indices.argtypes = [vp, i32p, C.c_int, C.c_int, f64p, f64p]
         _lib = L
     return _lib
 
@@ -565,6 +572,101 @@ class Context:
     def set_core_grad_chunk(self, n):
         """Samples per pass of the core-gradient calls (rounded up to a multiple of 64); 0: the default (tests, diagnostics)."""
         _chk(lib().tnml_set_core_grad_chunk(self._h, int(n)))
+
+    # ---- the gradient of the log-norm (DESIGN.md section 24)
+    def log_norm_grad(self, metric=None):
+        """(G, (sign, log|<W|W>_S|)): G a list of N arrays in the canonical core shapes, d log|<W|W>_S| / d A_i in float64 on the
+        device, rounded once to float32.  metric: None, (D, D) or (N, D, D) float64, symmetric.  Nothing on the device changes."""
+        mp, per_site = None, 0
+        if metric is not None:
+            metric = np.ascontiguousarray(metric, dtype=np.float64)
+            if metric.shape == (self.N, self.D, self.D):
+                per_site = 1
+            elif metric.shape != (self.D, self.D):
+                raise TnmlError(-1, 'the metric has shape %s, neither (D, D) nor (N, D, D)' % (metric.shape,))
+            mp = _ptr(metric, C.c_double)
+        n = C.c_size_t()
+        _chk(lib().tnml_cores_size(self._h, C.byref(n)))
+        flat = np.empty(n.value, dtype=np.float32)
+        out = np.zeros(2, dtype=np.float64)
+        _chk(lib().tnml_log_norm_grad(self._h, mp, per_site, _ptr(flat, C.c_float), flat.size, _ptr(out, C.c_double)))
+        return self._cut(flat), (float(out[0]), float(out[1]))
+
+    # ---- the likelihood of a batch and its gradient (DESIGN.md section 24)
+    def _grid_metric(self, S):
+        if S is None:
+            return None, None
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        if S.shape != (self.D, self.D):
+            raise TnmlError(-1, 'the metric has shape %s, not (D, D)' % (S.shape,))
+        return S, _ptr(S, C.c_double)
+
+    def _cut(self, flat):
+        """a flat gradient cut into the canonical core shapes (the bonds come from the host's bookkeeping: nothing is copied)"""
+        bond = np.empty(self.N - 1, dtype=np.int32)
+        lp = C.c_int()
+        _chk(lib().tnml_get_bonds(self._h, _ptr(bond, C.c_int32), C.byref(lp)))
+        G, off = [], 0
+        for shp in core_shapes(bond, lp.value, self.D, self.L):
+            k = int(np.prod(shp))
+            G.append(flat[off:off + k].reshape(shp).copy())
+            off += k
+        return G
+
+    def nll_grad(self, X, y=None, S=None):
+        """(G, out3): the descent direction of -log p(x, y) (y given) or -log p(x) over all cores in the canonical shapes, and
+        out3 = (-mean(log f^2 - log Z), log Z, samples with a non-finite cotangent).  X (b, N, D) features on the grid whose Gram
+        matrix is S (D, D) (None: the identity)."""
+        X = _f32(X)
+        assert X.ndim == 3 and X.shape[1] == self.N and X.shape[2] == self.D, \
+            "The 1 dimension of the input data must be the flattened number of pixels"
+        yp = None
+        if y is not None:
+            y = np.ascontiguousarray(y, dtype=np.int32)
+            assert y.shape == (X.shape[0],)
+            yp = _ptr(y, C.c_int32)
+        S, sp = self._grid_metric(S)
+        n = C.c_size_t()
+        _chk(lib().tnml_cores_size(self._h, C.byref(n)))
+        flat = np.empty(n.value, dtype=np.float32)
+        out = np.zeros(3, dtype=np.float64)
+        _chk(lib().tnml_nll_grad(self._h, _ptr(X, C.c_float), yp, X.shape[0], sp, _ptr(flat, C.c_float), flat.size, _ptr(out, C.c_double)))
+        return self._cut(flat), out
+
+    def nll_grad_indices(self, idx, labels=True, S=None):
+        """The same for the dataset samples idx, with the dataset's labels or without."""
+        idx = self._idx(idx)
+        S, sp = self._grid_metric(S)
+        n = C.c_size_t()
+        _chk(lib().tnml_cores_size(self._h, C.byref(n)))
+        flat = np.empty(n.value, dtype=np.float32)
+        out = np.zeros(3, dtype=np.float64)
+        _chk(lib().tnml_nll_grad_indices(self._h, _ptr(idx, C.c_int32), idx.size, int(bool(labels)), sp, _ptr(flat, C.c_float), flat.size,
+                                         _ptr(out, C.c_double)))
+        return self._cut(flat), out
+
+    def nll_eval(self, X, y=None, S=None):
+        """out3 alone for a host batch, without a gradient launch"""
+        X = _f32(X)
+        assert X.ndim == 3 and X.shape[1] == self.N and X.shape[2] == self.D, \
+            "The 1 dimension of the input data must be the flattened number of pixels"
+        yp = None
+        if y is not None:
+            y = np.ascontiguousarray(y, dtype=np.int32)
+            assert y.shape == (X.shape[0],)
+            yp = _ptr(y, C.c_int32)
+        S, sp = self._grid_metric(S)
+        out = np.zeros(3, dtype=np.float64)
+        _chk(lib().tnml_nll_eval(self._h, _ptr(X, C.c_float), yp, X.shape[0], sp, _ptr(out, C.c_double)))
+        return out
+
+    def nll_eval_indices(self, idx, labels=True, S=None):
+        """out3 alone for the dataset samples idx"""
+        idx = self._idx(idx)
+        S, sp = self._grid_metric(S)
+        out = np.zeros(3, dtype=np.float64)
+        _chk(lib().tnml_nll_eval_indices(self._h, _ptr(idx, C.c_int32), idx.size, int(bool(labels)), sp, _ptr(out, C.c_double)))
+        return out
 
     # ---- gradient training over all cores
     def optim_config(self, kind='sgd', momentum=0.0, beta1=0.9, beta2=0.999, eps=1e-8, clip=True):

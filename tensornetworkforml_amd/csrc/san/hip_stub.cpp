@@ -517,6 +517,68 @@ static void check_sample(const SampleParams &p, dim3 g, dim3 b, size_t shm, bool
     if (!seen[smp]) die("SampleParams: sample %d is in no tile", smp);
 }
 
+// the gradient of the log-norm (kernels_nll.hip): one parameter block for the environment kernel and the gradient kernel.  The table
+// is read here as the kernels read it: every core, both environment stacks and both exponent arrays over N + 1 slots, and every
+// core's part of G at its offset in the flat layout.
+static void check_lognorm(const LogNormParams &p, dim3 g, dim3 b, size_t shm, bool grad) {
+  scan(&p, sizeof p, "LogNormParams");
+  if (p.N < 2 || p.D < 2 || p.D > kMaxD || p.L < 1 || p.l_pos < 0 || p.l_pos >= p.N) die("LogNormParams: N %d D %d L %d l_pos %d", p.N, p.D, p.L, p.l_pos);
+  if (p.metric_sites != 0 && p.metric_sites != 1 && p.metric_sites != p.N) die("LogNormParams: metric_sites %d", p.metric_sites);
+  if (p.mode != 0 && p.mode != 1) die("LogNormParams: mode %d", p.mode);
+  need(p.tab, (size_t)2 * p.N * 4, "LogNormParams.tab");
+  int mb = 1;
+  size_t off = 0;
+  for (int i = 0; i < p.N; ++i) {
+    const int ml = i == 0 ? 1 : p.tab[i - 1], mr = i == p.N - 1 ? 1 : p.tab[i];
+    if (ml < 1 || mr < 1) die("LogNormParams: site %d is %d x %d", i, ml, mr);
+    mb = mb > mr ? mb : mr;
+    const size_t ne = (size_t)ml * p.D * mr * (i == p.l_pos ? p.L : 1);
+    if ((size_t)p.tab[p.N + i] != off) die("LogNormParams: core %d at offset %d, the flat layout has it at %zu", i, p.tab[p.N + i], off);
+    if (i == p.l_pos) need(p.lab, ne * 4, "LogNormParams.lab");
+    else {
+      if (ne > p.core_stride) die("LogNormParams: core %d of %zu floats in a slot of %zu", i, ne, p.core_stride);
+      need(p.cores + (size_t)i * p.core_stride, ne * 4, "LogNormParams.cores");
+    }
+    if (grad) need(p.G + off, ne * 4, "LogNormParams.G");
+    off += ne;
+  }
+  const size_t m2 = (size_t)mb * mb;
+  if (p.lds_m != mb || mb > kLnzMaxBond || p.env_stride < m2) die("LogNormParams: lds_m %d env_stride %zu for bond %d", p.lds_m, p.env_stride, mb);
+  if (p.metric_sites) need(p.metric, (size_t)p.metric_sites * p.D * p.D * 8, "LogNormParams.metric");
+  need(p.envL, (size_t)(p.N + 1) * p.env_stride * 8, "LogNormParams.envL");
+  need(p.envR, (size_t)(p.N + 1) * p.env_stride * 8, "LogNormParams.envR");
+  need(p.expL, (size_t)(p.N + 1) * 4, "LogNormParams.expL");
+  need(p.expR, (size_t)(p.N + 1) * 4, "LogNormParams.expR");
+  need(p.out, 2 * 8, "LogNormParams.out");
+  need(p.status, 2 * 4, "LogNormParams.status");
+  if (!grad) {
+    if (p.status[0] != 0 || p.status[1] != 0) die("LogNormParams: status words %d %d at launch", p.status[0], p.status[1]);
+    if (g.x != 2 || g.y != 1 || g.z != 1 || b.x != 1024) die("lognorm_env_kernel: grid %u block %u", g.x, b.x);
+    if (shm < lognorm_env_lds_bytes(mb, p.D)) die("lognorm_env_kernel: %zu bytes of LDS for bond %d", shm, mb);
+  } else {
+    if (g.x != (unsigned)p.N || g.y != (unsigned)p.L || g.z != 1 || b.x != 512) die("lognorm_grad_kernel: grid (%u, %u) block %u for N %d L %d", g.x, g.y, b.x, p.N, p.L);
+    if (shm < lognorm_grad_lds_bytes(mb, p.D)) die("lognorm_grad_kernel: %zu bytes of LDS for bond %d", shm, mb);
+  }
+}
+
+// the cotangent of the likelihood's data term (kernels_nll.hip): f and the labels over the chunk, cot over its padded columns, the
+// per-sample terms and flags at the chunk's offset within the batch
+static void check_nll_cot(const NllCotParams &p, dim3 g, dim3 b) {
+  scan(&p, sizeof p, "NllCotParams");
+  if (p.L < 1 || p.b < 1 || p.b > p.b_pad || p.b_pad % 64 || p.f_bpad < p.b_pad || p.off < 0 || p.batch < p.off + p.b)
+    die("NllCotParams: L %d b %d b_pad %d f_bpad %d off %d batch %d", p.L, p.b, p.b_pad, p.f_bpad, p.off, p.batch);
+  if ((size_t)g.x * b.x < (size_t)p.b_pad || g.y != 1 || b.x != 256) die("nll_cot_kernel: grid %u x %u for b_pad %d", g.x, b.x, p.b_pad);
+  need(p.f, ((size_t)(p.L - 1) * p.f_bpad + p.b) * 4, "NllCotParams.f");
+  if (p.y) {
+    need(p.y, (size_t)p.b * 4, "NllCotParams.y");
+    for (int s = 0; s < p.b; ++s)
+      if (p.y[s] < 0 || p.y[s] >= p.L) die("NllCotParams: label %d of sample %d outside [0, %d)", p.y[s], s, p.L);
+  }
+  if (p.cot) need(p.cot, (size_t)p.L * p.b_pad * 4, "NllCotParams.cot");
+  need(p.terms + p.off, (size_t)p.b * 8, "NllCotParams.terms");
+  need(p.bad + p.off, (size_t)p.b * 4, "NllCotParams.bad");
+}
+
 // the same given any set of known pixels (kernels_sample_masked.hip): one parameter block for the environment launch and the walk of
 // one chunk of tiles.  The bond, tile and row tables, the mask and the known levels are read here as the kernels read them: every
 // core, the stack slots and E of every row of the launch, the grid, the uniforms and the outputs with their extents; T the one the
@@ -698,6 +760,11 @@ static void tr_struct(const SampleMaskedParams &p) {
   I(N) I(D) I(L) I(l_pos) I(K) I(n) I(T) I(n_tiles) I(lds_m) I(mask_rows) P(bond) P(cores) P(lab) I(core_stride) P(S) P(phi) P(w) P(tile_class) P(tile_rows)
   P(mask) P(known) P(stack) I(env_stride) P(E) P(u) I(seed) P(levels) P(labels) P(logp0) P(status)
 }
+static void tr_struct(const LogNormParams &p) {
+  I(N) I(D) I(L) I(l_pos) I(metric_sites) I(lds_m) I(mode) P(tab) P(cores) P(lab) I(core_stride) P(metric) P(envL) P(envR) P(expL) P(expR) I(env_stride)
+  P(G) P(out) P(status)
+}
+static void tr_struct(const NllCotParams &p) { P(f) P(y) P(cot) P(terms) P(bad) I(L) I(b) I(b_pad) I(f_bpad) I(off) I(batch) }
 static void tr_struct(const InputGradPixels &p) { P(g) P(data) P(idx) P(out) I(b) I(N) I(D) }
 static void tr_struct(const BigExtArgs &p) { P(Eprev) P(x_km1) P(x_k) V(A) I(b_pad) P(Ecur) P(Pk) }
 static void tr_struct(const ChainSite &p) { I(core_off) I(is_label) I(n_in) I(n_out) I(s_in) I(s_d) I(s_out) I(x_site) I(env_out_off) }
@@ -741,6 +808,8 @@ static void tr_launch(const std::string &name, dim3 g, dim3 b, size_t shm, hipSt
     else if (is("AlgebraParams")) tr_struct(*(const AlgebraParams *)args[i]);
     else if (is("SampleParams")) tr_struct(*(const SampleParams *)args[i]);
     else if (is("SampleMaskedParams")) tr_struct(*(const SampleMaskedParams *)args[i]);
+    else if (is("NllCotParams")) tr_struct(*(const NllCotParams *)args[i]);
+    else if (is("LogNormParams")) tr_struct(*(const LogNormParams *)args[i]);
     else if (is("CoreView")) { const CoreView &v = *(const CoreView *)args[i]; tr(" [%s %d %d %d %d %d]", dp(v.base).c_str(), v.n_in, v.n_out, v.s_in, v.s_d, v.s_out); }
     else if (is("BigFrontTiles")) tr(" %d %d", ((int *)args[i])[0], ((int *)args[i])[1]);
     else if (is("float")) tr(" %.9g", *(float *)args[i]);
@@ -832,6 +901,15 @@ hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t s
     check_sample(*(const SampleParams *)args[0], g, b, shm, has("sample_walk_kernel"));
   } else if (has("sample_env_masked_kernel") || has("sample_walk_masked_kernel")) {
     check_sample_masked(*(const SampleMaskedParams *)args[0], g, b, shm, has("sample_walk_masked_kernel"));
+  } else if (has("lognorm_env_kernel") || has("lognorm_grad_kernel")) {
+    check_lognorm(*(const LogNormParams *)args[0], g, b, shm, has("lognorm_grad_kernel"));
+  } else if (has("nll_cot_kernel")) {
+    check_nll_cot(*(const NllCotParams *)args[0], g, b);
+  } else if (has("nll_sum_kernel")) {            // (terms, bad, n, acc)
+    const int n = *(int *)args[2];
+    if (n < 1 || g.x != 1 || b.x != 256) die("nll_sum_kernel: n %d grid %u block %u", n, g.x, b.x);
+    need(*(const double **)args[0], (size_t)n * 8, "nll_sum: terms"); need(*(const int **)args[1], (size_t)n * 4, "nll_sum: flags");
+    need(*(double **)args[3], 2 * 8, "nll_sum: sums");
   } else if (has("input_grad_onehot_kernel")) {   // (f, f_bpad, L, b, cot, b_pad)
     const int fbp = *(int *)args[1], L = *(int *)args[2], bb = *(int *)args[3], bp = *(int *)args[5];
     if (bb < 1 || bb > bp || bp > fbp || (size_t)g.x * b.x < (size_t)bp) die("input_grad_onehot_kernel: b %d b_pad %d f_bpad %d grid %u x %u", bb, bp, fbp, g.x, b.x);

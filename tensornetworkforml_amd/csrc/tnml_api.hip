@@ -366,6 +366,21 @@ struct tnml_ctx {
     std::vector<int> host;                   // host copies of the tables for the call in flight (they outlive the asynchronous upload)
     std::vector<double> hostd, hostE, hostp;
   } smk;
+  // the gradient of the log-norm.  One group, sized from m_cap, the largest bond of a call: the table of
+  // grad_table, the metric, both environment stacks with their exponents, the gradient (of cg_G's size), the two outputs, the status.
+  struct {
+    int *tab = nullptr, *expL = nullptr, *expR = nullptr, *status = nullptr;
+    double *metric = nullptr, *envL = nullptr, *envR = nullptr, *out = nullptr;
+    float *G = nullptr;
+    int m_cap = 0;
+    std::vector<int> tab_host;               // host copy of the table for the call in flight (it outlives the asynchronous upload)
+  } lnz;
+  // the likelihood of a batch: per-sample terms and flags of the call in flight, and their two sums
+  struct {
+    double *terms = nullptr, *acc = nullptr;
+    int *bad = nullptr;
+    int n_cap = 0;
+  } nll;
   // multi-GPU
   ncclComm_t comm = nullptr;
   int rank = 0, nranks = 1;
@@ -653,6 +668,15 @@ extern "C" int tnml_get_cores(tnml_ctx *c, float *flat, size_t capacity, int32_t
     off += ne;
   }
   if (bond) for (int i = 0; i < c->N - 1; ++i) bond[i] = c->bond[i];
+  if (l_pos) *l_pos = c->l_pos;
+  return TNML_OK;
+}
+
+// the bonds and the label position alone: host bookkeeping, nothing is copied from the device
+extern "C" int tnml_get_bonds(tnml_ctx *c, int32_t *bond, int *l_pos) {
+  if (!c || !bond) return fail(TNML_ERR_ARG, "NULL argument");
+  if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
+  for (int i = 0; i < c->N - 1; ++i) bond[i] = c->bond[i];
   if (l_pos) *l_pos = c->l_pos;
   return TNML_OK;
 }
@@ -2252,6 +2276,214 @@ static int smk_ensure(tnml_ctx *c, size_t tiles, size_t rows, size_t n, size_t m
   if (rc) return rc;
   g.tiles_cap = tiles_cap; g.rows_cap = rows_cap; g.n_cap = n_cap; g.mask_cap = mask_cap; g.u_cap = u_cap; g.stack_cap = stack_cap;
   return TNML_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// the gradient of the log-norm (kernels_nll.hip)
+// ---------------------------------------------------------------------------------------------
+// The group of the call, (re)sized when a bond outgrows it: all of it or none
+// (want_G: the gradient of its own that tnml_log_norm_grad stores to; the likelihood calls subtract into cg_G and do without)
+static int lnz_ensure(tnml_ctx *c, int mb, bool want_G) {
+  if (c->lnz.m_cap >= mb && c->lnz.m_cap > 0 && (!want_G || c->lnz.G)) return TNML_OK;
+  mb = std::max(mb, c->lnz.m_cap);
+  want_G = want_G || c->lnz.G;                                  // (once there, it stays a member)
+  const size_t N = (size_t)c->N, D = (size_t)c->D, m2 = (size_t)mb * mb;
+  c->lnz.m_cap = 0;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  int rc = make_group(c, "the buffers of the log-norm gradient", {
+      own_dev(c->lnz.tab, 2 * N), own_dev(c->lnz.metric, N * D * D), own_dev(c->lnz.envL, (N + 1) * m2), own_dev(c->lnz.envR, (N + 1) * m2),
+      own_dev(c->lnz.expL, N + 1), own_dev(c->lnz.expR, N + 1), own_dev_if(want_G, c->lnz.G, N * c->core_stride + c->lab_elems),
+      own_dev(c->lnz.out, 2), own_dev(c->lnz.status, 2)});
+  if (rc) return rc;
+  c->lnz.m_cap = mb;
+  return TNML_OK;
+}
+
+// what the calls refuse of a metric ([D][D] per site, n_metric of them) and of the bonds, before anything is launched
+static int lnz_check(const tnml_ctx *c, const char *what, const double *S, int n_metric, int mb) {
+  const int D = c->D;
+  for (int i = 0; i < n_metric; ++i)
+    for (int d = 0; d < D; ++d)
+      for (int e = 0; e < D; ++e) {
+        const double v = S[((size_t)i * D + d) * D + e], w = S[((size_t)i * D + e) * D + d];
+        if (!std::isfinite(v)) return fail(TNML_ERR_ARG, "%s: the metric of site %d is not finite at (%d, %d)", what, i, d, e);
+        if (!(std::fabs(v - w) <= 1e-12 * (std::fabs(v) + std::fabs(w))))                                 // (a Gram matrix summed in two orders)
+          return fail(TNML_ERR_ARG, "%s: the metric of site %d is not symmetric at (%d, %d): %.17g and %.17g", what, i, d, e, v, w);
+      }
+  const size_t lds = std::max(lognorm_env_lds_bytes(mb, D), lognorm_grad_lds_bytes(mb, D));
+  if (mb > kLnzMaxBond || lds > kLdsMax)
+    return fail(TNML_ERR_ARG, "%s at D = %d, bond %d: beyond bond %d, or %zu bytes of LDS for the two environments and their product beyond 160 KB",
+                what, D, mb, kLnzMaxBond, lds);
+  return TNML_OK;
+}
+
+// The launches of the norm term on the context's stream, after lnz_check and lnz_ensure: the table (tab_host outlives the upload), the
+// metric, the environment kernel and -- mode 0: Gz stored to G, mode 1: G -= Gz, mode -1: none -- the gradient kernel.  The status
+// word and {sign, log|Z|} stay in the group for the caller to read.
+static int lnz_enqueue(tnml_ctx *c, const std::vector<int> &tab_host, const double *S, int n_metric, int mb, int mode, float *G) {
+  auto &g = c->lnz;
+  const int D = c->D;
+  LogNormParams p{};
+  p.N = c->N; p.D = D; p.L = c->L; p.l_pos = c->l_pos;
+  p.metric_sites = n_metric; p.mode = mode < 0 ? 0 : mode;
+  p.tab = g.tab; p.cores = c->cores; p.lab = c->lab[c->lab_cur]; p.core_stride = c->core_stride;
+  p.metric = n_metric ? g.metric : nullptr;
+  p.envL = g.envL; p.envR = g.envR; p.expL = g.expL; p.expR = g.expR; p.env_stride = (size_t)g.m_cap * g.m_cap;
+  p.G = G; p.out = g.out; p.status = g.status;
+  HIP_TRY(hipMemcpyAsync(g.tab, tab_host.data(), tab_host.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(g.status, 0, 2 * sizeof(int), c->stream));
+  if (n_metric) {
+    HIP_TRY(hipMemcpyAsync(g.metric, S, (size_t)n_metric * D * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));                  // (the upload reads the caller's memory)
+  }
+  if (!launch_lognorm_env(p, mb, c->stream)) return fail(TNML_ERR_ARG, "internal: log-norm environment launch refused (bond %d)", mb);
+  HIP_TRY(hipGetLastError());
+  if (mode >= 0) {
+    if (!launch_lognorm_grad(p, mb, c->stream)) return fail(TNML_ERR_ARG, "internal: log-norm gradient launch refused (bond %d)", mb);
+    HIP_TRY(hipGetLastError());
+  }
+  return TNML_OK;
+}
+
+// the status word and {sign, log|Z|} of the launches above, after a synchronisation; `what` names the call in the refusal
+static int lnz_result(tnml_ctx *c, const char *what, double *sign_log2) {
+  int st2[2] = {0, 0};
+  double res[2] = {0.0, 0.0};
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpy(st2, c->lnz.status, 2 * sizeof(int), hipMemcpyDeviceToHost));     // (blocking copies: `st2` and `res` are locals)
+  const int st = st2[0] | st2[1];
+  HIP_TRY(hipMemcpy(res, c->lnz.out, 2 * sizeof(double), hipMemcpyDeviceToHost));
+  if (st & 1) return fail(TNML_ERR_NONFINITE, "%s: a core element or an environment is not finite", what);
+  sign_log2[0] = res[0]; sign_log2[1] = res[1];
+  if (st & 2) return fail(TNML_ERR_NONFINITE, "%s: <W|W> is zero, its logarithm has no gradient", what);
+  if (st & 4) return fail(TNML_ERR_NONFINITE, "%s: an element of the norm term's gradient is beyond float32", what);
+  return TNML_OK;
+}
+
+extern "C" int tnml_log_norm_grad(tnml_ctx *c, const double *S, int per_site, float *grad_flat, size_t capacity, double *sign_log2) {
+  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
+  if (!grad_flat || !sign_log2) return fail(TNML_ERR_ARG, "tnml_log_norm_grad: %s is NULL", grad_flat ? "sign_log2" : "grad_flat");
+  if (per_site != 0 && per_site != 1) return fail(TNML_ERR_ARG, "tnml_log_norm_grad: per_site %d is neither 0 nor 1", per_site);
+  if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
+  if (c->comm) return fail(TNML_ERR_STATE, "tnml_log_norm_grad runs on one GPU: this context has a communicator attached");
+  size_t total;
+  int mb, rc = grad_table(c, "tnml_log_norm_grad", c->lnz.tab_host, total, mb);
+  if (rc) return rc;
+  if (capacity < total) return fail(TNML_ERR_ARG, "tnml_log_norm_grad: capacity %zu < %zu floats", capacity, total);
+  const int n_metric = S ? (per_site ? c->N : 1) : 0;
+  if ((rc = lnz_check(c, "tnml_log_norm_grad", S, n_metric, mb))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = lnz_ensure(c, mb, true))) return rc;
+  if ((rc = lnz_enqueue(c, c->lnz.tab_host, S, n_metric, mb, 0, c->lnz.G))) return rc;
+  if ((rc = lnz_result(c, "tnml_log_norm_grad", sign_log2))) return rc;
+  HIP_TRY(hipMemcpyAsync(grad_flat, c->lnz.G, total * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return TNML_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// the negative log-likelihood of a batch and its gradient over all cores (layer 2)
+// ---------------------------------------------------------------------------------------------
+// per-sample terms and flags of a call, and the two sums: one group sized from the samples of a call
+static int nll_ensure(tnml_ctx *c, int n) {
+  if (n <= c->nll.n_cap) return TNML_OK;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->nll.n_cap = 0;
+  const size_t cap = ((size_t)n + 1023) / 1024 * 1024;
+  int rc = make_group(c, "the per-sample terms of the likelihood", {own_dev(c->nll.terms, cap), own_dev(c->nll.bad, cap), own_dev(c->nll.acc, 2)});
+  if (rc) return rc;
+  c->nll.n_cap = (int)cap;
+  return TNML_OK;
+}
+
+// X [b][N][D] and y [b] (or NULL: the label is summed) on the host, or the dataset rows idx[0..b) with their labels (use_labels) when
+// X is NULL.  grad_flat NULL: the value alone, no gradient launch.
+static int nll_grad_impl(tnml_ctx *c, const char *what, const float *X, const int32_t *y, const int32_t *idx, int b, bool use_labels,
+                         const double *S, float *grad_flat, size_t capacity, double *out3) {
+  const int L = c->L;
+  if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
+  if (y)
+    for (int i = 0; i < b; ++i)
+      if (y[i] < 0 || y[i] >= L) return fail(TNML_ERR_ARG, "label %d of sample %d outside [0, %d)", y[i], i, L);
+  size_t total;
+  std::vector<int> &tab = c->lnz.tab_host;                      // (a member: the uploads below are not waited for)
+  int mb, rc = grad_table(c, what, tab, total, mb);
+  if (rc) return rc;
+  const bool grad = grad_flat != nullptr;
+  if (grad && capacity < total) return fail(TNML_ERR_ARG, "%s: capacity %zu < %zu floats", what, capacity, total);
+  if (grad && (rc = grad_chain_fits(c, what, mb))) return rc;
+  if (!grad && c->scaled && (rc = scaled_pred_fits(c))) return rc;
+  if ((rc = lnz_check(c, what, S, S ? 1 : 0, mb))) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  if (idx && (rc = ds_upload_indices(c, idx, b))) return rc;    // refuses a bad index before anything is launched
+  const int chunk = std::min(grad_chunk_samples(c, c->cg_chunk), (b + 63) / 64 * 64);
+  if ((rc = pred_ensure_buffers(c, chunk))) return rc;
+  if (grad && (rc = cg_ensure_buffers(c, chunk))) return rc;
+  if ((rc = lnz_ensure(c, mb, false))) return rc;
+  if ((rc = nll_ensure(c, b))) return rc;
+  const int xbp = c->pred_cap;
+  if (grad) HIP_TRY(hipMemcpyAsync(c->cg_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if ((rc = pred_table(c))) return rc;
+  const bool labelled = idx ? use_labels : y != nullptr;
+  for (int off = 0; off < b; off += chunk) {
+    const int bc = std::min(chunk, b - off);
+    if ((rc = load_chunk(c, X, idx ? c->ds_idx : nullptr, y, off, bc, labelled ? c->ds_ypred : nullptr))) return rc;
+    if ((rc = pred_chain(c, bc))) return rc;
+    NllCotParams q{};
+    q.f = c->fpred; q.y = labelled ? c->ds_ypred : nullptr; q.cot = grad ? c->cg_cot : nullptr;
+    q.terms = c->nll.terms; q.bad = c->nll.bad; q.L = L; q.b = bc; q.b_pad = grad ? c->cg_cap : xbp; q.f_bpad = xbp; q.off = off; q.batch = b;
+    if (!launch_nll_cot(q, c->stream)) return fail(TNML_ERR_ARG, "internal: likelihood cotangent launch refused (b %d, b_pad %d)", bc, q.b_pad);
+    HIP_TRY(hipGetLastError());
+    if (grad && (rc = run_core_grad_chunk(c, bc, off == 0, mb))) return rc;
+  }
+  if (!launch_nll_sum(c->nll.terms, c->nll.bad, b, c->nll.acc, c->stream)) return fail(TNML_ERR_ARG, "internal: likelihood sum launch refused");
+  HIP_TRY(hipGetLastError());
+  if ((rc = lnz_enqueue(c, tab, S, S ? 1 : 0, mb, grad ? 1 : -1, grad ? c->cg_G : nullptr))) return rc;
+  double acc[2] = {0.0, 0.0}, sl[2] = {0.0, 0.0};
+  if ((rc = lnz_result(c, what, sl))) return rc;               // (synchronises; `acc` is a local: its copy is not left in flight)
+  HIP_TRY(hipMemcpy(acc, c->nll.acc, 2 * sizeof(double), hipMemcpyDeviceToHost));
+  out3[0] = -(acc[0] / (double)b - sl[1]);
+  out3[1] = sl[1];
+  out3[2] = acc[1];
+  if (acc[1] > 0)
+    return fail(TNML_ERR_NONFINITE, "%s: %g of %d samples have a cotangent that is not finite (f_y == 0, or an f beyond float32: calibrate the network)",
+                what, acc[1], b);
+  if (grad) {
+    HIP_TRY(hipMemcpyAsync(grad_flat, c->cg_G, total * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  return TNML_OK;
+}
+
+extern "C" int tnml_nll_grad(tnml_ctx *c, const float *X, const int32_t *y, int b, const double *S, float *grad_flat, size_t capacity, double *out3) {
+  if (!c || !X || !grad_flat || !out3) return fail(TNML_ERR_ARG, "NULL argument");
+  if (c->comm) return fail(TNML_ERR_STATE, "likelihood gradients are single-GPU only: a communicator is attached");
+  if (b < 1) return fail(TNML_ERR_ARG, "empty batch");
+  return nll_grad_impl(c, "tnml_nll_grad", X, y, nullptr, b, y != nullptr, S, grad_flat, capacity, out3);
+}
+
+extern "C" int tnml_nll_grad_indices(tnml_ctx *c, const int32_t *idx, int b, int use_labels, const double *S, float *grad_flat, size_t capacity,
+                                     double *out3) {
+  int rc = ds_usable(c);
+  if (rc) return rc;
+  if (!idx || !grad_flat || !out3) return fail(TNML_ERR_ARG, "NULL argument");
+  if (b < 1) return fail(TNML_ERR_ARG, "empty index list");
+  return nll_grad_impl(c, "tnml_nll_grad_indices", nullptr, nullptr, idx, b, use_labels != 0, S, grad_flat, capacity, out3);
+}
+
+extern "C" int tnml_nll_eval_indices(tnml_ctx *c, const int32_t *idx, int n, int use_labels, const double *S, double *out3) {
+  int rc = ds_usable(c);
+  if (rc) return rc;
+  if (!idx || !out3) return fail(TNML_ERR_ARG, "NULL argument");
+  if (n < 1) return fail(TNML_ERR_ARG, "empty index list");
+  return nll_grad_impl(c, "tnml_nll_eval_indices", nullptr, nullptr, idx, n, use_labels != 0, S, nullptr, 0, out3);
+}
+
+extern "C" int tnml_nll_eval(tnml_ctx *c, const float *X, const int32_t *y, int b, const double *S, double *out3) {
+  if (!c || !X || !out3) return fail(TNML_ERR_ARG, "NULL argument");
+  if (c->comm) return fail(TNML_ERR_STATE, "likelihoods are single-GPU only: a communicator is attached");
+  if (b < 1) return fail(TNML_ERR_ARG, "empty batch");
+  return nll_grad_impl(c, "tnml_nll_eval", X, y, nullptr, b, y != nullptr, S, nullptr, 0, out3);
 }
 
 extern "C" int tnml_set_sample_stack_bytes(tnml_ctx *c, size_t bytes) {

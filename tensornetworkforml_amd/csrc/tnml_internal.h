@@ -533,4 +533,44 @@ int sample_masked_tile(int mb, int D, int L, int K);
 // the environment launch and (walk) the walk launch of one chunk; mb: largest bond.  false: refused (geometry / LDS)
 bool launch_sample_masked(const SampleMaskedParams &p, int mb, bool walk, hipStream_t st);
 
+// The gradient of the log-norm (kernels_nll.hip): one parameter block for the environment kernel (two
+// workgroups, one per direction) and the gradient kernel (grid (N, L)).  L_i 2^expL[i] and R_i 2^expR[i] are the environments.
+constexpr int kLnzMaxBond = 64;
+struct LogNormParams {
+  int N, D, L, l_pos;
+  int metric_sites;        // 0: identity, 1: one [D][D] for all sites, N: [N][D][D]
+  int lds_m;               // LDS geometry: the largest bond (the launch functions fill it)
+  int mode;                // gradient kernel: 0 stores Gz, 1 replaces G[e] by G[e] - Gz[e]
+  const int *tab;          // the table of CoreGradParams: bonds, then every core's offset in the flat layout
+  const float *cores, *lab;
+  size_t core_stride;
+  const double *metric;
+  double *envL, *envR;     // [N+1][env_stride] each: L_i for i = 0 .. N-1 (L_0 = 1), R_i for i = 0 .. N (R_N = 1)
+  int *expL, *expR;        // [N+1] each: the running exponents
+  size_t env_stride;
+  float *G;                // the layout of tnml_get_cores
+  double *out;             // [2] {sign of <W|W>_S, log|<W|W>_S|}
+  int *status;             // [0] (environment launch): bit 1 a non-finite environment, bit 2 <W|W>_S == 0; [1] (gradient launch): bit 4 a gradient element beyond float32
+};
+size_t lognorm_env_lds_bytes(int mb, int D);
+size_t lognorm_grad_lds_bytes(int mb, int D);
+// mb: largest bond.  false: refused (geometry / LDS)
+bool launch_lognorm_env(const LogNormParams &p, int mb, hipStream_t st);
+bool launch_lognorm_grad(const LogNormParams &p, int mb, hipStream_t st);
+// The likelihood of a batch (kernels_nll.hip): the cotangent of the data term of a chunk, its per-sample terms, and their sum.
+struct NllCotParams {
+  const float *f;          // [L][f_bpad]: the prediction chain's output for the chunk
+  const int *y;            // [b] labels of the chunk's samples, or nullptr: the label is summed
+  float *cot;              // [L][b_pad]: zero for samples b .. b_pad-1; nullptr: the value alone is wanted
+  double *terms;           // [n] of the call: terms[off + s] = log f_y^2 or log sum_l f_l^2
+  int *bad;                // [n] of the call: bad[off + s] = 1 where a cotangent or the term is not finite
+  int L, b, b_pad, f_bpad;
+  int off;                 // the chunk's first sample within the batch
+  int batch;               // samples of the batch the mean runs over
+};
+// false: refused (geometry)
+bool launch_nll_cot(const NllCotParams &p, hipStream_t st);
+// acc[0] = sum terms[0 .. n), acc[1] = sum bad[0 .. n), in an order that depends on n alone
+bool launch_nll_sum(const double *terms, const int *bad, int n, double *acc, hipStream_t st);
+
 }  // namespace tnml
