@@ -609,6 +609,36 @@ int tnml_nll_grad_indices(tnml_ctx *ctx, const int32_t *idx, int b, int use_labe
 int tnml_nll_eval(tnml_ctx *ctx, const float *X, const int32_t *y, int b, const double *S, double *out3);
 int tnml_nll_eval_indices(tnml_ctx *ctx, const int32_t *idx, int n, int use_labels, const double *S, double *out3);
 
+/* ---- likelihood training ----------------------------------------------- */
+/* Optimiser steps on G = Gd - Gz of the calls above, with the optimiser of tnml_optim_config and its state rules: the cores stay on
+ * the device, nothing of G reaches the host.  Per step: the chunks and kernels of tnml_nll_grad (tnml_set_core_grad_chunk,
+ * tnml_set_chain_scaling apply), the sum of the batch's terms, the norm term subtracted on the device, a one-workgroup record, then
+ * the update kernel of tnml_gd_step on G.
+ * renorm (0 / 1, TNML_ERR_ARG otherwise).  sum(G_i A_i) = 0 at every site, so a plain step only ever grows a core,
+ * |A + lr G|^2 = |A|^2 + lr^2 |G|^2, and over an epoch f leaves float32 although the loss does not see a core's scale.  renorm = 1:
+ * the update ends with A' <- A' sqrt(sum A^2 / sum A'^2) per core -- both sums in float64 in the fixed order of the clip's sums, A'
+ * unrounded, the factor applied in float64 before the one rounding of the store; no factor where sum A'^2 is 0 or not finite; with
+ * lr = 0 the core is unchanged bit for bit.  The optimiser state is not rescaled.  renorm = 0 is the plain rule.
+ * values4 / values_out [n_steps][4], n_steps = ceil(n / batch): { the value of tnml_nll_eval on batch k BEFORE its step, log Z before
+ * the step, samples of the batch whose cotangent is not finite, status bits }.  Bits: 1 / 2 / 4 the status of the norm term (a
+ * non-finite environment; Z == 0; a gradient element beyond float32), 8 a batch with a non-finite cotangent, 16 the step was NOT
+ * applied.
+ * THE GUARD.  A step whose batch or norm term is bad sets a sticky word on the device; the update of that step and of every later
+ * step of the call returns without touching cores or state, so after the first bad step k the cores and the state are those after
+ * step k - 1.  The call then returns TNML_ERR_NONFINITE naming k and the count, with values_out filled and Adam's t advanced by the
+ * applied steps only.  The word is cleared at the start of every call.
+ * tnml_nll_train_indices keeps the form of tnml_gd_train_indices: index list, tables and the metric uploaded once, every step
+ * enqueued without a wait, one synchronisation at the end.  AFTER a call the context is as after tnml_gd_train_indices.
+ * REFUSALS, all before anything is launched: those of tnml_nll_grad(_indices) and of tnml_gd_step / tnml_gd_train_indices. */
+int tnml_nll_step(tnml_ctx *ctx, const float *X, const int32_t *y, int b, const double *S, float lr, float weight_dec, int renorm,
+                  double *values4);
+int tnml_nll_train_indices(tnml_ctx *ctx, const int32_t *idx, int n, int batch, int use_labels, const double *S, float lr,
+                           float weight_dec, int renorm, double *values_out);
+/* on = 1: the environment walk of the norm term (two workgroups, cores only) runs on a second stream beside the chunks of its step,
+ * forked by an event behind the previous update and joined by one before the norm gradient.  Same kernels, inputs and orders: the
+ * results are bit-equal.  Default 0 (DESIGN.md section 25 has the measurement).  on outside {0, 1}: TNML_ERR_ARG. */
+int tnml_set_nll_overlap(tnml_ctx *ctx, int on);
+
 /* Host-side planning helper, exported so that CPU tests can check the bond bookkeeping without a
  * GPU: truncation rank kept by tensor_svd (Network_class.py:894-945) for a step on sites
  * (p, p+1).  Returns m >= 1, or TNML_ERR_SHAPE where the reference itself raises. */

@@ -1052,6 +1052,73 @@ class Network():
                   % (epoch, n_epochs, acc.mean(), val_acc[-1]))
         return val_acc, np.array(hist)
 
+    def nll_step(self, indices_or_X, y=None, labels=True, lr=1e-3, weight_dec=0.0, renorm=True, levels=256, grid=None, weights=None):
+        """One optimiser step (configure_optimizer) on the device on the gradient of the negative log-likelihood, at the current
+        bonds and label position.  indices_or_X: a one-dimensional list of indices into the attached dataset,
+        with its labels or (labels=False) without -- the value then leaves out the sum log w term, as nll_gradient_indices; or images
+        X (b, N) with y or None, as nll_gradient.  The metric is the Gram matrix of the grid, as nll_gradient forms it.  renorm:
+        every core keeps its Frobenius norm (a plain step only ever grows it, and the likelihood does not see it).  Returns
+        (nll, log Z) of the batch BEFORE the step.  A batch with a sample of f_y == 0 raises and changes nothing.  A forward is needed
+        before the next sweep."""
+        if np.ndim(indices_or_X) == 1:
+            _, phi, w = self._pixel_grid(levels, grid, weights)
+            ctx = self._require_dataset()
+            idx = np.asarray(indices_or_X)
+            try:
+                v = ctx.nll_train_indices(idx, max(idx.size, 1), labels, np.einsum('k,kd,ke->de', w, phi, phi), lr, weight_dec, renorm)[0]
+            finally:
+                self._after_device_update()
+            return float(v[0]), float(v[1])
+        feats, y, S, logw = self._likelihood_batch(indices_or_X, y, levels, grid, weights)
+        ctx = self._sync_to_device(max(self._b, 1))
+        try:
+            v = ctx.nll_step(feats, y, S, lr, weight_dec, renorm)
+        finally:
+            self._after_device_update()
+        return float(v[0]) + logw, float(v[1])
+
+    def train_generative(self, train_index_loader, val_index_loader, lr, n_epochs=10, weight_dec=0.0, optimizer='sgd', momentum=0.0,
+                         betas=(0.9, 0.999), eps=1e-8, clip=True, labels=True, renorm=True, levels=256, grid=None, weights=None):
+        """Fit the model's own distribution p(x, l) (labels=False: p(x)) to the attached dataset by gradient descent on the negative
+        log-likelihood over all cores: the generative companion of `train_gradient`, at fixed bonds and any label position.  Every
+        batch of the index loader is one optimiser step; an epoch is one device call with one synchronisation (batches of one size,
+        the last one may be shorter; a loader of mixed sizes takes a call per run of equal sizes).  The dataset's pixels must lie on
+        the grid.  Prints train_gradient's lines with the mean training NLL, the validation NLL and the validation accuracy.
+        Returns (val_nll, hist), hist of shape (n_epochs, n_batches): the NLL of every batch before its step (without the sum log w
+        term)."""
+        ctx = self._require_dataset()
+        self._check_forward_position(self.l_pos)
+        ctx.optim_config(optimizer, momentum, betas[0], betas[1], eps, clip and optimizer != 'adam')
+        _, phi, w = self._pixel_grid(levels, grid, weights)
+        S = np.einsum('k,kd,ke->de', w, phi, phi)
+        val_nll, hist = [], []
+        print("\n --- TRAINING PROCEDURE ---")
+        for epoch in range(n_epochs):
+            batches = [np.asarray(idx).ravel() for idx in train_index_loader]
+            nll = np.zeros(len(batches))
+            i = 0
+            while i < len(batches):
+                # batches of one size in a row are one call, and a shorter one behind them is its ragged last step
+                j = i + 1
+                while j < len(batches) and len(batches[j]) == len(batches[i]):
+                    j += 1
+                if j == len(batches) - 1 and len(batches[j]) < len(batches[i]):
+                    j += 1
+                try:
+                    nll[i:j] = ctx.nll_train_indices(np.concatenate(batches[i:j]), len(batches[i]), labels, S, lr, weight_dec, renorm)[:, 0]
+                finally:
+                    self._after_device_update()
+                print('\r' + "Epoch %d/%d - train NLL : %.4f - completed : %.2f "
+                      % (epoch, n_epochs, nll[j - 1], j * 100 / len(batches)) + '%', end=' ')
+                i = j
+            hist.append(nll)
+            sizes = np.array([len(idx) for idx in val_index_loader], dtype=np.float64)
+            epoch_val = np.array([ctx.nll_eval_indices(idx, labels, S)[0] for idx in val_index_loader])
+            val_nll.append(float((epoch_val * sizes).sum() / sizes.sum()) if len(sizes) else float('nan'))
+            print('\r' + "Epoch %d/%d - train NLL : %.4f - val NLL: %.4f - val accuracy: %.4f"
+                  % (epoch, n_epochs, nll.mean(), val_nll[-1], self.evaluate(val_index_loader)[0] if len(sizes) else float('nan')))
+        return val_nll, np.array(hist)
+
     def evaluate(self, indices, activated=True):
         """(accuracy, mean absolute error) of the network over samples of the attached dataset, reduced on the device.
         `indices` is an index loader -- the result is then the mean over its batches of the per-batch accuracy and error,

@@ -43,6 +43,7 @@ SYMBOLS = [
     'tnml_inner', 'tnml_axpby',
     'tnml_sample', 'tnml_sample_masked', 'tnml_set_sample_stack_bytes',
     'tnml_get_bonds', 'tnml_log_norm_grad', 'tnml_nll_grad', 'tnml_nll_grad_indices', 'tnml_nll_eval', 'tnml_nll_eval_indices',
+    'tnml_nll_step', 'tnml_nll_train_indices', 'tnml_set_nll_overlap',
 ]
 
 
@@ -160,6 +161,9 @@ def lib():
         L.tnml_nll_grad_indices.argtypes = [vp, i32p, C.c_int, C.c_int, f64p, f32p, C.c_size_t, f64p]
         L.tnml_nll_eval.argtypes = [vp, f32p, i32p, C.c_int, f64p, f64p]
         L.tnml_nll_eval_indices.argtypes = [vp, i32p, C.c_int, C.c_int, f64p, f64p]
+        L.tnml_nll_step.argtypes = [vp, f32p, i32p, C.c_int, f64p, C.c_float, C.c_float, C.c_int, f64p]
+        L.tnml_nll_train_indices.argtypes = [vp, i32p, C.c_int, C.c_int, C.c_int, f64p, C.c_float, C.c_float, C.c_int, f64p]
+        L.tnml_set_nll_overlap.argtypes = [vp, C.c_int]
         _lib = L
     return _lib
 
@@ -667,6 +671,55 @@ class Context:
         out = np.zeros(3, dtype=np.float64)
         _chk(lib().tnml_nll_eval_indices(self._h, _ptr(idx, C.c_int32), idx.size, int(bool(labels)), sp, _ptr(out, C.c_double)))
         return out
+
+    # ---- likelihood training
+    NLL_BAD_BATCH, NLL_NOT_APPLIED = 8, 16                      # bits of a step's fourth value, beside the norm term's 1 / 2 / 4
+
+    @staticmethod
+    def _chk_values(rc, values):
+        """_chk, with the per-step values of the call on the error (TNML_ERR_NONFINITE fills them before it returns)"""
+        try:
+            _chk(rc)
+        except TnmlError as e:
+            e.values = values
+            raise
+
+    def nll_step(self, X, y=None, S=None, lr=1e-3, weight_dec=0.0, renorm=True):
+        """One optimiser step (optim_config) on the gradient of -log p(x, y) (y given) or -log p(x) of a host batch X (b, N, D).
+        -> float64 (4,): (value before the step as nll_eval gives it, log Z before the step, samples with a non-finite cotangent,
+        status bits).  renorm: every core keeps its Frobenius norm."""
+        X = _f32(X)
+        assert X.ndim == 3 and X.shape[1] == self.N and X.shape[2] == self.D, \
+            "The 1 dimension of the input data must be the flattened number of pixels"
+        yp = None
+        if y is not None:
+            y = np.ascontiguousarray(y, dtype=np.int32)
+            assert y.shape == (X.shape[0],)
+            yp = _ptr(y, C.c_int32)
+        S, sp = self._grid_metric(S)
+        out = np.zeros(4, dtype=np.float64)
+        self._chk_values(lib().tnml_nll_step(self._h, _ptr(X, C.c_float), yp, X.shape[0], sp, float(lr), float(weight_dec),
+                                             int(renorm),
+                                             _ptr(out, C.c_double)), out)
+        return out
+
+    def nll_train_indices(self, idx, batch, labels=True, S=None, lr=1e-3, weight_dec=0.0, renorm=True):
+        """ceil(n / batch) such steps over the dataset samples idx, batch after batch, in one call with one synchronisation.
+        -> float64 (n_steps, 4), the values of nll_step per step.  After a bad step (a non-finite cotangent or norm term) no later
+        step is applied; the call raises TnmlError(-7) whose .values holds the array."""
+        idx = self._idx(idx)
+        batch = int(batch)
+        S, sp = self._grid_metric(S)
+        vals = np.zeros((max(-(-idx.size // batch), 1) if batch >= 1 else 1, 4), dtype=np.float64)
+        self._chk_values(lib().tnml_nll_train_indices(self._h, _ptr(idx, C.c_int32), idx.size, batch, int(bool(labels)), sp, float(lr),
+                                                      float(weight_dec),
+                                                      int(renorm),
+                                                      _ptr(vals, C.c_double)), vals)
+        return vals
+
+    def set_nll_overlap(self, on):
+        """The norm walk of a likelihood step on a second stream beside the step's chunks (bit-equal results either way)."""
+        _chk(lib().tnml_set_nll_overlap(self._h, int(on)))
 
     # ---- gradient training over all cores
     def optim_config(self, kind='sgd', momentum=0.0, beta1=0.9, beta2=0.999, eps=1e-8, clip=True):

@@ -22,6 +22,8 @@
 //                        terms[off + s], and bad[off + s] = 1 where a cotangent or the term is not finite (f_y == 0, a non-finite f).
 //   nll_sum_kernel       one workgroup: acc[0] = sum of terms[0 .. n), acc[1] = sum of bad[0 .. n).  A thread sums its elements in
 //                        ascending order, a fixed tree combines the 256 partial sums: the result depends on n alone, not on the chunks.
+//   nll_record_kernel    one workgroup, after nll_sum_kernel and the norm launches of a likelihood step (section 25): the step's four
+//                        values into its slot and the sticky skip word that optim_step_kernel reads first.  Plain stores.
 // Status words: status[0], written by the environment launch alone, bit 1 a non-finite environment, bit 2 <W|W>_S == 0; status[1],
 // written by the gradient launch alone, bit 4 a gradient element beyond float32.  The gradient kernel returns at once where
 // status[0] is set: it reads nothing that a workgroup of its own launch writes.
@@ -243,6 +245,27 @@ __global__ __launch_bounds__(kNllThreads) void nll_sum_kernel(const double *__re
     __syncthreads();
   }
   if (tid == 0) { acc[0] = red[0][0]; acc[1] = red[1][0]; }
+}
+
+__global__ __launch_bounds__(64) void nll_record_kernel(const double *__restrict__ acc, const double *__restrict__ out, const int *__restrict__ status,
+                                                        double *__restrict__ rec, int *__restrict__ skip) {
+  if (threadIdx.x != 0) return;
+  const double nbad = acc[1];
+  int bits = status[0] | status[1];
+  if (!(nbad == 0.0)) bits |= kNllStepBadBatch;                   // (a NaN count is a bad batch too)
+  int sk = *skip;
+  if (bits) { sk = 1; *skip = 1; }
+  if (sk) bits |= kNllStepNotApplied;
+  rec[0] = acc[0];
+  rec[1] = out[1];
+  rec[2] = nbad;
+  rec[3] = (double)bits;
+}
+
+bool launch_nll_record(const double *acc, const double *out, const int *status, double *rec, int *skip, hipStream_t st) {
+  if (!acc || !out || !status || !rec || !skip) return false;
+  hipLaunchKernelGGL(nll_record_kernel, dim3(1), dim3(64), 0, st, acc, out, status, rec, skip);
+  return true;
 }
 
 bool launch_nll_cot(const NllCotParams &p, hipStream_t st) {

@@ -674,6 +674,8 @@ static void check_optim_step(const OptimStepParams &p, dim3 g, dim3 b) {
     need(p.G + off, ne * 4, "OptimStepParams.G");
     if (p.s0) need(p.s0 + off, ne * 4, "OptimStepParams.s0");
     if (p.s1) need(p.s1 + off, ne * 4, "OptimStepParams.s1");
+    if (p.skip) need(p.skip, 4, "OptimStepParams.skip");
+    if (p.renorm != 0 && p.renorm != 1) die("OptimStepParams: renorm %d", p.renorm);
     off += ne;
   }
 }
@@ -747,6 +749,7 @@ static void tr_struct(const LossCotParams &p) { P(f) P(y) P(cot) I(L) I(b) I(b_p
 static void tr_struct(const OptimStepParams &p) {
   P(tab) P(cores) P(labcore) P(G) P(s0) P(s1) I(core_stride) I(N) I(D) I(L) I(l_pos) I(kind) I(clip) R(lr) R(wd) R(mu) R(beta1) R(beta2) R(eps)
   R(corr1) R(corr2)
+  if (p.renorm || p.skip) { I(renorm) P(skip) }                  // (likelihood training alone: the traces of the discriminative path stay as they were)
 }
 static void tr_struct(const AlgebraParams &p) {
   I(N) I(D) I(L) I(l_pos) I(n_prod) I(metric_sites) I(lds_m2) P(bond) P(off) P(w_plain) P(w_lab) P(v_plain) P(v_lab) P(metric) P(stage) I(stage_stride)
@@ -910,6 +913,11 @@ hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t s
     if (n < 1 || g.x != 1 || b.x != 256) die("nll_sum_kernel: n %d grid %u block %u", n, g.x, b.x);
     need(*(const double **)args[0], (size_t)n * 8, "nll_sum: terms"); need(*(const int **)args[1], (size_t)n * 4, "nll_sum: flags");
     need(*(double **)args[3], 2 * 8, "nll_sum: sums");
+  } else if (has("nll_record_kernel")) {         // (acc, out, status, rec, skip)
+    if (g.x != 1) die("nll_record_kernel: grid %u", g.x);
+    need(*(const double **)args[0], 2 * 8, "nll_record: sums"); need(*(const double **)args[1], 2 * 8, "nll_record: sign and log|Z|");
+    need(*(const int **)args[2], 2 * 4, "nll_record: status words"); need(*(double **)args[3], 4 * 8, "nll_record: the step's slot");
+    need(*(int **)args[4], 4, "nll_record: skip word");
   } else if (has("input_grad_onehot_kernel")) {   // (f, f_bpad, L, b, cot, b_pad)
     const int fbp = *(int *)args[1], L = *(int *)args[2], bb = *(int *)args[3], bp = *(int *)args[5];
     if (bb < 1 || bb > bp || bp > fbp || (size_t)g.x * b.x < (size_t)bp) die("input_grad_onehot_kernel: b %d b_pad %d f_bpad %d grid %u x %u", bb, bp, fbp, g.x, b.x);

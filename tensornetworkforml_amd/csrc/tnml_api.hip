@@ -381,6 +381,16 @@ struct tnml_ctx {
     int *bad = nullptr;
     int n_cap = 0;
   } nll;
+  // likelihood training.  One group, created by the first step and regrown with the steps of a call: the
+  // per-step records [cap][4], the sticky skip word of the guard, and the two events that carry the norm walk to stream2 and back.
+  struct {
+    double *rec = nullptr;
+    int *skip = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    int cap = 0;
+    int overlap = 0;                         // tnml_set_nll_overlap: the norm walk on stream2 beside the chunks of the step
+    std::vector<double> metric_host;         // host copy of the metric for the call in flight (it outlives the asynchronous upload)
+  } nst;
   // multi-GPU
   ncclComm_t comm = nullptr;
   int rank = 0, nranks = 1;
@@ -1723,23 +1733,60 @@ static int opt_ensure_metrics(tnml_ctx *c, int n_steps) {
   return TNML_OK;
 }
 
+// What a training call runs between the prediction chain of a chunk and the optimiser step: the discriminative loss of section 17
+// or the negative log-likelihood of section 25.  Everything else of the call -- chunks, core gradients, optimiser tail -- is shared.
+struct TrainObjective {
+  bool nll;                  // false: metrics + loss derivative per chunk; true: likelihood cotangent per chunk, norm term per step
+  const char *what;          // names the call in a refusal
+  int act_fn, loss_fn;       // discriminative
+  float T;
+  bool labelled;             // likelihood: joint (labels) or marginal (the label summed)
+  const double *S;           // likelihood: metric [D][D] or NULL
+  int renorm;                // likelihood: the third pass of the update kernel
+};
+
+static int lnz_check(const tnml_ctx *c, const char *what, const double *S, int n_metric, int mb);      // (with the norm term, below)
+static int lnz_ensure(tnml_ctx *c, int mb, bool want_G);
+static int lnz_upload(tnml_ctx *c, const std::vector<int> &tab_host, const double *S, int n_metric, bool wait);
+static int lnz_launch_env(tnml_ctx *c, int n_metric, int mb, hipStream_t st);
+static int lnz_launch_grad(tnml_ctx *c, int n_metric, int mb, int mode, float *G);
+static int nll_ensure(tnml_ctx *c, int n);
+
+static int nst_ensure(tnml_ctx *c, int n_steps) {
+  if (n_steps <= c->nst.cap) return TNML_OK;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->nst.cap = 0;
+  int rc = make_group(c, "the records of the likelihood steps", {
+      own_dev(c->nst.rec, (size_t)n_steps * 4), own_dev(c->nst.skip, 1),
+      own_event(c->nst.ev_fork, hipEventDisableTiming), own_event(c->nst.ev_join, hipEventDisableTiming)});
+  if (rc) return rc;
+  c->nst.cap = n_steps;
+  return TNML_OK;
+}
+
 // n_steps = ceil(n / batch) steps over X [n][N][D], y [n] on the host, or over the dataset rows idx[0..n) when X is NULL.  The
-// per-chunk body is core_grad_impl's with the loss derivative as the cotangent.
-static int gd_impl(tnml_ctx *c, const float *X, const int32_t *y, const int32_t *idx, int n, int batch, float lr, float wd, int act_fn,
-                   int loss_fn, float T, double *metrics_out) {
+// per-chunk body is core_grad_impl's with the objective's cotangent.  out: [n_steps][3] metrics (discriminative, or NULL) or
+// [n_steps][4] values (likelihood).
+static int train_impl(tnml_ctx *c, const TrainObjective &obj, const float *X, const int32_t *y, const int32_t *idx, int n, int batch, float lr,
+                      float wd, double *out) {
   const int N = c->N, D = c->D, L = c->L;
-  if (act_fn < 0 || act_fn > 2 || loss_fn < 0 || loss_fn > 2) return fail(TNML_ERR_ARG, "unknown activation / loss");
+  const int act_fn = obj.act_fn, loss_fn = obj.loss_fn;
+  const float T = obj.T;
+  if (!obj.nll && (act_fn < 0 || act_fn > 2 || loss_fn < 0 || loss_fn > 2)) return fail(TNML_ERR_ARG, "unknown activation / loss");
+  if (obj.nll && obj.renorm != 0 && obj.renorm != 1) return fail(TNML_ERR_ARG, "%s: renorm %d is neither 0 nor 1", obj.what, obj.renorm);
   if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
   if (y)
     for (int i = 0; i < n; ++i)
       if (y[i] < 0 || y[i] >= L) return fail(TNML_ERR_ARG, "label %d of sample %d outside [0, %d)", y[i], i, L);
   size_t total;
   std::vector<int> &tab = c->opt_tab;                           // (a member: the upload below is not waited for)
-  int mb, rc = grad_table(c, "gradient step", tab, total, mb);
+  int mb, rc = grad_table(c, obj.what, tab, total, mb);
   if (rc) return rc;
-  if ((rc = grad_chain_fits(c, "gradient step", mb))) return rc;
-  if (dataset_metrics_lds_bytes(L) > 64 * 1024 || loss_cot_lds_bytes(L) > 64 * 1024)
+  if ((rc = grad_chain_fits(c, obj.what, mb))) return rc;
+  if (!obj.nll && (dataset_metrics_lds_bytes(L) > 64 * 1024 || loss_cot_lds_bytes(L) > 64 * 1024))
     return fail(TNML_ERR_ARG, "metrics / loss-derivative kernel: %d labels exceed its LDS tile", L);
+  const int n_metric = obj.nll && obj.S ? 1 : 0;
+  if (obj.nll && (rc = lnz_check(c, obj.what, obj.S, n_metric, mb))) return rc;
   const bool stateful = opt_stateful(c);
   if (stateful && c->opt_s0 && (c->opt.bond != c->bond || c->opt.l_pos != c->l_pos))
     return fail(TNML_ERR_STATE, "the optimiser state belongs to other bonds or another l_pos (l_pos %d then, %d now): call tnml_optim_reset",
@@ -1750,28 +1797,65 @@ static int gd_impl(tnml_ctx *c, const float *X, const int32_t *y, const int32_t 
   const int chunk = std::min(grad_chunk_samples(c, c->cg_chunk), (std::min(batch, n) + 63) / 64 * 64);
   if ((rc = pred_ensure_buffers(c, chunk))) return rc;
   if ((rc = cg_ensure_buffers(c, chunk))) return rc;
-  if ((rc = ds_ensure_metrics(c, c->pred_cap))) return rc;
+  if (!obj.nll && (rc = ds_ensure_metrics(c, c->pred_cap))) return rc;
   if ((rc = opt_ensure_state(c))) return rc;
-  if ((rc = opt_ensure_metrics(c, n_steps))) return rc;
+  if (!obj.nll && (rc = opt_ensure_metrics(c, n_steps))) return rc;
+  if (obj.nll) {
+    if ((rc = lnz_ensure(c, mb, false))) return rc;
+    if ((rc = nll_ensure(c, std::min(batch, n)))) return rc;
+    if ((rc = nst_ensure(c, n_steps))) return rc;
+  }
   const int bp = c->cg_cap, xbp = c->pred_cap;
   HIP_TRY(hipMemcpyAsync(c->cg_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
   if ((rc = pred_table(c))) return rc;
+  const bool overlap = obj.nll && c->nst.overlap;
+  const bool labelled = obj.nll ? obj.labelled : true;
+  const long long t_start = c->opt.t;
+  if (obj.nll) {                                                // once per call: the table and the metric of the norm term, the guard cleared
+    if (n_metric) c->nst.metric_host.assign(obj.S, obj.S + (size_t)D * D);
+    if ((rc = lnz_upload(c, tab, n_metric ? c->nst.metric_host.data() : nullptr, n_metric, false))) return rc;
+    HIP_TRY(hipMemsetAsync(c->nst.skip, 0, sizeof(int), c->stream));
+  }
   cores_changed(c);                                             // from here on
   for (int k = 0; k < n_steps; ++k) {
     const int s0 = k * batch, bk = std::min(batch, n - s0);
+    if (overlap) {                                              // the norm walk reads the cores alone: beside the chunks, on stream2
+      HIP_TRY(hipEventRecord(c->nst.ev_fork, c->stream));       // (behind the update of step k - 1 and its record)
+      HIP_TRY(hipStreamWaitEvent(c->stream2, c->nst.ev_fork, 0));
+      if ((rc = lnz_launch_env(c, n_metric, mb, c->stream2))) return rc;
+      HIP_TRY(hipEventRecord(c->nst.ev_join, c->stream2));
+    }
     for (int off = 0; off < bk; off += chunk) {
       const int bc = std::min(chunk, bk - off);
-      if ((rc = load_chunk(c, X, idx ? c->ds_idx : nullptr, y, s0 + off, bc, c->ds_ypred))) return rc;
+      if ((rc = load_chunk(c, X, idx ? c->ds_idx : nullptr, y, s0 + off, bc, labelled ? c->ds_ypred : nullptr))) return rc;
       if ((rc = pred_chain(c, bc))) return rc;
-      if (!launch_dataset_metrics(c->fpred, c->ds_ypred, L, bc, xbp, act_fn, T, c->ds_part, off == 0, c->ds_acc, c->stream))
-        return fail(TNML_ERR_ARG, "internal: metrics launch refused");
-      HIP_TRY(hipGetLastError());
-      LossCotParams q{};
-      q.f = c->fpred; q.y = c->ds_ypred; q.cot = c->cg_cot; q.L = L; q.b = bc; q.b_pad = bp; q.f_bpad = xbp;
-      q.act_fn = act_fn; q.loss_fn = loss_fn; q.T = T;
-      if (!launch_loss_cot(q, c->stream)) return fail(TNML_ERR_ARG, "internal: loss-derivative launch refused (b %d, b_pad %d)", bc, bp);
-      HIP_TRY(hipGetLastError());
+      if (obj.nll) {
+        NllCotParams q{};
+        q.f = c->fpred; q.y = labelled ? c->ds_ypred : nullptr; q.cot = c->cg_cot;
+        q.terms = c->nll.terms; q.bad = c->nll.bad; q.L = L; q.b = bc; q.b_pad = bp; q.f_bpad = xbp; q.off = off; q.batch = bk;
+        if (!launch_nll_cot(q, c->stream)) return fail(TNML_ERR_ARG, "internal: likelihood cotangent launch refused (b %d, b_pad %d)", bc, bp);
+        HIP_TRY(hipGetLastError());
+      } else {
+        if (!launch_dataset_metrics(c->fpred, c->ds_ypred, L, bc, xbp, act_fn, T, c->ds_part, off == 0, c->ds_acc, c->stream))
+          return fail(TNML_ERR_ARG, "internal: metrics launch refused");
+        HIP_TRY(hipGetLastError());
+        LossCotParams q{};
+        q.f = c->fpred; q.y = c->ds_ypred; q.cot = c->cg_cot; q.L = L; q.b = bc; q.b_pad = bp; q.f_bpad = xbp;
+        q.act_fn = act_fn; q.loss_fn = loss_fn; q.T = T;
+        if (!launch_loss_cot(q, c->stream)) return fail(TNML_ERR_ARG, "internal: loss-derivative launch refused (b %d, b_pad %d)", bc, bp);
+        HIP_TRY(hipGetLastError());
+      }
       if ((rc = run_core_grad_chunk(c, bc, off == 0, mb))) return rc;
+    }
+    if (obj.nll) {                                              // G = Gd - Gz, the step's record, the guard
+      if (!launch_nll_sum(c->nll.terms, c->nll.bad, bk, c->nll.acc, c->stream)) return fail(TNML_ERR_ARG, "internal: likelihood sum launch refused");
+      HIP_TRY(hipGetLastError());
+      if (overlap) HIP_TRY(hipStreamWaitEvent(c->stream, c->nst.ev_join, 0));
+      else if ((rc = lnz_launch_env(c, n_metric, mb, c->stream))) return rc;
+      if ((rc = lnz_launch_grad(c, n_metric, mb, 1, c->cg_G))) return rc;
+      if (!launch_nll_record(c->nll.acc, c->lnz.out, c->lnz.status, c->nst.rec + (size_t)k * 4, c->nst.skip, c->stream))
+        return fail(TNML_ERR_ARG, "internal: likelihood record launch refused");
+      HIP_TRY(hipGetLastError());
     }
     OptimStepParams o{};
     o.tab = c->cg_tab; o.cores = c->cores; o.labcore = c->lab[c->lab_cur]; o.G = c->cg_G;
@@ -1785,22 +1869,50 @@ static int gd_impl(tnml_ctx *c, const float *X, const int32_t *y, const int32_t 
       o.corr1 = 1.0 - std::pow(c->opt.beta1, t);
       o.corr2 = 1.0 - std::pow(c->opt.beta2, t);
     }
+    if (obj.nll) { o.renorm = obj.renorm; o.skip = c->nst.skip; }
     if (!launch_optim_step(o, c->stream)) return fail(TNML_ERR_ARG, "internal: optimiser step launch refused");
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->opt_met + (size_t)k * 4, c->ds_acc, 4 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (!obj.nll) HIP_TRY(hipMemcpyAsync(c->opt_met + (size_t)k * 4, c->ds_acc, 4 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   }
   std::vector<double> met((size_t)n_steps * 4);
-  HIP_TRY(hipMemcpyAsync(met.data(), c->opt_met, met.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(met.data(), obj.nll ? c->nst.rec : c->opt_met, met.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   int bad = -1;
+  if (obj.nll) {
+    int applied = 0;
+    for (int k = 0; k < n_steps; ++k) {
+      const double *r = &met[(size_t)k * 4];
+      const int bk = std::min(batch, n - k * batch), bits = (int)r[3];
+      out[(size_t)k * 4 + 0] = -(r[0] / (double)bk - r[1]);
+      out[(size_t)k * 4 + 1] = r[1];
+      out[(size_t)k * 4 + 2] = r[2];
+      out[(size_t)k * 4 + 3] = r[3];
+      if (!(bits & kNllStepNotApplied)) ++applied;
+      else if (bad < 0) bad = k;
+    }
+    if (c->opt.kind == TNML_OPT_ADAM) c->opt.t = t_start + applied;     // (the steps behind the guard took no step)
+    if (bad >= 0) {
+      const int bits = (int)met[(size_t)bad * 4 + 3];
+      return fail(TNML_ERR_NONFINITE, "%s: step %d of %d saw %g samples with a cotangent that is not finite (f_y == 0, or an f beyond float32: calibrate the "
+                  "network), norm status %d; %d steps were applied, the cores and the optimiser state are what they left",
+                  obj.what, bad, n_steps, met[(size_t)bad * 4 + 2], bits & 7, applied);
+    }
+    return TNML_OK;
+  }
   for (int k = 0; k < n_steps; ++k) {
-    if (metrics_out) for (int j = 0; j < 3; ++j) metrics_out[(size_t)k * 3 + j] = met[(size_t)k * 4 + j];
+    if (out) for (int j = 0; j < 3; ++j) out[(size_t)k * 3 + j] = met[(size_t)k * 4 + j];
     if (met[(size_t)k * 4 + 2] > 0 && bad < 0) bad = k;
   }
   if (bad >= 0)
     return fail(TNML_ERR_NONFINITE, "step %d of %d saw %g samples with a non-finite activated output; every step ran and the cores are what they became",
                 bad, n_steps, met[(size_t)bad * 4 + 2]);
   return TNML_OK;
+}
+
+static int gd_impl(tnml_ctx *c, const float *X, const int32_t *y, const int32_t *idx, int n, int batch, float lr, float wd, int act_fn,
+                   int loss_fn, float T, double *metrics_out) {
+  const TrainObjective obj{false, "gradient step", act_fn, loss_fn, T, true, nullptr, 0};
+  return train_impl(c, obj, X, y, idx, n, batch, lr, wd, metrics_out);
 }
 
 extern "C" int tnml_gd_train_indices(tnml_ctx *c, const int32_t *idx, int n, int batch, float lr, float weight_dec, int act_fn, int loss_fn,
@@ -2317,32 +2429,56 @@ static int lnz_check(const tnml_ctx *c, const char *what, const double *S, int n
   return TNML_OK;
 }
 
-// The launches of the norm term on the context's stream, after lnz_check and lnz_ensure: the table (tab_host outlives the upload), the
-// metric, the environment kernel and -- mode 0: Gz stored to G, mode 1: G -= Gz, mode -1: none -- the gradient kernel.  The status
-// word and {sign, log|Z|} stay in the group for the caller to read.
-static int lnz_enqueue(tnml_ctx *c, const std::vector<int> &tab_host, const double *S, int n_metric, int mb, int mode, float *G) {
-  auto &g = c->lnz;
-  const int D = c->D;
+// The norm term after lnz_check and lnz_ensure, in three parts so that a call of many steps uploads once.  lnz_upload: the table
+// (tab_host outlives the upload), the status words cleared, the metric; wait: S is the caller's memory, the upload is waited for --
+// otherwise S outlives it as well.  lnz_launch_env: the environment kernel on `st`, behind a clearing of the status words of its own
+// when `st` is not where lnz_upload cleared them or a step was there since.  lnz_launch_grad -- mode 0: Gz stored to G, mode 1:
+// G -= Gz -- the gradient kernel on the context's stream.  The status words and {sign, log|Z|} stay in the group for the reader.
+static LogNormParams lnz_params(const tnml_ctx *c, int n_metric, int mode, float *G) {
+  const auto &g = c->lnz;
   LogNormParams p{};
-  p.N = c->N; p.D = D; p.L = c->L; p.l_pos = c->l_pos;
+  p.N = c->N; p.D = c->D; p.L = c->L; p.l_pos = c->l_pos;
   p.metric_sites = n_metric; p.mode = mode < 0 ? 0 : mode;
   p.tab = g.tab; p.cores = c->cores; p.lab = c->lab[c->lab_cur]; p.core_stride = c->core_stride;
   p.metric = n_metric ? g.metric : nullptr;
   p.envL = g.envL; p.envR = g.envR; p.expL = g.expL; p.expR = g.expR; p.env_stride = (size_t)g.m_cap * g.m_cap;
   p.G = G; p.out = g.out; p.status = g.status;
+  return p;
+}
+
+static int lnz_upload(tnml_ctx *c, const std::vector<int> &tab_host, const double *S, int n_metric, bool wait) {
+  auto &g = c->lnz;
+  const int D = c->D;
   HIP_TRY(hipMemcpyAsync(g.tab, tab_host.data(), tab_host.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemsetAsync(g.status, 0, 2 * sizeof(int), c->stream));
   if (n_metric) {
     HIP_TRY(hipMemcpyAsync(g.metric, S, (size_t)n_metric * D * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));                  // (the upload reads the caller's memory)
-  }
-  if (!launch_lognorm_env(p, mb, c->stream)) return fail(TNML_ERR_ARG, "internal: log-norm environment launch refused (bond %d)", mb);
-  HIP_TRY(hipGetLastError());
-  if (mode >= 0) {
-    if (!launch_lognorm_grad(p, mb, c->stream)) return fail(TNML_ERR_ARG, "internal: log-norm gradient launch refused (bond %d)", mb);
-    HIP_TRY(hipGetLastError());
+    if (wait) HIP_TRY(hipStreamSynchronize(c->stream));         // (the upload reads the caller's memory)
   }
   return TNML_OK;
+}
+
+// (the steps of a training call: every step clears the words the one before it left, on the stream of its environment kernel)
+static int lnz_launch_env(tnml_ctx *c, int n_metric, int mb, hipStream_t st) {
+  HIP_TRY(hipMemsetAsync(c->lnz.status, 0, 2 * sizeof(int), st));
+  if (!launch_lognorm_env(lnz_params(c, n_metric, 0, nullptr), mb, st)) return fail(TNML_ERR_ARG, "internal: log-norm environment launch refused (bond %d)", mb);
+  HIP_TRY(hipGetLastError());
+  return TNML_OK;
+}
+
+static int lnz_launch_grad(tnml_ctx *c, int n_metric, int mb, int mode, float *G) {
+  if (!launch_lognorm_grad(lnz_params(c, n_metric, mode, G), mb, c->stream)) return fail(TNML_ERR_ARG, "internal: log-norm gradient launch refused (bond %d)", mb);
+  HIP_TRY(hipGetLastError());
+  return TNML_OK;
+}
+
+// one call, one norm term: upload and launches on the context's stream (mode -1: no gradient launch)
+static int lnz_enqueue(tnml_ctx *c, const std::vector<int> &tab_host, const double *S, int n_metric, int mb, int mode, float *G) {
+  int rc = lnz_upload(c, tab_host, S, n_metric, true);
+  if (rc) return rc;
+  if (!launch_lognorm_env(lnz_params(c, n_metric, mode, G), mb, c->stream)) return fail(TNML_ERR_ARG, "internal: log-norm environment launch refused (bond %d)", mb);
+  HIP_TRY(hipGetLastError());
+  return mode >= 0 ? lnz_launch_grad(c, n_metric, mb, mode, G) : TNML_OK;
 }
 
 // the status word and {sign, log|Z|} of the launches above, after a synchronisation; `what` names the call in the refusal
@@ -2484,6 +2620,36 @@ extern "C" int tnml_nll_eval(tnml_ctx *c, const float *X, const int32_t *y, int 
   if (c->comm) return fail(TNML_ERR_STATE, "likelihoods are single-GPU only: a communicator is attached");
   if (b < 1) return fail(TNML_ERR_ARG, "empty batch");
   return nll_grad_impl(c, "tnml_nll_eval", X, y, nullptr, b, y != nullptr, S, nullptr, 0, out3);
+}
+
+// ---------------------------------------------------------------------------------------------
+// likelihood training: optimiser steps on the gradient of the negative log-likelihood
+// ---------------------------------------------------------------------------------------------
+extern "C" int tnml_nll_step(tnml_ctx *c, const float *X, const int32_t *y, int b, const double *S, float lr, float weight_dec, int renorm,
+                             double *values4) {
+  if (!c || !X || !values4) return fail(TNML_ERR_ARG, "NULL argument");
+  if (c->comm) return fail(TNML_ERR_STATE, "likelihood training is single-GPU only: a communicator is attached");
+  if (b < 1) return fail(TNML_ERR_ARG, "empty batch");
+  const TrainObjective obj{true, "tnml_nll_step", 0, 0, 1.f, y != nullptr, S, renorm};
+  return train_impl(c, obj, X, y, nullptr, b, b, lr, weight_dec, values4);
+}
+
+extern "C" int tnml_nll_train_indices(tnml_ctx *c, const int32_t *idx, int n, int batch, int use_labels, const double *S, float lr,
+                                      float weight_dec, int renorm, double *values_out) {
+  int rc = ds_usable(c);
+  if (rc) return rc;
+  if (!idx || !values_out) return fail(TNML_ERR_ARG, "NULL argument");
+  if (n < 1) return fail(TNML_ERR_ARG, "empty index list");
+  if (batch < 1) return fail(TNML_ERR_ARG, "batch %d < 1", batch);
+  const TrainObjective obj{true, "tnml_nll_train_indices", 0, 0, 1.f, use_labels != 0, S, renorm};
+  return train_impl(c, obj, nullptr, nullptr, idx, n, batch, lr, weight_dec, values_out);
+}
+
+extern "C" int tnml_set_nll_overlap(tnml_ctx *c, int on) {
+  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
+  if (on != 0 && on != 1) return fail(TNML_ERR_ARG, "tnml_set_nll_overlap: on %d is neither 0 nor 1", on);
+  c->nst.overlap = on;
+  return TNML_OK;
 }
 
 extern "C" int tnml_set_sample_stack_bytes(tnml_ctx *c, size_t bytes) {

@@ -384,6 +384,9 @@ struct OptimStepParams {
   float lr, wd;
   double mu, beta1, beta2, eps;
   double corr1, corr2;     // Adam: 1 - beta1^t and 1 - beta2^t of this step
+  // likelihood training; both off for the discriminative path
+  int renorm;              // 1: a third pass gives every core the Frobenius norm it had before the step
+  const int *skip;         // nullptr, or the sticky word of nll_record_kernel: non-zero, the launch touches neither cores nor state
 };
 size_t loss_cot_lds_bytes(int L);
 // false: refused (geometry / LDS)
@@ -572,5 +575,11 @@ struct NllCotParams {
 bool launch_nll_cot(const NllCotParams &p, hipStream_t st);
 // acc[0] = sum terms[0 .. n), acc[1] = sum bad[0 .. n), in an order that depends on n alone
 bool launch_nll_sum(const double *terms, const int *bad, int n, double *acc, hipStream_t st);
+// The record and guard of one likelihood step: one workgroup after nll_sum_kernel and the norm launches.
+// rec[0 .. 4) = {acc[0] (the sum of the batch's terms), out[1] (log|Z|), acc[1] (samples with a non-finite cotangent), status bits};
+// the bits are status[0] | status[1] of the norm launches, kNllStepBadBatch where acc[1] > 0, kNllStepNotApplied where *skip is set
+// on leaving.  *skip is set, never cleared, when any of the other bits is.
+constexpr int kNllStepBadBatch = 8, kNllStepNotApplied = 16;
+bool launch_nll_record(const double *acc, const double *out, const int *status, double *rec, int *skip, hipStream_t st);
 
 }  // namespace tnml

@@ -42,10 +42,20 @@ def main(argv=None):
                     help='upload the data set once and train from index batches formed on the device (Network.train_resident)')
     ap.add_argument('--steps-per-batch', dest='steps_per_batch', type=int, default=None, metavar='K',
                     help='change the batch every K sweep steps instead of every sweep (needs --resident)')
+    ap.add_argument('--objective', type=str, default='loss', choices=['loss', 'nll'],
+                    help="nll: fit the model's own distribution p(x, l) by gradient descent on the negative log-likelihood "
+                         '(Network.train_generative; needs --resident)')
+    ap.add_argument('--optimizer', type=str, default='sgd', choices=['sgd', 'adam'], help='the optimiser of --objective nll')
+    ap.add_argument('--no-renorm', dest='renorm', action='store_false',
+                    help='likelihood steps without the renormalisation of the cores (needs --objective nll)')
     ap.add_argument('--out', type=str, default='trained_MNIST_model.dat')
     args = ap.parse_args(argv)
     if args.steps_per_batch is not None and not args.resident:
         ap.error('--steps-per-batch needs --resident')
+    if args.objective == 'nll' and not args.resident:
+        ap.error('--objective nll needs --resident')
+    if not args.renorm and args.objective != 'nll':
+        ap.error('--no-renorm needs --objective nll')
 
     train_data, train_labels, test_data, test_labels = gen.get_MNIST_dataset(args.data_dir)
     data = pooling(np.concatenate((train_data, test_data)))
@@ -67,6 +77,14 @@ def main(argv=None):
                      loss_fn=args.loss_fn, trunc=args.trunc)
     if args.resident:
         _, train_idx, val_idx, _ = gen.prepare_device_dataset(net, data01, labels01, 1, 0.2, train_batch, 128, 128, D=args.D)
+        if args.objective == 'nll':
+            # (pixels 0 .. 255 lie on the grid of 256 levels once normalised; the likelihood's norm is taken on that grid)
+            val_nll, nll_hist = net.train_generative(train_idx, val_idx, lr=args.lr, n_epochs=args.n_epochs, weight_dec=args.L2_decay,
+                                                     optimizer=args.optimizer, renorm=args.renorm)
+            with open(args.out, 'wb') as fh:
+                pickle.dump(net, fh)
+            print('validation NLL per epoch:', ['%.4f' % v for v in val_nll])
+            return val_nll, nll_hist
         val_acc, var_hist = net.train_resident(train_idx, val_idx, lr=args.lr, n_epochs=args.n_epochs, weight_dec=args.L2_decay,
                                                steps_per_batch=args.steps_per_batch)
     else:

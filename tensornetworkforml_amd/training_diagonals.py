@@ -39,6 +39,11 @@ def main(argv=None):
                     help='change the batch every K sweep steps instead of every sweep (needs --resident)')
     ap.add_argument('--optimizer', type=str, default=None, choices=['sgd', 'adam'],
                     help='gradient descent over all cores at fixed bonds instead of sweeps (Network.train_gradient; needs --resident)')
+    ap.add_argument('--objective', type=str, default='loss', choices=['loss', 'nll'],
+                    help="nll: fit the model's own distribution p(x, l) by gradient descent on the negative log-likelihood "
+                         '(Network.train_generative; needs --resident; --optimizer defaults to sgd)')
+    ap.add_argument('--no-renorm', dest='renorm', action='store_false',
+                    help='likelihood steps without the renormalisation of the cores (needs --objective nll)')
     ap.add_argument('--compress', type=int, default=None, metavar='M',
                     help='after training, cut every bond to M on its Schmidt decomposition (Network.compress; needs --resident)')
     ap.add_argument('--scaled-chains', dest='scaled_chains', action='store_true',
@@ -49,6 +54,12 @@ def main(argv=None):
         ap.error('--compress needs --resident')
     if args.optimizer is not None and not args.resident:
         ap.error('--optimizer needs --resident')
+    if args.objective == 'nll' and not args.resident:
+        ap.error('--objective nll needs --resident')
+    if not args.renorm and args.objective != 'nll':
+        ap.error('--no-renorm needs --objective nll')
+    if args.objective == 'nll' and args.optimizer is None:
+        args.optimizer = 'sgd'
     if args.scaled_chains and args.optimizer is None:
         ap.error('--scaled-chains needs --resident --optimizer')
     if args.steps_per_batch is not None and not args.resident:
@@ -68,6 +79,14 @@ def main(argv=None):
                      act_fn=args.act_fn, loss_fn=args.loss_fn, trunc=args.trunc)
     if args.resident:
         _, train_idx, val_idx, _ = gen.prepare_device_dataset(net, data, label, 1, 0.2, train_batch, 128, 128, D=args.D)
+        if args.objective == 'nll':
+            net.scaled_chains = args.scaled_chains
+            val_nll, nll_hist = net.train_generative(train_idx, val_idx, lr=args.lr, n_epochs=args.n_epochs, weight_dec=args.L2_decay,
+                                                     optimizer=args.optimizer, renorm=args.renorm)
+            with open(args.out, 'wb') as fh:
+                pickle.dump(net, fh)
+            print('validation NLL per epoch:', ['%.4f' % v for v in val_nll])
+            return val_nll, nll_hist
         if args.optimizer is not None:
             net.scaled_chains = args.scaled_chains
             val_acc, var_hist = net.train_gradient(train_idx, val_idx, lr=args.lr, n_epochs=args.n_epochs, weight_dec=args.L2_decay,
