@@ -11,10 +11,12 @@
 //                       R_{i+1} into LDS, U = V . A_i and T = U . R_{i+1} on the f64 matrix cores (mm_lds), then per sample
 //                       Q = T U^T, the K densities w_k phi_k^T Q phi_k (four consecutive levels per lane), an inclusive scan over
 //                       the wave, the search, the new v = phi_k^T U and its power-of-two rescale.  On the label site the classes
-//                       are streamed one slice at a time: P(l) for every l, the draw, then the slices that were chosen.
+//                       are streamed one slice at a time: P(l) for every l, the draw, then the slices that were chosen.  The draw
+//                       itself is sample_device.h's, shared with kernels_sample_masked.hip.
 // Status word: bit 1 a non-finite environment or density, bit 2 a sample whose densities sum to nothing (a clamped class or
 // prefix of zero weight); status[1] is the smallest such sample.
 #include "small_gemm_device.h"
+#include "sample_device.h"
 
 #include <cmath>
 
@@ -26,9 +28,6 @@ constexpr int kSmpWalkThreads = 512;         // the walk: eight waves, two sampl
 constexpr int kSmpWalkWaves = kSmpWalkThreads / 64;
 constexpr int kSmpPerWave = kSmpTile / kSmpWalkWaves;
 constexpr int kSmpAcc = 4;                  // elements of R' a thread owns at the most: bonds up to 64
-constexpr double kSmpDblMax = 1.7976931348623157e308;
-
-static size_t smp_even(size_t x) { return (x + 1) & ~(size_t)1; }
 
 size_t sample_env_lds_bytes(int mb, int D) {
   const size_t m = (size_t)mb;
@@ -40,8 +39,6 @@ size_t sample_walk_lds_bytes(int mb, int D, int L, int K) {
          smp_even(m * D * m) * sizeof(float) + (size_t)kSmpTile * sizeof(int);
 }
 
-__device__ inline int smp_ml(const SampleParams &p, int i) { return i == 0 ? 1 : p.bond[i - 1]; }
-__device__ inline int smp_mr(const SampleParams &p, int i) { return i == p.N - 1 ? 1 : p.bond[i]; }
 // R_i of compact slot `slot`: the shared stack beyond the label site, the slot's own up to it
 __device__ inline double *smp_env(const SampleParams &p, int slot, int i) {
   return i > p.l_pos ? p.env_shared + (size_t)i * p.env_stride : p.env_slots + ((size_t)slot * (p.l_pos + 1) + i) * p.env_stride;
@@ -67,14 +64,14 @@ __global__ __launch_bounds__(kSmpThreads) void sample_env_kernel(SampleParams p)
   if (p.phase == 1) {
     if (tid == 0) { R[0] = 1.0; p.env_shared[(size_t)N * p.env_stride] = 1.0; }
   } else {
-    const int nr = smp_mr(p, l);                                 // R starts as R_{l+1}, nr x nr
+    const int nr = smp_mr(p.bond, N, l);                         // R starts as R_{l+1}, nr x nr
     const double *src = p.env_shared + (size_t)(l + 1) * p.env_stride;
     for (int e = tid; e < nr * nr; e += kSmpThreads) R[e] = src[e];
   }
   int bad = 0, it = 0;
   __syncthreads();
   for (int i = first; i >= last; --i, ++it) {
-    const int ml = smp_ml(p, i), mr = smp_mr(p, i), Dm = D * mr;
+    const int ml = smp_ml(p.bond, i), mr = smp_mr(p.bond, N, i), Dm = D * mr;
     const bool lab = i == l;
     const int Lx = lab ? p.L : 1, l0 = lab && q >= 0 ? q : 0, l1 = lab && q < 0 ? p.L : l0 + 1;
     const float *A = lab ? p.lab : p.cores + (size_t)i * p.core_stride;
@@ -138,14 +135,6 @@ __global__ __launch_bounds__(kSmpThreads) void sample_env_kernel(SampleParams p)
   if (bad && tid == 0) atomicOr(p.status, 1);
 }
 
-__device__ inline double smp_uniform(unsigned long long seed, long long s, int j, int N) {
-  unsigned long long z = seed + ((unsigned long long)s * (unsigned long long)(N + 1) + (unsigned long long)j + 1ull) * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z = z ^ (z >> 31);
-  return (double)(z >> 11) * 1.1102230246251565e-16;             // 2^-53
-}
-
 // the LDS areas of the walk kernel
 struct SmpLds {
   double *R, *U, *T, *V, *phi, *w, *Q, *S, *P;
@@ -168,129 +157,46 @@ __device__ inline void smp_products(const SmpLds &s, int m, int ml, int mr, int 
   __syncthreads();
 }
 
-// Q[d][d'] = sum_c T[d][c] U[d'][c] of one sample of the wave into LDS
-__device__ inline void smp_form_Q(const SmpLds &s, int smp, int lane, int mr, int D) {
-  if (lane < D * D) {
-    const double *t = s.T + (size_t)(smp * D + lane / D) * mr, *u = s.U + (size_t)(smp * D + lane % D) * mr;
-    double v = 0.0;
-    for (int c = 0; c < mr; ++c) v = fma(t[c], u[c], v);
-    s.Q[smp * D * D + lane] = v;
-  }
-}
-
 // what a wave carries for each of its two samples from site to site (the same in every lane)
 struct SmpState {
   int sample, label, dead;
   double logp0, logp1;
 };
 
-// The draw of one site for the wave's sample, from Q in LDS: densities, scan, search (or the clamped level), logp, the new v.
+// u[j] of the wave's sample, j the site or N for the label; a padding row draws with 0.5 and writes nothing
+__device__ inline double smp_u(const SampleParams &p, const SmpState &st, int j) {
+  return st.sample >= 0 ? (p.u ? p.u[(size_t)st.sample * (p.N + 1) + j] : smp_uniform(p.seed, st.sample, j, p.N)) : 0.5;
+}
+
+// The draw of one site for the wave's sample, from Q in LDS: the level (the clamped one inside the prefix), logp, the new v.
 // active: the sample takes part (its label is the staged slice); otherwise nothing is written.
 __device__ inline void smp_draw_pixel(const SampleParams &p, const SmpLds &s, SmpState &st, int smp, int lane, int i, int m, int mr, bool active) {
-  const int D = p.D, K = p.K, N = p.N;
-  const double *Q = s.Q + smp * D * D;
-  double pl[4];
-  bool nonfinite = false;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int k = 4 * lane + j;
-    double v = 0.0;
-    if (k < K) {
-      const double *ph = s.phi + (size_t)k * D;
-      double a = 0.0;
-      for (int d = 0; d < D; ++d) {
-        double t = 0.0;
-        for (int dd = 0; dd < D; ++dd) t = fma(Q[d * D + dd], ph[dd], t);
-        a = fma(ph[d], t, a);
-      }
-      v = s.w[k] * a;
-      if (!(fabs(v) <= kSmpDblMax)) { nonfinite = true; v = 0.0; }
-      v = v > 0.0 ? v : 0.0;
-    }
-    pl[j] = v;
-  }
-  const double c0 = pl[0], c1 = c0 + pl[1], c2 = c1 + pl[2], c3 = c2 + pl[3];
-  double x = c3;
-  for (int o = 1; o < 64; o <<= 1) {
-    const double y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  double excl = __shfl_up(x, 1, 64);
-  if (lane == 0) excl = 0.0;
-  const double total = __shfl(x, 63, 64);
-  const double u = st.sample >= 0 ? (p.u ? p.u[(size_t)st.sample * (N + 1) + i] : smp_uniform(p.seed, st.sample, i, N)) : 0.5;
-  const double t = u * total;
-  const double cl[4] = {excl + c0, excl + c1, excl + c2, excl + c3};
-  int cand = 1 << 20, lastpos = -1;
-#pragma unroll
-  for (int j = 3; j >= 0; --j) {
-    const int k = 4 * lane + j;
-    if (k < K && cl[j] > t) cand = k;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (pl[j] > 0.0) lastpos = 4 * lane + j;
-  for (int o = 32; o > 0; o >>= 1) {
-    cand = min(cand, __shfl_xor(cand, o, 64));
-    lastpos = max(lastpos, __shfl_xor(lastpos, o, 64));
-    nonfinite = nonfinite || __shfl_xor((int)nonfinite, o, 64);
-  }
-  int k = cand < K ? cand : (lastpos >= 0 ? lastpos : 0);
+  const int D = p.D;
   const bool clamped = i < p.n_given && st.sample >= 0;
-  if (clamped) k = p.given[(size_t)st.sample * p.n_given + i];
-  const int j = k & 3;
-  const double mine = j == 0 ? pl[0] : j == 1 ? pl[1] : j == 2 ? pl[2] : pl[3];
-  const double psel = __shfl(mine, k >> 2, 64);
-  // the new v and its rescale
-  double v = 0.0;
-  if (lane < mr) {
-    const double *ph = s.phi + (size_t)k * D;
-    for (int d = 0; d < D; ++d) v = fma(ph[d], s.U[(size_t)(smp * D + d) * mr + lane], v);
-  }
-  double mx = fabs(v);
-  for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
-  if (mx > 0.0 && mx <= kSmpDblMax) v = ldexp(v, -(ilogb(mx) + 1));
+  const SmpPick pk = smp_pick_level(s.Q + smp * D * D, s.phi, s.w, p.K, D, lane, smp_u(p, st, i), clamped ? p.given[(size_t)st.sample * p.n_given + i] : -1);
+  const double v = smp_next_v(s.phi + (size_t)pk.k * D, s.U + (size_t)smp * D * mr, D, mr, lane);
   if (active && st.sample >= 0) {
-    if (!st.dead) {
-      if (nonfinite) { st.dead = 1; if (lane == 0) atomicOr(p.status, 1); }
-      else if (!(total > 0.0)) { st.dead = 1; if (lane == 0) { atomicOr(p.status, 2); atomicMin(p.status + 1, st.sample); } }
-    }
-    const double term = log(psel / total);
+    smp_mark_dead(p.status, st.sample, st.dead, lane, pk.nonfinite, pk.total);
+    const double term = log(pk.psel / pk.total);
     st.logp0 += term;
     if (clamped) st.logp1 += term;
     if (lane < mr) s.V[(size_t)smp * m + lane] = v;
-    if (lane == 0) p.levels[(size_t)st.sample * N + i] = k;
+    if (lane == 0) p.levels[(size_t)st.sample * p.N + i] = pk.k;
   }
 }
 
-// The label of the wave's sample from P(l') in LDS, by u[N] and the rule of the pixels (every lane computes the same)
+// The label of the wave's sample from P(l') in LDS, by u[N]
 __device__ inline void smp_draw_label(const SampleParams &p, const SmpLds &s, SmpState &st, int smp, int lane) {
-  const int L = p.L, N = p.N;
-  double total = 0.0;
-  bool nonfinite = false;
-  for (int lp = 0; lp < L; ++lp) {
-    const double a = s.P[smp * L + lp];
-    if (!(fabs(a) <= kSmpDblMax)) nonfinite = true;
-    else total += a > 0.0 ? a : 0.0;
-  }
-  const double u = st.sample >= 0 ? (p.u ? p.u[(size_t)st.sample * (N + 1) + N] : smp_uniform(p.seed, st.sample, N, N)) : 0.5;
-  const double t = u * total;
-  int pick = -1, lastpos = 0;
-  double c = 0.0, psel = 0.0, plast = 0.0;
-  for (int lp = 0; lp < L; ++lp) {
-    const double a0 = s.P[smp * L + lp], a = a0 > 0.0 && a0 <= kSmpDblMax ? a0 : 0.0;
-    c += a;
-    if (pick < 0 && c > t) { pick = lp; psel = a; }
-    if (a > 0.0) { lastpos = lp; plast = a; }
-  }
-  if (pick < 0) { pick = lastpos; psel = plast; }
-  st.label = pick;
+  const SmpPick pk = smp_pick_label(s.P + smp * p.L, p.L, smp_u(p, st, p.N));
+  st.label = pk.k;
   if (st.sample >= 0) {
-    if (nonfinite) { st.dead = 1; if (lane == 0) atomicOr(p.status, 1); }
-    else if (!(total > 0.0)) { st.dead = 1; if (lane == 0) { atomicOr(p.status, 2); atomicMin(p.status + 1, st.sample); } }
-    st.logp0 += log(psel / total);
+    // (smp_mark_dead leaves a sample alone that a pixel before the label has marked already: its bit and its number are in the
+    // status word, and sums that are not finite at the label without having been so before it come from an environment or a metric
+    // that is not finite, for which sample_env_kernel has set bit 1 itself)
+    smp_mark_dead(p.status, st.sample, st.dead, lane, pk.nonfinite, pk.total);
+    st.logp0 += log(pk.psel / pk.total);
   }
-  if (lane == 0) s.lab[smp] = st.sample >= 0 ? pick : -1;
+  if (lane == 0) s.lab[smp] = st.sample >= 0 ? pk.k : -1;
 }
 
 __global__ __launch_bounds__(kSmpWalkThreads) void sample_walk_kernel(SampleParams p) {
@@ -308,7 +214,7 @@ __global__ __launch_bounds__(kSmpWalkThreads) void sample_walk_kernel(SamplePara
   s.S = s.Q + kSmpTile * D * D;
   s.P = s.S + D * D;
   s.A = (float *)(s.P + (size_t)kSmpTile * L);
-  s.lab = (int *)(s.A + (((size_t)m * D * m + 1) & ~(size_t)1));
+  s.lab = (int *)(s.A + smp_even((size_t)m * D * m));
   const int slot = p.tile_slot[tile], q = p.slot_class[slot];
   SmpState st[kSmpPerWave];
 #pragma unroll
@@ -324,7 +230,7 @@ __global__ __launch_bounds__(kSmpWalkThreads) void sample_walk_kernel(SamplePara
   for (int e = tid; e < kSmpTile * m; e += kSmpWalkThreads) s.V[e] = (e % m) == 0 ? 1.0 : 0.0;
   __syncthreads();
   for (int i = 0; i < N; ++i) {
-    const int ml = smp_ml(p, i), mr = smp_mr(p, i), nA = ml * D * mr;
+    const int ml = smp_ml(p.bond, i), mr = smp_mr(p.bond, N, i), nA = ml * D * mr;
     const double *Rg = smp_env(p, slot, i + 1);
     for (int e = tid; e < mr * mr; e += kSmpWalkThreads) s.R[e] = Rg[e];
     // One pass per staged core slice.  A plain site and a label site with a given class have one; a label site whose label is
@@ -348,7 +254,10 @@ __global__ __launch_bounds__(kSmpWalkThreads) void sample_walk_kernel(SamplePara
       __syncthreads();
       smp_products(s, m, ml, mr, D);
 #pragma unroll
-      for (int h = 0; h < kSmpPerWave; ++h) smp_form_Q(s, wave + h * kSmpWalkWaves, lane, mr, D);
+      for (int h = 0; h < kSmpPerWave; ++h) {
+        const int smp = wave + h * kSmpWalkWaves;
+        smp_form_Q(s.T + (size_t)smp * D * mr, s.U + (size_t)smp * D * mr, s.Q + smp * D * D, D, mr, lane);
+      }
       __syncthreads();
 #pragma unroll
       for (int h = 0; h < kSmpPerWave; ++h) {

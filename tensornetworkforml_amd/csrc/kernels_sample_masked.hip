@@ -14,9 +14,10 @@
 //                              E[row] = log R_{s,0} + ln2 sum k (-inf where R_{s,0} <= 0).
 //   sample_walk_masked_kernel  the walk of kernels_sample.hip with T_s = U_s . R_{s,i+1} as a product batched per row; on a known site
 //                              nothing is drawn and no density is formed, v' = phi_k^T U only; the label is drawn with the row's own
-//                              metric of the label site.
+//                              metric of the label site.  The draw itself is sample_device.h's, as in kernels_sample.hip.
 // Status word: bit 1 a non-finite environment or density, bit 2 a sample whose densities sum to nothing; status[1] the smallest such.
 #include "small_gemm_device.h"
+#include "sample_device.h"
 
 #include <cmath>
 
@@ -25,23 +26,18 @@ namespace tnml {
 constexpr int kSmkThreads = 512;
 constexpr int kSmkWaves = kSmkThreads / 64;
 constexpr int kSmkPerWave = kSmkMaxTile / kSmkWaves;        // rows of a tile a wave of the walk owns at the most
-constexpr double kSmkDblMax = 1.7976931348623157e308;
 constexpr double kSmkLn2 = 0.6931471805599453;
-
-__host__ __device__ static inline size_t smk_even(size_t x) { return (x + 1) & ~(size_t)1; }
 
 size_t sample_masked_env_lds_bytes(int mb, int D, int T) {
   const size_t m = (size_t)mb, t = (size_t)T;
-  return (t * m * m + t * m * D * m + t * D * D) * sizeof(double) + 2 * t * sizeof(int) + smk_even(m * D * m) * sizeof(float);
+  return (t * m * m + t * m * D * m + t * D * D) * sizeof(double) + 2 * t * sizeof(int) + smp_even(m * D * m) * sizeof(float);
 }
 size_t sample_masked_walk_lds_bytes(int mb, int D, int L, int K, int T) {
   const size_t m = (size_t)mb, t = (size_t)T;
-  return (t * m * m + 2 * t * D * m + t * m + (size_t)K * D + K + 2 * t * D * D + t * L) * sizeof(double) + smk_even(m * D * m) * sizeof(float) +
+  return (t * m * m + 2 * t * D * m + t * m + (size_t)K * D + K + 2 * t * D * D + t * L) * sizeof(double) + smp_even(m * D * m) * sizeof(float) +
          2 * t * sizeof(int);
 }
 
-__device__ inline int smk_ml(const SampleMaskedParams &p, int i) { return i == 0 ? 1 : p.bond[i - 1]; }
-__device__ inline int smk_mr(const SampleMaskedParams &p, int i) { return i == p.N - 1 ? 1 : p.bond[i]; }
 // R_{s,i} of row `row` of the launch
 __device__ inline double *smk_env(const SampleMaskedParams &p, int row, int i) {
   return p.stack + ((size_t)row * (p.N + 1) + i) * p.env_stride;
@@ -80,7 +76,7 @@ __global__ __launch_bounds__(kSmkThreads) void sample_env_masked_kernel(SampleMa
   }
   __syncthreads();
   for (int i = N - 1; i >= 0; --i) {
-    const int ml = smk_ml(p, i), mr = smk_mr(p, i), Dm = D * mr, Tm = T * mr;
+    const int ml = smp_ml(p.bond, i), mr = smp_mr(p.bond, N, i), Dm = D * mr, Tm = T * mr;
     const bool lab = i == l;
     const int Lx = lab ? p.L : 1, l0 = lab && q >= 0 ? q : 0, l1 = lab && q < 0 ? p.L : l0 + 1;
     const float *Ag = lab ? p.lab : p.cores + (size_t)i * p.core_stride;
@@ -132,11 +128,11 @@ __global__ __launch_bounds__(kSmkThreads) void sample_env_masked_kernel(SampleMa
       double mx = 0.0;
       for (int e = lane; e < ml * ml; e += 64) {
         const double a = fabs(out[e]);
-        mx = fmax(mx, a <= kSmkDblMax ? a : INFINITY);          // (a NaN fails the comparison)
+        mx = fmax(mx, a <= kSmpDblMax ? a : INFINITY);          // (a NaN fails the comparison)
       }
       for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
       int kexp = 0;
-      if (!(mx <= kSmkDblMax)) { if (lane == 0) atomicOr(p.status, 1); }
+      if (!(mx <= kSmpDblMax)) { if (lane == 0) atomicOr(p.status, 1); }
       else if (mx > 0.0) kexp = ilogb(mx) + 1;
       for (int e = lane; e < ml * ml; e += 64) {
         const double v = ldexp(out[e], -kexp);
@@ -154,15 +150,6 @@ __global__ __launch_bounds__(kSmkThreads) void sample_env_masked_kernel(SampleMa
   }
 }
 
-// the counter hash of kernels_sample.hip: SplitMix64 of seed + (s (N + 1) + j + 1) GOLDEN, s the CALL's sample number
-__device__ inline double smk_uniform(unsigned long long seed, long long s, int j, int N) {
-  unsigned long long z = seed + ((unsigned long long)s * (unsigned long long)(N + 1) + (unsigned long long)j + 1ull) * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z = z ^ (z >> 31);
-  return (double)(z >> 11) * 1.1102230246251565e-16;             // 2^-53
-}
-
 // the LDS areas of the walk kernel
 struct SmkLds {
   double *R, *U, *T, *V, *phi, *w, *Q, *S, *P;
@@ -176,117 +163,38 @@ struct SmkState {
   double logp0;
 };
 
-__device__ inline void smk_dead(const SampleMaskedParams &p, SmkState &st, int lane, bool nonfinite, double total) {
-  if (st.dead) return;
-  if (nonfinite) { st.dead = 1; if (lane == 0) atomicOr(p.status, 1); }
-  else if (!(total > 0.0)) { st.dead = 1; if (lane == 0) { atomicOr(p.status, 2); atomicMin(p.status + 1, st.sample); } }
+// u[j] of the row's sample, j the site or N for the label
+__device__ inline double smk_u(const SampleMaskedParams &p, const SmkState &st, int j) {
+  return p.u ? p.u[(size_t)st.sample * (p.N + 1) + j] : smp_uniform(p.seed, st.sample, j, p.N);
 }
 
-// One site of the wave's row smp (a sample): on a free site Q, the densities, the scan, the search and the log share; on a known
-// one the given level; then the new v = phi_k^T U and its power-of-two rescale.
+// One site of the wave's row smp (a sample): on a free site Q, the draw of the level and the log share; on a known one the given
+// level; then the new v.
 __device__ inline void smk_pixel(const SampleMaskedParams &p, const SmkLds &s, SmkState &st, int smp, int lane, int i, int m, int mr) {
-  const int D = p.D, K = p.K, N = p.N;
+  const int D = p.D;
+  const double *U = s.U + (size_t)smp * D * mr;
   int k = smk_known(p, st.sample, i);
   if (k < 0) {
-    // Q[d][d'] = sum_c T[d][c] U[d'][c]
-    if (lane < D * D) {
-      const double *t = s.T + (size_t)(smp * D + lane / D) * mr, *u = s.U + (size_t)(smp * D + lane % D) * mr;
-      double v = 0.0;
-      for (int c = 0; c < mr; ++c) v = fma(t[c], u[c], v);
-      s.Q[smp * D * D + lane] = v;
-    }
+    double *Q = s.Q + smp * D * D;
+    smp_form_Q(s.T + (size_t)smp * D * mr, U, Q, D, mr, lane);
     __builtin_amdgcn_wave_barrier();
-    const double *Q = s.Q + smp * D * D;
-    double pl[4];
-    bool nonfinite = false;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int kk = 4 * lane + j;
-      double v = 0.0;
-      if (kk < K) {
-        const double *ph = s.phi + (size_t)kk * D;
-        double a = 0.0;
-        for (int d = 0; d < D; ++d) {
-          double t = 0.0;
-          for (int dd = 0; dd < D; ++dd) t = fma(Q[d * D + dd], ph[dd], t);
-          a = fma(ph[d], t, a);
-        }
-        v = s.w[kk] * a;
-        if (!(fabs(v) <= kSmkDblMax)) { nonfinite = true; v = 0.0; }
-        v = v > 0.0 ? v : 0.0;
-      }
-      pl[j] = v;
-    }
-    const double c0 = pl[0], c1 = c0 + pl[1], c2 = c1 + pl[2], c3 = c2 + pl[3];
-    double x = c3;
-    for (int o = 1; o < 64; o <<= 1) {
-      const double y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
-    }
-    double excl = __shfl_up(x, 1, 64);
-    if (lane == 0) excl = 0.0;
-    const double total = __shfl(x, 63, 64);
-    const double u = p.u ? p.u[(size_t)st.sample * (N + 1) + i] : smk_uniform(p.seed, st.sample, i, N);
-    const double t = u * total;
-    const double cl[4] = {excl + c0, excl + c1, excl + c2, excl + c3};
-    int cand = 1 << 20, lastpos = -1;
-#pragma unroll
-    for (int j = 3; j >= 0; --j) {
-      const int kk = 4 * lane + j;
-      if (kk < K && cl[j] > t) cand = kk;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (pl[j] > 0.0) lastpos = 4 * lane + j;
-    for (int o = 32; o > 0; o >>= 1) {
-      cand = min(cand, __shfl_xor(cand, o, 64));
-      lastpos = max(lastpos, __shfl_xor(lastpos, o, 64));
-      nonfinite = nonfinite || __shfl_xor((int)nonfinite, o, 64);
-    }
-    k = cand < K ? cand : (lastpos >= 0 ? lastpos : 0);
-    const int j = k & 3;
-    const double mine = j == 0 ? pl[0] : j == 1 ? pl[1] : j == 2 ? pl[2] : pl[3];
-    const double psel = __shfl(mine, k >> 2, 64);
-    smk_dead(p, st, lane, nonfinite, total);
-    st.logp0 += log(psel / total);
+    const SmpPick pk = smp_pick_level(Q, s.phi, s.w, p.K, D, lane, smk_u(p, st, i), -1);
+    k = pk.k;
+    smp_mark_dead(p.status, st.sample, st.dead, lane, pk.nonfinite, pk.total);
+    st.logp0 += log(pk.psel / pk.total);
   }
-  double v = 0.0;
-  if (lane < mr) {
-    const double *ph = s.phi + (size_t)k * D;
-    for (int d = 0; d < D; ++d) v = fma(ph[d], s.U[(size_t)(smp * D + d) * mr + lane], v);
-  }
-  double mx = fabs(v);
-  for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
-  if (mx > 0.0 && mx <= kSmkDblMax) v = ldexp(v, -(ilogb(mx) + 1));
+  const double v = smp_next_v(s.phi + (size_t)k * D, U, D, mr, lane);
   if (lane < mr) s.V[(size_t)smp * m + lane] = v;
-  if (lane == 0) p.levels[(size_t)st.sample * N + i] = k;
+  if (lane == 0) p.levels[(size_t)st.sample * p.N + i] = k;
 }
 
-// The label of the wave's row from P(l') in LDS, by u[N] and the rule of the pixels (every lane computes the same)
+// The label of the wave's row from P(l') in LDS, by u[N]
 __device__ inline void smk_label(const SampleMaskedParams &p, const SmkLds &s, SmkState &st, int smp, int lane) {
-  const int L = p.L, N = p.N;
-  double total = 0.0;
-  bool nonfinite = false;
-  for (int lp = 0; lp < L; ++lp) {
-    const double a = s.P[smp * L + lp];
-    if (!(fabs(a) <= kSmkDblMax)) nonfinite = true;
-    else total += a > 0.0 ? a : 0.0;
-  }
-  const double u = p.u ? p.u[(size_t)st.sample * (N + 1) + N] : smk_uniform(p.seed, st.sample, N, N);
-  const double t = u * total;
-  int pick = -1, lastpos = 0;
-  double c = 0.0, psel = 0.0, plast = 0.0;
-  for (int lp = 0; lp < L; ++lp) {
-    const double a0 = s.P[smp * L + lp], a = a0 > 0.0 && a0 <= kSmkDblMax ? a0 : 0.0;
-    c += a;
-    if (pick < 0 && c > t) { pick = lp; psel = a; }
-    if (a > 0.0) { lastpos = lp; plast = a; }
-  }
-  if (pick < 0) { pick = lastpos; psel = plast; }
-  st.label = pick;
-  smk_dead(p, st, lane, nonfinite, total);
-  st.logp0 += log(psel / total);
-  if (lane == 0) s.lab[smp] = pick;
+  const SmpPick pk = smp_pick_label(s.P + smp * p.L, p.L, smk_u(p, st, p.N));
+  st.label = pk.k;
+  smp_mark_dead(p.status, st.sample, st.dead, lane, pk.nonfinite, pk.total);
+  st.logp0 += log(pk.psel / pk.total);
+  if (lane == 0) s.lab[smp] = pk.k;
 }
 
 __global__ __launch_bounds__(kSmkThreads) void sample_walk_masked_kernel(SampleMaskedParams p) {
@@ -304,7 +212,7 @@ __global__ __launch_bounds__(kSmkThreads) void sample_walk_masked_kernel(SampleM
   s.S = s.Q + T * D * D;                                          // [T][D][D]: the rows' metric of the label site
   s.P = s.S + T * D * D;                                          // [T][L]
   s.A = (float *)(s.P + (size_t)T * L);
-  s.lab = (int *)(s.A + smk_even((size_t)m * D * m));
+  s.lab = (int *)(s.A + smp_even((size_t)m * D * m));
   s.srow = s.lab + T;
   const int q = p.tile_class[tile];
   SmkState st[kSmkPerWave];
@@ -323,7 +231,7 @@ __global__ __launch_bounds__(kSmkThreads) void sample_walk_masked_kernel(SampleM
   __syncthreads();
   smk_metric(p, s.srow, l, s.S);
   for (int i = 0; i < N; ++i) {
-    const int ml = smk_ml(p, i), mr = smk_mr(p, i), nA = ml * D * mr, Dm = D * mr, m2 = mr * mr;
+    const int ml = smp_ml(p.bond, i), mr = smp_mr(p.bond, N, i), nA = ml * D * mr, Dm = D * mr, m2 = mr * mr;
     for (int e = tid; e < T * m2; e += kSmkThreads) {
       const int r = e / m2;
       s.R[e] = smk_env(p, tile * T + r, i + 1)[e - r * m2];

@@ -2251,34 +2251,86 @@ static int smp_ensure(tnml_ctx *c, size_t n, size_t given, size_t u, size_t tile
   return TNML_OK;
 }
 
+// The host front that tnml_sample and tnml_sample_masked (below) share: the refusals that read the same in both, each in the place
+// it has in the call's own order (`what` names the call), and what both upload alike.
+static int smp_check_sizes(const char *what, const double *phi, const double *w, int n, int K) {
+  if (!phi || !w) return fail(TNML_ERR_ARG, "%s: %s is NULL", what, phi ? "w" : "phi");
+  if (n < 1) return fail(TNML_ERR_ARG, "%s: n = %d < 1", what, n);
+  if (K < 2 || K > kSmpMaxK) return fail(TNML_ERR_ARG, "%s: K = %d outside [2, %d]", what, K, kSmpMaxK);
+  return TNML_OK;
+}
+
+static int smp_check_grid(const char *what, int K, int D, const double *phi, const double *w) {
+  for (int k = 0; k < K; ++k) {
+    if (!(w[k] > 0.0) || !std::isfinite(w[k])) return fail(TNML_ERR_ARG, "%s: weight %d is %g (weights are positive and finite)", what, k, w[k]);
+    for (int d = 0; d < D; ++d)
+      if (!std::isfinite(phi[(size_t)k * D + d])) return fail(TNML_ERR_ARG, "%s: phi[%d][%d] is not finite", what, k, d);
+  }
+  return TNML_OK;
+}
+
+static int smp_check_classes(const char *what, const int32_t *classes, int n, int L) {
+  if (classes)
+    for (int s = 0; s < n; ++s)
+      if (classes[s] < -1 || classes[s] >= L) return fail(TNML_ERR_ARG, "%s: class %d of sample %d outside [-1, %d)", what, (int)classes[s], s, L);
+  return TNML_OK;
+}
+
+static int smp_check_uniforms(const char *what, const double *u, int n, int N) {
+  if (u)
+    for (size_t e = 0; e < (size_t)n * (N + 1); ++e)
+      if (!(u[e] >= 0.0 && u[e] < 1.0)) return fail(TNML_ERR_ARG, "%s: u[%zu][%zu] = %g outside [0, 1)", what, e / (N + 1), e % (N + 1), u[e]);
+  return TNML_OK;
+}
+
+static int smp_check_state(const tnml_ctx *c, const char *what) {
+  if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
+  if (c->comm) return fail(TNML_ERR_STATE, "%s runs on one GPU: this context has a communicator attached", what);
+  return TNML_OK;
+}
+
+// the first N entries of a call's host tables: the bond to the right of every site, 1 behind the last
+static void smp_bond_table(const tnml_ctx *c, std::vector<int> &host) {
+  for (int i = 0; i < c->N - 1; ++i) host[i] = c->bond[i];
+  host[c->N - 1] = 1;
+}
+
+// the grid's metric S = sum_k w_k phi_k phi_k^T, in this order
+static void smp_grid_metric(std::vector<double> &S, int K, int D, const double *phi, const double *w) {
+  S.assign((size_t)D * D, 0.0);
+  for (int k = 0; k < K; ++k)
+    for (int d = 0; d < D; ++d)
+      for (int e = 0; e < D; ++e) S[(size_t)d * D + e] += w[k] * phi[(size_t)k * D + d] * phi[(size_t)k * D + e];
+}
+
+// S (from g.hostd), phi, w and the initial status words into the group g of the call (c->smp or c->smk), in this order
+template <class Group>
+static int smp_upload_grid(tnml_ctx *c, Group &g, int K, const double *phi, const double *w) {
+  static const int init_status[2] = {0, INT_MAX};
+  const size_t D = (size_t)c->D;
+  HIP_TRY(hipMemcpyAsync(g.S, g.hostd.data(), D * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(g.phi, phi, (size_t)K * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(g.w, w, (size_t)K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(g.status, init_status, sizeof init_status, hipMemcpyHostToDevice, c->stream));
+  return TNML_OK;
+}
+
 extern "C" int tnml_sample(tnml_ctx *c, int n, int K, const double *phi, const double *w, const int32_t *classes, const int32_t *given,
                            int n_given, const double *u, uint64_t seed, int32_t *levels_out, int32_t *labels_out, double *logp_out) {
+  const char *what = "tnml_sample";
   if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
   if (!levels_out || !labels_out || !logp_out) return fail(TNML_ERR_ARG, "tnml_sample: an output is NULL");
-  if (!phi || !w) return fail(TNML_ERR_ARG, "tnml_sample: %s is NULL", phi ? "w" : "phi");
-  if (n < 1) return fail(TNML_ERR_ARG, "tnml_sample: n = %d < 1", n);
-  if (K < 2 || K > kSmpMaxK) return fail(TNML_ERR_ARG, "tnml_sample: K = %d outside [2, %d]", K, kSmpMaxK);
+  int rc = smp_check_sizes(what, phi, w, n, K);
+  if (rc) return rc;
   const int N = c->N, D = c->D, L = c->L;
   if (n_given < 0 || n_given > N) return fail(TNML_ERR_ARG, "tnml_sample: n_given = %d outside [0, %d]", n_given, N);
   if (n_given > 0 && !given) return fail(TNML_ERR_ARG, "tnml_sample: given is NULL with n_given = %d", n_given);
-  for (int k = 0; k < K; ++k) {
-    if (!(w[k] > 0.0) || !std::isfinite(w[k])) return fail(TNML_ERR_ARG, "tnml_sample: weight %d is %g (weights are positive and finite)", k, w[k]);
-    for (int d = 0; d < D; ++d)
-      if (!std::isfinite(phi[(size_t)k * D + d])) return fail(TNML_ERR_ARG, "tnml_sample: phi[%d][%d] is not finite", k, d);
-  }
-  if (classes)
-    for (int s = 0; s < n; ++s)
-      if (classes[s] < -1 || classes[s] >= L) return fail(TNML_ERR_ARG, "tnml_sample: class %d of sample %d outside [-1, %d)", (int)classes[s], s, L);
+  if ((rc = smp_check_grid(what, K, D, phi, w)) || (rc = smp_check_classes(what, classes, n, L))) return rc;
   for (size_t e = 0; e < (size_t)n * n_given; ++e)
     if (given[e] < 0 || given[e] >= K)
       return fail(TNML_ERR_ARG, "tnml_sample: given level %d of sample %zu, site %zu outside [0, %d)", (int)given[e], e / n_given, e % n_given, K);
-  if (u)
-    for (size_t e = 0; e < (size_t)n * (N + 1); ++e)
-      if (!(u[e] >= 0.0 && u[e] < 1.0)) return fail(TNML_ERR_ARG, "tnml_sample: u[%zu][%zu] = %g outside [0, 1)", e / (N + 1), e % (N + 1), u[e]);
-  if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
-  if (c->comm) return fail(TNML_ERR_STATE, "tnml_sample runs on one GPU: this context has a communicator attached");
-  int mb = 1;
-  for (int i = 0; i < N - 1; ++i) mb = std::max(mb, c->bond[i]);
+  if ((rc = smp_check_uniforms(what, u, n, N)) || (rc = smp_check_state(c, what))) return rc;
+  const int mb = largest_bond(c);
   const size_t lds = std::max(sample_env_lds_bytes(mb, D), sample_walk_lds_bytes(mb, D, L, K));
   if (lds > kLdsMax || mb > kSmpMaxBond)
     return fail(TNML_ERR_SHAPE, "tnml_sample at bond %d, D = %d, L = %d, K = %d: the core, the environment and the tile of %d samples take %zu bytes of LDS "
@@ -2293,8 +2345,7 @@ extern "C" int tnml_sample(tnml_ctx *c, int n, int K, const double *phi, const d
   // host tables: bond [N] | slot_class [n_slots] | tile_slot [n_tiles] | tile_samples [n_tiles][16] | classes [n]
   const size_t o_slot = (size_t)N, o_tslot = o_slot + n_slots, o_tsmp = o_tslot + n_tiles, o_cls = o_tsmp + (size_t)n_tiles * kSmpTile;
   g.host.assign(o_cls + n, -1);
-  for (int i = 0; i < N - 1; ++i) g.host[i] = c->bond[i];
-  g.host[N - 1] = 1;
+  smp_bond_table(c, g.host);
   {
     std::vector<int> next((size_t)L + 1, 0);
     int t = 0;
@@ -2312,25 +2363,17 @@ extern "C" int tnml_sample(tnml_ctx *c, int n, int K, const double *phi, const d
       g.host[o_cls + s] = q - 1;
     }
   }
-  // the grid's metric S = sum_k w_k phi_k phi_k^T, in this order
-  g.hostd.assign((size_t)D * D, 0.0);
-  for (int k = 0; k < K; ++k)
-    for (int d = 0; d < D; ++d)
-      for (int e = 0; e < D; ++e) g.hostd[(size_t)d * D + e] += w[k] * phi[(size_t)k * D + d] * phi[(size_t)k * D + e];
+  smp_grid_metric(g.hostd, K, D, phi, w);
   HIP_TRY(hipSetDevice(c->device));
-  int rc = smp_ensure(c, (size_t)n, (size_t)n * n_given, u ? (size_t)n * (N + 1) : 0, (size_t)n_tiles, (size_t)n_slots,
+  rc = smp_ensure(c, (size_t)n, (size_t)n * n_given, u ? (size_t)n * (N + 1) : 0, (size_t)n_tiles, (size_t)n_slots,
                       (size_t)n_slots * (c->l_pos + 1), mb);
   if (rc) return rc;
-  const int init_status[2] = {0, INT_MAX};
   HIP_TRY(hipMemcpyAsync(g.bond, g.host.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(g.slot_class, g.host.data() + o_slot, (size_t)n_slots * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(g.tile_slot, g.host.data() + o_tslot, (size_t)n_tiles * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(g.tile_samples, g.host.data() + o_tsmp, (size_t)n_tiles * kSmpTile * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(g.classes, g.host.data() + o_cls, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(g.S, g.hostd.data(), (size_t)D * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(g.phi, phi, (size_t)K * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(g.w, w, (size_t)K * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(g.status, init_status, sizeof init_status, hipMemcpyHostToDevice, c->stream));
+  if ((rc = smp_upload_grid(c, g, K, phi, w))) return rc;
   if (n_given) HIP_TRY(hipMemcpyAsync(g.given, given, (size_t)n * n_given * sizeof(int), hipMemcpyHostToDevice, c->stream));
   if (u) HIP_TRY(hipMemcpyAsync(g.u, u, (size_t)n * (N + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
   SampleParams p{};
@@ -2387,6 +2430,140 @@ static int smk_ensure(tnml_ctx *c, size_t tiles, size_t rows, size_t n, size_t m
       own_dev(g.logp0, n_cap), own_dev(g.status, 2)});
   if (rc) return rc;
   g.tiles_cap = tiles_cap; g.rows_cap = rows_cap; g.n_cap = n_cap; g.mask_cap = mask_cap; g.u_cap = u_cap; g.stack_cap = stack_cap;
+  return TNML_OK;
+}
+
+extern "C" int tnml_set_sample_stack_bytes(tnml_ctx *c, size_t bytes) {
+  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
+  if (bytes < 1) return fail(TNML_ERR_ARG, "tnml_set_sample_stack_bytes: a budget of 0 bytes holds no tile");
+  c->smk.stack_bytes = bytes;
+  return TNML_OK;
+}
+
+extern "C" int tnml_sample_masked(tnml_ctx *c, int n, int K, const double *phi, const double *w, const int32_t *classes, const uint8_t *mask,
+                                  int mask_rows, const int32_t *known, const double *u, uint64_t seed, int draw, int32_t *levels_out,
+                                  int32_t *labels_out, double *logp_out, double *class_logw_out) {
+  const char *what = "tnml_sample_masked";
+  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
+  if (!logp_out) return fail(TNML_ERR_ARG, "tnml_sample_masked: logp_out is NULL");
+  if (draw && (!levels_out || !labels_out)) return fail(TNML_ERR_ARG, "tnml_sample_masked: draw with a NULL %s", levels_out ? "labels_out" : "levels_out");
+  int rc = smp_check_sizes(what, phi, w, n, K);
+  if (rc) return rc;
+  const int N = c->N, D = c->D, L = c->L;
+  if (mask_rows != 1 && mask_rows != n) return fail(TNML_ERR_ARG, "tnml_sample_masked: mask_rows = %d, neither 1 nor n = %d", mask_rows, n);
+  if (!mask) return fail(TNML_ERR_ARG, "tnml_sample_masked: mask is NULL");
+  if ((rc = smp_check_grid(what, K, D, phi, w)) || (rc = smp_check_classes(what, classes, n, L))) return rc;
+  for (int s = 0; s < n; ++s) {
+    const uint8_t *ms = mask + (size_t)(mask_rows == 1 ? 0 : s) * N;
+    for (int i = 0; i < N; ++i) {
+      if (!ms[i]) continue;
+      if (!known) return fail(TNML_ERR_ARG, "tnml_sample_masked: known is NULL and the mask of sample %d has site %d set", s, i);
+      const int32_t k = known[(size_t)s * N + i];
+      if (k < 0 || k >= K) return fail(TNML_ERR_ARG, "tnml_sample_masked: known level %d of sample %d, site %d outside [0, %d)", (int)k, s, i, K);
+    }
+  }
+  if ((rc = smp_check_uniforms(what, u, n, N)) || (rc = smp_check_state(c, what))) return rc;
+  const int mb = largest_bond(c);
+  const int T = mb > kSmpMaxBond ? 0 : sample_masked_tile(mb, D, L, K);
+  if (T < 1)
+    return fail(TNML_ERR_SHAPE, "tnml_sample_masked at bond %d, D = %d, L = %d, K = %d: the core, the environment and the products of one sample take "
+                "%zu bytes of LDS (160 KB and bonds up to %d fit)", mb, D, L, K,
+                std::max(sample_masked_env_lds_bytes(mb, D, 1), sample_masked_walk_lds_bytes(mb, D, L, K, 1)), kSmpMaxBond);
+  const size_t m2 = (size_t)mb * mb, tile_stack = (size_t)T * (N + 1) * m2;
+  auto &g = c->smk;
+  if (g.stack_bytes / sizeof(double) < tile_stack)
+    return fail(TNML_ERR_ARG, "tnml_sample_masked: one tile of %d samples needs a stack of %zu bytes, the budget of tnml_set_sample_stack_bytes is %zu",
+                T, tile_stack * sizeof(double), g.stack_bytes);
+  // rows of a class slot: its normaliser (the empty mask), then its samples; slots in the order -1, 0 .. L-1 of those the call
+  // uses (all of them for class_logw_out); tiles of T rows of one slot each, padded with empty masks
+  std::vector<int> count((size_t)L + 1, 0), first_tile((size_t)L + 1, -1), next((size_t)L + 1, 0);
+  for (int s = 0; s < n; ++s) count[(classes ? classes[s] : -1) + 1]++;
+  int n_tiles = 0;
+  for (int q = 0; q <= L; ++q)
+    if (count[q] || class_logw_out) { first_tile[q] = n_tiles; next[q] = n_tiles * T + 1; n_tiles += (count[q] + 1 + T - 1) / T; }
+  const size_t rows = (size_t)n_tiles * T;
+  // host tables: bond [N] | tile_class [n_tiles] | tile_rows [rows] | row of sample [n]
+  const size_t o_tcls = (size_t)N, o_rows = o_tcls + n_tiles, o_rof = o_rows + rows;
+  g.host.assign(o_rof + n, -1);
+  smp_bond_table(c, g.host);
+  for (int q = 0; q <= L; ++q)
+    if (first_tile[q] >= 0)
+      for (int t = first_tile[q]; t < first_tile[q] + (count[q] + T) / T; ++t) g.host[o_tcls + t] = q - 1;
+  for (int s = 0; s < n; ++s) {
+    const int q = (classes ? classes[s] : -1) + 1;
+    g.host[o_rof + s] = next[q];
+    g.host[o_rows + next[q]++] = s;
+  }
+  smp_grid_metric(g.hostd, K, D, phi, w);
+  const size_t chunk_tiles = std::min((size_t)n_tiles, g.stack_bytes / sizeof(double) / tile_stack);
+  HIP_TRY(hipSetDevice(c->device));
+  rc = smk_ensure(c, (size_t)n_tiles, rows, (size_t)n, (size_t)mask_rows, u ? (size_t)n * (N + 1) : 0, chunk_tiles * tile_stack);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(g.bond, g.host.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(g.tile_class, g.host.data() + o_tcls, (size_t)n_tiles * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(g.tile_rows, g.host.data() + o_rows, rows * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(g.mask, mask, (size_t)mask_rows * N, hipMemcpyHostToDevice, c->stream));
+  if (known) HIP_TRY(hipMemcpyAsync(g.known, known, (size_t)n * N * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if ((rc = smp_upload_grid(c, g, K, phi, w))) return rc;
+  if (u) HIP_TRY(hipMemcpyAsync(g.u, u, (size_t)n * (N + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  SampleMaskedParams p{};
+  p.N = N; p.D = D; p.L = L; p.l_pos = c->l_pos; p.K = K; p.n = n; p.T = T; p.mask_rows = mask_rows;
+  p.bond = g.bond; p.cores = c->cores; p.lab = c->lab[c->lab_cur]; p.core_stride = c->core_stride;
+  p.S = g.S; p.phi = g.phi; p.w = g.w; p.mask = g.mask; p.known = g.known;
+  p.stack = g.stack; p.env_stride = m2;
+  p.u = u ? g.u : nullptr; p.seed = seed;
+  p.levels = g.levels; p.labels = g.labels; p.logp0 = g.logp0; p.status = g.status;
+  // chunks of whole tiles: every chunk reuses the stack, the launches of one stream follow each other
+  for (size_t t0 = 0; t0 < (size_t)n_tiles; t0 += chunk_tiles) {
+    p.n_tiles = (int)std::min(chunk_tiles, (size_t)n_tiles - t0);
+    p.tile_class = g.tile_class + t0; p.tile_rows = g.tile_rows + t0 * T; p.E = g.E + t0 * T;
+    if (!launch_sample_masked(p, mb, draw != 0, c->stream)) {
+      (void)hipStreamSynchronize(c->stream);                     // (the uploads read the caller's memory)
+      return fail(TNML_ERR_SHAPE, "tnml_sample_masked: the launch was refused (bond %d)", mb);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  int st[2] = {0, 0};
+  g.hostE.resize(rows);
+  HIP_TRY(hipMemcpyAsync(st, g.status, sizeof st, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(g.hostE.data(), g.E, rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const double *E = g.hostE.data();
+  auto norm_of = [&](int cls) { return E[(size_t)first_tile[cls + 1] * T]; };
+  bool nonfinite = (st[0] & 1) != 0;
+  for (int q = 0; q <= L; ++q)
+    if (first_tile[q] >= 0 && std::isnan(norm_of(q - 1))) nonfinite = true;
+  for (int s = 0; s < n; ++s)
+    if (std::isnan(E[g.host[o_rof + s]])) nonfinite = true;
+  if (nonfinite) return fail(TNML_ERR_NONFINITE, "tnml_sample_masked: a core element is not finite");
+  for (int s = 0; s < n; ++s) {
+    const int cls = classes ? classes[s] : -1;
+    if (std::isinf(norm_of(cls))) {
+      if (cls >= 0) return fail(TNML_ERR_ARG, "tnml_sample_masked: sample %d is conditioned on class %d, which the model gives zero weight", s, cls);
+      return fail(TNML_ERR_ARG, "tnml_sample_masked: the model is zero (sample %d, class -1)", s);
+    }
+    if (std::isinf(E[g.host[o_rof + s]]))
+      return fail(TNML_ERR_ARG, "tnml_sample_masked: the known pixels of sample %d (class %d) have zero weight", s, cls);
+  }
+  if (st[0] & 2) {
+    const int s = st[1] >= 0 && st[1] < n ? st[1] : 0;
+    return fail(TNML_ERR_ARG, "tnml_sample_masked: the densities of sample %d (class %d) sum to nothing behind its known pixels", s, classes ? classes[s] : -1);
+  }
+  if (draw) {
+    g.hostp.resize((size_t)n);
+    HIP_TRY(hipMemcpyAsync(levels_out, g.levels, (size_t)n * N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(labels_out, g.labels, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(g.hostp.data(), g.logp0, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+  }
+  for (int s = 0; s < n; ++s) {
+    const int cls = classes ? classes[s] : -1;
+    logp_out[2 * (size_t)s] = draw ? g.hostp[s] : 0.0;
+    logp_out[2 * (size_t)s + 1] = E[g.host[o_rof + s]] - norm_of(cls);
+    if (!draw && labels_out) labels_out[s] = cls;
+  }
+  if (class_logw_out)
+    for (int cl = 0; cl < L; ++cl) class_logw_out[cl] = std::isinf(norm_of(cl)) ? -INFINITY : norm_of(cl) - norm_of(-1);
   return TNML_OK;
 }
 
@@ -2649,162 +2826,6 @@ extern "C" int tnml_set_nll_overlap(tnml_ctx *c, int on) {
   if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
   if (on != 0 && on != 1) return fail(TNML_ERR_ARG, "tnml_set_nll_overlap: on %d is neither 0 nor 1", on);
   c->nst.overlap = on;
-  return TNML_OK;
-}
-
-extern "C" int tnml_set_sample_stack_bytes(tnml_ctx *c, size_t bytes) {
-  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
-  if (bytes < 1) return fail(TNML_ERR_ARG, "tnml_set_sample_stack_bytes: a budget of 0 bytes holds no tile");
-  c->smk.stack_bytes = bytes;
-  return TNML_OK;
-}
-
-extern "C" int tnml_sample_masked(tnml_ctx *c, int n, int K, const double *phi, const double *w, const int32_t *classes, const uint8_t *mask,
-                                  int mask_rows, const int32_t *known, const double *u, uint64_t seed, int draw, int32_t *levels_out,
-                                  int32_t *labels_out, double *logp_out, double *class_logw_out) {
-  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
-  if (!logp_out) return fail(TNML_ERR_ARG, "tnml_sample_masked: logp_out is NULL");
-  if (draw && (!levels_out || !labels_out)) return fail(TNML_ERR_ARG, "tnml_sample_masked: draw with a NULL %s", levels_out ? "labels_out" : "levels_out");
-  if (!phi || !w) return fail(TNML_ERR_ARG, "tnml_sample_masked: %s is NULL", phi ? "w" : "phi");
-  if (n < 1) return fail(TNML_ERR_ARG, "tnml_sample_masked: n = %d < 1", n);
-  if (K < 2 || K > kSmpMaxK) return fail(TNML_ERR_ARG, "tnml_sample_masked: K = %d outside [2, %d]", K, kSmpMaxK);
-  const int N = c->N, D = c->D, L = c->L;
-  if (mask_rows != 1 && mask_rows != n) return fail(TNML_ERR_ARG, "tnml_sample_masked: mask_rows = %d, neither 1 nor n = %d", mask_rows, n);
-  if (!mask) return fail(TNML_ERR_ARG, "tnml_sample_masked: mask is NULL");
-  for (int k = 0; k < K; ++k) {
-    if (!(w[k] > 0.0) || !std::isfinite(w[k])) return fail(TNML_ERR_ARG, "tnml_sample_masked: weight %d is %g (weights are positive and finite)", k, w[k]);
-    for (int d = 0; d < D; ++d)
-      if (!std::isfinite(phi[(size_t)k * D + d])) return fail(TNML_ERR_ARG, "tnml_sample_masked: phi[%d][%d] is not finite", k, d);
-  }
-  if (classes)
-    for (int s = 0; s < n; ++s)
-      if (classes[s] < -1 || classes[s] >= L)
-        return fail(TNML_ERR_ARG, "tnml_sample_masked: class %d of sample %d outside [-1, %d)", (int)classes[s], s, L);
-  for (int s = 0; s < n; ++s) {
-    const uint8_t *ms = mask + (size_t)(mask_rows == 1 ? 0 : s) * N;
-    for (int i = 0; i < N; ++i) {
-      if (!ms[i]) continue;
-      if (!known) return fail(TNML_ERR_ARG, "tnml_sample_masked: known is NULL and the mask of sample %d has site %d set", s, i);
-      const int32_t k = known[(size_t)s * N + i];
-      if (k < 0 || k >= K) return fail(TNML_ERR_ARG, "tnml_sample_masked: known level %d of sample %d, site %d outside [0, %d)", (int)k, s, i, K);
-    }
-  }
-  if (u)
-    for (size_t e = 0; e < (size_t)n * (N + 1); ++e)
-      if (!(u[e] >= 0.0 && u[e] < 1.0)) return fail(TNML_ERR_ARG, "tnml_sample_masked: u[%zu][%zu] = %g outside [0, 1)", e / (N + 1), e % (N + 1), u[e]);
-  if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
-  if (c->comm) return fail(TNML_ERR_STATE, "tnml_sample_masked runs on one GPU: this context has a communicator attached");
-  int mb = 1;
-  for (int i = 0; i < N - 1; ++i) mb = std::max(mb, c->bond[i]);
-  const int T = mb > kSmpMaxBond ? 0 : sample_masked_tile(mb, D, L, K);
-  if (T < 1)
-    return fail(TNML_ERR_SHAPE, "tnml_sample_masked at bond %d, D = %d, L = %d, K = %d: the core, the environment and the products of one sample take "
-                "%zu bytes of LDS (160 KB and bonds up to %d fit)", mb, D, L, K,
-                std::max(sample_masked_env_lds_bytes(mb, D, 1), sample_masked_walk_lds_bytes(mb, D, L, K, 1)), kSmpMaxBond);
-  const size_t m2 = (size_t)mb * mb, tile_stack = (size_t)T * (N + 1) * m2;
-  auto &g = c->smk;
-  if (g.stack_bytes / sizeof(double) < tile_stack)
-    return fail(TNML_ERR_ARG, "tnml_sample_masked: one tile of %d samples needs a stack of %zu bytes, the budget of tnml_set_sample_stack_bytes is %zu",
-                T, tile_stack * sizeof(double), g.stack_bytes);
-  // rows of a class slot: its normaliser (the empty mask), then its samples; slots in the order -1, 0 .. L-1 of those the call
-  // uses (all of them for class_logw_out); tiles of T rows of one slot each, padded with empty masks
-  std::vector<int> count((size_t)L + 1, 0), first_tile((size_t)L + 1, -1), next((size_t)L + 1, 0);
-  for (int s = 0; s < n; ++s) count[(classes ? classes[s] : -1) + 1]++;
-  int n_tiles = 0;
-  for (int q = 0; q <= L; ++q)
-    if (count[q] || class_logw_out) { first_tile[q] = n_tiles; next[q] = n_tiles * T + 1; n_tiles += (count[q] + 1 + T - 1) / T; }
-  const size_t rows = (size_t)n_tiles * T;
-  // host tables: bond [N] | tile_class [n_tiles] | tile_rows [rows] | row of sample [n]
-  const size_t o_tcls = (size_t)N, o_rows = o_tcls + n_tiles, o_rof = o_rows + rows;
-  g.host.assign(o_rof + n, -1);
-  for (int i = 0; i < N - 1; ++i) g.host[i] = c->bond[i];
-  g.host[N - 1] = 1;
-  for (int q = 0; q <= L; ++q)
-    if (first_tile[q] >= 0)
-      for (int t = first_tile[q]; t < first_tile[q] + (count[q] + T) / T; ++t) g.host[o_tcls + t] = q - 1;
-  for (int s = 0; s < n; ++s) {
-    const int q = (classes ? classes[s] : -1) + 1;
-    g.host[o_rof + s] = next[q];
-    g.host[o_rows + next[q]++] = s;
-  }
-  // the grid's metric S = sum_k w_k phi_k phi_k^T, in this order
-  g.hostd.assign((size_t)D * D, 0.0);
-  for (int k = 0; k < K; ++k)
-    for (int d = 0; d < D; ++d)
-      for (int e = 0; e < D; ++e) g.hostd[(size_t)d * D + e] += w[k] * phi[(size_t)k * D + d] * phi[(size_t)k * D + e];
-  const size_t chunk_tiles = std::min((size_t)n_tiles, g.stack_bytes / sizeof(double) / tile_stack);
-  HIP_TRY(hipSetDevice(c->device));
-  int rc = smk_ensure(c, (size_t)n_tiles, rows, (size_t)n, (size_t)mask_rows, u ? (size_t)n * (N + 1) : 0, chunk_tiles * tile_stack);
-  if (rc) return rc;
-  const int init_status[2] = {0, INT_MAX};
-  HIP_TRY(hipMemcpyAsync(g.bond, g.host.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(g.tile_class, g.host.data() + o_tcls, (size_t)n_tiles * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(g.tile_rows, g.host.data() + o_rows, rows * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(g.mask, mask, (size_t)mask_rows * N, hipMemcpyHostToDevice, c->stream));
-  if (known) HIP_TRY(hipMemcpyAsync(g.known, known, (size_t)n * N * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(g.S, g.hostd.data(), (size_t)D * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(g.phi, phi, (size_t)K * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(g.w, w, (size_t)K * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(g.status, init_status, sizeof init_status, hipMemcpyHostToDevice, c->stream));
-  if (u) HIP_TRY(hipMemcpyAsync(g.u, u, (size_t)n * (N + 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  SampleMaskedParams p{};
-  p.N = N; p.D = D; p.L = L; p.l_pos = c->l_pos; p.K = K; p.n = n; p.T = T; p.mask_rows = mask_rows;
-  p.bond = g.bond; p.cores = c->cores; p.lab = c->lab[c->lab_cur]; p.core_stride = c->core_stride;
-  p.S = g.S; p.phi = g.phi; p.w = g.w; p.mask = g.mask; p.known = g.known;
-  p.stack = g.stack; p.env_stride = m2;
-  p.u = u ? g.u : nullptr; p.seed = seed;
-  p.levels = g.levels; p.labels = g.labels; p.logp0 = g.logp0; p.status = g.status;
-  // chunks of whole tiles: every chunk reuses the stack, the launches of one stream follow each other
-  for (size_t t0 = 0; t0 < (size_t)n_tiles; t0 += chunk_tiles) {
-    p.n_tiles = (int)std::min(chunk_tiles, (size_t)n_tiles - t0);
-    p.tile_class = g.tile_class + t0; p.tile_rows = g.tile_rows + t0 * T; p.E = g.E + t0 * T;
-    if (!launch_sample_masked(p, mb, draw != 0, c->stream)) {
-      (void)hipStreamSynchronize(c->stream);                     // (the uploads read the caller's memory)
-      return fail(TNML_ERR_SHAPE, "tnml_sample_masked: the launch was refused (bond %d)", mb);
-    }
-  }
-  HIP_TRY(hipGetLastError());
-  int st[2] = {0, 0};
-  g.hostE.resize(rows);
-  HIP_TRY(hipMemcpyAsync(st, g.status, sizeof st, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(g.hostE.data(), g.E, rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  const double *E = g.hostE.data();
-  auto norm_of = [&](int cls) { return E[(size_t)first_tile[cls + 1] * T]; };
-  bool nonfinite = (st[0] & 1) != 0;
-  for (int q = 0; q <= L; ++q)
-    if (first_tile[q] >= 0 && std::isnan(norm_of(q - 1))) nonfinite = true;
-  for (int s = 0; s < n; ++s)
-    if (std::isnan(E[g.host[o_rof + s]])) nonfinite = true;
-  if (nonfinite) return fail(TNML_ERR_NONFINITE, "tnml_sample_masked: a core element is not finite");
-  for (int s = 0; s < n; ++s) {
-    const int cls = classes ? classes[s] : -1;
-    if (std::isinf(norm_of(cls))) {
-      if (cls >= 0) return fail(TNML_ERR_ARG, "tnml_sample_masked: sample %d is conditioned on class %d, which the model gives zero weight", s, cls);
-      return fail(TNML_ERR_ARG, "tnml_sample_masked: the model is zero (sample %d, class -1)", s);
-    }
-    if (std::isinf(E[g.host[o_rof + s]]))
-      return fail(TNML_ERR_ARG, "tnml_sample_masked: the known pixels of sample %d (class %d) have zero weight", s, cls);
-  }
-  if (st[0] & 2) {
-    const int s = st[1] >= 0 && st[1] < n ? st[1] : 0;
-    return fail(TNML_ERR_ARG, "tnml_sample_masked: the densities of sample %d (class %d) sum to nothing behind its known pixels", s, classes ? classes[s] : -1);
-  }
-  if (draw) {
-    g.hostp.resize((size_t)n);
-    HIP_TRY(hipMemcpyAsync(levels_out, g.levels, (size_t)n * N * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(labels_out, g.labels, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(g.hostp.data(), g.logp0, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  }
-  for (int s = 0; s < n; ++s) {
-    const int cls = classes ? classes[s] : -1;
-    logp_out[2 * (size_t)s] = draw ? g.hostp[s] : 0.0;
-    logp_out[2 * (size_t)s + 1] = E[g.host[o_rof + s]] - norm_of(cls);
-    if (!draw && labels_out) labels_out[s] = cls;
-  }
-  if (class_logw_out)
-    for (int cl = 0; cl < L; ++cl) class_logw_out[cl] = std::isinf(norm_of(cl)) ? -INFINITY : norm_of(cl) - norm_of(-1);
   return TNML_OK;
 }
 
