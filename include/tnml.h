@@ -571,6 +571,33 @@ int tnml_sample_masked(tnml_ctx *ctx, int n, int K, const double *phi, const dou
 /* bytes of the environment stack a chunk of tnml_sample_masked may take (0: TNML_ERR_ARG) */
 int tnml_set_sample_stack_bytes(tnml_ctx *ctx, size_t bytes);
 
+/* ---- per-pixel conditionals ------------------------------------------- */
+/* What the model believes about every single pixel given the pixels it was shown.  n, K, phi, w, classes, mask, mask_rows and known
+ * are tnml_sample_masked's, and so are the per-sample environments R_{s,i} from the right.  A second walk carries the matching
+ * environment from the left, Lf_{s,0} = 1,
+ *   Lf_{s,i+1}[c,c'] = sum_{a,a',d,d'} Lf_{s,i}[a,a'] S_{s,i}[d,d'] A_i[a,d,c] A_i[a',d',c']
+ * (label slices as on the right, an exact power of two per site whose exponent is discarded), and meets R_{s,i+1} at every site in
+ * the one-site matrix that leaves out the site's own metric:
+ *   Q_{s,i}[d,d'] = sum_{a,a',c,c'} Lf_{s,i}[a,a'] A_i[a,d,c] R_{s,i+1}[c,c'] A_i[a',d',c']
+ *   p_{s,i}(k)    = max(0, w_k phi_k^T Q_{s,i} phi_k) / tr(S Q_{s,i})
+ * = p(x_i = k | the known pixels other than i [, class]): the posterior marginal of a free site, the leave-one-out conditional of a
+ * known one, by one code path.
+ * values [K] or NULL: the number each level stands for in the mean and the variance (NULL: the level index).
+ * q_out [n][N][D][D]: Q / tr(S Q).  stats_out [n][N][4]: the mean sum_k p(k) values[k]; the variance sum_k p(k) (values[k] - mean)^2;
+ * the entropy -sum_k p(k) log p(k) (a zero density adds nothing); log p(k_s[i]) on a known site and 0 on a free one.
+ * mode_out [n][N]: the first k of largest density.  logp_out [n]: log p(known levels [| class]), column 1 of tnml_sample_masked with
+ * draw = 0, bit for bit.  Each output may be NULL, not all of them.
+ * Chunks, the stack budget and the class-slot tiles are tnml_sample_masked's; the tile is the largest of 16, 8, 4, 2, 1 at which both
+ * kernels of this call fit 160 KB of LDS, and no result depends on it, on the chunking or on the other samples.  Every sum runs in a
+ * fixed order.  Nothing else on the device changes, and no forward is needed afterwards.
+ * Refused before anything is launched: the list of tnml_sample_masked (without its output and uniform rules), and TNML_ERR_ARG when
+ * every output is NULL or a value is not finite; TNML_ERR_SHAPE for a bond above 64 (TNML_SITE_COND_MAX_BOND), or LDS: the message
+ * names the bytes.  After the run: the errors of tnml_sample_masked. */
+#define TNML_SITE_COND_MAX_BOND 64
+int tnml_site_conditionals(tnml_ctx *ctx, int n, int K, const double *phi, const double *w, const double *values,
+                           const int32_t *classes, const uint8_t *mask, int mask_rows, const int32_t *known,
+                           double *q_out, double *stats_out, int32_t *mode_out, double *logp_out);
+
 /* ---- the gradient of the log-norm ------------------------------------ */
 /* grad_flat receives Gz_i = d log|<W|W>_S| / d A_i for every core, in the layout of tnml_get_cores (capacity in floats, at least
  * tnml_cores_size; floats behind the gradient are left alone), and sign_log2 [2] = {sign of <W|W>_S, log|<W|W>_S|}, the pair

@@ -971,6 +971,44 @@ class Network():
         log_post = lp - (top + np.log(np.exp(lp - top).sum(axis=1, keepdims=True)))
         return log_post.argmax(axis=1), log_post
 
+    # ------------------------------------------------------------------------------------------
+    # per-pixel conditionals: posterior means, uncertainty and surprise maps
+    # ------------------------------------------------------------------------------------------
+    def pixel_conditionals(self, X, mask=None, classes=None, levels=256, grid=None, weights=None):
+        """What the model believes about every single pixel given the pixels it was shown, exactly, in one device call ->
+        (mean, std, mode, entropy, logp_known, Q).  X (n, N) pixel values on the grid or integer levels, read where mask ((N,) or
+        (n, N) bool; None: every pixel known) is set.  Per (sample, site), each (n, N): mean, std and mode (a pixel value) of
+        p(x_i | the known pixels other than i [, class]) -- the posterior marginal of a hidden pixel, the leave-one-out conditional
+        of a known one --, its entropy, and log p(x_i = its given value | the others) on a known pixel (0 on a hidden one).
+        Q (n, N, D, D) gives the whole table through pixel_probs."""
+        x, phi, w = self._pixel_grid(levels, grid, weights)
+        n = len(X)
+        m, lev = self._masked_levels(X, np.ones(self.N, dtype=bool) if mask is None else mask, x, n)
+        ctx = self._sync_to_device(max(self._b, 1))
+        q, stats, mode, _ = ctx.site_conditionals(n, phi, w, m, lev, self._classes_of(classes, n), x, want=('q', 'stats', 'mode'))
+        return stats[..., 0], np.sqrt(np.maximum(stats[..., 1], 0.0)), x[mode], stats[..., 2], stats[..., 3], q
+
+    def expected_image(self, X, mask, classes=None, levels=256, grid=None, weights=None):
+        """Deterministic inpainting -> (image (n, N), std (n, N)): known pixels as given with std 0, hidden pixels the posterior mean
+        given the known ones [and the class] with the posterior's standard deviation."""
+        mean, std, _, _, _, _ = self.pixel_conditionals(X, mask, classes, levels, grid, weights)
+        mm = np.broadcast_to(np.asarray(mask) != 0, mean.shape)
+        x, _, _ = self._pixel_grid(levels, grid, weights)
+        X = np.asarray(X)
+        given = x[np.where(mm, X, 0)] if np.issubdtype(X.dtype, np.integer) else X.astype(np.float64)
+        return np.where(mm, given, mean), np.where(mm, 0.0, std)
+
+    def pixel_surprise(self, X, classes=None, levels=256, grid=None, weights=None):
+        """-log p(x_i | all other pixels [, class]) per pixel, (n, N): where an image is unlikely.  Its sum over the sites is the
+        negative log pseudo-likelihood."""
+        return -self.pixel_conditionals(X, None, classes, levels, grid, weights)[4]
+
+    def pixel_probs(self, Q, levels=256, grid=None, weights=None):
+        """The table p(x_i = k | ...) (.., K) from Q (.., D, D) of pixel_conditionals, on the host:
+        max(0, w_k phi_k^T Q phi_k) (Q is normalised so that the table sums to 1)"""
+        _, phi, w = self._pixel_grid(levels, grid, weights)
+        return np.maximum(0.0, w * np.einsum('kd,...de,ke->...k', phi, np.asarray(Q, dtype=np.float64), phi))
+
     def class_log_weights(self, levels=256, grid=None, weights=None):
         """log P(l) of the joint distribution, (L,): <W_l|W_l>_S / <W|W>_S by Network.inner under the grid's metric S, W_l the
         chain with every label slice but l zeroed"""

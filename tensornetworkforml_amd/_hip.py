@@ -20,6 +20,7 @@ DATASET_FORM = {'features': 0, 'pixels': 1}
 WRT = {'features': 0, 'pixels': 1}
 OPTIM = {'sgd': 0, 'adam': 1}
 DBG = {'B': 0, 'dB_raw': 1, 'B_new': 2, 'sigma': 3, 'scalars': 4, 'L2_grad': 5}
+SITE_COND_MAX_BOND = 64      # TNML_SITE_COND_MAX_BOND of include/tnml.h: the largest bond site_conditionals takes
 
 # every symbol include/tnml.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -41,7 +42,7 @@ SYMBOLS = [
     'tnml_set_chain_scaling', 'tnml_predict_scaled',
     'tnml_set_shape_kernels', 'tnml_fixed_shape_steps', 'tnml_set_persist_reduce', 'tnml_slice_reduce_steps',
     'tnml_inner', 'tnml_axpby',
-    'tnml_sample', 'tnml_sample_masked', 'tnml_set_sample_stack_bytes',
+    'tnml_sample', 'tnml_sample_masked', 'tnml_set_sample_stack_bytes', 'tnml_site_conditionals',
     'tnml_get_bonds', 'tnml_log_norm_grad', 'tnml_nll_grad', 'tnml_nll_grad_indices', 'tnml_nll_eval', 'tnml_nll_eval_indices',
     'tnml_nll_step', 'tnml_nll_train_indices', 'tnml_set_nll_overlap',
 ]
@@ -155,6 +156,7 @@ def lib():
         L.tnml_sample_masked.argtypes = [vp, C.c_int, C.c_int, f64p, f64p, i32p, C.POINTER(C.c_uint8), C.c_int, i32p, f64p, C.c_uint64, C.c_int,
                                          i32p, i32p, f64p, f64p]
         L.tnml_set_sample_stack_bytes.argtypes = [vp, C.c_size_t]
+        L.tnml_site_conditionals.argtypes = [vp, C.c_int, C.c_int, f64p, f64p, f64p, i32p, C.POINTER(C.c_uint8), C.c_int, i32p, f64p, f64p, i32p, f64p]
         L.tnml_get_bonds.argtypes = [vp, i32p, C.POINTER(C.c_int)]
         L.tnml_log_norm_grad.argtypes = [vp, f64p, C.c_int, f32p, C.c_size_t, f64p]
         L.tnml_nll_grad.argtypes = [vp, f32p, i32p, C.c_int, f64p, f32p, C.c_size_t, f64p]
@@ -411,6 +413,51 @@ class Context:
     def set_sample_stack_bytes(self, nbytes):
         """the bytes of environment stack one chunk of sample_masked may take (default 1 GiB)"""
         _chk(lib().tnml_set_sample_stack_bytes(self._h, int(nbytes)))
+
+    # ---- per-pixel conditionals (DESIGN.md section 26)
+    def site_conditionals(self, n, phi, w, mask, known, classes=None, values=None, want=('q', 'stats', 'mode', 'logp')):
+        """-> (q (n, N, D, D) float64, stats (n, N, 4) float64, mode (n, N) int32, logp (n,) float64), None for what `want` leaves out.
+        p(x_i = k | the known pixels other than i [, class]) = max(0, w_k phi_k^T q phi_k) at every site: the posterior marginal of
+        a free site, the leave-one-out conditional of a known one.  stats: mean and variance over `values` (K,) (None: the level
+        index), entropy, log p(known level) (0 on a free site); mode: the first level of largest density; logp: log p(known
+        [| class]).  mask, known, classes as sample_masked."""
+        n = int(n)
+        phi = np.ascontiguousarray(phi, dtype=np.float64)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if phi.ndim != 2 or phi.shape[1] != self.D or w.shape != (phi.shape[0],):
+            raise TnmlError(-1, 'the grid has phi %s and w %s, not (K, %d) and (K,)' % (phi.shape, w.shape, self.D))
+        if mask is None:
+            raise TnmlError(-1, 'mask is None')
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if mask.shape not in ((self.N,), (n, self.N)):
+            raise TnmlError(-1, 'mask has shape %s, neither (%d,) nor (%d, %d)' % (mask.shape, self.N, n, self.N))
+        mask_rows = 1 if mask.ndim == 1 else n
+        cp = kp = vp = None
+        if classes is not None:
+            classes = np.ascontiguousarray(classes, dtype=np.int32)
+            if classes.shape != (n,):
+                raise TnmlError(-1, 'classes has shape %s, not (%d,)' % (classes.shape, n))
+            cp = _ptr(classes, C.c_int32)
+        if known is not None:
+            known = np.ascontiguousarray(known, dtype=np.int32)
+            if known.shape != (n, self.N):
+                raise TnmlError(-1, 'known has shape %s, not (%d, %d)' % (known.shape, n, self.N))
+            kp = _ptr(known, C.c_int32)
+        if values is not None:
+            values = np.ascontiguousarray(values, dtype=np.float64)
+            if values.shape != w.shape:
+                raise TnmlError(-1, 'values has shape %s, not %s' % (values.shape, w.shape))
+            vp = _ptr(values, C.c_double)
+        m = max(n, 0)
+        q = np.empty((m, self.N, self.D, self.D), dtype=np.float64) if 'q' in want else None
+        stats = np.empty((m, self.N, 4), dtype=np.float64) if 'stats' in want else None
+        mode = np.empty((m, self.N), dtype=np.int32) if 'mode' in want else None
+        logp = np.empty(m, dtype=np.float64) if 'logp' in want else None
+        _chk(lib().tnml_site_conditionals(self._h, n, phi.shape[0], _ptr(phi, C.c_double), _ptr(w, C.c_double), vp, cp, _ptr(mask, C.c_uint8),
+                                          mask_rows, kp, None if q is None else _ptr(q, C.c_double),
+                                          None if stats is None else _ptr(stats, C.c_double), None if mode is None else _ptr(mode, C.c_int32),
+                                          None if logp is None else _ptr(logp, C.c_double)))
+        return q, stats, mode, logp
 
     # ---- batch
     def set_input(self, X, y=None):

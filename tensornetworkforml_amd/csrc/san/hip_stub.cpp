@@ -585,6 +585,10 @@ static void check_nll_cot(const NllCotParams &p, dim3 g, dim3 b) {
 // host derives for both kernels; no sample twice in a launch.  The (sample, class) pairs of the launches since the last
 // san_stub_masked_reset are kept for san_stub_masked_check: every sample of a call in exactly one tile, and that tile of its class.
 static std::vector<std::pair<int, int>> g_masked_rows[2];        // [0] environment launches, [1] walk launches
+// san_stub_site_cond_call(1): the environment launches that follow are those of tnml_site_conditionals, whose tile is site_cond_tile's;
+// the block of the last environment launch, for the site_cond_kernel launch behind it
+static int g_site_cond_call = 0;
+static SampleMaskedParams g_last_env{};
 static void check_sample_masked(const SampleMaskedParams &p, dim3 g, dim3 b, size_t shm, bool walk) {
   scan(&p, sizeof p, "SampleMaskedParams");
   if (p.N < 2 || p.D < 2 || p.D > kMaxD || p.L < 1 || p.l_pos < 0 || p.l_pos >= p.N) die("SampleMaskedParams: N %d D %d L %d l_pos %d", p.N, p.D, p.L, p.l_pos);
@@ -601,7 +605,9 @@ static void check_sample_masked(const SampleMaskedParams &p, dim3 g, dim3 b, siz
   }
   const size_t m2 = (size_t)mb * mb, rows = (size_t)p.n_tiles * p.T;
   if (p.lds_m != mb || mb > kSmpMaxBond || p.env_stride < m2) die("SampleMaskedParams: lds_m %d env_stride %zu for bond %d", p.lds_m, p.env_stride, mb);
-  if (p.T < 1 || p.T != sample_masked_tile(mb, p.D, p.L, p.K)) die("SampleMaskedParams: tiles of %d rows, %d fit at bond %d", p.T, sample_masked_tile(mb, p.D, p.L, p.K), mb);
+  const int want_T = g_site_cond_call ? site_cond_tile(mb, p.D, p.L, p.K) : sample_masked_tile(mb, p.D, p.L, p.K);
+  if (p.T < 1 || p.T != want_T) die("SampleMaskedParams: tiles of %d rows, %d fit at bond %d", p.T, want_T, mb);
+  if (!walk) g_last_env = p;
   need(p.S, (size_t)p.D * p.D * 8, "SampleMaskedParams.S");
   need(p.phi, (size_t)p.K * p.D * 8, "SampleMaskedParams.phi");
   need(p.w, (size_t)p.K * 8, "SampleMaskedParams.w");
@@ -637,6 +643,29 @@ static void check_sample_masked(const SampleMaskedParams &p, dim3 g, dim3 b, siz
         if (ms[i] && (p.known[(size_t)smp * p.N + i] < 0 || p.known[(size_t)smp * p.N + i] >= p.K)) die("SampleMaskedParams: known level of sample %d site %d", smp, i);
     }
   }
+}
+
+// per-pixel conditionals (kernels_site_cond.hip): site_cond_kernel behind the environment launch of the same chunk.  Its block m
+// is that launch's, field for field (the same tile, tables, rows and stack; lds_m filled in); the values, the left environments of
+// the launch's rows and the outputs the call asked for with their extents; grid, block and LDS.
+static void check_site_cond(const SiteCondParams &p, dim3 g, dim3 b, size_t shm) {
+  scan(&p, sizeof p, "SiteCondParams");
+  if (!g_site_cond_call) die("site_cond_kernel outside a tnml_site_conditionals call");
+  const SampleMaskedParams &m = p.m, &e = g_last_env;
+  if (m.T != e.T || m.n_tiles != e.n_tiles || m.lds_m != e.lds_m || m.n != e.n || m.tile_class != e.tile_class || m.tile_rows != e.tile_rows ||
+      m.stack != e.stack || m.env_stride != e.env_stride || m.mask != e.mask || m.known != e.known || m.mask_rows != e.mask_rows || m.bond != e.bond ||
+      m.cores != e.cores || m.lab != e.lab || m.S != e.S || m.phi != e.phi || m.w != e.w || m.status != e.status)
+    die("site_cond_kernel: its block is not the one of the environment launch before it (T %d against %d)", m.T, e.T);
+  const size_t rows = (size_t)m.n_tiles * m.T, sites = (size_t)m.n * m.N;
+  if (m.T != site_cond_tile(m.lds_m, m.D, m.L, m.K) || m.lds_m > kSccMaxBond) die("site_cond_kernel: tiles of %d rows at bond %d", m.T, m.lds_m);
+  need(p.values, (size_t)m.K * 8, "SiteCondParams.values");
+  need(p.lf_next, rows * m.env_stride * 8, "SiteCondParams.lf_next");
+  if (!p.q && !p.stats && !p.mode) die("site_cond_kernel: no output");
+  if (p.q) need(p.q, sites * m.D * m.D * 8, "SiteCondParams.q");
+  if (p.stats) need(p.stats, sites * 4 * 8, "SiteCondParams.stats");
+  if (p.mode) need(p.mode, sites * 4, "SiteCondParams.mode");
+  if (g.x != (unsigned)m.n_tiles || g.y != 1 || g.z != 1 || b.x != 512) die("site_cond_kernel: grid %u block %u for %d tiles", g.x, b.x, m.n_tiles);
+  if (shm < site_cond_lds_bytes(m.lds_m, m.D, m.K, m.T)) die("site_cond_kernel: %zu bytes of LDS for bond %d, T %d", shm, m.lds_m, m.T);
 }
 
 // gradient training (kernels_optim.hip).  loss_cot_kernel: f and cot at their own strides, the labels of the chunk, one thread per
@@ -763,6 +792,10 @@ static void tr_struct(const SampleMaskedParams &p) {
   I(N) I(D) I(L) I(l_pos) I(K) I(n) I(T) I(n_tiles) I(lds_m) I(mask_rows) P(bond) P(cores) P(lab) I(core_stride) P(S) P(phi) P(w) P(tile_class) P(tile_rows)
   P(mask) P(known) P(stack) I(env_stride) P(E) P(u) I(seed) P(levels) P(labels) P(logp0) P(status)
 }
+static void tr_struct(const SiteCondParams &p) {
+  tr_struct(p.m);
+  P(values) P(lf_next) P(q) P(stats) P(mode)
+}
 static void tr_struct(const LogNormParams &p) {
   I(N) I(D) I(L) I(l_pos) I(metric_sites) I(lds_m) I(mode) P(tab) P(cores) P(lab) I(core_stride) P(metric) P(envL) P(envR) P(expL) P(expR) I(env_stride)
   P(G) P(out) P(status)
@@ -811,6 +844,7 @@ static void tr_launch(const std::string &name, dim3 g, dim3 b, size_t shm, hipSt
     else if (is("AlgebraParams")) tr_struct(*(const AlgebraParams *)args[i]);
     else if (is("SampleParams")) tr_struct(*(const SampleParams *)args[i]);
     else if (is("SampleMaskedParams")) tr_struct(*(const SampleMaskedParams *)args[i]);
+    else if (is("SiteCondParams")) tr_struct(*(const SiteCondParams *)args[i]);
     else if (is("NllCotParams")) tr_struct(*(const NllCotParams *)args[i]);
     else if (is("LogNormParams")) tr_struct(*(const LogNormParams *)args[i]);
     else if (is("CoreView")) { const CoreView &v = *(const CoreView *)args[i]; tr(" [%s %d %d %d %d %d]", dp(v.base).c_str(), v.n_in, v.n_out, v.s_in, v.s_d, v.s_out); }
@@ -904,6 +938,8 @@ hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t s
     check_sample(*(const SampleParams *)args[0], g, b, shm, has("sample_walk_kernel"));
   } else if (has("sample_env_masked_kernel") || has("sample_walk_masked_kernel")) {
     check_sample_masked(*(const SampleMaskedParams *)args[0], g, b, shm, has("sample_walk_masked_kernel"));
+  } else if (has("site_cond_kernel")) {
+    check_site_cond(*(const SiteCondParams *)args[0], g, b, shm);
   } else if (has("lognorm_env_kernel") || has("lognorm_grad_kernel")) {
     check_lognorm(*(const LogNormParams *)args[0], g, b, shm, has("lognorm_grad_kernel"));
   } else if (has("nll_cot_kernel")) {
@@ -1150,6 +1186,8 @@ void san_stub_masked_check(int walk, int n, const int32_t *classes) {
   for (int s = 0; s < n; ++s)
     if (cls[s] != (classes ? classes[s] : -1)) die("tnml_sample_masked: sample %d of class %d is in %s", s, classes ? classes[s] : -1, cls[s] == INT_MIN ? "no tile" : "a tile of another class");
 }
+// the calls that follow are tnml_site_conditionals' (1) or the sampler's (0): which tile rule the environment launches are held to
+void san_stub_site_cond_call(int on) { g_site_cond_call = on; }
 // the records of the last persistent launch as the "device" holds them (n steps; record n is the batch side's prologue)
 const void *san_stub_last_persist(int *n_steps) { *n_steps = g_last_persist_n; return g_last_persist; }
 }

@@ -391,6 +391,15 @@ struct tnml_ctx {
     int overlap = 0;                         // tnml_set_nll_overlap: the norm walk on stream2 beside the chunks of the step
     std::vector<double> metric_host;         // host copy of the metric for the call in flight (it outlives the asynchronous upload)
   } nst;
+  // per-pixel conditionals.  One group of its own, regrown when a call needs more of any member: the values
+  // of the levels, the left environments behind the site a row of one chunk is on (lf_cap doubles), and the three outputs of n_cap
+  // samples.  The tables, the grid, the stack and E are the masked group's (smk), through smk_ensure.
+  struct {
+    double *values = nullptr, *lf_next = nullptr, *q = nullptr, *stats = nullptr;
+    int *mode = nullptr;
+    size_t n_cap = 0, lf_cap = 0;
+    std::vector<double> values_host;         // host copy of the values for the call in flight (it outlives the asynchronous upload)
+  } scc;
   // multi-GPU
   ncclComm_t comm = nullptr;
   int rank = 0, nranks = 1;
@@ -2440,40 +2449,67 @@ extern "C" int tnml_set_sample_stack_bytes(tnml_ctx *c, size_t bytes) {
   return TNML_OK;
 }
 
-extern "C" int tnml_sample_masked(tnml_ctx *c, int n, int K, const double *phi, const double *w, const int32_t *classes, const uint8_t *mask,
-                                  int mask_rows, const int32_t *known, const double *u, uint64_t seed, int draw, int32_t *levels_out,
-                                  int32_t *labels_out, double *logp_out, double *class_logw_out) {
-  const char *what = "tnml_sample_masked";
-  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
-  if (!logp_out) return fail(TNML_ERR_ARG, "tnml_sample_masked: logp_out is NULL");
-  if (draw && (!levels_out || !labels_out)) return fail(TNML_ERR_ARG, "tnml_sample_masked: draw with a NULL %s", levels_out ? "labels_out" : "levels_out");
+// The group of tnml_site_conditionals (section 26), (re)sized when a member is too small: all of it or none
+static int scc_ensure(tnml_ctx *c, size_t n, size_t lf) {
+  auto &g = c->scc;
+  if (g.lf_cap > 0 && g.n_cap >= n && g.lf_cap >= lf) return TNML_OK;
+  const size_t N = (size_t)c->N, D = (size_t)c->D;
+  const size_t n_cap = std::max(g.n_cap, n), lf_cap = std::max(g.lf_cap, lf);
+  g.n_cap = g.lf_cap = 0;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  int rc = make_group(c, "the buffers of the per-pixel conditionals", {
+      own_dev(g.values, (size_t)kSmpMaxK), own_dev(g.lf_next, lf_cap), own_dev(g.q, n_cap * N * D * D), own_dev(g.stats, n_cap * N * 4),
+      own_dev(g.mode, n_cap * N)});
+  if (rc) return rc;
+  g.n_cap = n_cap; g.lf_cap = lf_cap;
+  return TNML_OK;
+}
+
+// The front of tnml_sample_masked and of tnml_site_conditionals (section 26; sc: what that call adds, NULL for the sampler): the
+// refusals, the class-slot tiles, the chunks under the stack budget, the launches and the errors after the run.  `what` names the call.
+struct SiteCondCall {
+  const double *values;
+  double *q_out, *stats_out;
+  int32_t *mode_out;
+};
+
+static int smk_run(tnml_ctx *c, const char *what, const SiteCondCall *sc, int n, int K, const double *phi, const double *w,
+                   const int32_t *classes, const uint8_t *mask, int mask_rows, const int32_t *known, const double *u, uint64_t seed, int draw,
+                   int32_t *levels_out, int32_t *labels_out, double *logp_out, double *class_logw_out) {
   int rc = smp_check_sizes(what, phi, w, n, K);
   if (rc) return rc;
   const int N = c->N, D = c->D, L = c->L;
-  if (mask_rows != 1 && mask_rows != n) return fail(TNML_ERR_ARG, "tnml_sample_masked: mask_rows = %d, neither 1 nor n = %d", mask_rows, n);
-  if (!mask) return fail(TNML_ERR_ARG, "tnml_sample_masked: mask is NULL");
+  if (mask_rows != 1 && mask_rows != n) return fail(TNML_ERR_ARG, "%s: mask_rows = %d, neither 1 nor n = %d", what, mask_rows, n);
+  if (!mask) return fail(TNML_ERR_ARG, "%s: mask is NULL", what);
   if ((rc = smp_check_grid(what, K, D, phi, w)) || (rc = smp_check_classes(what, classes, n, L))) return rc;
   for (int s = 0; s < n; ++s) {
     const uint8_t *ms = mask + (size_t)(mask_rows == 1 ? 0 : s) * N;
     for (int i = 0; i < N; ++i) {
       if (!ms[i]) continue;
-      if (!known) return fail(TNML_ERR_ARG, "tnml_sample_masked: known is NULL and the mask of sample %d has site %d set", s, i);
+      if (!known) return fail(TNML_ERR_ARG, "%s: known is NULL and the mask of sample %d has site %d set", what, s, i);
       const int32_t k = known[(size_t)s * N + i];
-      if (k < 0 || k >= K) return fail(TNML_ERR_ARG, "tnml_sample_masked: known level %d of sample %d, site %d outside [0, %d)", (int)k, s, i, K);
+      if (k < 0 || k >= K) return fail(TNML_ERR_ARG, "%s: known level %d of sample %d, site %d outside [0, %d)", what, (int)k, s, i, K);
     }
   }
+  if (sc && sc->values)
+    for (int k = 0; k < K; ++k)
+      if (!std::isfinite(sc->values[k])) return fail(TNML_ERR_ARG, "%s: values[%d] is not finite", what, k);
   if ((rc = smp_check_uniforms(what, u, n, N)) || (rc = smp_check_state(c, what))) return rc;
   const int mb = largest_bond(c);
-  const int T = mb > kSmpMaxBond ? 0 : sample_masked_tile(mb, D, L, K);
+  const int T = sc ? site_cond_tile(mb, D, L, K) : mb > kSmpMaxBond ? 0 : sample_masked_tile(mb, D, L, K);
+  if (T < 1 && sc)
+    return fail(TNML_ERR_SHAPE, "%s at bond %d, D = %d, L = %d, K = %d: the core, both environments and the products of one sample take "
+                "%zu bytes of LDS (160 KB and bonds up to %d fit)", what, mb, D, L, K,
+                std::max(sample_masked_env_lds_bytes(mb, D, 1), site_cond_lds_bytes(mb, D, K, 1)), kSccMaxBond);
   if (T < 1)
-    return fail(TNML_ERR_SHAPE, "tnml_sample_masked at bond %d, D = %d, L = %d, K = %d: the core, the environment and the products of one sample take "
-                "%zu bytes of LDS (160 KB and bonds up to %d fit)", mb, D, L, K,
+    return fail(TNML_ERR_SHAPE, "%s at bond %d, D = %d, L = %d, K = %d: the core, the environment and the products of one sample take "
+                "%zu bytes of LDS (160 KB and bonds up to %d fit)", what, mb, D, L, K,
                 std::max(sample_masked_env_lds_bytes(mb, D, 1), sample_masked_walk_lds_bytes(mb, D, L, K, 1)), kSmpMaxBond);
   const size_t m2 = (size_t)mb * mb, tile_stack = (size_t)T * (N + 1) * m2;
   auto &g = c->smk;
   if (g.stack_bytes / sizeof(double) < tile_stack)
-    return fail(TNML_ERR_ARG, "tnml_sample_masked: one tile of %d samples needs a stack of %zu bytes, the budget of tnml_set_sample_stack_bytes is %zu",
-                T, tile_stack * sizeof(double), g.stack_bytes);
+    return fail(TNML_ERR_ARG, "%s: one tile of %d samples needs a stack of %zu bytes, the budget of tnml_set_sample_stack_bytes is %zu",
+                what, T, tile_stack * sizeof(double), g.stack_bytes);
   // rows of a class slot: its normaliser (the empty mask), then its samples; slots in the order -1, 0 .. L-1 of those the call
   // uses (all of them for class_logw_out); tiles of T rows of one slot each, padded with empty masks
   std::vector<int> count((size_t)L + 1, 0), first_tile((size_t)L + 1, -1), next((size_t)L + 1, 0);
@@ -2499,6 +2535,8 @@ extern "C" int tnml_sample_masked(tnml_ctx *c, int n, int K, const double *phi, 
   HIP_TRY(hipSetDevice(c->device));
   rc = smk_ensure(c, (size_t)n_tiles, rows, (size_t)n, (size_t)mask_rows, u ? (size_t)n * (N + 1) : 0, chunk_tiles * tile_stack);
   if (rc) return rc;
+  const bool left = sc && (sc->q_out || sc->stats_out || sc->mode_out);   // (logp_out alone: the environments only)
+  if (left && (rc = scc_ensure(c, (size_t)n, chunk_tiles * T * m2))) return rc;
   HIP_TRY(hipMemcpyAsync(g.bond, g.host.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(g.tile_class, g.host.data() + o_tcls, (size_t)n_tiles * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(g.tile_rows, g.host.data() + o_rows, rows * sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -2513,13 +2551,23 @@ extern "C" int tnml_sample_masked(tnml_ctx *c, int n, int K, const double *phi, 
   p.stack = g.stack; p.env_stride = m2;
   p.u = u ? g.u : nullptr; p.seed = seed;
   p.levels = g.levels; p.labels = g.labels; p.logp0 = g.logp0; p.status = g.status;
+  SiteCondParams sp{};
+  if (left) {
+    auto &h = c->scc;
+    h.values_host.resize((size_t)K);
+    for (int k = 0; k < K; ++k) h.values_host[k] = sc->values ? sc->values[k] : (double)k;
+    HIP_TRY(hipMemcpyAsync(h.values, h.values_host.data(), (size_t)K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    sp.values = h.values; sp.lf_next = h.lf_next;
+    sp.q = sc->q_out ? h.q : nullptr; sp.stats = sc->stats_out ? h.stats : nullptr; sp.mode = sc->mode_out ? h.mode : nullptr;
+  }
   // chunks of whole tiles: every chunk reuses the stack, the launches of one stream follow each other
   for (size_t t0 = 0; t0 < (size_t)n_tiles; t0 += chunk_tiles) {
     p.n_tiles = (int)std::min(chunk_tiles, (size_t)n_tiles - t0);
     p.tile_class = g.tile_class + t0; p.tile_rows = g.tile_rows + t0 * T; p.E = g.E + t0 * T;
-    if (!launch_sample_masked(p, mb, draw != 0, c->stream)) {
+    sp.m = p;
+    if (!(left ? launch_site_cond(sp, mb, c->stream) : launch_sample_masked(p, mb, draw != 0, c->stream))) {
       (void)hipStreamSynchronize(c->stream);                     // (the uploads read the caller's memory)
-      return fail(TNML_ERR_SHAPE, "tnml_sample_masked: the launch was refused (bond %d)", mb);
+      return fail(TNML_ERR_SHAPE, "%s: the launch was refused (bond %d)", what, mb);
     }
   }
   HIP_TRY(hipGetLastError());
@@ -2535,19 +2583,30 @@ extern "C" int tnml_sample_masked(tnml_ctx *c, int n, int K, const double *phi, 
     if (first_tile[q] >= 0 && std::isnan(norm_of(q - 1))) nonfinite = true;
   for (int s = 0; s < n; ++s)
     if (std::isnan(E[g.host[o_rof + s]])) nonfinite = true;
-  if (nonfinite) return fail(TNML_ERR_NONFINITE, "tnml_sample_masked: a core element is not finite");
+  if (nonfinite) return fail(TNML_ERR_NONFINITE, "%s: a core element is not finite", what);
   for (int s = 0; s < n; ++s) {
     const int cls = classes ? classes[s] : -1;
     if (std::isinf(norm_of(cls))) {
-      if (cls >= 0) return fail(TNML_ERR_ARG, "tnml_sample_masked: sample %d is conditioned on class %d, which the model gives zero weight", s, cls);
-      return fail(TNML_ERR_ARG, "tnml_sample_masked: the model is zero (sample %d, class -1)", s);
+      if (cls >= 0) return fail(TNML_ERR_ARG, "%s: sample %d is conditioned on class %d, which the model gives zero weight", what, s, cls);
+      return fail(TNML_ERR_ARG, "%s: the model is zero (sample %d, class -1)", what, s);
     }
     if (std::isinf(E[g.host[o_rof + s]]))
-      return fail(TNML_ERR_ARG, "tnml_sample_masked: the known pixels of sample %d (class %d) have zero weight", s, cls);
+      return fail(TNML_ERR_ARG, "%s: the known pixels of sample %d (class %d) have zero weight", what, s, cls);
   }
   if (st[0] & 2) {
     const int s = st[1] >= 0 && st[1] < n ? st[1] : 0;
-    return fail(TNML_ERR_ARG, "tnml_sample_masked: the densities of sample %d (class %d) sum to nothing behind its known pixels", s, classes ? classes[s] : -1);
+    return fail(TNML_ERR_ARG, "%s: the densities of sample %d (class %d) sum to nothing behind its known pixels", what, s, classes ? classes[s] : -1);
+  }
+  if (sc) {
+    auto &h = c->scc;
+    const size_t sites = (size_t)n * N;
+    if (sc->q_out) HIP_TRY(hipMemcpyAsync(sc->q_out, h.q, sites * D * D * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (sc->stats_out) HIP_TRY(hipMemcpyAsync(sc->stats_out, h.stats, sites * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (sc->mode_out) HIP_TRY(hipMemcpyAsync(sc->mode_out, h.mode, sites * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (left) HIP_TRY(hipStreamSynchronize(c->stream));
+    if (logp_out)
+      for (int s = 0; s < n; ++s) logp_out[s] = E[g.host[o_rof + s]] - norm_of(classes ? classes[s] : -1);
+    return TNML_OK;
   }
   if (draw) {
     g.hostp.resize((size_t)n);
@@ -2565,6 +2624,28 @@ extern "C" int tnml_sample_masked(tnml_ctx *c, int n, int K, const double *phi, 
   if (class_logw_out)
     for (int cl = 0; cl < L; ++cl) class_logw_out[cl] = std::isinf(norm_of(cl)) ? -INFINITY : norm_of(cl) - norm_of(-1);
   return TNML_OK;
+}
+
+extern "C" int tnml_sample_masked(tnml_ctx *c, int n, int K, const double *phi, const double *w, const int32_t *classes, const uint8_t *mask,
+                                  int mask_rows, const int32_t *known, const double *u, uint64_t seed, int draw, int32_t *levels_out,
+                                  int32_t *labels_out, double *logp_out, double *class_logw_out) {
+  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
+  if (!logp_out) return fail(TNML_ERR_ARG, "tnml_sample_masked: logp_out is NULL");
+  if (draw && (!levels_out || !labels_out)) return fail(TNML_ERR_ARG, "tnml_sample_masked: draw with a NULL %s", levels_out ? "labels_out" : "levels_out");
+  return smk_run(c, "tnml_sample_masked", nullptr, n, K, phi, w, classes, mask, mask_rows, known, u, seed, draw, levels_out, labels_out, logp_out,
+                 class_logw_out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// per-pixel conditionals (kernels_site_cond.hip)
+// ---------------------------------------------------------------------------------------------
+extern "C" int tnml_site_conditionals(tnml_ctx *c, int n, int K, const double *phi, const double *w, const double *values,
+                                      const int32_t *classes, const uint8_t *mask, int mask_rows, const int32_t *known, double *q_out,
+                                      double *stats_out, int32_t *mode_out, double *logp_out) {
+  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
+  if (!q_out && !stats_out && !mode_out && !logp_out) return fail(TNML_ERR_ARG, "tnml_site_conditionals: every output is NULL");
+  const SiteCondCall sc{values, q_out, stats_out, mode_out};
+  return smk_run(c, "tnml_site_conditionals", &sc, n, K, phi, w, classes, mask, mask_rows, known, nullptr, 0, 0, nullptr, nullptr, logp_out, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------

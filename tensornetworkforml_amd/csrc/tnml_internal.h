@@ -536,6 +536,26 @@ int sample_masked_tile(int mb, int D, int L, int K);
 // the environment launch and (walk) the walk launch of one chunk; mb: largest bond.  false: refused (geometry / LDS)
 bool launch_sample_masked(const SampleMaskedParams &p, int mb, bool walk, hipStream_t st);
 
+// Per-pixel conditionals (kernels_site_cond.hip): the environment launch above with the tile of this call, then
+// site_cond_kernel on the same tiles, rows and stack.  The left environment is formed kSccRows rows at a time, so that its two
+// products with the core are never whole in LDS together; that number is part of every result (it fixes the order of the sums).
+constexpr int kSccMaxBond = TNML_SITE_COND_MAX_BOND;   // the one bond limit of tnml_site_conditionals
+constexpr int kSccRows = 16;
+struct SiteCondParams {
+  SampleMaskedParams m;    // the block of the environment launch: tables, grid, stack, E, status (u, levels, labels, logp0 unused)
+  const double *values;    // [K] the number each level stands for
+  double *lf_next;         // [n_tiles T][env_stride] the left environment behind the site a row is on, before its power of two
+  double *q;               // [n][N][D][D]  Q / tr(S Q)
+  double *stats;           // [n][N][4]     mean, variance, entropy, log p(known level) (0 on a free site)
+  int *mode;               // [n][N]
+};
+size_t site_cond_lds_bytes(int mb, int D, int K, int T);
+// the largest T of 16, 8, 4, 2, 1 at which the environment kernel and site_cond_kernel both fit 160 KB of LDS (and which
+// sample_masked_tile allows, whose launch function is used); 0: none does
+int site_cond_tile(int mb, int D, int L, int K);
+// the environment launch and site_cond_kernel of one chunk; mb: largest bond.  false: refused (geometry / LDS)
+bool launch_site_cond(const SiteCondParams &p, int mb, hipStream_t st);
+
 // The gradient of the log-norm (kernels_nll.hip): one parameter block for the environment kernel (two
 // workgroups, one per direction) and the gradient kernel (grid (N, L)).  L_i 2^expL[i] and R_i 2^expR[i] are the environments.
 constexpr int kLnzMaxBond = 64;

@@ -102,9 +102,46 @@ def print_occluded(net, pixels, labels, fraction, seed, chunk=1024):
     return acc_m, acc_z
 
 
+def write_inpainted_mean(net, path, pixels, n, which, seed):
+    """The first n test images rounded to 8 bits, one half kept (`which`), every hidden pixel the model's posterior mean given the
+    kept ones (Network.expected_image) -> (n, h, w).  Prints the mean absolute error on the hidden pixels beside that of one drawn
+    completion (Network.sample with the same mask), and the mean posterior standard deviation there."""
+    lev = _levels8(pixels)[:n]
+    n = len(lev)
+    side = int(round(np.sqrt(net.N)))
+    if side * side != net.N:
+        raise SystemExit('--inpaint-mean needs a square image, the network has N = %d sites' % net.N)
+    mask = known_half(which, side)
+    img, std = net.expected_image(lev, mask)
+    drawn, _, _, _ = net.sample(n, given=lev, mask=mask, seed=seed)
+    np.save(path, img.reshape(n, side, side))
+    truth = lev[:, ~mask] / 255.0
+    print('\tPosterior mean of %d images, %s known: mean absolute error on the hidden pixels %.4f, of one drawn completion %.4f, '
+          'mean posterior std %.4f' % (n, which, float(np.abs(img[:, ~mask] - truth).mean()), float(np.abs(drawn[:, ~mask] - truth).mean()),
+                                       float(std[:, ~mask].mean())))
+    print('\tPosterior means written to', path, (n, side, side))
+    return img, std
+
+
+def write_surprise(net, path, pixels, n):
+    """-log p(x_i | all other pixels) of every pixel of the first n test images rounded to 8 bits (Network.pixel_surprise) -> (n, h, w)
+    where N is a square.  Prints the mean negative log pseudo-likelihood per image."""
+    lev = _levels8(pixels)[:n]
+    sur = net.pixel_surprise(lev)
+    side = int(round(np.sqrt(net.N)))
+    np.save(path, sur.reshape(len(lev), side, side) if side * side == net.N else sur)
+    print('\tSurprise maps of %d images: mean -log pseudo-likelihood %.4f (%.4f per pixel)' % (len(lev), float(sur.sum(1).mean()), float(sur.mean())))
+    print('\tSurprise maps written to', path, sur.shape)
+    return sur
+
+
 def run_masked_arguments(net, args, pixels, labels):
     if args.inpaint:
         write_inpainted(net, args.inpaint, pixels, labels, args.sample_n, args.inpaint_known, args.seed)
+    if args.inpaint_mean:
+        write_inpainted_mean(net, args.inpaint_mean, pixels, args.sample_n, args.inpaint_known, args.seed)
+    if args.surprise:
+        write_surprise(net, args.surprise, pixels, args.sample_n)
     if args.occluded is not None:
         print_occluded(net, pixels, labels, args.occluded, args.seed)
 
@@ -119,7 +156,12 @@ def add_sample_arguments(ap):
     ap.add_argument('--inpaint', metavar='OUT.npy', default=None,
                     help='keep one half of the first --sample-n test images (8-bit pixels) and let the model draw the rest and the label')
     ap.add_argument('--inpaint-known', dest='inpaint_known', choices=['top', 'bottom', 'left', 'right', 'checker'], default='top',
-                    help='the pixels --inpaint keeps')
+                    help='the pixels --inpaint and --inpaint-mean keep')
+    ap.add_argument('--inpaint-mean', dest='inpaint_mean', metavar='OUT.npy', default=None,
+                    help="keep one half of the first --sample-n test images and fill the rest with the model's posterior mean per pixel "
+                         '(Network.expected_image); prints its error on the hidden pixels beside that of one drawn completion')
+    ap.add_argument('--surprise', metavar='OUT.npy', default=None,
+                    help='write -log p(x_i | all other pixels) per pixel of the first --sample-n test images (Network.pixel_surprise)')
     ap.add_argument('--occluded', metavar='FRACTION', type=float, default=None,
                     help='hide a seeded random FRACTION of every test image and print the accuracy of Network.classify_masked next to '
                          'that of the classifier on the same images with the hidden pixels set to 0')
