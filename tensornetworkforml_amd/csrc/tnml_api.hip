@@ -532,6 +532,10 @@ extern "C" int tnml_create(tnml_ctx **out, int N, int D, int L, int Mmax, int b_
   HIP_TRY(hipMemset(c->pipe.cnt, 0, 32 * sizeof(unsigned)));
   HIP_TRY(hipMemsetAsync(c->status, 0, 2 * sizeof(int), c->stream));
   HIP_TRY(hipMemsetAsync(c->counters, 0, kCounterSlots * sizeof(unsigned long long), c->stream));
+  // both label buffers start zeroed: a sweep step writes the elements of its label core alone into the buffer it switches to, and
+  // tnml_get_core_slots hands out the whole buffer -- the padding must not be what the allocation happened to hold
+  HIP_TRY(hipMemsetAsync(c->lab[0], 0, c->lab_elems * sizeof(float), c->stream));
+  HIP_TRY(hipMemsetAsync(c->lab[1], 0, c->lab_elems * sizeof(float), c->stream));
   rc = size_batch_group(c.get(), b_capacity);
   if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(c->stream));
