@@ -415,6 +415,17 @@ struct tnml_ctx {
 // no step may start from a pre-gradient left earlier (cores, batch, labels or the launch form changed)
 static void drop_pregradients(tnml_ctx *c) { c->pipe.Z.valid = false; c->bigpipe.Z.valid = false; }
 
+// The resident batch changed (tnml_set_input, tnml_select_batch, tnml_select_indices, a regrown batch group): what was computed from
+// its samples is gone -- the environment stacks, f, the updated merged tensor of a previous step, the pre-gradients.  The norm
+// environments (Ln_valid / Rn_valid) are contractions of the cores alone and stay, as does the optimiser binding.  tnml_set_labels
+// drops the pre-gradients only: the stacks and f do not see the labels.
+static void batch_changed(tnml_ctx *c) {
+  c->envs_valid_L = c->envs_valid_R = false;
+  c->f_current = false;
+  c->Bnew_valid = false;
+  drop_pregradients(c);
+}
+
 // ---------------------------------------------------------------------------------------------
 extern "C" const char *tnml_last_error(void) { return g_err.c_str(); }
 extern "C" const char *tnml_version(void) { return "tnml-hip 0.1 (gfx950)"; }
@@ -438,9 +449,7 @@ static int size_batch_group(tnml_ctx *c, int b_cap) {
   const int b_pad = (b_cap + 63) / 64 * 64, ntiles = b_pad / kTS;
   c->b = c->b_cap = c->b_pad = c->nblk_cap = 0;
   c->have_input = c->have_labels = false;
-  c->envs_valid_L = c->envs_valid_R = false;
-  c->f_current = c->Bnew_valid = false;
-  drop_pregradients(c);
+  batch_changed(c);
   c->own.release(c->bigpipe.Pk);
   // batch-side workgroups of the pipelined step: at most kPipeMaxWide (from the device's CU count), each looping over pipe_tpw sample tiles
   const int kPipeMaxWide = std::max(16, c->num_cus - 16);      // + update workgroup and its helpers: all resident, one per CU
@@ -619,6 +628,28 @@ static size_t core_elems(const tnml_ctx *c, const std::vector<int> &bond, int i,
   return (size_t)ml * c->D * mr * (i == l_pos ? c->L : 1);
 }
 
+// The model changed (tnml_set_cores, tnml_scale_cores, a training step, a committed orthogonalisation / compression / sum): nothing
+// computed from the cores is current any more.  The ONE place that says which state hangs on the cores:
+//   envs_valid_L/R, f_current   the environment stacks and f of the resident batch are products of the old cores
+//   Ln_valid / Rn_valid         the norm environments of the L2 term are contractions of the old cores
+//   Bnew_valid                  the updated merged tensor of a previous step belongs to the old chain: no mid-sweep continuation
+//   the pre-gradient tickets    a pre-gradient a step left for its successor was formed with the old cores' environments
+// What does NOT hang on the cores stays: the resident batch and its labels, the staged batches, the dataset, every capacity group.
+static void cores_changed(tnml_ctx *c) {
+  c->envs_valid_L = c->envs_valid_R = false;
+  c->Ln_valid = c->Rn_valid = false;
+  c->f_current = false;
+  c->Bnew_valid = false;
+  drop_pregradients(c);
+}
+
+// vel / m / v describe the cores element by element: a commit that changes the gauge, the bonds or the meaning of an element leaves
+// them unbound (tnml_gd_step / tnml_nll_step refuse until tnml_optim_reset).  tnml_set_cores and a sweep need no call: the binding is
+// the pair (bonds, l_pos), which the step compares.
+static void unbind_optimiser(tnml_ctx *c) {
+  if (c->opt_s0) c->opt.l_pos = -1;
+}
+
 extern "C" int tnml_set_cores(tnml_ctx *c, const float *flat, size_t n_floats, const int32_t *bond, int l_pos) {
   if (!c || !flat || !bond) return fail(TNML_ERR_ARG, "NULL argument");
   if (l_pos < 0 || l_pos >= c->N) return fail(TNML_ERR_ARG, "l_pos %d out of range", l_pos);
@@ -656,11 +687,7 @@ extern "C" int tnml_set_cores(tnml_ctx *c, const float *flat, size_t n_floats, c
   c->bond = nb;
   c->l_pos = l_pos;
   c->cores_set = true;
-  c->envs_valid_L = c->envs_valid_R = false;
-  c->Ln_valid = c->Rn_valid = false;
-  c->f_current = false;
-  c->Bnew_valid = false;
-  drop_pregradients(c);
+  cores_changed(c);
   return TNML_OK;
 }
 
@@ -716,15 +743,6 @@ extern "C" int tnml_get_core_slots(tnml_ctx *c, float *slots, size_t slots_capac
   return TNML_OK;
 }
 
-// every core changed in place (same bonds, same l_pos): nothing computed from the cores is current any more
-static void cores_changed(tnml_ctx *c) {
-  c->envs_valid_L = c->envs_valid_R = false;
-  c->Ln_valid = c->Rn_valid = false;
-  c->f_current = false;
-  c->Bnew_valid = false;
-  drop_pregradients(c);
-}
-
 extern "C" int tnml_scale_cores(tnml_ctx *c, double factor) {
   if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
   if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
@@ -765,10 +783,7 @@ extern "C" int tnml_set_input(tnml_ctx *c, const float *X, const int32_t *y, int
   HIP_TRY(hipStreamSynchronize(c->stream));   // X / y host buffers may be released by the caller
   c->have_input = true;
   c->have_labels = (y != nullptr);
-  c->envs_valid_L = c->envs_valid_R = false;
-  c->f_current = false;
-  c->Bnew_valid = false;
-  drop_pregradients(c);
+  batch_changed(c);
   return TNML_OK;
 }
 
@@ -815,10 +830,7 @@ extern "C" int tnml_select_batch(tnml_ctx *c, int slot) {
   HIP_TRY(hipMemcpyAsync(c->y, c->stageY[slot], (size_t)b * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
   c->have_input = true;
   c->have_labels = true;
-  c->envs_valid_L = c->envs_valid_R = false;
-  c->f_current = false;
-  c->Bnew_valid = false;
-  drop_pregradients(c);
+  batch_changed(c);
   return TNML_OK;
 }
 
@@ -1331,10 +1343,7 @@ extern "C" int tnml_select_indices(tnml_ctx *c, const int32_t *idx, int b) {
   if (rc) return rc;
   c->have_input = true;
   c->have_labels = true;
-  c->envs_valid_L = c->envs_valid_R = false;
-  c->f_current = false;
-  c->Bnew_valid = false;
-  drop_pregradients(c);
+  batch_changed(c);
   return TNML_OK;
 }
 
@@ -2043,12 +2052,8 @@ static int orth_impl(tnml_ctx *c, int mode, int m_max, double threshold, double 
   HIP_TRY(hipMemcpyAsync(c->lab[c->lab_cur], c->orth.out_lab, c->lab_elems * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
   c->bond = nb;
   for (int i = 0; i < N - 1; ++i) bond_out[i] = nb[i];
-  c->envs_valid_L = c->envs_valid_R = false;
-  c->Ln_valid = c->Rn_valid = false;
-  c->f_current = false;
-  c->Bnew_valid = false;
-  drop_pregradients(c);
-  if (c->opt_s0) c->opt.l_pos = -1;                            // vel / m / v refer to the old gauge: unbound until tnml_optim_reset
+  cores_changed(c);
+  unbind_optimiser(c);                                          // vel / m / v refer to the old gauge
   return TNML_OK;
 }
 
@@ -2230,7 +2235,7 @@ extern "C" int tnml_axpby(tnml_ctx *c, double alpha, double beta, const float *o
   c->bond = nb;
   for (int i = 0; i < N - 1; ++i) bond_out[i] = nb[i];
   cores_changed(c);
-  if (c->opt_s0) c->opt.l_pos = -1;                            // vel / m / v refer to the old cores: unbound until tnml_optim_reset
+  unbind_optimiser(c);                                          // vel / m / v refer to the old cores
   return TNML_OK;
 }
 
