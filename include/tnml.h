@@ -598,6 +598,37 @@ int tnml_site_conditionals(tnml_ctx *ctx, int n, int K, const double *phi, const
                            const int32_t *classes, const uint8_t *mask, int mask_rows, const int32_t *known,
                            double *q_out, double *stats_out, int32_t *mode_out, double *logp_out);
 
+/* ---- pixel-pair marginals --------------------------------------------- */
+/* The joint marginal of every pair of pixels, exactly and without sampling.  K, phi, w and values are tnml_site_conditionals';
+ * S = sum_k w_k phi_k phi_k^T.  class_slot -1: the label is summed; q >= 0: slice q of the label site alone, and everything is
+ * conditional on that class.  With L_i, R_i the metric environments of tnml_log_norm_grad for S (and the class slot):
+ *   B_j[e,e'][a,a']      = sum_{c,c'} A_j[a,e,c] R_{j+1}[c,c'] A_j[a',e',c']
+ *   q1_j[e,e']           = sum_{a,a'} L_j[a,a'] B_j[e,e'][a,a'] / tr(S q1_j)
+ *   C_i,i+1[d,d'][c,c']  = sum_{a,a'} L_i[a,a'] A_i[a,d,c] A_i[a',d',c']
+ *   C_i,j+1[d,d'][c,c']  = sum S[e,e'] A_j[a,e,c] C_i,j[d,d'][a,a'] A_j[a',e',c']             (j > i)
+ *   Q_ij[d,d'][e,e']     = sum_{a,a'} C_i,j[d,d'][a,a'] B_j[e,e'][a,a'],   q_ij = Q_ij / sum S[d,d'] S[e,e'] Q_ij[d,d'][e,e']
+ *   p_ij(k,k')           = max(0, w_k w_k' sum phi_k[d] phi_k[d'] q_ij[d,d'][e,e'] phi_k'[e] phi_k'[e'])
+ * = p(x_i = k, x_j = k' [| class]).  Every C matrix is multiplied by an exact power of two after every site; the exponents of the
+ * D^2 matrices of a row are brought together before q_ij is normalised and none survives.
+ * rows [n_rows]: distinct sites.  Row r covers the pairs (rows[r], j), j > rows[r]; entries with j <= rows[r] are written as 0.
+ * q1_out [N][D][D].  stats1_out [N][3]: mean, variance and entropy of p_i(k) = max(0, w_k phi_k^T q1_i phi_k) over values.
+ * q_out [n_rows][N][D^2][D^2]: q_ij, indexed [(d,d')][(e,e')].  stats_out [n_rows][N][3]: with p_i, p_j the marginals summed from
+ * the clamped table p_ij and their means and variances over values, the covariance sum p_ij(k,k') values[k] values[k'] -
+ * mean_i mean_j; the correlation, covariance over the two standard deviations, 0 where a variance is 0; the mutual information
+ * sum p_ij log(p_ij / (p_i p_j)) in nats, formed as sum p_ij log p_ij - sum p_i log p_i - sum p_j log p_j (a zero density adds
+ * nothing).  Each output may be NULL, not all of them; with n_rows = 0 only the per-site part runs.
+ * Rows run in ascending site order in chunks whose buffers stay within tnml_set_sample_stack_bytes; a row's result depends neither
+ * on the other rows nor on the chunking.  Every sum runs in a fixed order: two calls are bit-equal.  Nothing else on the device
+ * changes, and no forward is needed afterwards.
+ * Refused before anything is launched: TNML_ERR_ARG (a NULL ctx, phi or w; K outside [2, 256]; a weight not positive and finite; a
+ * grid point or a value not finite; class_slot outside [-1, L); n_rows < 0; rows NULL with n_rows > 0; a row outside [0, N) or
+ * repeated; every output NULL, or only pair outputs with n_rows = 0; a budget below one row's need); TNML_ERR_STATE (cores never
+ * set; a communicator attached); TNML_ERR_SHAPE for a bond above 64 (TNML_PAIR_MAX_BOND), or LDS: the message names the bytes.
+ * After the run: TNML_ERR_NONFINITE for a non-finite environment, Z == 0, or a marginal whose normaliser is zero or not finite. */
+#define TNML_PAIR_MAX_BOND 64
+int tnml_pair_marginals(tnml_ctx *ctx, int K, const double *phi, const double *w, const double *values, int class_slot,
+                        const int32_t *rows, int n_rows, double *q1_out, double *stats1_out, double *q_out, double *stats_out);
+
 /* ---- the gradient of the log-norm ------------------------------------ */
 /* grad_flat receives Gz_i = d log|<W|W>_S| / d A_i for every core, in the layout of tnml_get_cores (capacity in floats, at least
  * tnml_cores_size; floats behind the gradient are left alone), and sign_log2 [2] = {sign of <W|W>_S, log|<W|W>_S|}, the pair

@@ -1009,6 +1009,78 @@ class Network():
         _, phi, w = self._pixel_grid(levels, grid, weights)
         return np.maximum(0.0, w * np.einsum('kd,...de,ke->...k', phi, np.asarray(Q, dtype=np.float64), phi))
 
+    # ------------------------------------------------------------------------------------------
+    # pixel-pair marginals: mutual information and covariance maps
+    # ------------------------------------------------------------------------------------------
+    def _class_slot(self, classes):
+        if classes is None:
+            return -1
+        c = int(classes)
+        if not -1 <= c < self.L:
+            raise ValueError('class %d outside [-1, %d)' % (c, self.L))
+        return c
+
+    def _pair_call(self, rows, classes, levels, grid, weights, want):
+        x, phi, w = self._pixel_grid(levels, grid, weights)
+        rows = np.arange(self.N, dtype=np.int32) if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+        ctx = self._sync_to_device(max(self._b, 1))
+        return rows, ctx.pair_marginals(phi, w, rows, self._class_slot(classes), x, want=want)
+
+    def pixel_pair_marginals(self, rows=None, classes=None, levels=256, grid=None, weights=None):
+        """The joint marginal of pairs of pixels, exactly, in one device call -> (q (R, N, D, D, D, D), q1 (N, D, D)).  rows: the
+        sites i of the pairs (i, j), j > i (None: all sites); q[r, j] is zero for j <= rows[r].  classes None: the label summed; an
+        int: given that class.  pair_probs gives the table p(x_i, x_j) of q, pixel_probs the table p(x_j) of q1."""
+        rows, (q1, _, q, _) = self._pair_call(rows, classes, levels, grid, weights, ('q1', 'q'))
+        D = self.D
+        return q.reshape(len(rows), self.N, D, D, D, D), q1
+
+    def pair_probs(self, q, levels=256, grid=None, weights=None):
+        """The table p(x_i = k, x_j = k') (.., K, K) from q (.., D, D, D, D) of pixel_pair_marginals, on the host:
+        max(0, w_k w_k' sum phi_k[d] phi_k[d'] q[d,d',e,e'] phi_k'[e] phi_k'[e']) (q is normalised so that the table sums to 1)"""
+        _, phi, w = self._pixel_grid(levels, grid, weights)
+        q = np.asarray(q, dtype=np.float64)
+        G = np.einsum('kd,kx,...dxeg->...keg', phi, phi, q)
+        return np.maximum(0.0, (w[:, None] * w[None, :]) * np.einsum('...keg,je,jg->...kj', G, phi, phi))
+
+    @staticmethod
+    def _symmetric(upper, diagonal):
+        """the (N, N) map of its part above the diagonal (rows i, columns j > i) and its diagonal"""
+        out = np.triu(upper, 1)
+        out = out + out.T
+        out[np.diag_indices_from(out)] = diagonal
+        return out
+
+    def mutual_information(self, classes=None, levels=256, grid=None, weights=None):
+        """I(x_i; x_j) in nats for every pair of pixels, (N, N), symmetric; the diagonal is the entropy of p(x_i).  classes None:
+        the label summed; an int: given that class.  How far correlations reach along the chain, and whether the pixel order puts
+        strongly coupled pixels close together.  Formed as a difference of entropies: entries below about 1e-14 nats are rounding
+        noise and may be slightly negative.  One device call over all rows, the same one as pixel_correlations: a caller who wants
+        both maps takes them from one Context.pair_marginals call (stats[..., 0], [..., 1], [..., 2])."""
+        _, (_, stats1, _, stats) = self._pair_call(None, classes, levels, grid, weights, ('stats1', 'stats'))
+        return self._symmetric(stats[..., 2], stats1[:, 2])
+
+    def pixel_correlations(self, classes=None, levels=256, grid=None, weights=None):
+        """-> (cov (N, N), corr (N, N), mean (N,), std (N,)) of the pixel values under the model; both maps symmetric, the diagonals
+        the variance and 1.  One device call over all rows (see mutual_information)."""
+        _, (_, stats1, _, stats) = self._pair_call(None, classes, levels, grid, weights, ('stats1', 'stats'))
+        return (self._symmetric(stats[..., 0], stats1[:, 1]), self._symmetric(stats[..., 1], 1.0), stats1[:, 0].copy(),
+                np.sqrt(np.maximum(stats1[:, 1], 0.0)))
+
+    def pixel_label_information(self, levels=256, grid=None, weights=None):
+        """I(x_i; l) = sum_c P(c) KL(p(x_i | c) || p(x_i)) in nats, (N,): which pixels carry the class, without data.  L + 1
+        per-site device calls (no pair rows) and class_log_weights."""
+        none = np.zeros(0, dtype=np.int32)
+        p = self.pixel_probs(self._pair_call(none, None, levels, grid, weights, ('q1',))[1][0], levels, grid, weights)
+        pc = np.exp(self.class_log_weights(levels, grid, weights))
+        out = np.zeros(self.N)
+        for c in range(self.L):
+            if not pc[c] > 0.0:
+                continue
+            pk = self.pixel_probs(self._pair_call(none, c, levels, grid, weights, ('q1',))[1][0], levels, grid, weights)
+            with np.errstate(divide='ignore', invalid='ignore'):
+                out += pc[c] * np.where((pk > 0.0) & (p > 0.0), pk * np.log(pk / p), 0.0).sum(-1)      # (p = 0 < pk: rounding at a node)
+        return out
+
     def class_log_weights(self, levels=256, grid=None, weights=None):
         """log P(l) of the joint distribution, (L,): <W_l|W_l>_S / <W|W>_S by Network.inner under the grid's metric S, W_l the
         chain with every label slice but l zeroed"""

@@ -21,6 +21,7 @@ WRT = {'features': 0, 'pixels': 1}
 OPTIM = {'sgd': 0, 'adam': 1}
 DBG = {'B': 0, 'dB_raw': 1, 'B_new': 2, 'sigma': 3, 'scalars': 4, 'L2_grad': 5}
 SITE_COND_MAX_BOND = 64      # TNML_SITE_COND_MAX_BOND of include/tnml.h: the largest bond site_conditionals takes
+PAIR_MAX_BOND = 64           # TNML_PAIR_MAX_BOND of include/tnml.h: the largest bond pair_marginals takes
 
 # every symbol include/tnml.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -42,7 +43,7 @@ SYMBOLS = [
     'tnml_set_chain_scaling', 'tnml_predict_scaled',
     'tnml_set_shape_kernels', 'tnml_fixed_shape_steps', 'tnml_set_persist_reduce', 'tnml_slice_reduce_steps',
     'tnml_inner', 'tnml_axpby',
-    'tnml_sample', 'tnml_sample_masked', 'tnml_set_sample_stack_bytes', 'tnml_site_conditionals',
+    'tnml_sample', 'tnml_sample_masked', 'tnml_set_sample_stack_bytes', 'tnml_site_conditionals', 'tnml_pair_marginals',
     'tnml_get_bonds', 'tnml_log_norm_grad', 'tnml_nll_grad', 'tnml_nll_grad_indices', 'tnml_nll_eval', 'tnml_nll_eval_indices',
     'tnml_nll_step', 'tnml_nll_train_indices', 'tnml_set_nll_overlap',
 ]
@@ -157,6 +158,7 @@ def lib():
                                          i32p, i32p, f64p, f64p]
         L.tnml_set_sample_stack_bytes.argtypes = [vp, C.c_size_t]
         L.tnml_site_conditionals.argtypes = [vp, C.c_int, C.c_int, f64p, f64p, f64p, i32p, C.POINTER(C.c_uint8), C.c_int, i32p, f64p, f64p, i32p, f64p]
+        L.tnml_pair_marginals.argtypes = [vp, C.c_int, f64p, f64p, f64p, C.c_int, i32p, C.c_int, f64p, f64p, f64p, f64p]
         L.tnml_get_bonds.argtypes = [vp, i32p, C.POINTER(C.c_int)]
         L.tnml_log_norm_grad.argtypes = [vp, f64p, C.c_int, f32p, C.c_size_t, f64p]
         L.tnml_nll_grad.argtypes = [vp, f32p, i32p, C.c_int, f64p, f32p, C.c_size_t, f64p]
@@ -458,6 +460,36 @@ class Context:
                                           None if stats is None else _ptr(stats, C.c_double), None if mode is None else _ptr(mode, C.c_int32),
                                           None if logp is None else _ptr(logp, C.c_double)))
         return q, stats, mode, logp
+
+    # ---- pixel-pair marginals
+    def pair_marginals(self, phi, w, rows=None, class_slot=-1, values=None, want=('q1', 'stats1', 'q', 'stats')):
+        """-> (q1 (N, D, D), stats1 (N, 3), q (R, N, D*D, D*D), stats (R, N, 3)) float64, None for what `want` leaves out.
+        p(x_i = k, x_j = k' [| class]) = max(0, w_k w_k' sum phi_k[d] phi_k[d'] q[r, j, (d,d'), (e,e')] phi_k'[e] phi_k'[e']) for
+        i = rows[r] < j, zeros for j <= i.  stats1: mean, variance, entropy of p_i over `values` (K,) (None: the level index);
+        stats: covariance, correlation, mutual information in nats.  rows: distinct sites (None or empty: the per-site part
+        alone); class_slot -1: the label summed, q >= 0: given class q."""
+        phi = np.ascontiguousarray(phi, dtype=np.float64)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if phi.ndim != 2 or phi.shape[1] != self.D or w.shape != (phi.shape[0],):
+            raise TnmlError(-1, 'the grid has phi %s and w %s, not (K, %d) and (K,)' % (phi.shape, w.shape, self.D))
+        rows = np.zeros(0, dtype=np.int32) if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+        if rows.ndim != 1:
+            raise TnmlError(-1, 'rows has shape %s, not (R,)' % (rows.shape,))
+        vp = None
+        if values is not None:
+            values = np.ascontiguousarray(values, dtype=np.float64)
+            if values.shape != w.shape:
+                raise TnmlError(-1, 'values has shape %s, not %s' % (values.shape, w.shape))
+            vp = _ptr(values, C.c_double)
+        R, DD = rows.shape[0], self.D * self.D
+        q1 = np.empty((self.N, self.D, self.D), dtype=np.float64) if 'q1' in want else None
+        stats1 = np.empty((self.N, 3), dtype=np.float64) if 'stats1' in want else None
+        q = np.empty((R, self.N, DD, DD), dtype=np.float64) if 'q' in want else None
+        stats = np.empty((R, self.N, 3), dtype=np.float64) if 'stats' in want else None
+        opt = lambda a: None if a is None else _ptr(a, C.c_double)
+        _chk(lib().tnml_pair_marginals(self._h, phi.shape[0], _ptr(phi, C.c_double), _ptr(w, C.c_double), vp, int(class_slot),
+                                       _ptr(rows, C.c_int32) if R else None, R, opt(q1), opt(stats1), opt(q), opt(stats)))
+        return q1, stats1, q, stats
 
     # ---- batch
     def set_input(self, X, y=None):

@@ -4,7 +4,7 @@
 // kernels is a launch boundary.
 //   lognorm_env_kernel   two workgroups.  Workgroup 0 walks L_1 .. L_{N-1}, L_{i+1}[c][c'] = sum S[d][d'] A_i[a][d][c] L_i[a][a'] A_i[a'][d'][c'],
 //                        L_0 = 1; workgroup 1 walks R_{N-1} .. R_0, R_i[a][a'] = sum S[d][d'] A_i[a][d][c] R_{i+1}[c][c'] A_i[a'][d'][c'], R_N = 1;
-//                        the label is summed on the label site.  Every matrix is multiplied by an exact 2^-k, k = ilogb(max|.|) + 1,
+//                        the label is summed on the label site (class_plus1 0) or slice class_plus1 - 1 alone is taken.  Every matrix is multiplied by an exact 2^-k, k = ilogb(max|.|) + 1,
 //                        and stored with the RUNNING exponent of its side: L_i 2^eL_i and R_i 2^eR_i are the true environments, and
 //                        <W|W>_S = R_0 2^eR_0.  Per site and label slice, with E the environment the walk comes from:
 //                          1  T = A . E (right walk, rows (a, d)) or E^T . A (left walk, columns (d, c)) on the f64 matrix cores, the
@@ -28,6 +28,7 @@
 // written by the gradient launch alone, bit 4 a gradient element beyond float32.  The gradient kernel returns at once where
 // status[0] is set: it reads nothing that a workgroup of its own launch writes.
 #include "small_gemm_device.h"
+#include "lognorm_device.h"
 
 #include <cmath>
 
@@ -36,7 +37,6 @@ namespace tnml {
 constexpr int kLnzEnvThreads = 1024;
 constexpr int kLnzEnvWaves = kLnzEnvThreads / 64;
 constexpr int kLnzGradThreads = 512;
-constexpr double kLnzDblMax = 1.7976931348623157e308;
 
 size_t lognorm_env_lds_bytes(int mb, int D) {
   const size_t m = (size_t)mb;
@@ -45,32 +45,6 @@ size_t lognorm_env_lds_bytes(int mb, int D) {
 size_t lognorm_grad_lds_bytes(int mb, int D) {
   const size_t m = (size_t)mb;
   return (2 * m * m + m * D * m) * sizeof(double);
-}
-
-__device__ inline int lnz_ml(const LogNormParams &p, int i) { return i == 0 ? 1 : p.tab[i - 1]; }
-__device__ inline int lnz_mr(const LogNormParams &p, int i) { return i == p.N - 1 ? 1 : p.tab[i]; }
-__device__ inline const double *lnz_metric(const LogNormParams &p, int i) {
-  return p.metric_sites == 0 ? nullptr : p.metric + (p.metric_sites == 1 ? 0 : (size_t)i * p.D * p.D);
-}
-
-// T[a][d][c] <- sum_d' S[d][d'] T[a][d'][c] in place: the thread of (a, c) owns its D elements
-__device__ inline void lnz_fold_metric(double *T, const double *S, int ml, int mr, int D, int nthreads) {
-  for (int e = threadIdx.x; e < ml * mr; e += nthreads) {
-    const int a = e / mr, c = e % mr;
-    double *t = T + (size_t)a * D * mr + c;
-    double in[kMaxD];
-#pragma unroll
-    for (int d = 0; d < kMaxD; ++d) in[d] = d < D ? t[(size_t)d * mr] : 0.0;
-#pragma unroll
-    for (int d = 0; d < kMaxD; ++d)
-      if (d < D) {
-        double v = 0.0;
-#pragma unroll
-        for (int dd = 0; dd < kMaxD; ++dd)
-          if (dd < D) v = fma(S[d * D + dd], in[dd], v);
-        t[(size_t)d * mr] = v;
-      }
-  }
 }
 
 __device__ double lnz_block_max(double x, double *red) {
@@ -108,7 +82,8 @@ __global__ __launch_bounds__(kLnzEnvThreads) void lognorm_env_kernel(LogNormPara
     const float *A = lab ? p.lab : p.cores + (size_t)i * p.core_stride;
     const double *S = lnz_metric(p, i);
     for (int e = tid; e < nout * nout; e += kLnzEnvThreads) En[e] = 0.0;     // (product 3 is behind two barriers)
-    for (int lp = 0; lp < Lx; ++lp) {
+    const int l0 = lab && p.class_plus1 > 0 ? p.class_plus1 - 1 : 0, l1 = lab && p.class_plus1 > 0 ? l0 + 1 : Lx;   // (a class: its slice alone)
+    for (int lp = l0; lp < l1; ++lp) {
       const float *Al = A + lp;
       if (right)   // T[(a, d)][c'] = sum_c A[a][d][c] E[c][c']
         mm_lds(1, ml * D, mr, mr, Al, 0, mr * Lx, Lx, E, 0, mr, 1, [&](int, int r, int j, double v) { T[r * mr + j] = v; });
@@ -282,7 +257,8 @@ bool launch_nll_sum(const double *terms, const int *bad, int n, double *acc, hip
 
 static bool lnz_geometry(const LogNormParams &p) {
   return p.N >= 2 && p.D >= 2 && p.D <= kMaxD && p.L >= 1 && p.l_pos >= 0 && p.l_pos < p.N &&
-         (p.metric_sites == 0 || p.metric_sites == 1 || p.metric_sites == p.N) && (p.mode == 0 || p.mode == 1);
+         (p.metric_sites == 0 || p.metric_sites == 1 || p.metric_sites == p.N) && (p.mode == 0 || p.mode == 1) && p.class_plus1 >= 0 &&
+         p.class_plus1 <= p.L;
 }
 
 bool launch_lognorm_env(const LogNormParams &p, int mb, hipStream_t st) {
@@ -296,7 +272,7 @@ bool launch_lognorm_env(const LogNormParams &p, int mb, hipStream_t st) {
 }
 
 bool launch_lognorm_grad(const LogNormParams &p, int mb, hipStream_t st) {
-  if (!lnz_geometry(p) || mb < 1 || mb > kLnzMaxBond) return false;
+  if (!lnz_geometry(p) || p.class_plus1 != 0 || mb < 1 || mb > kLnzMaxBond) return false;
   const size_t m = (size_t)mb, lds = lognorm_grad_lds_bytes(mb, p.D);
   if (lds > 160 * 1024 || p.env_stride < m * m) return false;
   LogNormParams q = p;

@@ -520,8 +520,8 @@ static void check_sample(const SampleParams &p, dim3 g, dim3 b, size_t shm, bool
 // the gradient of the log-norm (kernels_nll.hip): one parameter block for the environment kernel and the gradient kernel.  The table
 // is read here as the kernels read it: every core, both environment stacks and both exponent arrays over N + 1 slots, and every
 // core's part of G at its offset in the flat layout.
-static void check_lognorm(const LogNormParams &p, dim3 g, dim3 b, size_t shm, bool grad) {
-  scan(&p, sizeof p, "LogNormParams");
+// the block's own extents -> the largest bond (grad: every core's part of G as well)
+static int lognorm_extents(const LogNormParams &p, bool grad) {
   if (p.N < 2 || p.D < 2 || p.D > kMaxD || p.L < 1 || p.l_pos < 0 || p.l_pos >= p.N) die("LogNormParams: N %d D %d L %d l_pos %d", p.N, p.D, p.L, p.l_pos);
   if (p.metric_sites != 0 && p.metric_sites != 1 && p.metric_sites != p.N) die("LogNormParams: metric_sites %d", p.metric_sites);
   if (p.mode != 0 && p.mode != 1) die("LogNormParams: mode %d", p.mode);
@@ -551,6 +551,13 @@ static void check_lognorm(const LogNormParams &p, dim3 g, dim3 b, size_t shm, bo
   need(p.expR, (size_t)(p.N + 1) * 4, "LogNormParams.expR");
   need(p.out, 2 * 8, "LogNormParams.out");
   need(p.status, 2 * 4, "LogNormParams.status");
+  if (p.class_plus1 < 0 || p.class_plus1 > p.L || (grad && p.class_plus1 != 0)) die("LogNormParams: class slot %d of %d labels", p.class_plus1 - 1, p.L);
+  return mb;
+}
+
+static void check_lognorm(const LogNormParams &p, dim3 g, dim3 b, size_t shm, bool grad) {
+  scan(&p, sizeof p, "LogNormParams");
+  const int mb = lognorm_extents(p, grad);
   if (!grad) {
     if (p.status[0] != 0 || p.status[1] != 0) die("LogNormParams: status words %d %d at launch", p.status[0], p.status[1]);
     if (g.x != 2 || g.y != 1 || g.z != 1 || b.x != 1024) die("lognorm_env_kernel: grid %u block %u", g.x, b.x);
@@ -558,6 +565,46 @@ static void check_lognorm(const LogNormParams &p, dim3 g, dim3 b, size_t shm, bo
   } else {
     if (g.x != (unsigned)p.N || g.y != (unsigned)p.L || g.z != 1 || b.x != 512) die("lognorm_grad_kernel: grid (%u, %u) block %u for N %d L %d", g.x, g.y, b.x, p.N, p.L);
     if (shm < lognorm_grad_lds_bytes(mb, p.D)) die("lognorm_grad_kernel: %zu bytes of LDS for bond %d", shm, mb);
+  }
+}
+
+// pixel-pair marginals (kernels_pair.hip): the three launches behind the environment launch of the call.  Their block e is that
+// launch's with the grid's metric; the grid, the values, B_j of every site and the per-site outputs; for the row launches the chunk's
+// sites (distinct, ascending, inside the chain) and Q, its exponents and the statistics over the chunk's rows; grid, block and LDS.
+static void check_pair(const PairParams &p, dim3 g, dim3 b, size_t shm, int which) {      // 0 close, 1 walk, 2 statistics
+  scan(&p, sizeof p, "PairParams");
+  const LogNormParams &e = p.e;
+  const int mb = lognorm_extents(e, false);
+  if (e.metric_sites != 1 || mb > kPairMaxBond) die("PairParams: metric_sites %d bond %d", e.metric_sites, mb);
+  if (p.K < 2 || p.K > kSmpMaxK) die("PairParams: K %d", p.K);
+  const size_t N = (size_t)e.N, DD = (size_t)e.D * e.D;
+  need(p.phi, (size_t)p.K * e.D * 8, "PairParams.phi");
+  need(p.w, (size_t)p.K * 8, "PairParams.w");
+  need(p.values, (size_t)p.K * 8, "PairParams.values");
+  need(p.B, N * DD * e.env_stride * 8, "PairParams.B");
+  need(p.q1, N * DD * 8, "PairParams.q1");
+  need(p.stats1, N * 3 * 8, "PairParams.stats1");
+  if (which == 0) {
+    if (g.x != (unsigned)e.N || g.y != 1 || g.z != 1 || b.x != (unsigned)kPairCloseThreads) die("pair_close_kernel: grid %u block %u for N %d", g.x, b.x, e.N);
+    if (shm < pair_close_lds_bytes(mb, e.D, p.K)) die("pair_close_kernel: %zu bytes of LDS for bond %d", shm, mb);
+    return;
+  }
+  if (p.n_rows < 1 || p.n_rows > e.N) die("PairParams: %d rows", p.n_rows);
+  const size_t R = (size_t)p.n_rows;
+  need(p.rows, R * 4, "PairParams.rows");
+  for (int r = 0; r < p.n_rows; ++r)
+    if (p.rows[r] < 0 || p.rows[r] >= e.N || (r > 0 && p.rows[r] <= p.rows[r - 1])) die("PairParams: rows[%d] = %d (N %d, ascending)", r, p.rows[r], e.N);
+  need(p.Q, R * N * DD * DD * 8, "PairParams.Q");
+  need(p.qexp, R * N * DD * 4, "PairParams.qexp");
+  need(p.stats, R * N * 3 * 8, "PairParams.stats");
+  if (which == 1) {
+    if (g.x != (unsigned)p.n_rows || g.y != (unsigned)DD || g.z != 1 || b.x != (unsigned)pair_walk_threads(mb))
+      die("pair_walk_kernel: grid (%u, %u) block %u for %d rows at D %d, bond %d", g.x, g.y, b.x, p.n_rows, e.D, mb);
+    if (shm < pair_walk_lds_bytes(mb, e.D)) die("pair_walk_kernel: %zu bytes of LDS for bond %d", shm, mb);
+  } else {
+    if (g.x != (unsigned)e.N || g.y != (unsigned)p.n_rows || g.z != 1 || b.x != (unsigned)kPairStatThreads)
+      die("pair_stats_kernel: grid (%u, %u) block %u for N %d, %d rows", g.x, g.y, b.x, e.N, p.n_rows);
+    if (shm < pair_stats_lds_bytes(e.D, p.K)) die("pair_stats_kernel: %zu bytes of LDS for D %d K %d", shm, e.D, p.K);
   }
 }
 
@@ -800,6 +847,10 @@ static void tr_struct(const LogNormParams &p) {
   I(N) I(D) I(L) I(l_pos) I(metric_sites) I(lds_m) I(mode) P(tab) P(cores) P(lab) I(core_stride) P(metric) P(envL) P(envR) P(expL) P(expR) I(env_stride)
   P(G) P(out) P(status)
 }
+static void tr_struct(const PairParams &p) {
+  tr_struct(p.e);
+  I(e.class_plus1) I(K) I(n_rows) P(phi) P(w) P(values) P(rows) P(B) P(q1) P(stats1) P(Q) P(qexp) P(stats)
+}
 static void tr_struct(const NllCotParams &p) { P(f) P(y) P(cot) P(terms) P(bad) I(L) I(b) I(b_pad) I(f_bpad) I(off) I(batch) }
 static void tr_struct(const InputGradPixels &p) { P(g) P(data) P(idx) P(out) I(b) I(N) I(D) }
 static void tr_struct(const BigExtArgs &p) { P(Eprev) P(x_km1) P(x_k) V(A) I(b_pad) P(Ecur) P(Pk) }
@@ -845,6 +896,7 @@ static void tr_launch(const std::string &name, dim3 g, dim3 b, size_t shm, hipSt
     else if (is("SampleParams")) tr_struct(*(const SampleParams *)args[i]);
     else if (is("SampleMaskedParams")) tr_struct(*(const SampleMaskedParams *)args[i]);
     else if (is("SiteCondParams")) tr_struct(*(const SiteCondParams *)args[i]);
+    else if (is("PairParams")) tr_struct(*(const PairParams *)args[i]);
     else if (is("NllCotParams")) tr_struct(*(const NllCotParams *)args[i]);
     else if (is("LogNormParams")) tr_struct(*(const LogNormParams *)args[i]);
     else if (is("CoreView")) { const CoreView &v = *(const CoreView *)args[i]; tr(" [%s %d %d %d %d %d]", dp(v.base).c_str(), v.n_in, v.n_out, v.s_in, v.s_d, v.s_out); }
@@ -940,6 +992,8 @@ hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t s
     check_sample_masked(*(const SampleMaskedParams *)args[0], g, b, shm, has("sample_walk_masked_kernel"));
   } else if (has("site_cond_kernel")) {
     check_site_cond(*(const SiteCondParams *)args[0], g, b, shm);
+  } else if (has("pair_close_kernel") || has("pair_walk_kernel") || has("pair_stats_kernel")) {
+    check_pair(*(const PairParams *)args[0], g, b, shm, has("pair_close_kernel") ? 0 : has("pair_walk_kernel") ? 1 : 2);
   } else if (has("lognorm_env_kernel") || has("lognorm_grad_kernel")) {
     check_lognorm(*(const LogNormParams *)args[0], g, b, shm, has("lognorm_grad_kernel"));
   } else if (has("nll_cot_kernel")) {

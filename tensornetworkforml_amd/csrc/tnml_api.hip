@@ -400,6 +400,18 @@ struct tnml_ctx {
     size_t n_cap = 0, lf_cap = 0;
     std::vector<double> values_host;         // host copy of the values for the call in flight (it outlives the asynchronous upload)
   } scc;
+  // pixel-pair marginals.  One group of its own, regrown when a bond or a chunk outgrows it: the table of
+  // grad_table, the grid with its metric and values, both environment stacks of the call's class slot with their exponents, B_j
+  // of every site, the per-site outputs, and for rows_cap rows of one chunk the sites, Q, its exponents and the pair statistics.
+  struct {
+    int *tab = nullptr, *expL = nullptr, *expR = nullptr, *status = nullptr, *rows = nullptr, *qexp = nullptr;
+    double *S = nullptr, *phi = nullptr, *w = nullptr, *values = nullptr, *envL = nullptr, *envR = nullptr, *out = nullptr;
+    double *B = nullptr, *q1 = nullptr, *stats1 = nullptr, *Q = nullptr, *stats = nullptr;
+    int m_cap = 0;
+    size_t rows_cap = 0;
+    std::vector<int> tab_host, rows_host, sites_host;   // host copies for the call in flight (they outlive the asynchronous uploads)
+    std::vector<double> hostd;               // S, the values, phi, w
+  } pair;
   // multi-GPU
   ncclComm_t comm = nullptr;
   int rank = 0, nranks = 1;
@@ -2780,6 +2792,136 @@ extern "C" int tnml_log_norm_grad(tnml_ctx *c, const double *S, int per_site, fl
   if ((rc = lnz_enqueue(c, c->lnz.tab_host, S, n_metric, mb, 0, c->lnz.G))) return rc;
   if ((rc = lnz_result(c, "tnml_log_norm_grad", sign_log2))) return rc;
   HIP_TRY(hipMemcpyAsync(grad_flat, c->lnz.G, total * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return TNML_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// pixel-pair marginals (kernels_pair.hip)
+// ---------------------------------------------------------------------------------------------
+// The group of the call, (re)sized when the largest bond or the rows of a chunk outgrow it: all of it or none
+static int pair_ensure(tnml_ctx *c, int mb, size_t rows) {
+  auto &g = c->pair;
+  if (g.m_cap >= mb && g.m_cap > 0 && g.rows_cap >= rows) return TNML_OK;
+  mb = std::max(mb, g.m_cap);
+  const size_t rows_cap = std::max(std::max(g.rows_cap, rows), (size_t)1);
+  const size_t N = (size_t)c->N, D = (size_t)c->D, DD = D * D, m2 = (size_t)mb * mb;
+  g.m_cap = 0;
+  g.rows_cap = 0;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  int rc = make_group(c, "the buffers of the pair marginals", {
+      own_dev(g.tab, 2 * N), own_dev(g.S, DD), own_dev(g.phi, (size_t)kSmpMaxK * D), own_dev(g.w, (size_t)kSmpMaxK),
+      own_dev(g.values, (size_t)kSmpMaxK), own_dev(g.envL, (N + 1) * m2), own_dev(g.envR, (N + 1) * m2), own_dev(g.expL, N + 1),
+      own_dev(g.expR, N + 1), own_dev(g.out, 2), own_dev(g.status, 2), own_dev(g.B, N * DD * m2), own_dev(g.q1, N * DD),
+      own_dev(g.stats1, N * 3), own_dev(g.rows, N), own_dev(g.Q, rows_cap * N * DD * DD), own_dev(g.qexp, rows_cap * N * DD),
+      own_dev(g.stats, rows_cap * N * 3)});
+  if (rc) return rc;
+  g.m_cap = mb;
+  g.rows_cap = rows_cap;
+  return TNML_OK;
+}
+
+extern "C" int tnml_pair_marginals(tnml_ctx *c, int K, const double *phi, const double *w, const double *values, int class_slot,
+                                   const int32_t *rows, int n_rows, double *q1_out, double *stats1_out, double *q_out, double *stats_out) {
+  const char *what = "tnml_pair_marginals";
+  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
+  if (n_rows < 0) return fail(TNML_ERR_ARG, "%s: n_rows = %d < 0", what, n_rows);
+  const bool pairs = n_rows > 0 && (q_out || stats_out);
+  if (!q1_out && !stats1_out && !pairs) return fail(TNML_ERR_ARG, "%s: every output is NULL%s", what, n_rows == 0 && (q_out || stats_out) ? " or has no row" : "");
+  int rc = smp_check_sizes(what, phi, w, 1, K);
+  if (rc) return rc;
+  const int N = c->N, D = c->D, L = c->L, DD = D * D;
+  if ((rc = smp_check_grid(what, K, D, phi, w))) return rc;
+  if (values)
+    for (int k = 0; k < K; ++k)
+      if (!std::isfinite(values[k])) return fail(TNML_ERR_ARG, "%s: values[%d] is not finite", what, k);
+  if (class_slot < -1 || class_slot >= L) return fail(TNML_ERR_ARG, "%s: class slot %d outside [-1, %d)", what, class_slot, L);
+  if (n_rows > 0 && !rows) return fail(TNML_ERR_ARG, "%s: rows is NULL with n_rows = %d", what, n_rows);
+  auto &g = c->pair;
+  {
+    std::vector<char> seen((size_t)N, 0);
+    for (int r = 0; r < n_rows; ++r) {
+      if (rows[r] < 0 || rows[r] >= N) return fail(TNML_ERR_ARG, "%s: rows[%d] = %d outside [0, %d)", what, r, (int)rows[r], N);
+      if (seen[rows[r]]) return fail(TNML_ERR_ARG, "%s: rows[%d] = %d is repeated", what, r, (int)rows[r]);
+      seen[rows[r]] = 1;
+    }
+  }
+  if ((rc = smp_check_state(c, what))) return rc;
+  size_t total;
+  int mb;
+  if ((rc = grad_table(c, what, g.tab_host, total, mb))) return rc;
+  const size_t lds = std::max(std::max(lognorm_env_lds_bytes(mb, D), pair_close_lds_bytes(mb, D, K)),
+                              std::max(pair_walk_lds_bytes(mb, D), pair_stats_lds_bytes(D, K)));
+  if (mb > kPairMaxBond || lds > kLdsMax)
+    return fail(TNML_ERR_SHAPE, "%s at bond %d, D = %d, K = %d: two environments and their product with a core, or the table of one pair, take %zu "
+                "bytes of LDS (160 KB and bonds up to %d fit)", what, mb, D, K, lds, kPairMaxBond);
+  // rows in ascending site order (the longest walks start first), in chunks whose Q, exponents and statistics stay under the budget
+  const size_t row_bytes = (size_t)N * ((size_t)DD * DD * sizeof(double) + (size_t)DD * sizeof(int) + 3 * sizeof(double));
+  size_t chunk = 0;
+  if (pairs) {
+    chunk = std::min((size_t)n_rows, c->smk.stack_bytes / row_bytes);
+    if (chunk < 1)
+      return fail(TNML_ERR_ARG, "%s: one row needs %zu bytes, the budget of tnml_set_sample_stack_bytes is %zu", what, row_bytes, c->smk.stack_bytes);
+    g.rows_host.resize((size_t)n_rows);                             // positions in the caller's list, by ascending site
+    for (int r = 0; r < n_rows; ++r) g.rows_host[r] = r;
+    std::sort(g.rows_host.begin(), g.rows_host.end(), [&](int x, int y) { return rows[x] < rows[y]; });
+  }
+  smp_grid_metric(g.hostd, K, D, phi, w);
+  // S | values | phi | w: the uploads below read the group's copy, never the caller's memory
+  const size_t o_val = (size_t)DD, o_phi = o_val + K, o_w = o_phi + (size_t)K * D;
+  g.hostd.resize(o_w + K);
+  for (int k = 0; k < K; ++k) g.hostd[o_val + k] = values ? values[k] : (double)k;
+  std::copy(phi, phi + (size_t)K * D, g.hostd.begin() + o_phi);
+  std::copy(w, w + K, g.hostd.begin() + o_w);
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = pair_ensure(c, mb, chunk))) return rc;
+  HIP_TRY(hipMemcpyAsync(g.tab, g.tab_host.data(), g.tab_host.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(g.status, 0, 2 * sizeof(int), c->stream));
+  HIP_TRY(hipMemcpyAsync(g.S, g.hostd.data(), (size_t)DD * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(g.values, g.hostd.data() + o_val, (size_t)K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(g.phi, g.hostd.data() + o_phi, (size_t)K * D * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(g.w, g.hostd.data() + o_w, (size_t)K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  PairParams p{};
+  LogNormParams &e = p.e;
+  e.N = N; e.D = D; e.L = L; e.l_pos = c->l_pos; e.metric_sites = 1; e.mode = 0; e.class_plus1 = class_slot + 1;
+  e.tab = g.tab; e.cores = c->cores; e.lab = c->lab[c->lab_cur]; e.core_stride = c->core_stride; e.metric = g.S;
+  e.envL = g.envL; e.envR = g.envR; e.expL = g.expL; e.expR = g.expR; e.env_stride = (size_t)g.m_cap * g.m_cap;
+  e.out = g.out; e.status = g.status;
+  p.K = K; p.phi = g.phi; p.w = g.w; p.values = g.values; p.B = g.B; p.q1 = g.q1; p.stats1 = g.stats1;
+  p.rows = g.rows; p.Q = g.Q; p.qexp = g.qexp; p.stats = g.stats;
+  auto refused = [&](const char *which) {
+    return fail(TNML_ERR_SHAPE, "%s: the %s launch was refused (bond %d)", what, which, mb);
+  };
+  if (!launch_lognorm_env(e, mb, c->stream)) return refused("environment");
+  if (!launch_pair_close(p, mb, c->stream)) return refused("per-site");
+  HIP_TRY(hipGetLastError());
+  if (pairs) {
+    std::vector<int> &sites = g.sites_host;                        // (a member: it outlives the asynchronous uploads)
+    sites.resize((size_t)n_rows);
+    for (int r = 0; r < n_rows; ++r) sites[r] = rows[g.rows_host[r]];
+    for (size_t r0 = 0; r0 < (size_t)n_rows; r0 += chunk) {
+      const size_t nr = std::min(chunk, (size_t)n_rows - r0);
+      // (the chunk before this one has been copied out and waited for)
+      HIP_TRY(hipMemcpyAsync(g.rows, sites.data() + r0, nr * sizeof(int), hipMemcpyHostToDevice, c->stream));
+      p.n_rows = (int)nr;
+      if (!launch_pair_rows(p, mb, c->stream)) return refused("row");
+      HIP_TRY(hipGetLastError());
+      for (size_t r = 0; r < nr; ++r) {
+        const size_t to = (size_t)g.rows_host[r0 + r];
+        if (q_out) HIP_TRY(hipMemcpyAsync(q_out + to * N * DD * DD, g.Q + r * N * DD * DD, (size_t)N * DD * DD * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (stats_out) HIP_TRY(hipMemcpyAsync(stats_out + to * N * 3, g.stats + r * N * 3, (size_t)N * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      }
+      HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+  }
+  int st[2] = {0, 0};
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpy(st, g.status, sizeof st, hipMemcpyDeviceToHost));      // (a blocking copy: `st` is a local)
+  if (st[0] & 1) return fail(TNML_ERR_NONFINITE, "%s: a core element or an environment is not finite", what);
+  if (st[0] & 2) return fail(TNML_ERR_NONFINITE, "%s: the model's norm Z is zero%s", what, class_slot >= 0 ? " for this class" : "");
+  if (st[1] & 1) return fail(TNML_ERR_NONFINITE, "%s: a marginal's normaliser is zero or not finite", what);
+  if (q1_out) HIP_TRY(hipMemcpyAsync(q1_out, g.q1, (size_t)N * DD * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (stats1_out) HIP_TRY(hipMemcpyAsync(stats1_out, g.stats1, (size_t)N * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return TNML_OK;
 }

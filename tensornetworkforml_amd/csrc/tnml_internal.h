@@ -564,6 +564,7 @@ struct LogNormParams {
   int metric_sites;        // 0: identity, 1: one [D][D] for all sites, N: [N][D][D]
   int lds_m;               // LDS geometry: the largest bond (the launch functions fill it)
   int mode;                // gradient kernel: 0 stores Gz, 1 replaces G[e] by G[e] - Gz[e]
+  int class_plus1;         // environment kernel: 0 the label is summed (what a zeroed block means), q + 1 slice q of the label site alone (the gradient kernel needs 0)
   const int *tab;          // the table of CoreGradParams: bonds, then every core's offset in the flat layout
   const float *cores, *lab;
   size_t core_stride;
@@ -601,5 +602,34 @@ bool launch_nll_sum(const double *terms, const int *bad, int n, double *acc, hip
 // on leaving.  *skip is set, never cleared, when any of the other bits is.
 constexpr int kNllStepBadBatch = 8, kNllStepNotApplied = 16;
 bool launch_nll_record(const double *acc, const double *out, const int *status, double *rec, int *skip, hipStream_t st);
+
+// Pixel-pair marginals (kernels_pair.hip): the environment launch above with the grid's metric and the call's
+// class slot into the group's own stacks, then pair_close_kernel (one workgroup per site), and per chunk of rows pair_walk_kernel
+// (grid (rows, D^2)) and pair_stats_kernel (grid (N, rows)).  Status word e.status[1]: bit 1 a non-finite or vanishing normaliser.
+constexpr int kPairMaxBond = kLnzMaxBond;
+constexpr int kPairCloseThreads = 1024;
+constexpr int kPairStatThreads = 256;
+struct PairParams {
+  LogNormParams e;         // the block of the environment launch: table, cores, metric (the grid's S), stacks, exponents, status
+  int K;
+  int n_rows;              // rows of this chunk
+  const double *phi, *w;   // [K][D], [K]
+  const double *values;    // [K] the number each level stands for
+  const int *rows;         // [n_rows] the sites the chunk's rows start from
+  double *B;               // [N][D^2][env_stride]: B_j[e,e'][a,a'], site j closed from the right
+  double *q1;              // [N][D][D]
+  double *stats1;          // [N][3] mean, variance, entropy
+  double *Q;               // [n_rows][N][D^2][D^2]: the walk stores Q_ij unnormalised, the statistics kernel normalises in place
+  int *qexp;               // [n_rows][N][D^2]: the running exponent of the walk (row, d, d') at site j
+  double *stats;           // [n_rows][N][3] covariance, correlation, mutual information
+};
+size_t pair_close_lds_bytes(int mb, int D, int K);
+size_t pair_walk_lds_bytes(int mb, int D);
+size_t pair_stats_lds_bytes(int D, int K);
+// threads of a walk workgroup at largest bond mb (the result does not depend on it)
+int pair_walk_threads(int mb);
+// mb: largest bond.  false: refused (geometry / LDS)
+bool launch_pair_close(const PairParams &p, int mb, hipStream_t st);
+bool launch_pair_rows(const PairParams &p, int mb, hipStream_t st);
 
 }  // namespace tnml

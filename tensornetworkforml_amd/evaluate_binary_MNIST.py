@@ -72,7 +72,7 @@ def main(argv=None):
     if args.log_prob:
         from tensornetworkforml_amd.evaluate_diagonals import print_log_prob
         print_log_prob(net, data01, labels01)
-    if args.inpaint or args.inpaint_mean or args.surprise or args.occluded is not None:
+    if args.inpaint or args.inpaint_mean or args.surprise or args.mutual_info or args.occluded is not None:
         from tensornetworkforml_amd.evaluate_diagonals import run_masked_arguments
         run_masked_arguments(net, args, data01, labels01)
     if args.saliency:

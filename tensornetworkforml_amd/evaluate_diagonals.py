@@ -135,7 +135,26 @@ def write_surprise(net, path, pixels, n):
     return sur
 
 
+def write_mutual_information(net, path):
+    """The (N, N) map of I(x_i; x_j) in nats under the model, the label summed, the entropies on the diagonal
+    (Network.mutual_information).  Prints the mean over the pairs at distance |i - j| = 1, 2, 4, ... along the chain and the ten
+    sites of largest I(x_i; l) (Network.pixel_label_information)."""
+    mi = net.mutual_information()
+    np.save(path, mi)
+    dist = 1
+    while dist < net.N:
+        print('\tMutual information at distance %4d: mean %.3e nats over %d pairs' % (dist, float(np.diagonal(mi, dist).mean()), net.N - dist))
+        dist *= 2
+    info = net.pixel_label_information()
+    top = np.argsort(-info, kind='stable')[:10]
+    print('\tSites of largest I(x_i; l): ' + ', '.join('%d (%.3e)' % (int(i), float(info[i])) for i in top))
+    print('\tMutual information map written to', path, mi.shape)
+    return mi, info
+
+
 def run_masked_arguments(net, args, pixels, labels):
+    if args.mutual_info:
+        write_mutual_information(net, args.mutual_info)
     if args.inpaint:
         write_inpainted(net, args.inpaint, pixels, labels, args.sample_n, args.inpaint_known, args.seed)
     if args.inpaint_mean:
@@ -162,6 +181,9 @@ def add_sample_arguments(ap):
                          '(Network.expected_image); prints its error on the hidden pixels beside that of one drawn completion')
     ap.add_argument('--surprise', metavar='OUT.npy', default=None,
                     help='write -log p(x_i | all other pixels) per pixel of the first --sample-n test images (Network.pixel_surprise)')
+    ap.add_argument('--mutual-info', dest='mutual_info', metavar='OUT.npy', default=None,
+                    help='write the map of the mutual information I(x_i; x_j) of every pair of pixels under the model (Network.mutual_information); '
+                         'prints its mean by distance along the chain and the ten pixels that carry most information about the class')
     ap.add_argument('--occluded', metavar='FRACTION', type=float, default=None,
                     help='hide a seeded random FRACTION of every test image and print the accuracy of Network.classify_masked next to '
                          'that of the classifier on the same images with the hidden pixels set to 0')
