@@ -1,4 +1,4 @@
-// CPU stand-in for the HIP runtime and RCCL, for ONE purpose: running the HOST side of this library (tnml_api.hip and the launch
+// CPU stand-in for the HIP runtime and RCCL, for ONE purpose: running the HOST side of this library (tnml_api.hip, the api_*.hip files and the launch
 // wrappers of kernels_*.hip, compiled `--cuda-host-only -fsanitize=address,undefined`) on a machine without a GPU, so that the
 // planning of whole sweeps -- strides, slot offsets, buffer sizing, the pipelined / classic / persistent state machine -- runs under
 // AddressSanitizer and UBSan (GPU sanitizers are not available on this pool).  Nothing here computes: kernels are never executed.

@@ -1,4 +1,4 @@
-// Inner products and linear combinations of two MPS (tnml_inner / tnml_axpby of tnml_api.hip and the launch wrappers of
+// Inner products and linear combinations of two MPS (tnml_inner / tnml_axpby of api_mps.hip and the launch wrappers of
 // kernels_algebra.hip) planned by the real host code, built --cuda-host-only with AddressSanitizer and UBSan, against the stand-in
 // runtime of hip_stub.cpp, which reads both bond and offset tables of every launch as the kernels do and checks every core of
 // either chain, the staging areas, the half results, the outputs and the float32 result with its extent.  Nothing computes there:

@@ -1,5 +1,5 @@
 // The device-resident dataset (tnml_dataset_attach / tnml_select_indices / tnml_predict_indices / tnml_eval_indices /
-// tnml_resident_metrics / tnml_dataset_read of tnml_api.hip and the launch wrappers of kernels_dataset.hip) planned by the real host
+// tnml_resident_metrics / tnml_dataset_read of api_dataset.hip and the launch wrappers of kernels_dataset.hip) planned by the real host
 // code, built --cuda-host-only with AddressSanitizer and UBSan, against the stand-in runtime of hip_stub.cpp.  The binary is linked
 // with -Wl,--wrap=hipLaunchKernel: every launch of kernels_dataset.hip passes through check_* below first, which checks the grid and
 // every pointer of the argument block together with the extent the kernel touches -- for the gather THROUGH the index list the host

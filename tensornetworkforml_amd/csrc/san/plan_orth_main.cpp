@@ -1,4 +1,4 @@
-// Orthogonal form, compression and bond spectra (tnml_orthogonalize / tnml_compress / tnml_bond_spectra of tnml_api.hip and the launch
+// Orthogonal form, compression and bond spectra (tnml_orthogonalize / tnml_compress / tnml_bond_spectra of api_mps.hip and the launch
 // wrapper of kernels_orth.hip) planned by the real host code, built --cuda-host-only with AddressSanitizer and UBSan, against the
 // stand-in runtime of hip_stub.cpp, which walks the operation list of every call and checks every slot, scratch and output pointer
 // of the parameter block with its extent.  Nothing computes there: the scratch bond table comes back as it was uploaded, so every

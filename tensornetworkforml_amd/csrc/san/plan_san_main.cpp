@@ -1,4 +1,4 @@
-// Whole sweeps of the BASELINE shapes planned by the real host code of the library (tnml_api.hip + the launch wrappers, built
+// Whole sweeps of the BASELINE shapes planned by the real host code of the library (tnml_api.hip, the api_*.hip files + the launch wrappers, built
 // --cuda-host-only with AddressSanitizer and UBSan) against the stand-in runtime of hip_stub.cpp, which checks every copy and every
 // launch argument block against the allocation registry.  `make san` builds and runs it; tests/test_host_api.py runs `make san`.
 #include <cstdio>

@@ -1,29 +1,13 @@
 // Host side of libtnml_hip.so: context, device buffers, per-step planning in the sweep-relative
 // frame, the sweep driver (wide -> reduce -> [RCCL all-reduce] -> narrow per step, all enqueued on
 // one stream without host synchronisation) and the C ABI of include/tnml.h.
-#include <rccl/rccl.h>
-
-#include <algorithm>
-#include <climits>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <cstdlib>
-#include <initializer_list>
-#include <memory>
-#include <utility>
-
-#include "tnml_internal.h"
+#include "tnml_host.h"
 #include "small_gemm_device.h"
-#include "wide_pipe_device.h"
 #include "grad_chain_device.h"
-
-using namespace tnml;
 
 static thread_local std::string g_err;
 
-static int fail(int code, const char *fmt, ...) {
+int tnml::fail(int code, const char *fmt, ...) {
   char buf[1024];
   va_list ap;
   va_start(ap, fmt);
@@ -31,411 +15,6 @@ static int fail(int code, const char *fmt, ...) {
   va_end(ap);
   g_err = buf;
   return code;
-}
-
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) return fail(TNML_ERR_HIP, "%s failed: %s (%s:%d)", #expr,           \
-                                      hipGetErrorString(e_), __FILE__, __LINE__);              \
-  } while (0)
-
-#define NCCL_TRY(expr)                                                                         \
-  do {                                                                                         \
-    ncclResult_t r_ = (expr);                                                                  \
-    if (r_ != ncclSuccess) return fail(TNML_ERR_COMM, "%s failed: %s (%s:%d)", #expr,         \
-                                       ncclGetErrorString(r_), __FILE__, __LINE__);            \
-  } while (0)
-
-static constexpr size_t kLdsMax = 160 * 1024;      // LDS of a workgroup on gfx950: what a launch may ask for
-
-// What one tnml_sweep call fixes for all its steps: the arguments of the call (mode 1: standalone update_B, Bdirect_dev: merged tensor
-// to use instead of the product of the two cores), whether it starts a segment, its sample tiles, its closing timing event.
-struct SweepCall {
-  int left_dir, n_steps;
-  float lr, weight_dec;
-  int l2_flag, act_fn, loss_fn;
-  float T;
-  int trunc_policy;
-  float *metrics_out, *f_out;
-  int mode;
-  const float *Bdirect_dev;
-  hipEvent_t sw_ev1;
-  bool seg_start;
-  int nblk;
-};
-
-// A reduced pre-gradient left in zred for the next step: the step (relative index k) of a sweep call with these arguments may start
-// from it.  rows / cols: its shape as a matrix, where the taker checks it (large-tensor pipeline).
-struct ZTicket {
-  bool valid = false;
-  int k = -1, left = 0, act = 0, loss = 0, rows = 0, cols = 0;
-  float T = 0.f;
-  bool matches(const SweepCall &s, int k_) const {
-    return valid && k == k_ && left == s.left_dir && act == s.act_fn && loss == s.loss_fn && T == s.T;
-  }
-  void leave(const SweepCall &s, int k_, bool valid_, int rows_ = 0, int cols_ = 0) {
-    valid = valid_; k = k_; left = s.left_dir; act = s.act_fn; loss = s.loss_fn; T = s.T; rows = rows_; cols = cols_;
-  }
-};
-
-// Who owns what ("Who owns what").  Everything a context creates in the runtime -- device memory, pinned host memory,
-// events, streams -- is created by Owner::make and recorded there; the members of tnml_ctx stay the raw handles the argument blocks
-// of the kernels copy by value.  ~Owner releases what is still recorded, newest first, so `delete ctx` is the whole teardown and a
-// tnml_create that fails half-way leaks nothing.  No other code of this file calls the runtime's create / destroy functions.
-//
-// Capacity groups.  Buffers sized from the same quantity are (re)sized by ONE function, which writes each member's size once and
-// hands the list to make().  make() frees every member first and creates them afterwards (the batch group's two environment stacks
-// are ~0.8 GB each at C5: old and new together would double the peak), and frees them all again when one creation fails.  The rule
-// for every group: after a failed (re)size the group is completely empty, its capacity field is 0 and every flag that depends on it
-// (have_input, have_labels, envs_valid_*, f_current, big_ready, ...) is cleared -- the group's function does that BEFORE it calls
-// make(); the call returns TNML_ERR_HIP; the same call repeated later succeeds; and no call in between launches with a null or
-// undersized member, because every reader goes through that capacity field or one of those flags.
-struct Owner {
-  enum Kind { kDev, kPinned, kEvent, kStream };
-  struct Member { void **slot; size_t arg; Kind kind; bool wanted = true; };   // arg: bytes (memory) or creation flags (event); !wanted: released, not created
-  std::vector<std::pair<void *, Kind>> held;                   // by value: the slots may be locals or move (sweep_ev)
-
-  Owner() = default;
-  Owner(const Owner &) = delete;
-  Owner &operator=(const Owner &) = delete;
-  ~Owner() { for (; !held.empty(); held.pop_back()) destroy(held.back().first, held.back().second); }
-
-  static void destroy(void *h, Kind k) {
-    switch (k) {
-      case kDev: (void)hipFree(h); break;
-      case kPinned: (void)hipHostFree(h); break;
-      case kEvent: (void)hipEventDestroy((hipEvent_t)h); break;
-      case kStream: (void)hipStreamDestroy((hipStream_t)h); break;
-    }
-  }
-  template <class T> void release(T *&p) {                     // free, un-record, null
-    for (size_t i = held.size(); p && i-- > 0;)
-      if (held[i].first == (void *)p) { destroy(held[i].first, held[i].second); held.erase(held.begin() + i); break; }
-    p = nullptr;
-  }
-  // all of the list or none of it: whatever the slots hold is released first
-  hipError_t make(std::initializer_list<Member> group) {
-    for (const Member &m : group) release(*m.slot);
-    for (const Member &m : group) {
-      if (!m.wanted) continue;
-      void *h = nullptr;
-      hipError_t e = hipSuccess;
-      switch (m.kind) {
-        case kDev: e = hipMalloc(&h, m.arg); break;
-        case kPinned: e = hipHostMalloc(&h, m.arg); break;
-        case kEvent: e = hipEventCreateWithFlags((hipEvent_t *)&h, (unsigned)m.arg); break;
-        case kStream: e = hipStreamCreateWithFlags((hipStream_t *)&h, hipStreamNonBlocking); break;
-      }
-      if (e != hipSuccess) {
-        for (const Member &u : group) release(*u.slot);
-        return e;
-      }
-      held.emplace_back(h, m.kind);
-      *m.slot = h;
-    }
-    return hipSuccess;
-  }
-};
-template <class T> static Owner::Member own_dev(T *&p, size_t count) { return {(void **)&p, count * sizeof(T), Owner::kDev}; }
-template <class T> static Owner::Member own_dev_if(bool wanted, T *&p, size_t count) { return {(void **)&p, count * sizeof(T), Owner::kDev, wanted}; }
-template <class T> static Owner::Member own_pinned(T *&p, size_t count) { return {(void **)&p, count * sizeof(T), Owner::kPinned}; }
-static Owner::Member own_event(hipEvent_t &e, unsigned flags) { return {(void **)&e, flags, Owner::kEvent}; }
-static Owner::Member own_stream(hipStream_t &s) { return {(void **)&s, 0, Owner::kStream}; }
-
-struct tnml_ctx {
-  Owner own;                            // (first member: destroyed last)
-  int N = 0, D = 0, L = 0, Mmax = 0;   // Mmax = buffer capacity per bond
-  int Mpol = 0;                         // the M of Network(N, M, ...): fixed-policy rank
-  int b = 0, b_pad = 0, b_cap = 0;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipStream_t stream2 = nullptr;             // large-tensor steps: merged tensor and Nh^T.B beside the batch kernel; persistent sweep: helper grid
-  hipStream_t stream3 = nullptr;             // persistent sweep in three launches: batch-side grid
-  hipEvent_t ev_p0 = nullptr, ev_p2 = nullptr, ev_p3 = nullptr;
-  int persist_mode = 1;                      // tnml_set_persistent: 0 per-step launches, 1 one kernel per sweep (default), 2 one kernel per role
-  hipEvent_t ev_main = nullptr, ev_prep = nullptr;
-  // communicator path of the pipelined step: update side on `stream`, batch side + all-reduce of the pre-gradient on `stream2`
-  struct {
-    // (ev_upd[i]: an update launch has ended; ev_bat[i]: a batch-side launch and the exchange behind it have ended)
-    hipEvent_t ev_upd[2] = {nullptr, nullptr}, ev_bat[2] = {nullptr, nullptr};
-    int upd = 0, bat = 0;                    // index of the event recorded last
-    bool pending = false;                    // stream2 holds batch-side work `stream` has not waited for yet
-    bool enabled = true;                     // tnml_set_comm_overlap
-    // hand-offs without events, as in the large-tensor pipeline below: [0] "Z (all-reduced) is ready", [1] "update launch done"
-    unsigned *flags = nullptr;
-    unsigned zseq = 0, dseq = 0;
-    bool flags_enabled = true, done_valid = false, zsig_valid = false;
-  } split;
-  // pipelined large-tensor step (kernels_big.hip): the batch kernel of step k+1 runs on stream2 beside the SVD of step k and leaves
-  // the reduced pre-gradient Z_{k+1} in zred; the step then starts with the contraction A_k^T . Z instead of the batch kernel
-  struct {
-    bool enabled = true;                     // tnml_set_step_pipeline(ctx, 0) turns it off together with the in-LDS pipeline
-    ZTicket Z;
-    float *Pk = nullptr;                     // [D * Mmax][b_pad]  E_k (x) x_k, the row operand of Z_{k+1}
-    hipEvent_t ev_upd = nullptr, ev_z = nullptr;
-    bool pending = false;                    // stream2 holds batch work of the pipelined large-tensor step the context's stream has not joined
-    // hand-offs of that pipeline without events (kernels_big.hip, big_signal_kernel): [0] "Z of the next step is ready" (side stream ->
-    // context's stream), [1] "B_new is ready" (context's stream -> side stream); sequence numbers
-    unsigned *flags = nullptr;
-    unsigned zsig_seq = 0, bsig_seq = 0;
-    bool flags_enabled = true;
-    bool ext_on_side = false;                // the last environment extension of the pipeline ran on the side stream
-  } bigpipe;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, pev0 = nullptr, pev1 = nullptr;
-  // host bookkeeping
-  std::vector<int> bond;
-  int l_pos = 0;
-  bool cores_set = false;
-  bool have_input = false, have_labels = false;
-  bool envs_valid_L = false, envs_valid_R = false;  // forward built the stack this side
-  bool Ln_valid = false, Rn_valid = false;
-  bool f_current = false;     // ctx->f holds the f the next step must start from
-  bool Bnew_valid = false;    // ctx->Bnew holds the updated B of the previous step
-  int prev_h = 0, prev_g = 0; // dims of Bnew (relative frame)
-  int prev_left_dir = 0;
-  int last_bsize = 0, last_n = 0, last_h = 0, last_g = 0, last_left_dir = 0;
-  bool debug = false, profile = false, stamps = false;
-  bool check_launches = false;               // tnml_debug_enable bit 2: read the launch status back after every kernel launch
-  int sync_interval = 256;                   // tnml_set_sync_interval: drain the stream every so many steps (0 = never)
-  double svd_stop2 = kSvdStop2Default;
-  double chol_thr = kCholThrDefault;         // off(G) / trace(G) above which the pivoted-Cholesky step runs (0 disables it)
-  double trunc_thr = 0.999;                  // adaptive truncation threshold (tensor_svd's default argument)
-  double prof_ms[4] = {0, 0, 0, 0};
-  long long prof_n[4] = {0, 0, 0, 0};
-  // whole-sweep timing without any synchronisation inside the timed region (tnml_profile_enable(ctx, 2)): one event pair per
-  // tnml_sweep call, read back by tnml_profile_get(which = 4)
-  bool sweep_timing = false;
-  std::vector<hipEvent_t> sweep_ev;          // pairs
-  size_t sweep_ev_used = 0;
-  double sweep_ms = 0;
-  long long sweep_launches = 0, step_launches = 0;
-  // tnml_get_counters: work since the last tnml_profile_reset, from the dimensions of every step actually run
-  double cnt_steps = 0, cnt_bytes = 0, cnt_flops = 0, cnt_fwd_bytes = 0, cnt_fwd = 0;
-  // staged batches (tnml_stage_batch / tnml_select_batch): device-resident [b][N][D] inputs + labels
-  static constexpr int kStageSlots = 8;
-  float *stageX[kStageSlots] = {nullptr};
-  int *stageY[kStageSlots] = {nullptr};
-  int stageB[kStageSlots] = {0};
-  // device buffers
-  size_t core_stride = 0, lab_elems = 0, bmax = 0;
-  float *X = nullptr, *Xstage = nullptr;
-  int *y = nullptr;
-  float *f = nullptr, *ftmp = nullptr, *ftmp2 = nullptr;
-  float *Lenv = nullptr, *Renv = nullptr;
-  float *cores = nullptr, *lab[2] = {nullptr, nullptr};
-  int lab_cur = 0;
-  double *Ln = nullptr, *Rn = nullptr;
-  float *Bnew = nullptr, *slabs = nullptr, *red = nullptr, *metrics = nullptr, *scal = nullptr;
-  float *Bscr = nullptr, *Bscr2 = nullptr;   // scratch merged tensors of the standalone entry points
-  BigScratch big{};                          // HBM scratch of the large-tensor path, allocated on first use
-  bool big_ready = false;
-  bool force_big = false;                    // tnml_set_narrow_path
-  bool chain_plain = false;                  // tnml_set_chain_path
-  bool any_pos = false;                      // tnml_set_any_position
-  bool seg_starting = false;                 // the sweep call in flight starts a segment and has not planned its first step yet
-  float *predEnv = nullptr;                  // prediction at an intermediate label site: [2][Mmax][pred_cap], the two environments next to it
-  float *prepB = nullptr;                    // fused narrow launch: merged tensor / L2 term from the helper workgroups
-  double *prepG = nullptr;
-  unsigned *sync = nullptr;
-  // pipelined step (wide_pipe_device.h): partial / group / reduced pre-gradients, arrival counters, B_new flag
-  float *zslabs = nullptr, *gslabs = nullptr, *zred = nullptr;
-  int zstride = 0;
-  struct {
-    bool enabled = true;                     // tnml_set_step_pipeline
-    int tiles = 2;                           // sample tiles per batch-side workgroup where the SVD is long enough to hide them
-    unsigned *cnt = nullptr;                 // [0..15] group counters, [16] top counter, [17] flag
-    int nwide = 0, tpw = 1, ngroups = 0;
-    ZTicket Z;                               // zred holds the pre-gradient of relative step Z.k of a sweep in direction Z.left
-    unsigned token = 0;
-  } pipe;
-  // persistent sweep (sweep_persist_kernel): per-step records (device + two pinned host staging buffers), second buffers of the
-  // reduced pre-gradient, T_k buffers, per-step arrival counters, the flag words of the launch
-  bool persist_enabled = true;               // tnml_set_persistent
-  bool shape_kernels = true;                 // tnml_set_shape_kernels: persistent sweeps may run the bodies compiled for a step shape
-  int fixed_steps = 0;                       // steps of the last persistent sweep that did (tnml_fixed_shape_steps)
-  bool persist_slices = true;                // tnml_set_persist_reduce: pre-gradients beyond one level are reduced in slices by many workgroups
-  int slice_steps = 0;                       // records of the last persistent sweep that were (tnml_slice_reduce_steps)
-  PersistStep *pst_dev = nullptr, *pst_host[2] = {nullptr, nullptr};
-  hipEvent_t pst_ev[2] = {nullptr, nullptr};
-  int pst_cur = 0;
-  float *zred2 = nullptr, *prepRaw = nullptr;
-  double *Tbuf[2] = {nullptr, nullptr}, *TNbuf[2] = {nullptr, nullptr}, *Apub = nullptr;
-  unsigned *pst_cnt = nullptr, *pst_flags = nullptr;
-  long long persist_sweeps = 0;
-  int num_cus = 256;
-  float *Xpred_stage = nullptr, *Xpred = nullptr, *fpred = nullptr;   // tnml_predict's own batch (the resident one is untouched)
-  int pred_cap = 0;
-  // range-safe chains (tnml_set_chain_scaling).  Members of the prediction group once a scaled prediction has
-  // been asked for: mantissas [L][pred_cap], exponents [pred_cap], the bond table [N] of scaled_pred_kernel.  The exponent stacks
-  // [N][cap] of pass A are members of the two gradient groups while the switch is on.
-  bool scaled = false;
-  float *pred_mant = nullptr;
-  int *pred_expo = nullptr, *pred_bond = nullptr, *ig_estack = nullptr, *cg_estack = nullptr;
-  int slab_stride = 0, nblk_cap = 0, metrics_cap = 0;
-  double *dbg = nullptr;
-  size_t dbg_elems = 0;
-  int *status = nullptr;
-  unsigned long long *counters = nullptr;
-  char *tables = nullptr;      // device scratch for ChainSite / NormChainSite tables
-  size_t tables_bytes = 0;
-  double *anyd_W = nullptr, *anyd_T2 = nullptr;   // generic-D update kernel: Jacobi vectors beyond LDS, behind core + its norm product
-  // device-resident dataset (tnml_dataset_attach): features [n][N][D] or pixels [n][N], labels [n]; the index list of the call in
-  // flight lives in ds_idx (device), filled through one of two pinned host buffers so that the caller's list is free on return
-  float *ds_data = nullptr;
-  int *ds_labels = nullptr;
-  int ds_n = 0, ds_form = 0;
-  double ds_coef[kMaxD] = {0};
-  int *ds_idx = nullptr, *ds_idx_host[2] = {nullptr, nullptr};
-  hipEvent_t ds_idx_ev[2] = {nullptr, nullptr};
-  bool ds_idx_busy[2] = {false, false};
-  int ds_idx_cap = 0, ds_idx_cur = 0;
-  int *ds_ypred = nullptr;                   // [pred_cap] labels of the chunk tnml_eval_indices is evaluating, beside Xpred / fpred
-  double *ds_part = nullptr, *ds_acc = nullptr;   // block partials and the four accumulators of the metrics kernels
-  int ds_part_cap = 0;
-  // input gradients (tnml_input_grad): one group sized from ig_cap samples -- the stack of pass A
-  // [N][Mmax][ig_cap], cot [L][ig_cap], g [ig_cap][N][D], its pixel form [ig_cap][N], cf [ig_cap] -- and the bond table [N]
-  float *ig_stack = nullptr, *ig_cot = nullptr, *ig_g = nullptr, *ig_gpix = nullptr, *ig_cf = nullptr;
-  int *ig_bond = nullptr;
-  int ig_cap = 0, ig_chunk = 0;              // ig_chunk: tnml_set_input_grad_chunk (0 = default)
-  // core gradients (tnml_core_grad): one group sized from cg_cap samples -- the stacks of both passes
-  // [N][Mmax][cg_cap], cot [L][cg_cap], cf [cg_cap] -- with the table [2N] (bonds, then every core's offset in the flat layout) and
-  // G, the gradient in the layout of tnml_get_cores, sized for every bond at its capacity
-  float *cg_stackP = nullptr, *cg_stackQ = nullptr, *cg_cot = nullptr, *cg_cf = nullptr, *cg_G = nullptr;
-  int *cg_tab = nullptr;
-  int cg_cap = 0, cg_chunk = 0;              // cg_chunk: tnml_set_core_grad_chunk (0 = default)
-  // gradient training (tnml_gd_train_indices).  State group: opt_s0 / opt_s1 (SGD vel / Adam m, v) in the
-  // layout and of the size of cg_G, created by the first step of a stateful optimiser and bound to that step's bonds and l_pos.
-  // Metrics group: [opt_met_cap][4] doubles, one row per step of the call in flight.
-  struct {
-    int kind = TNML_OPT_SGD, clip = 1;
-    double momentum = 0.0, beta1 = 0.9, beta2 = 0.999, eps = 1e-8;
-    long long t = 0;                         // Adam steps taken since the last reset
-    std::vector<int> bond;                   // what the state is bound to (meaningful while opt_s0 exists)
-    int l_pos = -1;
-  } opt;
-  float *opt_s0 = nullptr, *opt_s1 = nullptr;
-  double *opt_met = nullptr;
-  int opt_met_cap = 0;
-  std::vector<int> opt_tab;                  // host copy of cg_tab for the call in flight (outlives the asynchronous upload)
-  // orthogonal form / compression / bond spectra.  One group, created by the first call: the float64 work copy
-  // of the slots and the label buffer, the absorbed site, the carried factors, the float32 result the commit copies from, the
-  // operation list, the scratch bond table and the outputs of the call.
-  struct {
-    double *W = nullptr, *Mbuf = nullptr, *aux = nullptr, *sigma = nullptr, *disc = nullptr, *result = nullptr;
-    float *out_cores = nullptr, *out_lab = nullptr;
-    OrthOp *ops = nullptr;
-    int *bond = nullptr, *rank = nullptr, *status = nullptr;
-    bool ready = false;
-  } orth;
-  // inner products and linear combinations.  One group, sized from the second chain: its cores (flat layout,
-  // v_cap floats), the bond and offset tables of both chains, the metric, the staging areas and half results of the six workgroups
-  // (sized from m_cap, the largest bond of either chain), the six outputs, the float32 result tnml_axpby commits from, the status.
-  struct {
-    float *V = nullptr, *out_cores = nullptr, *out_lab = nullptr;
-    int *bond = nullptr, *half_expo = nullptr, *status = nullptr;
-    long long *off = nullptr;
-    double *metric = nullptr, *stage = nullptr, *half_E = nullptr, *out = nullptr;
-    size_t v_cap = 0;
-    int m_cap = 0;
-    std::vector<int> bond_host;              // host copies of the two tables for the call in flight (they outlive the asynchronous upload)
-    std::vector<long long> off_host;
-  } alg;
-  // samples and log-likelihoods.  One group, regrown when a call needs more of any member: the tables of the
-  // call (bonds, slots, tiles, classes, given levels), the grid and its metric, the uniforms (u_cap doubles, 1 when they are hashed),
-  // the environment stacks (shared part and env_slots per-slot parts of lpos_cap sites each, env_stride doubles a site), the
-  // staging areas of the environment workgroups, the outputs and the status words.
-  struct {
-    int *bond = nullptr, *slot_class = nullptr, *tile_slot = nullptr, *tile_samples = nullptr, *classes = nullptr, *given = nullptr;
-    int *levels = nullptr, *labels = nullptr, *status = nullptr;
-    double *S = nullptr, *phi = nullptr, *w = nullptr, *u = nullptr, *env_shared = nullptr, *env_slots = nullptr, *stage = nullptr, *logp = nullptr;
-    size_t n_cap = 0, given_cap = 0, u_cap = 0, tiles_cap = 0, slots_cap = 0, slot_sites_cap = 0;
-    int m_cap = 0;
-    std::vector<int> host;                   // host copies of the tables for the call in flight (they outlive the asynchronous upload)
-    std::vector<double> hostd;
-  } smp;
-  // the same given any set of known pixels.  One group of its own, regrown when a call needs more of any
-  // member: the tables of the call (bonds, tiles, rows, mask, known levels), the grid and its metric, the uniforms, the per-row
-  // environment stack of one chunk (stack_cap doubles, at most stack_bytes), E per row, the outputs and the status words.
-  struct {
-    int *bond = nullptr, *tile_class = nullptr, *tile_rows = nullptr, *known = nullptr, *levels = nullptr, *labels = nullptr, *status = nullptr;
-    unsigned char *mask = nullptr;
-    double *S = nullptr, *phi = nullptr, *w = nullptr, *u = nullptr, *stack = nullptr, *E = nullptr, *logp0 = nullptr;
-    size_t tiles_cap = 0, rows_cap = 0, n_cap = 0, mask_cap = 0, u_cap = 0, stack_cap = 0;
-    size_t stack_bytes = (size_t)1 << 30;    // tnml_set_sample_stack_bytes
-    std::vector<int> host;                   // host copies of the tables for the call in flight (they outlive the asynchronous upload)
-    std::vector<double> hostd, hostE, hostp;
-  } smk;
-  // the gradient of the log-norm.  One group, sized from m_cap, the largest bond of a call: the table of
-  // grad_table, the metric, both environment stacks with their exponents, the gradient (of cg_G's size), the two outputs, the status.
-  struct {
-    int *tab = nullptr, *expL = nullptr, *expR = nullptr, *status = nullptr;
-    double *metric = nullptr, *envL = nullptr, *envR = nullptr, *out = nullptr;
-    float *G = nullptr;
-    int m_cap = 0;
-    std::vector<int> tab_host;               // host copy of the table for the call in flight (it outlives the asynchronous upload)
-  } lnz;
-  // the likelihood of a batch: per-sample terms and flags of the call in flight, and their two sums
-  struct {
-    double *terms = nullptr, *acc = nullptr;
-    int *bad = nullptr;
-    int n_cap = 0;
-  } nll;
-  // likelihood training.  One group, created by the first step and regrown with the steps of a call: the
-  // per-step records [cap][4], the sticky skip word of the guard, and the two events that carry the norm walk to stream2 and back.
-  struct {
-    double *rec = nullptr;
-    int *skip = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int cap = 0;
-    int overlap = 0;                         // tnml_set_nll_overlap: the norm walk on stream2 beside the chunks of the step
-    std::vector<double> metric_host;         // host copy of the metric for the call in flight (it outlives the asynchronous upload)
-  } nst;
-  // per-pixel conditionals.  One group of its own, regrown when a call needs more of any member: the values
-  // of the levels, the left environments behind the site a row of one chunk is on (lf_cap doubles), and the three outputs of n_cap
-  // samples.  The tables, the grid, the stack and E are the masked group's (smk), through smk_ensure.
-  struct {
-    double *values = nullptr, *lf_next = nullptr, *q = nullptr, *stats = nullptr;
-    int *mode = nullptr;
-    size_t n_cap = 0, lf_cap = 0;
-    std::vector<double> values_host;         // host copy of the values for the call in flight (it outlives the asynchronous upload)
-  } scc;
-  // pixel-pair marginals.  One group of its own, regrown when a bond or a chunk outgrows it: the table of
-  // grad_table, the grid with its metric and values, both environment stacks of the call's class slot with their exponents, B_j
-  // of every site, the per-site outputs, and for rows_cap rows of one chunk the sites, Q, its exponents and the pair statistics.
-  struct {
-    int *tab = nullptr, *expL = nullptr, *expR = nullptr, *status = nullptr, *rows = nullptr, *qexp = nullptr;
-    double *S = nullptr, *phi = nullptr, *w = nullptr, *values = nullptr, *envL = nullptr, *envR = nullptr, *out = nullptr;
-    double *B = nullptr, *q1 = nullptr, *stats1 = nullptr, *Q = nullptr, *stats = nullptr;
-    int m_cap = 0;
-    size_t rows_cap = 0;
-    std::vector<int> tab_host, rows_host, sites_host;   // host copies for the call in flight (they outlive the asynchronous uploads)
-    std::vector<double> hostd;               // S, the values, phi, w
-  } pair;
-  // multi-GPU
-  ncclComm_t comm = nullptr;
-  int rank = 0, nranks = 1;
-
-  int ml(int i) const { return i == 0 ? 1 : bond[i - 1]; }
-  int mr(int i) const { return i == N - 1 ? 1 : bond[i]; }
-  float *env_slot(float *base, int site) const { return base + (size_t)site * Mmax * b_pad; }
-  long long env_off(int site) const { return (long long)site * Mmax * b_pad; }
-  float *core_slot(int site) const { return cores + (size_t)site * core_stride; }
-  double *norm_slot(double *base, int site) const { return base + (size_t)site * Mmax * Mmax; }
-};
-
-// no step may start from a pre-gradient left earlier (cores, batch, labels or the launch form changed)
-static void drop_pregradients(tnml_ctx *c) { c->pipe.Z.valid = false; c->bigpipe.Z.valid = false; }
-
-// The resident batch changed (tnml_set_input, tnml_select_batch, tnml_select_indices, a regrown batch group): what was computed from
-// its samples is gone -- the environment stacks, f, the updated merged tensor of a previous step, the pre-gradients.  The norm
-// environments (Ln_valid / Rn_valid) are contractions of the cores alone and stay, as does the optimiser binding.  tnml_set_labels
-// drops the pre-gradients only: the stacks and f do not see the labels.
-static void batch_changed(tnml_ctx *c) {
-  c->envs_valid_L = c->envs_valid_R = false;
-  c->f_current = false;
-  c->Bnew_valid = false;
-  drop_pregradients(c);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -451,13 +30,13 @@ extern "C" int tnml_device_count(void) {
 #include "host_plan.inc"      // tnml_trunc_rank, canon_to_rel: pure host arithmetic, also built with sanitizers (make san)
 
 // one (re)size of a group: the message names the group
-static int make_group(tnml_ctx *c, const char *what, std::initializer_list<Owner::Member> group) {
+int tnml::make_group(tnml_ctx *c, const char *what, std::initializer_list<Owner::Member> group) {
   const hipError_t e = c->own.make(group);
   return e == hipSuccess ? TNML_OK : fail(TNML_ERR_HIP, "allocating %s failed: %s", what, hipGetErrorString(e));
 }
 
 // Batch group: everything sized from b_pad (bigpipe.Pk too: batch_Pk below creates it on first use, this releases it)
-static int size_batch_group(tnml_ctx *c, int b_cap) {
+int tnml::size_batch_group(tnml_ctx *c, int b_cap) {
   const int b_pad = (b_cap + 63) / 64 * 64, ntiles = b_pad / kTS;
   c->b = c->b_cap = c->b_pad = c->nblk_cap = 0;
   c->have_input = c->have_labels = false;
@@ -635,31 +214,9 @@ extern "C" int tnml_comm_init(tnml_ctx *c, int rank, int nranks, const void *uid
 // ---------------------------------------------------------------------------------------------
 // parameters
 // ---------------------------------------------------------------------------------------------
-static size_t core_elems(const tnml_ctx *c, const std::vector<int> &bond, int i, int l_pos) {
+size_t tnml::core_elems(const tnml_ctx *c, const std::vector<int> &bond, int i, int l_pos) {
   const int ml = i == 0 ? 1 : bond[i - 1], mr = i == c->N - 1 ? 1 : bond[i];
   return (size_t)ml * c->D * mr * (i == l_pos ? c->L : 1);
-}
-
-// The model changed (tnml_set_cores, tnml_scale_cores, a training step, a committed orthogonalisation / compression / sum): nothing
-// computed from the cores is current any more.  The ONE place that says which state hangs on the cores:
-//   envs_valid_L/R, f_current   the environment stacks and f of the resident batch are products of the old cores
-//   Ln_valid / Rn_valid         the norm environments of the L2 term are contractions of the old cores
-//   Bnew_valid                  the updated merged tensor of a previous step belongs to the old chain: no mid-sweep continuation
-//   the pre-gradient tickets    a pre-gradient a step left for its successor was formed with the old cores' environments
-// What does NOT hang on the cores stays: the resident batch and its labels, the staged batches, the dataset, every capacity group.
-static void cores_changed(tnml_ctx *c) {
-  c->envs_valid_L = c->envs_valid_R = false;
-  c->Ln_valid = c->Rn_valid = false;
-  c->f_current = false;
-  c->Bnew_valid = false;
-  drop_pregradients(c);
-}
-
-// vel / m / v describe the cores element by element: a commit that changes the gauge, the bonds or the meaning of an element leaves
-// them unbound (tnml_gd_step / tnml_nll_step refuse until tnml_optim_reset).  tnml_set_cores and a sweep need no call: the binding is
-// the pair (bonds, l_pos), which the step compares.
-static void unbind_optimiser(tnml_ctx *c) {
-  if (c->opt_s0) c->opt.l_pos = -1;
 }
 
 extern "C" int tnml_set_cores(tnml_ctx *c, const float *flat, size_t n_floats, const int32_t *bond, int l_pos) {
@@ -1039,7 +596,7 @@ extern "C" int tnml_forward(tnml_ctx *c, float *f_out) {
 // Prediction group, grown to bp samples: tnml_predict's own batch -- Xpred_stage [b][N][D] as uploaded, Xpred [N][pred_cap][D],
 // fpred [L][pred_cap] -- with the two environments next to an intermediate label site (predEnv) and the labels of the chunk
 // tnml_eval_indices is evaluating (ds_ypred)
-static int pred_ensure_buffers(tnml_ctx *c, int bp, bool scaled_out = false) {
+int tnml::pred_ensure_buffers(tnml_ctx *c, int bp, bool scaled_out) {
   const bool sc = c->scaled || scaled_out || c->pred_mant;     // (once there, the scaled members stay members)
   if (bp <= c->pred_cap && (!sc || c->pred_mant)) return TNML_OK;
   bp = std::max(bp, c->pred_cap);                              // (the gradient groups were sized against this capacity)
@@ -1067,7 +624,7 @@ static int scaled_pred_fits(const tnml_ctx *c) {
 }
 
 // may a prediction run at this label position (and, with scaled chains, at these bonds)?
-static int pred_allowed(tnml_ctx *c) {
+int tnml::pred_allowed(tnml_ctx *c) {
   if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
   if (label_inside(c) && !c->any_pos)
     return fail(TNML_ERR_STATE, "forward should not be called if l has an intermediate position (l_pos = %d)", c->l_pos);
@@ -1076,7 +633,7 @@ static int pred_allowed(tnml_ctx *c) {
 
 // the chain table of a prediction: towards the label site, or the two half-chains
 // (scaled chains: the bond table of scaled_pred_kernel; c->bond is not written while a call is in flight)
-static int pred_table(tnml_ctx *c, bool scaled = false) {
+int tnml::pred_table(tnml_ctx *c, bool scaled) {
   if (c->scaled || scaled) {
     HIP_TRY(hipMemcpyAsync(c->pred_bond, c->bond.data(), (size_t)(c->N - 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
     return TNML_OK;
@@ -1098,7 +655,7 @@ static int pred_chain_scaled(tnml_ctx *c, int b) {
 }
 
 // one chain towards the label site over Xpred -> fpred, no environment stored (the chain table must be uploaded)
-static int pred_chain(tnml_ctx *c, int b) {
+int tnml::pred_chain(tnml_ctx *c, int b) {
   if (c->scaled) return pred_chain_scaled(c, b);
   const int N = c->N, D = c->D, L = c->L, bpad = c->pred_cap;
   if (label_inside(c)) {
@@ -1115,22 +672,6 @@ static int pred_chain(tnml_ctx *c, int b) {
   } else
   launch_env_chain((const ChainSite *)c->tables, N, c->cores, c->lab[c->lab_cur], c->Xpred, nullptr, c->fpred, b, bpad, L,
                    c->Mmax, nullptr, c->stream, c->chain_plain);
-  HIP_TRY(hipGetLastError());
-  return TNML_OK;
-}
-
-static int ds_gather(tnml_ctx *c, const int *idx_dev, int b, int b_pad, float *X_out, int *y_out);     // (with the dataset, below)
-
-// Samples off .. off + bc of a call into the prediction group, site-major in Xpred [N][pred_cap][D]: the dataset rows idx_dev[off ..)
-// with their labels to y_out (or nullptr), or, idx_dev == nullptr, X [..][N][D] of the host through Xpred_stage with y (or nullptr) to
-// ds_ypred
-static int load_chunk(tnml_ctx *c, const float *X, const int *idx_dev, const int32_t *y, int off, int bc, int *y_out) {
-  const int N = c->N, D = c->D;
-  if (idx_dev) return ds_gather(c, idx_dev + off, bc, c->pred_cap, c->Xpred, y_out);
-  HIP_TRY(hipMemcpyAsync(c->Xpred_stage, X + (size_t)off * N * D, (size_t)bc * N * D * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  if (y) HIP_TRY(hipMemcpyAsync(c->ds_ypred, y + off, (size_t)bc * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  if (D != kD) launch_transpose_input_anyd(c->Xpred_stage, c->Xpred, bc, c->pred_cap, N, D, c->stream);
-  else launch_transpose_input(c->Xpred_stage, c->Xpred, bc, c->pred_cap, N, c->stream);
   HIP_TRY(hipGetLastError());
   return TNML_OK;
 }
@@ -1247,227 +788,6 @@ extern "C" int tnml_activation(tnml_ctx *c, int act_fn, int loss_fn, float T, in
   HIP_TRY(hipGetLastError());
   if (act_out) { int rc = copy_f_out(c, c->ftmp, act_out); if (rc) return rc; }
   if (lossder_out) { int rc = copy_f_out(c, c->ftmp2, lossder_out); if (rc) return rc; }
-  return TNML_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// device-resident dataset: upload once, then batches and evaluations by index list
-// ---------------------------------------------------------------------------------------------
-static int ds_usable(tnml_ctx *c) {
-  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
-  if (c->comm) return fail(TNML_ERR_STATE, "a resident dataset is not sharded over ranks: the dataset calls are single-GPU only");
-  if (!c->ds_data) return fail(TNML_ERR_STATE, "no dataset attached: call tnml_dataset_attach first");
-  return TNML_OK;
-}
-
-static void ds_drop(tnml_ctx *c) { c->own.release(c->ds_data); c->own.release(c->ds_labels); c->ds_n = 0; }
-
-extern "C" int tnml_dataset_attach(tnml_ctx *c, const float *data, const int32_t *labels, int n, int N, int D, int form) {
-  if (!c || !data || !labels) return fail(TNML_ERR_ARG, "NULL argument");
-  if (c->comm) return fail(TNML_ERR_STATE, "a resident dataset is not sharded over ranks: the dataset calls are single-GPU only");
-  if (n < 1) return fail(TNML_ERR_ARG, "empty dataset");
-  if (N != c->N || D != c->D) return fail(TNML_ERR_ARG, "dataset for N = %d, D = %d attached to a context with N = %d, D = %d", N, D, c->N, c->D);
-  if (form != TNML_DATASET_FEATURES && form != TNML_DATASET_PIXELS) return fail(TNML_ERR_ARG, "unknown dataset form %d", form);
-  for (int i = 0; i < n; ++i)
-    if (labels[i] < 0 || labels[i] >= c->L) return fail(TNML_ERR_ARG, "label %d of sample %d outside [0, %d)", labels[i], i, c->L);
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipStreamSynchronize(c->stream));          // an earlier dataset may still be read
-  // Dataset group (sized from n): both arrays or none (ds_usable asks for ds_data)
-  const size_t per = (size_t)c->N * (form == TNML_DATASET_PIXELS ? 1 : c->D);
-  c->ds_n = 0;
-  hipError_t e = c->own.make({own_dev(c->ds_data, (size_t)n * per), own_dev(c->ds_labels, (size_t)n)});
-  if (e == hipSuccess) e = hipMemcpy(c->ds_data, data, (size_t)n * per * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(c->ds_labels, labels, (size_t)n * sizeof(int), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    ds_drop(c);
-    return fail(TNML_ERR_HIP, "uploading a dataset of %d samples failed: %s", n, hipGetErrorString(e));
-  }
-  c->ds_n = n; c->ds_form = form;
-  double binom = 1.0;                                 // C(D-1, s), exact in float64 for D <= kMaxD
-  for (int s = 0; s < c->D; ++s) {
-    c->ds_coef[s] = std::sqrt(binom);
-    binom = binom * (double)(c->D - 1 - s) / (double)(s + 1);
-  }
-  return TNML_OK;
-}
-
-extern "C" int tnml_dataset_detach(tnml_ctx *c) {
-  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  ds_drop(c);
-  return TNML_OK;
-}
-
-extern "C" int tnml_dataset_size(tnml_ctx *c) { return c ? c->ds_n : TNML_ERR_ARG; }
-
-// idx[0..b) validated against [0, n) and copied to ds_idx; the caller's list is free when this returns and nothing waits for the
-// device except for a pinned buffer whose previous copy (two calls back) has not been consumed yet
-static int ds_upload_indices(tnml_ctx *c, const int32_t *idx, int b) {
-  for (int i = 0; i < b; ++i)
-    if (idx[i] < 0 || idx[i] >= c->ds_n) return fail(TNML_ERR_ARG, "index %d at position %d outside [0, %d)", idx[i], i, c->ds_n);
-  if (b > c->ds_idx_cap) {                   // Index-list group: the device list, its two pinned buffers and their events
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const size_t cap = ((size_t)b + 1023) / 1024 * 1024;
-    c->ds_idx_cap = 0;
-    c->ds_idx_busy[0] = c->ds_idx_busy[1] = false;
-    int rc = make_group(c, "the index list", {
-        own_dev(c->ds_idx, cap), own_pinned(c->ds_idx_host[0], cap), own_pinned(c->ds_idx_host[1], cap),
-        own_event(c->ds_idx_ev[0], hipEventDisableTiming), own_event(c->ds_idx_ev[1], hipEventDisableTiming)});
-    if (rc) return rc;
-    c->ds_idx_cap = (int)cap;
-  }
-  const int slot = (c->ds_idx_cur ^= 1);
-  if (c->ds_idx_busy[slot]) HIP_TRY(hipEventSynchronize(c->ds_idx_ev[slot]));
-  memcpy(c->ds_idx_host[slot], idx, (size_t)b * sizeof(int));
-  HIP_TRY(hipMemcpyAsync(c->ds_idx, c->ds_idx_host[slot], (size_t)b * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipEventRecord(c->ds_idx_ev[slot], c->stream));
-  c->ds_idx_busy[slot] = true;
-  return TNML_OK;
-}
-
-static int ds_gather(tnml_ctx *c, const int *idx_dev, int b, int b_pad, float *X_out, int *y_out) {
-  DatasetGather g{};
-  g.data = c->ds_data; g.labels = c->ds_labels; g.idx = idx_dev; g.out = X_out; g.y_out = y_out;
-  g.b = b; g.b_pad = b_pad; g.N = c->N; g.D = c->D; g.pixels = (c->ds_form == TNML_DATASET_PIXELS);
-  for (int s = 0; s < kMaxD; ++s) g.coef[s] = c->ds_coef[s];
-  if (!launch_dataset_gather(g, c->stream)) return fail(TNML_ERR_ARG, "internal: dataset gather refused (b %d, b_pad %d)", b, b_pad);
-  HIP_TRY(hipGetLastError());
-  return TNML_OK;
-}
-
-extern "C" int tnml_select_indices(tnml_ctx *c, const int32_t *idx, int b) {
-  int rc = ds_usable(c);
-  if (rc) return rc;
-  if (!idx) return fail(TNML_ERR_ARG, "NULL argument");
-  if (b < 1) return fail(TNML_ERR_ARG, "empty batch");
-  HIP_TRY(hipSetDevice(c->device));
-  rc = ds_upload_indices(c, idx, b);                  // refuses a bad index before anything of the resident batch is touched
-  if (rc) return rc;
-  if (b > c->b_cap) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    rc = size_batch_group(c, b);
-    if (rc != TNML_OK) return rc;
-  }
-  c->b = b;
-  // what tnml_set_input does after its host -> device copy, with the rows picked by index, on the device and without waiting
-  rc = ds_gather(c, c->ds_idx, b, c->b_pad, c->X, c->y);
-  if (rc) return rc;
-  c->have_input = true;
-  c->have_labels = true;
-  batch_changed(c);
-  return TNML_OK;
-}
-
-// Metrics group: the block partials of b_pad samples and the four accumulators (restarted by every call that uses them)
-static int ds_ensure_metrics(tnml_ctx *c, int b_pad) {
-  const int nblk = (b_pad + kDsMetricThreads - 1) / kDsMetricThreads;
-  if (nblk <= c->ds_part_cap) return TNML_OK;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  c->ds_part_cap = 0;
-  int rc = make_group(c, "the metrics partials", {own_dev(c->ds_part, (size_t)nblk * 4), own_dev(c->ds_acc, 4)});
-  if (rc) return rc;
-  c->ds_part_cap = nblk;
-  return TNML_OK;
-}
-
-static int ds_forward_allowed(tnml_ctx *c) { return pred_allowed(c); }
-
-extern "C" int tnml_predict_indices(tnml_ctx *c, const int32_t *idx, int b, float *f_out) {
-  int rc = ds_usable(c);
-  if (rc) return rc;
-  if (!idx || !f_out) return fail(TNML_ERR_ARG, "NULL argument");
-  if (b < 1) return fail(TNML_ERR_ARG, "empty batch");
-  if ((rc = ds_forward_allowed(c))) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  if ((rc = ds_upload_indices(c, idx, b))) return rc;
-  if ((rc = pred_ensure_buffers(c, (b + 63) / 64 * 64))) return rc;
-  if ((rc = load_chunk(c, nullptr, c->ds_idx, nullptr, 0, b, nullptr))) return rc;
-  if ((rc = pred_table(c))) return rc;
-  if ((rc = pred_chain(c, b))) return rc;
-  HIP_TRY(hipMemcpy2DAsync(f_out, (size_t)b * sizeof(float), c->fpred, (size_t)c->pred_cap * sizeof(float), (size_t)b * sizeof(float),
-                           c->L, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return TNML_OK;
-}
-
-static int ds_read_acc(tnml_ctx *c, double *out3) {
-  double acc[4] = {0, 0, 0, 0};
-  HIP_TRY(hipMemcpyAsync(acc, c->ds_acc, sizeof acc, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  out3[0] = acc[0]; out3[1] = acc[1]; out3[2] = acc[2];
-  return TNML_OK;
-}
-
-extern "C" int tnml_eval_indices(tnml_ctx *c, const int32_t *idx, int b, int act_fn, float T, double *out3) {
-  int rc = ds_usable(c);
-  if (rc) return rc;
-  if (!idx || !out3) return fail(TNML_ERR_ARG, "NULL argument");
-  if (b < 1) return fail(TNML_ERR_ARG, "empty index list");
-  if (act_fn < 0 || act_fn > 2) return fail(TNML_ERR_ARG, "unknown activation");
-  if (dataset_metrics_lds_bytes(c->L) > 64 * 1024) return fail(TNML_ERR_ARG, "metrics kernel: %d labels exceed its LDS tile", c->L);
-  if ((rc = ds_forward_allowed(c))) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  if ((rc = ds_upload_indices(c, idx, b))) return rc;
-  // chunks as wide as the prediction buffers (at least the resident batch's capacity); whole 256-sample blocks of the metrics
-  // kernel where they are wide enough, so that a sample's block does not depend on the chunking
-  if ((rc = pred_ensure_buffers(c, std::max({c->pred_cap, c->b_pad, 64})))) return rc;     // (64: both groups may be empty after a failed growth)
-  const int bpad = c->pred_cap;
-  const int chunk = bpad >= kDsMetricThreads ? bpad / kDsMetricThreads * kDsMetricThreads : bpad;
-  if ((rc = ds_ensure_metrics(c, bpad))) return rc;
-  if ((rc = pred_table(c))) return rc;
-  for (int off = 0; off < b; off += chunk) {
-    const int bc = std::min(chunk, b - off);
-    if ((rc = load_chunk(c, nullptr, c->ds_idx, nullptr, off, bc, c->ds_ypred))) return rc;
-    if ((rc = pred_chain(c, bc))) return rc;
-    if (!launch_dataset_metrics(c->fpred, c->ds_ypred, c->L, bc, bpad, act_fn, T, c->ds_part, off == 0, c->ds_acc, c->stream))
-      return fail(TNML_ERR_ARG, "internal: metrics launch refused");
-    HIP_TRY(hipGetLastError());
-  }
-  return ds_read_acc(c, out3);
-}
-
-extern "C" int tnml_resident_metrics(tnml_ctx *c, int act_fn, float T, double *out3) {
-  if (!c || !out3) return fail(TNML_ERR_ARG, "NULL argument");
-  if (c->comm) return fail(TNML_ERR_STATE, "the metrics of a sharded batch are not reduced over ranks: single-GPU only");
-  if (act_fn < 0 || act_fn > 2) return fail(TNML_ERR_ARG, "unknown activation");
-  if (!c->have_input || !c->have_labels) return fail(TNML_ERR_STATE, "no resident batch with labels");
-  if (!c->f_current) return fail(TNML_ERR_STATE, "no f on the device: call tnml_forward or tnml_sweep first");
-  if (dataset_metrics_lds_bytes(c->L) > 64 * 1024) return fail(TNML_ERR_ARG, "metrics kernel: %d labels exceed its LDS tile", c->L);
-  HIP_TRY(hipSetDevice(c->device));
-  int rc = ds_ensure_metrics(c, c->b_pad);
-  if (rc) return rc;
-  if (!launch_dataset_metrics(c->f, c->y, c->L, c->b, c->b_pad, act_fn, T, c->ds_part, 1, c->ds_acc, c->stream))
-    return fail(TNML_ERR_ARG, "internal: metrics launch refused");
-  HIP_TRY(hipGetLastError());
-  return ds_read_acc(c, out3);
-}
-
-extern "C" int tnml_dataset_read(tnml_ctx *c, const int32_t *idx, int b, float *X_out) {
-  int rc = ds_usable(c);
-  if (rc) return rc;
-  if (!idx || !X_out) return fail(TNML_ERR_ARG, "NULL argument");
-  if (b < 1) return fail(TNML_ERR_ARG, "empty index list");
-  HIP_TRY(hipSetDevice(c->device));
-  if ((rc = ds_upload_indices(c, idx, b))) return rc;
-  const int N = c->N, D = c->D, bp = (b + 63) / 64 * 64;
-  float *tmp = nullptr;                    // owned for the length of this call
-  if ((rc = make_group(c, "the gathered samples", {own_dev(tmp, (size_t)N * bp * D)}))) return rc;
-  rc = ds_gather(c, c->ds_idx, b, bp, tmp, nullptr);
-  std::vector<float> host;
-  if (!rc) {
-    host.resize((size_t)N * bp * D);
-    hipError_t e = hipMemcpyAsync(host.data(), tmp, host.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) rc = fail(TNML_ERR_HIP, "reading the gathered samples back failed: %s", hipGetErrorString(e));
-  } else {
-    (void)hipStreamSynchronize(c->stream);
-  }
-  c->own.release(tmp);
-  if (rc) return rc;
-  for (int s = 0; s < b; ++s)              // [N][bp][D] as the device forms it -> [b][N][D]
-    for (int n = 0; n < N; ++n)
-      memcpy(X_out + ((size_t)s * N + n) * D, host.data() + ((size_t)n * bp + s) * D, (size_t)D * sizeof(float));
   return TNML_OK;
 }
 
@@ -1970,287 +1290,6 @@ extern "C" int tnml_gd_step(tnml_ctx *c, const float *X, const int32_t *y, int b
 // ---------------------------------------------------------------------------------------------
 // norm environments of the side a sweep runs towards (only when not inherited from the last sweep)
 // ---------------------------------------------------------------------------------------------
-// ---------------------------------------------------------------------------------------------
-// orthogonal form about the label, compression, bond spectra (kernels_orth.hip)
-// ---------------------------------------------------------------------------------------------
-// Scratch group, on the first call: all of it or none (a failed allocation leaves it empty and the call repeatable)
-static int orth_ensure(tnml_ctx *c) {
-  if (c->orth.ready) return TNML_OK;
-  const size_t N = (size_t)c->N, cap = (size_t)c->Mmax;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  int rc = make_group(c, "the scratch of the orthogonal form", {
-      own_dev(c->orth.W, N * c->core_stride + c->lab_elems), own_dev(c->orth.Mbuf, c->lab_elems), own_dev(c->orth.aux, 4 * cap * cap),
-      own_dev(c->orth.sigma, N * cap), own_dev(c->orth.disc, N), own_dev(c->orth.result, 2),
-      own_dev(c->orth.out_cores, N * c->core_stride), own_dev(c->orth.out_lab, c->lab_elems),
-      own_dev(c->orth.ops, 3 * N + 2), own_dev(c->orth.bond, N), own_dev(c->orth.rank, N), own_dev(c->orth.status, 1)});
-  if (rc) return rc;
-  c->orth.ready = true;
-  return TNML_OK;
-}
-
-// mode 0: orthogonal form, 1: compression, 2: spectra only (nothing is committed)
-static int orth_impl(tnml_ctx *c, int mode, int m_max, double threshold, double rank_tol, int32_t *bond_out, double *sigma_out,
-                     double *discarded_out, double *log_norm_out) {
-  const char *what = mode == 0 ? "tnml_orthogonalize" : mode == 1 ? "tnml_compress" : "tnml_bond_spectra";
-  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
-  if (!bond_out || !log_norm_out || (mode != 0 && !sigma_out) || (mode == 1 && !discarded_out))
-    return fail(TNML_ERR_ARG, "%s: an output pointer is NULL", what);
-  if (mode == 1 && m_max < 1) return fail(TNML_ERR_ARG, "%s: m_max %d < 1", what, m_max);
-  if (mode == 1 && !(threshold > 0.0 && threshold <= 1.0)) return fail(TNML_ERR_ARG, "%s: threshold %g outside (0, 1]", what, threshold);
-  if (!(rank_tol >= 0.0 && rank_tol < 1.0)) return fail(TNML_ERR_ARG, "%s: rank_tol %g outside [0, 1)", what, rank_tol);
-  if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
-  if (c->comm) return fail(TNML_ERR_STATE, "%s runs on one GPU: this context has a communicator attached", what);
-  const int N = c->N, l = c->l_pos;
-  int mb = 1;
-  for (int i = 0; i < N - 1; ++i) mb = std::max(mb, c->bond[i]);
-  const size_t lds = orth_chain_lds_bytes(mb);
-  if (lds > kLdsMax)
-    return fail(TNML_ERR_SHAPE, "%s at bond %d: the Gram matrix and its eigenvectors take %zu bytes of LDS, beyond 160 KB", what, mb, lds);
-  HIP_TRY(hipSetDevice(c->device));
-  int rc = orth_ensure(c);
-  if (rc) return rc;
-  // the operations: every decomposition hands its carried factor to the next operation's site
-  std::vector<OrthOp> ops;
-  // (all three calls walk the same way -- centre to site 0, to site N-1 with the centre on every bond in turn, back to the label:
-  // a bond then ends at its Schmidt rank, not at the rank one side shows, and a second call keeps every bond)
-  const int cut = mode == 0 ? 0 : mode == 1 ? 2 : 1;
-  for (int i = N - 1; i > 0; --i) ops.push_back({i, kOrthLeft, 0, 0});      // rank rule only
-  for (int i = 0; i < N - 1; ++i) ops.push_back({i, kOrthRight, cut, 0});   // every bond with the centre on it
-  for (int i = N - 1; i > l; --i) ops.push_back({i, kOrthLeft, 0, 0});      // back to the label
-  ops.push_back({l, kOrthCentre, 0, 0});
-  OrthParams p{};
-  p.ops = c->orth.ops; p.n_ops = (int)ops.size();
-  p.N = N; p.D = c->D; p.L = c->L; p.l_pos = l;
-  p.bond = c->orth.bond; p.cores = c->cores; p.labcore = c->lab[c->lab_cur];
-  p.W = c->orth.W; p.Mbuf = c->orth.Mbuf; p.aux = c->orth.aux;
-  p.core_stride = c->core_stride; p.lab_elems = c->lab_elems; p.aux_stride = (size_t)c->Mmax * c->Mmax;
-  p.m_max = mode == 1 ? m_max : INT_MAX; p.threshold = mode == 1 ? threshold : 1.0; p.rank_tol = rank_tol;
-  p.sigma_out = c->orth.sigma; p.sigma_ld = c->Mmax; p.discarded_out = c->orth.disc; p.rank_out = c->orth.rank;
-  p.result = c->orth.result; p.status = c->orth.status;
-  p.out_cores = c->orth.out_cores; p.out_lab = c->orth.out_lab;
-  HIP_TRY(hipMemcpyAsync(c->orth.ops, ops.data(), ops.size() * sizeof(OrthOp), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->orth.bond, c->bond.data(), (size_t)(N - 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemsetAsync(c->orth.status, 0, sizeof(int), c->stream));
-  if (!launch_orth(p, mb, c->stream)) {
-    (void)hipStreamSynchronize(c->stream);                     // (the uploads read locals of this call)
-    return fail(TNML_ERR_SHAPE, "%s: the launch was refused (bond %d)", what, mb);
-  }
-  HIP_TRY(hipGetLastError());
-  int st = 0;
-  double res[2] = {0, 0};
-  std::vector<int> nb((size_t)N - 1), rk((size_t)N - 1);
-  HIP_TRY(hipMemcpyAsync(&st, c->orth.status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(res, c->orth.result, sizeof res, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(nb.data(), c->orth.bond, nb.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(rk.data(), c->orth.rank, rk.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));                    // (ops is a local: the upload has completed as well)
-  if (st == 1 || (st == 0 && !std::isfinite(res[0])))
-    return fail(TNML_ERR_NONFINITE, "%s: a core is not finite, beyond 1.8e19 in magnitude or zero, or the result does not fit float32", what);
-  if (st) return fail(TNML_ERR_NONFINITE, "%s: the Jacobi iteration or the re-orthogonalisation did not converge (status %d)", what, st);
-  for (int i = 0; i < N - 1; ++i)
-    if (nb[i] < 1 || nb[i] > c->bond[i]) return fail(TNML_ERR_STATE, "internal: %s produced bond %d at %d (was %d)", what, nb[i], i, c->bond[i]);
-  if (mode != 0) {
-    HIP_TRY(hipMemcpyAsync(sigma_out, c->orth.sigma, (size_t)(N - 1) * c->Mmax * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (mode == 1) HIP_TRY(hipMemcpyAsync(discarded_out, c->orth.disc, (size_t)(N - 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-  }
-  *log_norm_out = res[0];
-  if (mode == 2) {
-    for (int i = 0; i < N - 1; ++i) bond_out[i] = rk[i];
-    return TNML_OK;
-  }
-  // commit: device-to-device copy, then the bond table
-  HIP_TRY(hipMemcpyAsync(c->cores, c->orth.out_cores, (size_t)N * c->core_stride * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->lab[c->lab_cur], c->orth.out_lab, c->lab_elems * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-  c->bond = nb;
-  for (int i = 0; i < N - 1; ++i) bond_out[i] = nb[i];
-  cores_changed(c);
-  unbind_optimiser(c);                                          // vel / m / v refer to the old gauge
-  return TNML_OK;
-}
-
-extern "C" int tnml_orthogonalize(tnml_ctx *c, double rank_tol, int32_t *bond_out, double *log_norm_out) {
-  return orth_impl(c, 0, 0, 1.0, rank_tol, bond_out, nullptr, nullptr, log_norm_out);
-}
-
-extern "C" int tnml_compress(tnml_ctx *c, int m_max, double threshold, double rank_tol, int32_t *bond_out, double *sigma_out,
-                             double *discarded_out, double *log_norm_out) {
-  return orth_impl(c, 1, m_max, threshold, rank_tol, bond_out, sigma_out, discarded_out, log_norm_out);
-}
-
-extern "C" int tnml_bond_spectra(tnml_ctx *c, double rank_tol, int32_t *rank_out, double *sigma_out, double *log_norm_out) {
-  return orth_impl(c, 2, 0, 1.0, rank_tol, rank_out, sigma_out, nullptr, log_norm_out);
-}
-
-// ---------------------------------------------------------------------------------------------
-// inner products and linear combinations of two MPS (kernels_algebra.hip)
-// ---------------------------------------------------------------------------------------------
-// The group of the two calls, (re)sized when the second chain or a bond outgrows it: all of it or none
-static int alg_ensure(tnml_ctx *c, size_t v_floats, int mb) {
-  if (c->alg.v_cap >= v_floats && c->alg.m_cap >= mb && c->alg.m_cap > 0) return TNML_OK;
-  const size_t N = (size_t)c->N, D = (size_t)c->D;
-  const size_t v_cap = std::max(std::max(c->alg.v_cap, v_floats), (size_t)1);
-  const int m_cap = std::max(c->alg.m_cap, mb);
-  c->alg.v_cap = 0;
-  c->alg.m_cap = 0;
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  const size_t m2 = (size_t)m_cap * m_cap;
-  int rc = make_group(c, "the scratch of the inner products and linear combinations", {
-      own_dev(c->alg.V, v_cap), own_dev(c->alg.bond, 2 * N), own_dev(c->alg.off, 2 * N), own_dev(c->alg.metric, N * D * D),
-      own_dev(c->alg.stage, 12 * m2 * D), own_dev(c->alg.half_E, 6 * m2), own_dev(c->alg.half_expo, 8), own_dev(c->alg.out, 6),
-      own_dev(c->alg.out_cores, N * c->core_stride), own_dev(c->alg.out_lab, c->lab_elems), own_dev(c->alg.status, 1)});
-  if (rc) return rc;
-  c->alg.v_cap = v_cap;
-  c->alg.m_cap = m_cap;
-  return TNML_OK;
-}
-
-// what both calls check of the second chain; *mb_v: its largest bond
-static int alg_check_other(tnml_ctx *c, const char *what, size_t n_floats, const int32_t *other_bond, int other_l_pos, int *mb_v) {
-  if (!other_bond) return fail(TNML_ERR_ARG, "%s: other_bond is NULL", what);
-  if (other_l_pos != c->l_pos)
-    return fail(TNML_ERR_ARG, "%s: the second chain has its label on site %d, this context on site %d", what, other_l_pos, c->l_pos);
-  *mb_v = 1;
-  for (int i = 0; i < c->N - 1; ++i) {
-    if (other_bond[i] < 1) return fail(TNML_ERR_ARG, "%s: bond %d of the second chain is %d", what, i, other_bond[i]);
-    *mb_v = std::max(*mb_v, (int)other_bond[i]);
-  }
-  std::vector<int> nb(other_bond, other_bond + c->N - 1);
-  size_t total = 0;
-  for (int i = 0; i < c->N; ++i) total += core_elems(c, nb, i, c->l_pos);
-  if (total != n_floats) return fail(TNML_ERR_ARG, "%s: other_flat holds %zu floats, its bonds imply %zu", what, n_floats, total);
-  return TNML_OK;
-}
-
-// the tables of both chains and the second chain's cores to the device; the parameter block without the fields of one call
-static int alg_upload(tnml_ctx *c, const float *other_flat, size_t n_floats, const int32_t *other_bond, AlgebraParams *p) {
-  const int N = c->N;
-  c->alg.bond_host.assign(2 * (size_t)N, 1);
-  c->alg.off_host.assign(2 * (size_t)N, 0);
-  for (int i = 0; i < N - 1; ++i) c->alg.bond_host[i] = c->bond[i];
-  for (int i = 0; i < N; ++i) c->alg.off_host[i] = (long long)((size_t)i * c->core_stride);
-  size_t v_lab_off = 0;
-  if (other_flat) {
-    std::vector<int> nb(other_bond, other_bond + N - 1);
-    size_t off = 0;
-    for (int i = 0; i < N; ++i) {
-      if (i < N - 1) c->alg.bond_host[N - 1 + i] = nb[i];
-      c->alg.off_host[N + i] = (long long)off;
-      if (i == c->l_pos) v_lab_off = off;
-      off += core_elems(c, nb, i, c->l_pos);
-    }
-    HIP_TRY(hipMemcpyAsync(c->alg.V, other_flat, n_floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  }
-  HIP_TRY(hipMemcpyAsync(c->alg.bond, c->alg.bond_host.data(), 2 * (size_t)N * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->alg.off, c->alg.off_host.data(), 2 * (size_t)N * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemsetAsync(c->alg.status, 0, sizeof(int), c->stream));
-  *p = AlgebraParams{};
-  p->N = N; p->D = c->D; p->L = c->L; p->l_pos = c->l_pos;
-  p->n_prod = other_flat ? 3 : 1;
-  p->bond = c->alg.bond; p->off = c->alg.off;
-  p->w_plain = c->cores; p->w_lab = c->lab[c->lab_cur];
-  p->v_plain = other_flat ? c->alg.V : nullptr; p->v_lab = other_flat ? c->alg.V + v_lab_off : nullptr;
-  const size_t m2 = (size_t)c->alg.m_cap * c->alg.m_cap;
-  p->stage = c->alg.stage; p->stage_stride = m2 * c->D;
-  p->half_E = c->alg.half_E; p->half_stride = m2; p->half_expo = c->alg.half_expo;
-  p->out = c->alg.out; p->status = c->alg.status;
-  p->alpha = 1.0; p->beta = 1.0;
-  p->out_cores = c->alg.out_cores; p->out_lab = c->alg.out_lab;
-  p->core_stride = c->core_stride; p->lab_elems = c->lab_elems;
-  return TNML_OK;
-}
-
-extern "C" int tnml_inner(tnml_ctx *c, const float *other_flat, size_t n_floats, const int32_t *other_bond, int other_l_pos,
-                          const double *metric, int metric_sites, double *out6) {
-  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
-  if (!out6) return fail(TNML_ERR_ARG, "tnml_inner: out6 is NULL");
-  if (metric && metric_sites != 1 && metric_sites != c->N)
-    return fail(TNML_ERR_ARG, "tnml_inner: metric_sites %d is neither 1 nor N = %d", metric_sites, c->N);
-  int mb_v = 1;
-  if (other_flat) {
-    int rc = alg_check_other(c, "tnml_inner", n_floats, other_bond, other_l_pos, &mb_v);
-    if (rc) return rc;
-  }
-  if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
-  if (c->comm) return fail(TNML_ERR_STATE, "tnml_inner runs on one GPU: this context has a communicator attached");
-  int mb_w = 1;
-  for (int i = 0; i < c->N - 1; ++i) mb_w = std::max(mb_w, c->bond[i]);
-  if (!other_flat) mb_v = mb_w;
-  const size_t lds = algebra_chain_lds_bytes(mb_w, mb_v);
-  if (lds > kLdsMax)
-    return fail(TNML_ERR_SHAPE, "tnml_inner at bonds %d and %d: the transfer matrix and its product take %zu bytes of LDS, beyond 160 KB",
-                mb_w, mb_v, lds);
-  HIP_TRY(hipSetDevice(c->device));
-  int rc = alg_ensure(c, other_flat ? n_floats : 0, std::max(mb_w, mb_v));
-  if (rc) return rc;
-  AlgebraParams p;
-  rc = alg_upload(c, other_flat, n_floats, other_bond, &p);
-  if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-  if (metric) {
-    p.metric = c->alg.metric; p.metric_sites = metric_sites;
-    HIP_TRY(hipMemcpyAsync(c->alg.metric, metric, (size_t)metric_sites * c->D * c->D * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  }
-  if (!launch_inner(p, mb_w, mb_v, c->stream)) {
-    (void)hipStreamSynchronize(c->stream);                     // (the uploads read the caller's memory)
-    return fail(TNML_ERR_SHAPE, "tnml_inner: the launch was refused (bonds %d and %d)", mb_w, mb_v);
-  }
-  HIP_TRY(hipGetLastError());
-  int st = 0;
-  double res[6] = {0, 0, 0, 0, 0, 0};
-  HIP_TRY(hipMemcpyAsync(&st, c->alg.status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(res, c->alg.out, (size_t)2 * p.n_prod * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (st) return fail(TNML_ERR_NONFINITE, "tnml_inner: a core element is not finite");
-  for (int k = 0; k < 6; ++k) out6[k] = k < 2 * p.n_prod ? res[k] : (k % 2 ? -INFINITY : 0.0);
-  return TNML_OK;
-}
-
-extern "C" int tnml_axpby(tnml_ctx *c, double alpha, double beta, const float *other_flat, size_t n_floats,
-                          const int32_t *other_bond, int other_l_pos, int32_t *bond_out) {
-  if (!c) return fail(TNML_ERR_ARG, "ctx is NULL");
-  if (!bond_out || !other_flat) return fail(TNML_ERR_ARG, "tnml_axpby: %s is NULL", bond_out ? "other_flat" : "bond_out");
-  if (!std::isfinite(alpha) || !std::isfinite(beta)) return fail(TNML_ERR_ARG, "tnml_axpby: alpha %g or beta %g is not finite", alpha, beta);
-  int mb_v = 1;
-  int rc = alg_check_other(c, "tnml_axpby", n_floats, other_bond, other_l_pos, &mb_v);
-  if (rc) return rc;
-  if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
-  if (c->comm) return fail(TNML_ERR_STATE, "tnml_axpby runs on one GPU: this context has a communicator attached");
-  const int N = c->N;
-  std::vector<int> nb((size_t)N - 1);
-  int mb = 1;
-  for (int i = 0; i < N - 1; ++i) {
-    nb[i] = c->bond[i] + other_bond[i];
-    if (nb[i] > c->Mmax)
-      return fail(TNML_ERR_ARG, "tnml_axpby: bond %d would become %d + %d = %d, beyond the capacity %d of this context (created with M = %d)",
-                  i, c->bond[i], (int)other_bond[i], nb[i], c->Mmax, c->Mpol);
-    mb = std::max(mb, nb[i]);
-  }
-  HIP_TRY(hipSetDevice(c->device));
-  rc = alg_ensure(c, n_floats, mb);
-  if (rc) return rc;
-  AlgebraParams p;
-  rc = alg_upload(c, other_flat, n_floats, other_bond, &p);
-  if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-  p.alpha = alpha; p.beta = beta;
-  if (!launch_sum_place(p, c->stream)) {
-    (void)hipStreamSynchronize(c->stream);
-    return fail(TNML_ERR_SHAPE, "tnml_axpby: the launch was refused");
-  }
-  HIP_TRY(hipGetLastError());
-  int st = 0;
-  HIP_TRY(hipMemcpyAsync(&st, c->alg.status, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (st) return fail(TNML_ERR_NONFINITE, "tnml_axpby: an element of alpha W + beta V is not a finite float32");
-  // commit: device-to-device copy, then the bond table
-  HIP_TRY(hipMemcpyAsync(c->cores, c->alg.out_cores, (size_t)N * c->core_stride * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(c->lab[c->lab_cur], c->alg.out_lab, c->lab_elems * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-  c->bond = nb;
-  for (int i = 0; i < N - 1; ++i) bond_out[i] = nb[i];
-  cores_changed(c);
-  unbind_optimiser(c);                                          // vel / m / v refer to the old cores
-  return TNML_OK;
-}
-
 // ---------------------------------------------------------------------------------------------
 // samples and log-likelihoods of the Born distribution (kernels_sample.hip)
 // ---------------------------------------------------------------------------------------------

@@ -27,7 +27,10 @@ def test_every_pair_has_a_verdict():
     assert len(lc.MUTATORS) == 19 and len(lc.READERS) == 19 and len(lc.CONSUMERS) == 4
     for shape in lc.SHAPES:
         assert set(lc.LEFT_OUT[shape]) <= set(lc.CALLS)
-    api = open(os.path.join(CSRC, 'tnml_api.hip')).read()
+    host = re.compile(r'(?:tnml_api|api_\w+)\.hip')                  # the host files: the call families are split off one by one
+    files = {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if host.fullmatch(f)}
+    assert set(files) == {'tnml_api.hip', 'api_dataset.hip', 'api_mps.hip'}, sorted(files)
+    api = '\n'.join(files.values())                                 # a refusal may come from any call family
     for m in lc.MUTATORS:
         assert callable(lc.MUTATORS[m][0]) and lc.changes(m) in ('model', 'batch', 'labels', 'switch')
         for c in lc.CALLS:
@@ -35,14 +38,17 @@ def test_every_pair_has_a_verdict():
             assert kind in ('equal', 'refused', 'carried'), (m, c)
             if kind == 'refused':
                 assert remedy in ('forward', 'optim_reset') and c in lc.REFUSAL_WORDS, (m, c)
-                assert lc.REFUSAL_WORDS[c].split('%s')[0] in api, (c, 'the words of the refusal are not in tnml_api.hip')
+                assert lc.REFUSAL_WORDS[c].split('%s')[0] in api, (c, 'the words of the refusal are in no host file')
             if kind == 'carried':
-                assert cite and re.search(r'tnml_api\.hip, \w+', cite[0]) and cite[1], (m, c)
+                assert cite and re.search(host.pattern + r', \w+', cite[0]) and cite[1], (m, c)
             assert isinstance(lc.sensitive(m, c), bool)
     for (m, c), cite in lc.CARRIED.items():
         assert m in lc.MUTATORS and c in lc.CALLS
-        fn = re.search(r'tnml_api\.hip, (\w+)', cite[0]).group(1)
-        assert re.search(r'\b%s\(' % fn, api), (m, c, 'the cited function is not in tnml_api.hip')
+        cited = re.findall('(' + host.pattern + r'), (\w+)', cite[0])
+        assert cited, (m, c)
+        for name, fn in cited:                                      # every citation, in the file it names
+            assert name in files, (m, c, 'the cited file does not exist')
+            assert re.search(r'\b%s\(' % fn, files[name]), (m, c, 'the cited function is not in ' + name)
 
 
 def test_what_the_tables_say_about_known_pairs():

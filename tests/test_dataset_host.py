@@ -132,7 +132,7 @@ def test_network_without_a_dataset_says_so():
 
 
 def test_dataset_host_side_under_sanitizers():
-    """csrc/Makefile target `san-dataset`: tnml_api.hip's dataset entry points and the launch wrappers of kernels_dataset.hip,
+    """csrc/Makefile target `san-dataset`: api_dataset.hip's entry points and the launch wrappers of kernels_dataset.hip,
     built --cuda-host-only with -fsanitize=address,undefined, against the stand-in runtime of csrc/san/hip_stub.cpp
     (csrc/san/plan_dataset_main.cpp): both forms, ragged / one-sample / larger-than-capacity index batches, predict, evaluation of
     more samples than any buffer holds, detach and re-attach with another n, out-of-range and negative indices, at D = 2, 3 and 8;

@@ -144,6 +144,26 @@ def test_library_exports_every_declared_symbol():
     assert lib.tnml_version().startswith(b'tnml-hip')
 
 
+def test_library_exports_the_c_abi_and_nothing_else_unmangled():
+    """`nm -D --defined-only` of the built library: every function include/tnml.h declares is defined, and no other unmangled name of
+    the project's is exported -- the host files share their helpers (`fail`, `make_group`, ...) through csrc/tnml_host.h as hidden
+    members of namespace tnml, and a visible one could be interposed by another library of the process.  Mangled C++ names (`_Z...`)
+    cannot collide with a C symbol; other names with a leading underscore are reserved to the toolchain, which exports its own there
+    (one `__hip_cuid_<hash>` per translation unit, the linker's section marks)."""
+    import shutil
+    import subprocess
+    if shutil.which('nm') is None:
+        pytest.skip('no nm')
+    header = open(os.path.join(ROOT, 'include', 'tnml.h')).read()
+    declared = set(re.findall(r'\b(tnml_[A-Za-z0-9_]+)\s*\(', header)) - {'tnml_status'}
+    out = subprocess.run(['nm', '-D', '--defined-only', _hip.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1].split('@')[0] for line in out.splitlines() if line.strip()}
+    assert len(exported) > len(declared)                            # (the launch wrappers of namespace tnml are there, mangled)
+    assert not declared - exported, sorted(declared - exported)
+    unmangled = {s for s in exported if not s.startswith('_')}
+    assert unmangled == declared, sorted(unmangled ^ declared)
+
+
 def test_no_cpu_fallback():
     if _hip.device_count() > 0:
         pytest.skip('GPU present')
@@ -181,7 +201,7 @@ def test_random_init_matches_reference_draw_order():
 def test_host_side_under_sanitizers():
     """csrc/Makefile target `san`, both halves under -fsanitize=address,undefined:
       * the pure host arithmetic (truncation ranks, layout permutations: host_plan.inc) over a grid of shapes;
-      * the WHOLE host side of the library -- tnml_api.hip and the launch wrappers of kernels_*.hip, built --cuda-host-only --
+      * the WHOLE host side of the library -- tnml_api.hip, the api_*.hip files and the launch wrappers of kernels_*.hip, built --cuda-host-only --
         against the stand-in HIP / RCCL runtime of csrc/san/hip_stub.cpp, which checks every copy and the argument block of
         every launch (pointers AND the extents the kernels touch) against its allocation registry: whole sweeps of C2, C3
         and C5 at their true sizes in both directions through the C ABI, persistent / per-step / classic / large-tensor

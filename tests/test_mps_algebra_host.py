@@ -157,7 +157,7 @@ def test_calls_are_declared_exported_and_bound():
 
 
 def test_algebra_host_side_under_sanitizers():
-    """csrc/Makefile target `san-algebra`: tnml_inner / tnml_axpby of tnml_api.hip and the launch wrappers of kernels_algebra.hip,
+    """csrc/Makefile target `san-algebra`: tnml_inner / tnml_axpby of api_mps.hip and the launch wrappers of kernels_algebra.hip,
     built --cuda-host-only with -fsanitize=address,undefined, against the stand-in runtime of csrc/san/hip_stub.cpp
     (csrc/san/plan_algebra_main.cpp, a stand-alone program): C3 and C5 at true size with the label at both ends and inside, a ragged
     17-site chain with different bonds for W and V at every label position at D = 2, 3 and 8, N = 2, every refusal (none launches),

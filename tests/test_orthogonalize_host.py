@@ -125,7 +125,7 @@ def test_calls_are_declared_exported_and_bound():
 
 
 def test_orthogonal_form_host_side_under_sanitizers():
-    """csrc/Makefile target `san-orth`: the new calls of tnml_api.hip and the launch wrapper of kernels_orth.hip, built
+    """csrc/Makefile target `san-orth`: the calls of api_mps.hip and the launch wrapper of kernels_orth.hip, built
     --cuda-host-only with -fsanitize=address,undefined, against the stand-in runtime of csrc/san/hip_stub.cpp
     (csrc/san/plan_orth_main.cpp, a stand-alone program): C3 and C5 at true size, a ragged chain at every label position at
     D = 2, 3 and 8, all three calls, every refusal, the optimiser-state rule after a committed call, every allocation of the scratch
