@@ -697,6 +697,46 @@ int tnml_nll_train_indices(tnml_ctx *ctx, const int32_t *idx, int n, int batch, 
  * results are bit-equal.  Default 0 (DESIGN.md section 25 has the measurement).  on outside {0, 1}: TNML_ERR_ARG. */
 int tnml_set_nll_overlap(tnml_ctx *ctx, int on);
 
+/* ---- two-site likelihood sweep ------------------------------------------ */
+/* DMRG-style steps on the negative log-likelihood: the label sits on site l; a right step (left_dir 0) works on sites (p, p+1) with
+ * p = l, a left step on p = l - 1.  With B[a,d,e,c,l'] the product of the two cores, P / Q the per-sample chains behind / ahead of
+ * the pair and Lm = L_p, Rm = R_{p+2} the metric environments of tnml_log_norm_grad:
+ *   f[l',s] = sum P x_p x_{p+1} Q B,   cot as tnml_nll_grad,   Gd = sum_s cot P x_p x_{p+1} Q   (float32, matrix cores, fixed order)
+ *   T = Lm (S (x) S) B Rm,  Z_step = <B, T>,  Gz = 2 T / Z_step,  log Z = log|Z_step| + ln2 (expo_L[p] + expo_R[p+2])   (float64)
+ *   B' = B + lr (Gd - Gz);  renorm = 1: B' <- B' sqrt(sum B^2 / sum B'^2), no factor where sum B'^2 is 0 or not finite
+ *   split = tensor_svd's (U sqrt(S) behind, sqrt(S) Vh ahead with the label), B' rounded to float32 once where the SVD kernel takes
+ *   it; kept rank m = min(max_bond, short side of the merged matrix), and with threshold < 1 the fewest singular values whose
+ *   cumulative share sum_j<m sigma_j / sum sigma_j exceeds threshold (TNML_TRUNC_ADAPTIVE's rule), capped by that m.
+ * X, y (or NULL: the label is summed) and S ([D][D] or NULL) are tnml_nll_step's.  The call starts at the current l_pos -- any
+ * position, no tnml_set_any_position -- takes n_steps steps in the given direction and moves l_pos with them; a second call goes
+ * on where the first stopped.  It builds its own chains (the whole batch stays resident: one ahead stack of N x b_pad x capacity
+ * floats and the behind pair, no chunks) and stores nothing in the resident batch's stacks.
+ * values_out [n_steps][6]: { the value of tnml_nll_eval on the cores BEFORE the step, log Z before the step, samples whose cotangent
+ * is not finite, status bits (those of tnml_nll_step), the kept rank, the discarded weight sum_{j>=m} sigma_j^2 / sum sigma_j^2 }.
+ * With threshold < 1 the host learns the bond once per step (one wait per step); otherwise every step is enqueued without a wait and
+ * the call synchronises once.
+ * TRUNCATION WHEN THE LABEL MOVES.  The merged matrix has rank up to min(ml D, mr L) (right step), so with max_bond equal to the
+ * existing bond the split truncates even at lr = 0 and the value may RISE (by up to 1.9 nats on random chains of bond 4): this is
+ * the reference's sweep geometry.  A sweep meant to descend needs a max_bond that holds the full rank; threshold brings bonds back down.
+ * THE GUARD.  A step with a sample of f_y == 0, a non-finite cotangent or a bad norm term sets the sticky word of section 25; that
+ * step and every later step of the call hand B itself to the split (the rest of the call re-gauges and does not update), and the
+ * call returns TNML_ERR_NONFINITE naming the first bad step, with values_out filled.
+ * AFTER a call the context is as after tnml_compress: bonds and l_pos moved, the optimiser state unbound (tnml_optim_reset), the
+ * stacks and f of the resident batch stale (tnml_sweep / tnml_update_B return TNML_ERR_STATE until a tnml_forward).  Two calls with
+ * equal arguments on equal cores are bit-equal, and so is one call of n steps against two of k and n - k.
+ * REFUSALS, all before anything is launched: those of tnml_nll_grad(_indices); D != 2 (TNML_ERR_ARG: the generic-D update is not
+ * wired to this call); max_bond < 1 or above the context's bond capacity; threshold outside (0, 1]; renorm outside {0, 1};
+ * n_steps < 1; a step whose merged matrix has a short side above 128; a kernel that needs more than 160 KB of LDS (the message
+ * names the bytes); TNML_ERR_STATE for more steps than the chain has left in that direction and for a communicator. */
+int tnml_nll_sweep(tnml_ctx *ctx, const float *X, const int32_t *y, int b, const double *S, int left_dir, int n_steps, float lr,
+                   int renorm, int max_bond, double threshold, double *values_out);
+int tnml_nll_sweep_indices(tnml_ctx *ctx, const int32_t *idx, int b, int use_labels, const double *S, int left_dir, int n_steps,
+                           float lr, int renorm, int max_bond, double threshold, double *values_out);
+/* the last step of the last call, for tests: what = 0 B, 1 Gd, 2 Gz, 3 B_new as the split received it (canonical
+ * [ml][D][D][mr][L], float64), 4 sigma (descending, the short side's count).  TNML_ERR_STATE when no step has run. */
+enum { TNML_NLL_SWEEP_B = 0, TNML_NLL_SWEEP_GD = 1, TNML_NLL_SWEEP_GZ = 2, TNML_NLL_SWEEP_B_NEW = 3, TNML_NLL_SWEEP_SIGMA = 4 };
+int tnml_nll_sweep_debug(tnml_ctx *ctx, int what, double *out, size_t capacity, size_t *n);
+
 /* Host-side planning helper, exported so that CPU tests can check the bond bookkeeping without a
  * GPU: truncation rank kept by tensor_svd (Network_class.py:894-945) for a step on sites
  * (p, p+1).  Returns m >= 1, or TNML_ERR_SHAPE where the reference itself raises. */

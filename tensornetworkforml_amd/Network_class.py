@@ -1187,17 +1187,96 @@ class Network():
             self._after_device_update()
         return float(v[0]) + logw, float(v[1])
 
+    def nll_sweep(self, indices_or_X, y=None, labels=True, lr=1e-2, n_steps=None, left_dir=None, max_bond=None, threshold=1.0, renorm=True,
+                  levels=256, grid=None, weights=None):
+        """Two-site steps on the negative log-likelihood of one batch, on the device: merge the label site
+        with its neighbour, step on the merged tensor, split it by SVD and move the label -- the DMRG-style sweep of `sweep`, on the
+        objective of `nll_step`, with every bond set by the split.  indices_or_X, y, labels, the grid: as `nll_step`.  n_steps None:
+        to the end of the chain.  left_dir None: right from site 0, left from site N - 1, ValueError inside the chain.  max_bond
+        None: the network's M; threshold < 1: also the adaptive rank of trunc='adaptive'.
+        When the label moves, the merged matrix has rank up to min(ml D, mr L): with max_bond equal to the existing bond the split
+        truncates even at lr = 0 and the value can RISE (the reference's sweep geometry).  A sweep meant to descend needs a
+        max_bond that holds the full rank; threshold is the way to let bonds come back down.
+        Returns (values (n_steps, 6), bonds): per step the value BEFORE the step, log Z, samples with a non-finite cotangent, status
+        bits, kept rank, discarded weight; and the bond dimensions after the call.  A forward is needed before the next `sweep`."""
+        lp = self.l_pos
+        if left_dir is None:
+            if lp == 0:
+                left_dir = False
+            elif lp == self.N - 1:
+                left_dir = True
+            else:
+                raise ValueError('the label is on site %d, inside the chain: nll_sweep needs left_dir' % lp)
+        if n_steps is None:
+            n_steps = lp if left_dir else self.N - 1 - lp
+        max_bond = self.M if max_bond is None else int(max_bond)
+        if np.ndim(indices_or_X) == 1:
+            _, phi, w = self._pixel_grid(levels, grid, weights)
+            ctx = self._require_dataset()
+            try:
+                vals = ctx.nll_sweep_indices(np.asarray(indices_or_X), labels, np.einsum('k,kd,ke->de', w, phi, phi), left_dir, n_steps, lr,
+                                             renorm, max_bond, threshold)
+            finally:
+                self._after_device_update()
+        else:
+            feats, y, S, logw = self._likelihood_batch(indices_or_X, y, levels, grid, weights)
+            ctx = self._sync_to_device(max(self._b, 1))
+            try:
+                vals = ctx.nll_sweep(feats, y, S, left_dir, n_steps, lr, renorm, max_bond, threshold)
+            finally:
+                self._after_device_update()
+            vals[:, 0] += logw
+        return vals, [int(v) for v in ctx.bonds()[0]]
+
+    def _train_generative_sweep(self, ctx, train_index_loader, val_index_loader, lr, n_epochs, labels, renorm, S, max_bond, threshold):
+        """train_generative(method='sweep'): one full sweep per index batch, alternating direction"""
+        val_nll, hist = [], []
+        max_bond = self.M if max_bond is None else int(max_bond)
+        print("\n --- TRAINING PROCEDURE ---")
+        for epoch in range(n_epochs):
+            batches = [np.asarray(idx).ravel() for idx in train_index_loader]
+            nll = np.zeros(len(batches))
+            for i, idx in enumerate(batches):
+                lp = self.l_pos
+                if lp not in (0, self.N - 1):
+                    raise ValueError('the label is on site %d, inside the chain: a sweep starts from an end' % lp)
+                try:
+                    nll[i] = ctx.nll_sweep_indices(idx, labels, S, lp == self.N - 1, self.N - 1, lr, renorm, max_bond, threshold)[:, 0].mean()
+                finally:
+                    self._after_device_update()
+                print('\r' + "Epoch %d/%d - train NLL : %.4f - completed : %.2f "
+                      % (epoch, n_epochs, nll[i], (i + 1) * 100 / len(batches)) + '%', end=' ')
+            hist.append(nll)
+            sizes = np.array([len(idx) for idx in val_index_loader], dtype=np.float64)
+            epoch_val = np.array([ctx.nll_eval_indices(idx, labels, S)[0] for idx in val_index_loader])
+            val_nll.append(float((epoch_val * sizes).sum() / sizes.sum()) if len(sizes) else float('nan'))
+            print('\r' + "Epoch %d/%d - train NLL : %.4f - val NLL: %.4f - val accuracy: %.4f - largest bond: %d"
+                  % (epoch, n_epochs, nll.mean(), val_nll[-1], self.evaluate(val_index_loader)[0] if len(sizes) else float('nan'),
+                     int(ctx.bonds()[0].max())))
+        return val_nll, np.array(hist)
+
     def train_generative(self, train_index_loader, val_index_loader, lr, n_epochs=10, weight_dec=0.0, optimizer='sgd', momentum=0.0,
-                         betas=(0.9, 0.999), eps=1e-8, clip=True, labels=True, renorm=True, levels=256, grid=None, weights=None):
+                         betas=(0.9, 0.999), eps=1e-8, clip=True, labels=True, renorm=True, levels=256, grid=None, weights=None,
+                         method='gradient', max_bond=None, threshold=1.0):
         """Fit the model's own distribution p(x, l) (labels=False: p(x)) to the attached dataset by gradient descent on the negative
         log-likelihood over all cores: the generative companion of `train_gradient`, at fixed bonds and any label position.  Every
         batch of the index loader is one optimiser step; an epoch is one device call with one synchronisation (batches of one size,
         the last one may be shorter; a loader of mixed sizes takes a call per run of equal sizes).  The dataset's pixels must lie on
         the grid.  Prints train_gradient's lines with the mean training NLL, the validation NLL and the validation accuracy.
         Returns (val_nll, hist), hist of shape (n_epochs, n_batches): the NLL of every batch before its step (without the sum log w
-        term)."""
+        term).
+        method='sweep' (default 'gradient', the path above, untouched): every batch is one full two-site sweep of `nll_sweep`,
+        alternating direction, so that every bond is set by the split (max_bond, default M; threshold); weight_dec and the
+        optimiser arguments are not used, the lines printed end with the largest bond, and hist holds the mean over the steps of
+        a sweep.  See `nll_sweep` on max_bond: one that truncates lets the value rise."""
+        if method not in ('gradient', 'sweep'):
+            raise ValueError("method %r is neither 'gradient' nor 'sweep'" % (method,))
         ctx = self._require_dataset()
         self._check_forward_position(self.l_pos)
+        if method == 'sweep':
+            _, phi, w = self._pixel_grid(levels, grid, weights)
+            return self._train_generative_sweep(ctx, train_index_loader, val_index_loader, lr, n_epochs, labels, renorm,
+                                                np.einsum('k,kd,ke->de', w, phi, phi), max_bond, threshold)
         ctx.optim_config(optimizer, momentum, betas[0], betas[1], eps, clip and optimizer != 'adam')
         _, phi, w = self._pixel_grid(levels, grid, weights)
         S = np.einsum('k,kd,ke->de', w, phi, phi)

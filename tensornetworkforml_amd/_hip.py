@@ -46,7 +46,9 @@ SYMBOLS = [
     'tnml_sample', 'tnml_sample_masked', 'tnml_set_sample_stack_bytes', 'tnml_site_conditionals', 'tnml_pair_marginals',
     'tnml_get_bonds', 'tnml_log_norm_grad', 'tnml_nll_grad', 'tnml_nll_grad_indices', 'tnml_nll_eval', 'tnml_nll_eval_indices',
     'tnml_nll_step', 'tnml_nll_train_indices', 'tnml_set_nll_overlap',
+    'tnml_nll_sweep', 'tnml_nll_sweep_indices', 'tnml_nll_sweep_debug',
 ]
+NLL_SWEEP_DBG = {'B': 0, 'Gd': 1, 'Gz': 2, 'B_new': 3, 'sigma': 4}
 
 
 class TnmlError(RuntimeError):
@@ -167,6 +169,10 @@ def lib():
         L.tnml_nll_eval_indices.argtypes = [vp, i32p, C.c_int, C.c_int, f64p, f64p]
         L.tnml_nll_step.argtypes = [vp, f32p, i32p, C.c_int, f64p, C.c_float, C.c_float, C.c_int, f64p]
         L.tnml_nll_train_indices.argtypes = [vp, i32p, C.c_int, C.c_int, C.c_int, f64p, C.c_float, C.c_float, C.c_int, f64p]
+        L.tnml_nll_sweep.argtypes = [vp, f32p, i32p, C.c_int, f64p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_double, f64p]
+        L.tnml_nll_sweep_indices.argtypes = [vp, i32p, C.c_int, C.c_int, f64p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_double,
+                                             f64p]
+        L.tnml_nll_sweep_debug.argtypes = [vp, C.c_int, f64p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.tnml_set_nll_overlap.argtypes = [vp, C.c_int]
         _lib = L
     return _lib
@@ -795,6 +801,53 @@ class Context:
                                                       int(renorm),
                                                       _ptr(vals, C.c_double)), vals)
         return vals
+
+    # ---- two-site likelihood sweep
+    def bonds(self):
+        """(bonds (N - 1,), l_pos) from the host's bookkeeping: nothing is copied from the device"""
+        bond = np.empty(self.N - 1, dtype=np.int32)
+        lp = C.c_int()
+        _chk(lib().tnml_get_bonds(self._h, _ptr(bond, C.c_int32), C.byref(lp)))
+        return bond, lp.value
+
+    def nll_sweep(self, X, y=None, S=None, left_dir=False, n_steps=1, lr=1e-2, renorm=True, max_bond=None, threshold=1.0):
+        """n_steps two-site steps on -log p(x, y) (y given) or -log p(x) of a host batch X (b, N, D), from the current l_pos in the
+        given direction; the SVD of every step sets the bond (kept rank min(max_bond, short side), fewer under threshold < 1).
+        -> float64 (n_steps, 6): value before the step, log Z before the step, samples with a non-finite cotangent, status bits,
+        kept rank, discarded weight.  With max_bond equal to the existing bond a step truncates even at lr = 0 (the label changes
+        sides) and the value may rise: a sweep meant to descend needs a max_bond that holds the full rank."""
+        X = _f32(X)
+        assert X.ndim == 3 and X.shape[1] == self.N and X.shape[2] == self.D, \
+            "The 1 dimension of the input data must be the flattened number of pixels"
+        yp = None
+        if y is not None:
+            y = np.ascontiguousarray(y, dtype=np.int32)
+            assert y.shape == (X.shape[0],)
+            yp = _ptr(y, C.c_int32)
+        S, sp = self._grid_metric(S)
+        vals = np.zeros((max(int(n_steps), 1), 6), dtype=np.float64)
+        self._chk_values(lib().tnml_nll_sweep(self._h, _ptr(X, C.c_float), yp, X.shape[0], sp, int(bool(left_dir)), int(n_steps), float(lr),
+                                              int(renorm), int(self.M if max_bond is None else max_bond), float(threshold),
+                                              _ptr(vals, C.c_double)), vals)
+        return vals
+
+    def nll_sweep_indices(self, idx, labels=True, S=None, left_dir=False, n_steps=1, lr=1e-2, renorm=True, max_bond=None, threshold=1.0):
+        """The same for the dataset samples idx, with the dataset's labels or without."""
+        idx = self._idx(idx)
+        S, sp = self._grid_metric(S)
+        vals = np.zeros((max(int(n_steps), 1), 6), dtype=np.float64)
+        self._chk_values(lib().tnml_nll_sweep_indices(self._h, _ptr(idx, C.c_int32), idx.size, int(bool(labels)), sp, int(bool(left_dir)),
+                                                      int(n_steps), float(lr), int(renorm), int(self.M if max_bond is None else max_bond),
+                                                      float(threshold), _ptr(vals, C.c_double)), vals)
+        return vals
+
+    def nll_sweep_debug(self, what):
+        """'B', 'Gd', 'Gz', 'B_new' (flat float64, canonical (ml, D, D, mr, L)) or 'sigma' of the last step of the last sweep call"""
+        cap = self.bond_capacity ** 2 * self.D * self.D * self.L + 128
+        out = np.zeros(cap, dtype=np.float64)
+        n = C.c_size_t()
+        _chk(lib().tnml_nll_sweep_debug(self._h, NLL_SWEEP_DBG[what], _ptr(out, C.c_double), out.size, C.byref(n)))
+        return out[:n.value].copy()
 
     def set_nll_overlap(self, on):
         """The norm walk of a likelihood step on a second stream beside the step's chunks (bit-equal results either way)."""

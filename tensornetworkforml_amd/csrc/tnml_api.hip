@@ -153,7 +153,7 @@ extern "C" int tnml_destroy(tnml_ctx *c) {
 }
 
 // the device status word is sticky: read and clear it (the stream must be idle)
-static int check_status(tnml_ctx *c) {
+int tnml::check_status(tnml_ctx *c) {
   int st = 0;
   HIP_TRY(hipMemcpy(&st, c->status, sizeof(int), hipMemcpyDeviceToHost));
   if (!st) return TNML_OK;
@@ -928,7 +928,7 @@ extern "C" int tnml_set_input_grad_chunk(tnml_ctx *c, int samples) {
 // ---------------------------------------------------------------------------------------------
 // The table of CoreGradParams for the current cores: tab[0 .. N-2] the bonds, tab[N + i] the offset of core i in the flat layout of
 // tnml_get_cores; total: the floats of that layout, mb: the largest bond.  `what` names the call in the refusal.
-static int grad_table(const tnml_ctx *c, const char *what, std::vector<int> &tab, size_t &total, int &mb) {
+int tnml::grad_table(const tnml_ctx *c, const char *what, std::vector<int> &tab, size_t &total, int &mb) {
   const int N = c->N;
   tab.assign(2 * (size_t)N, 0);
   total = 0;
@@ -1099,12 +1099,7 @@ struct TrainObjective {
   int renorm;                // likelihood: the third pass of the update kernel
 };
 
-static int lnz_check(const tnml_ctx *c, const char *what, const double *S, int n_metric, int mb);      // (with the norm term, below)
-static int lnz_ensure(tnml_ctx *c, int mb, bool want_G);
-static int lnz_upload(tnml_ctx *c, const std::vector<int> &tab_host, const double *S, int n_metric, bool wait);
-static int lnz_launch_env(tnml_ctx *c, int n_metric, int mb, hipStream_t st);
-static int lnz_launch_grad(tnml_ctx *c, int n_metric, int mb, int mode, float *G);
-static int nll_ensure(tnml_ctx *c, int n);
+static int lnz_launch_grad(tnml_ctx *c, int n_metric, int mb, int mode, float *G);      // (with the norm term, below)
 
 static int nst_ensure(tnml_ctx *c, int n_steps) {
   if (n_steps <= c->nst.cap) return TNML_OK;
@@ -1713,7 +1708,7 @@ extern "C" int tnml_site_conditionals(tnml_ctx *c, int n, int K, const double *p
 // ---------------------------------------------------------------------------------------------
 // The group of the call, (re)sized when a bond outgrows it: all of it or none
 // (want_G: the gradient of its own that tnml_log_norm_grad stores to; the likelihood calls subtract into cg_G and do without)
-static int lnz_ensure(tnml_ctx *c, int mb, bool want_G) {
+int tnml::lnz_ensure(tnml_ctx *c, int mb, bool want_G) {
   if (c->lnz.m_cap >= mb && c->lnz.m_cap > 0 && (!want_G || c->lnz.G)) return TNML_OK;
   mb = std::max(mb, c->lnz.m_cap);
   want_G = want_G || c->lnz.G;                                  // (once there, it stays a member)
@@ -1730,7 +1725,7 @@ static int lnz_ensure(tnml_ctx *c, int mb, bool want_G) {
 }
 
 // what the calls refuse of a metric ([D][D] per site, n_metric of them) and of the bonds, before anything is launched
-static int lnz_check(const tnml_ctx *c, const char *what, const double *S, int n_metric, int mb) {
+int tnml::lnz_check(const tnml_ctx *c, const char *what, const double *S, int n_metric, int mb) {
   const int D = c->D;
   for (int i = 0; i < n_metric; ++i)
     for (int d = 0; d < D; ++d)
@@ -1764,7 +1759,7 @@ static LogNormParams lnz_params(const tnml_ctx *c, int n_metric, int mode, float
   return p;
 }
 
-static int lnz_upload(tnml_ctx *c, const std::vector<int> &tab_host, const double *S, int n_metric, bool wait) {
+int tnml::lnz_upload(tnml_ctx *c, const std::vector<int> &tab_host, const double *S, int n_metric, bool wait) {
   auto &g = c->lnz;
   const int D = c->D;
   HIP_TRY(hipMemcpyAsync(g.tab, tab_host.data(), tab_host.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -1777,7 +1772,7 @@ static int lnz_upload(tnml_ctx *c, const std::vector<int> &tab_host, const doubl
 }
 
 // (the steps of a training call: every step clears the words the one before it left, on the stream of its environment kernel)
-static int lnz_launch_env(tnml_ctx *c, int n_metric, int mb, hipStream_t st) {
+int tnml::lnz_launch_env(tnml_ctx *c, int n_metric, int mb, hipStream_t st) {
   HIP_TRY(hipMemsetAsync(c->lnz.status, 0, 2 * sizeof(int), st));
   if (!launch_lognorm_env(lnz_params(c, n_metric, 0, nullptr), mb, st)) return fail(TNML_ERR_ARG, "internal: log-norm environment launch refused (bond %d)", mb);
   HIP_TRY(hipGetLastError());
@@ -1969,7 +1964,7 @@ extern "C" int tnml_pair_marginals(tnml_ctx *c, int K, const double *phi, const 
 // the negative log-likelihood of a batch and its gradient over all cores (layer 2)
 // ---------------------------------------------------------------------------------------------
 // per-sample terms and flags of a call, and the two sums: one group sized from the samples of a call
-static int nll_ensure(tnml_ctx *c, int n) {
+int tnml::nll_ensure(tnml_ctx *c, int n) {
   if (n <= c->nll.n_cap) return TNML_OK;
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->nll.n_cap = 0;
@@ -2122,7 +2117,7 @@ static int ensure_big(tnml_ctx *c) {
 }
 
 // which path a step of these dimensions takes: 0 in-LDS, 1 large-tensor, <0 error already reported
-static int narrow_path(const tnml_ctx *c, int h, int g, int s, int L, int m) {
+int tnml::narrow_path(const tnml_ctx *c, int h, int g, int s, int L, int m) {
   const bool force_big = c->force_big;
   const int r = kD * h, cc = kD * g * L, nn = std::min(r, cc);
   const size_t lds = narrow_lds_bytes(h, g, s, L, m);
@@ -2133,8 +2128,8 @@ static int narrow_path(const tnml_ctx *c, int h, int g, int s, int L, int m) {
   return 1;
 }
 
-static int run_narrow(tnml_ctx *c, NarrowParams &n, int path, bool skip_prep = false, hipEvent_t after_update = nullptr,
-                      const BigFront *front = nullptr, unsigned *sig_flag = nullptr, unsigned sig_val = 0) {
+int tnml::run_narrow(tnml_ctx *c, NarrowParams &n, int path, bool skip_prep, hipEvent_t after_update, const BigFront *front,
+                     unsigned *sig_flag, unsigned sig_val) {
   if (path == 0) {
     size_t lds = narrow_lds_bytes(n.h, n.g, n.s, n.L, n.m);
     if (n.fused && !n.prep_ready) lds = std::max(lds, prep_slice_lds_bytes(n.h, n.g, n.s, n.L));   // slice workgroups ride along

@@ -406,6 +406,20 @@ struct tnml_ctx {
     std::vector<int> tab_host, rows_host, sites_host;   // host copies for the call in flight (they outlive the asynchronous uploads)
     std::vector<double> hostd;               // S, the values, phi, w
   } pair;
+  // two-site likelihood sweep.  One group of its own, regrown when a call needs more samples, a larger bond
+  // or more steps: the ahead stack [N][m_cap][b_cap] and the behind pair of the per-sample chains, the partial and reduced data
+  // gradient, the merged tensor (float64, float32, and what the split receives), the update's scratch and capture block, the
+  // records, the site tables, the metric and the sticky guard word.
+  struct {
+    float *stack = nullptr, *behind[2] = {nullptr, nullptr}, *slabs = nullptr, *Gd = nullptr, *B32 = nullptr, *Bout = nullptr;
+    double *B64 = nullptr, *T1 = nullptr, *T2 = nullptr, *dbg = nullptr, *rec = nullptr, *metric = nullptr, *sigma = nullptr;
+    NllSweepSite *sites = nullptr;
+    int *skip = nullptr;
+    int b_cap = 0, m_cap = 0, steps_cap = 0;
+    int last_h = 0, last_g = 0, last_nn = 0, last_left = 0;   // the last step of the last call (tnml_nll_sweep_debug); 0: none
+    std::vector<NllSweepSite> sites_host;    // host copies for the call in flight (they outlive the asynchronous uploads)
+    std::vector<double> metric_host;
+  } nsw;
   // multi-GPU
   ncclComm_t comm = nullptr;
   int rank = 0, nranks = 1;
@@ -470,6 +484,18 @@ int ds_usable(tnml_ctx *c);
 int ds_upload_indices(tnml_ctx *c, const int32_t *idx, int b);
 int ds_ensure_metrics(tnml_ctx *c, int b_pad);
 int load_chunk(tnml_ctx *c, const float *X, const int *idx_dev, const int32_t *y, int off, int bc, int *y_out);
+// what the two-site likelihood sweep (nll_sweep_host.hip) borrows: the sticky status word, the table of the gradient calls, the norm
+// term's checks, group, upload and environment launch, the per-sample terms, and the launch wrappers of the update / SVD kernels
+int check_status(tnml_ctx *c);
+int grad_table(const tnml_ctx *c, const char *what, std::vector<int> &tab, size_t &total, int &mb);
+int lnz_check(const tnml_ctx *c, const char *what, const double *S, int n_metric, int mb);
+int lnz_ensure(tnml_ctx *c, int mb, bool want_G);
+int lnz_upload(tnml_ctx *c, const std::vector<int> &tab_host, const double *S, int n_metric, bool wait);
+int lnz_launch_env(tnml_ctx *c, int n_metric, int mb, hipStream_t st);
+int nll_ensure(tnml_ctx *c, int n);
+int narrow_path(const tnml_ctx *c, int h, int g, int s, int L, int m);
+int run_narrow(tnml_ctx *c, NarrowParams &n, int path, bool skip_prep = false, hipEvent_t after_update = nullptr,
+               const BigFront *front = nullptr, unsigned *sig_flag = nullptr, unsigned sig_val = 0);
 }  // namespace tnml
 
 #pragma GCC visibility pop

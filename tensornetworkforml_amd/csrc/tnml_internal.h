@@ -632,4 +632,91 @@ int pair_walk_threads(int mb);
 bool launch_pair_close(const PairParams &p, int mb, hipStream_t st);
 bool launch_pair_rows(const PairParams &p, int mb, hipStream_t st);
 
+// Two-site likelihood sweep (kernels_nll_sweep.hip).  Everything is in the sweep-relative frame of section 4:
+// the step merges relative sites (k, k + 1), `behind` is the chain over the sites the sweep has left, `ahead` the chain over the
+// sites in front of the pair; the merged tensor is B[h][dk][dk1][g][l] (the relative layout of NarrowParams::Bdirect).
+constexpr int kNllsTile = 64;            // samples per workgroup of the chain and batch kernels
+constexpr int kNllsThreads = 256;
+constexpr int kNllsUpdThreads = 1024;
+constexpr int kNllsRec = 6;              // values per step: the record of tnml_nll_sweep
+// one site of a per-sample walk: out[o][s] = sum_{i, d} (in[i][s] x[s][d]) A(i, d, o)
+struct NllSweepSite {
+  long long core_off;      // float offset of the plain core from `cores`
+  long long out_off;       // float offset of the produced environment from `stack`, -1: not stored
+  int n_in, n_out, s_in, s_d, s_out;
+  int x_site;              // absolute site whose features are contracted
+};
+struct NllSweepChainParams {
+  const NllSweepSite *sites;   // [n_sites] in walk order
+  int n_sites;
+  const float *cores;
+  const float *X;          // [N][x_bpad][D]
+  float *stack;
+  long long init_off;      // float offset of the slot that receives the walk's start (ones), -1: not stored
+  float *last_out;         // [n_out of the last site][b_pad] the walk's end (ones for an empty walk), or nullptr
+  int b_pad, x_bpad, D, cap;   // cap: the largest environment of the walk (LDS geometry)
+};
+struct NllSweepMergeParams {
+  CoreView lab, pl;        // as NarrowParams: A(h, d, s, l) of the label site, A(s, d, g) of the site ahead
+  int h, g, s, D, L;
+  double *B64;             // [h][D][D][g][L]
+  float *B32;
+};
+struct NllSweepBatchParams {
+  int b, b_pad, x_bpad, D, L, batch;
+  int h, g, hp;            // behind / ahead bond of this step, behind bond of the step before (do_ext)
+  int do_ext;              // the behind chain is extended by the core the step before left: Hcur = (Hprev x_km1) . ext_core
+  const float *x_km1, *x_k, *x_kp1;   // [x_bpad][D]
+  const float *Hprev;      // [hp][b_pad]
+  float *Hcur;             // [h][b_pad]: read (do_ext == 0) or written
+  CoreView ext_core;       // A(hp, d, h)
+  const float *G;          // [g][b_pad] ahead chain
+  const float *B32;        // merged tensor, relative layout
+  const int *y;            // [b] labels, or nullptr: the label is summed
+  float *slabs;            // [tiles][bsize] partial Gd of every workgroup
+  double *terms;           // [b] log f_y^2 or log sum_l f_l^2
+  int *bad;                // [b] 1 where a cotangent or the term is not finite
+};
+struct NllSweepUpdateParams {
+  int D, L, h, g, bsize, batch, renorm;
+  float lr;
+  const double *B64;
+  const float *Gd;         // [bsize] reduced data gradient
+  const double *Nh, *Ng;   // behind (h x h) and ahead (g x g) metric environments with their running exponents
+  const int *expH, *expG;
+  const double *S;         // [D][D] or nullptr
+  const double *acc;       // {sum of the batch's terms, samples with a bad cotangent}
+  const int *env_status;   // status word of the environment launch
+  double *T1, *T2;         // [bsize] scratch
+  float *Bout;             // [bsize] what the split receives as Bdirect
+  double *dbg;             // [4][bsize] B, Gd, Gz, B_new
+  double *rec;             // [kNllsRec] of this step
+  int *skip;               // sticky guard word of the call
+};
+struct NllSweepExtendParams {
+  int right_walk;          // 1: R_i from R_{i+1} (a left step), 0: L_{i+1} from L_i (a right step)
+  int ml, mr, D, lds_m;    // the plain core [ml][D][mr] the step left behind; lds_m: LDS geometry (the launch function fills it)
+  const int *m_dev;        // the kept rank on the device (adaptive truncation) or nullptr: it replaces mr (right step) / ml (left step)
+  const float *core;
+  const double *S;         // [D][D] or nullptr
+  const double *Ein; double *Eout;   // dense square environments
+  const int *exp_in; int *exp_out;
+  const double *sigma;     // [n_sigma] singular values of the split, descending
+  int n_sigma, m_fixed;
+  double *sigma_out;       // [n_sigma] a copy that outlives the capture block of the SVD kernels
+  double *rec;             // the step's record: [4] kept rank, [5] discarded weight
+  int *status;             // bit 1: a non-finite environment
+};
+size_t nll_sweep_chain_lds_bytes(int cap, int D);
+size_t nll_sweep_batch_lds_bytes(int h, int g, int hp, int D, int L);
+size_t nll_sweep_update_lds_bytes();
+size_t nll_sweep_extend_lds_bytes(int mb, int D);
+// false: refused (geometry / LDS)
+bool launch_nll_sweep_chain(const NllSweepChainParams &p, int tiles, hipStream_t st);
+bool launch_nll_sweep_merge(const NllSweepMergeParams &p, hipStream_t st);
+bool launch_nll_sweep_batch(const NllSweepBatchParams &p, int tiles, hipStream_t st);
+bool launch_nll_sweep_reduce(const float *slabs, int tiles, int bsize, float *Gd, hipStream_t st);
+bool launch_nll_sweep_update(const NllSweepUpdateParams &p, hipStream_t st);
+bool launch_nll_sweep_extend(const NllSweepExtendParams &p, int mb, hipStream_t st);
+
 }  // namespace tnml

@@ -44,6 +44,12 @@ def main(argv=None):
                          '(Network.train_generative; needs --resident; --optimizer defaults to sgd)')
     ap.add_argument('--no-renorm', dest='renorm', action='store_false',
                     help='likelihood steps without the renormalisation of the cores (needs --objective nll)')
+    ap.add_argument('--method', type=str, default='gradient', choices=['gradient', 'sweep'],
+                    help='sweep: likelihood training by two-site sweeps whose SVD sets every bond (Network.nll_sweep; needs --objective nll)')
+    ap.add_argument('--max-bond', dest='max_bond', type=int, default=None, metavar='M',
+                    help='largest bond a likelihood sweep may keep (default --M; needs --method sweep)')
+    ap.add_argument('--threshold', type=float, default=1.0, metavar='T',
+                    help='adaptive truncation threshold of a likelihood sweep in (0, 1] (needs --method sweep)')
     ap.add_argument('--compress', type=int, default=None, metavar='M',
                     help='after training, cut every bond to M on its Schmidt decomposition (Network.compress; needs --resident)')
     ap.add_argument('--scaled-chains', dest='scaled_chains', action='store_true',
@@ -60,6 +66,10 @@ def main(argv=None):
         ap.error('--no-renorm needs --objective nll')
     if args.objective == 'nll' and args.optimizer is None:
         args.optimizer = 'sgd'
+    if args.method == 'sweep' and args.objective != 'nll':
+        ap.error('--method sweep needs --objective nll')
+    if (args.max_bond is not None or args.threshold != 1.0) and args.method != 'sweep':
+        ap.error('--max-bond and --threshold need --method sweep')
     if args.scaled_chains and args.optimizer is None:
         ap.error('--scaled-chains needs --resident --optimizer')
     if args.steps_per_batch is not None and not args.resident:
@@ -82,7 +92,8 @@ def main(argv=None):
         if args.objective == 'nll':
             net.scaled_chains = args.scaled_chains
             val_nll, nll_hist = net.train_generative(train_idx, val_idx, lr=args.lr, n_epochs=args.n_epochs, weight_dec=args.L2_decay,
-                                                     optimizer=args.optimizer, renorm=args.renorm)
+                                                     optimizer=args.optimizer, renorm=args.renorm, method=args.method,
+                                                     max_bond=args.max_bond, threshold=args.threshold)
             with open(args.out, 'wb') as fh:
                 pickle.dump(net, fh)
             print('validation NLL per epoch:', ['%.4f' % v for v in val_nll])

@@ -1,13 +1,13 @@
 #!/bin/bash
 # Register and scratch use of every kernel, from the compiler's own remarks (-Rpass-analysis=kernel-resource-usage) on the
-# kernel files that carry the sweep step, the input gradients, the core gradients, the optimiser step, the orthogonal form, the scaled prediction, the MPS algebra, the two samplers, the likelihood gradients, the per-pixel conditionals and the pair marginals: one line per kernel.  Device pass only, nothing is linked or written.
+# kernel files that carry the sweep step, the input gradients, the core gradients, the optimiser step, the orthogonal form, the scaled prediction, the MPS algebra, the two samplers, the likelihood gradients, the per-pixel conditionals, the pair marginals and the likelihood sweep: one line per kernel.  Device pass only, nothing is linked or written.
 # Usage: tools/resource_usage.sh [substring of file:kernel ...]     (no argument: every kernel)
 set -e -o pipefail
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 ARCH=${ARCH:-gfx950}
 cd "$(dirname "$0")/../tensornetworkforml_amd/csrc"
 printf '%-44s %6s %6s %6s %11s %11s %9s %6s\n' kernel SGPRs VGPRs AGPRs SGPR-spill VGPR-spill scratch-B LDS-B
-for f in kernels_narrow kernels_wide kernels_big kernels_anyd kernels_inputgrad kernels_coregrad kernels_optim kernels_orth kernels_scaled kernels_algebra kernels_sample kernels_sample_masked kernels_nll kernels_site_cond kernels_pair; do
+for f in kernels_narrow kernels_wide kernels_big kernels_anyd kernels_inputgrad kernels_coregrad kernels_optim kernels_orth kernels_scaled kernels_algebra kernels_sample kernels_sample_masked kernels_nll kernels_site_cond kernels_pair kernels_nll_sweep; do
   $HIPCC -O3 -std=c++17 -fPIC --offload-arch=$ARCH -I/opt/rocm/include --cuda-device-only -Rpass-analysis=kernel-resource-usage \
       -c $f.hip -o /dev/null 2>&1 | ${CXXFILT:-c++filt} |
   awk -v file=$f -v want="$*" '
