@@ -737,6 +737,43 @@ int tnml_nll_sweep_indices(tnml_ctx *ctx, const int32_t *idx, int b, int use_lab
 enum { TNML_NLL_SWEEP_B = 0, TNML_NLL_SWEEP_GD = 1, TNML_NLL_SWEEP_GZ = 2, TNML_NLL_SWEEP_B_NEW = 3, TNML_NLL_SWEEP_SIGMA = 4 };
 int tnml_nll_sweep_debug(tnml_ctx *ctx, int what, double *out, size_t capacity, size_t *n);
 
+/* ---- likelihood training from incomplete data --------------------------- */
+/* The gradient of log p(x_G [, c]) over all cores, x_G the known pixels of a sample: every sample has its own mask and its own
+ * optional label.  n, K, phi, w, mask, mask_rows and known are tnml_sample_masked's; classes [n] (or NULL: all -1) holds the label of
+ * a sample, or -1 where it is unknown and summed -- the JOINT probability p(x_G, c), not the conditional.  With S_{s,i} = w_k phi_k
+ * phi_k^T on a known site and S = sum_k w_k phi_k phi_k^T on a free one, R_{s,i} / Lf_{s,i} the per-sample environments of
+ * tnml_sample_masked / tnml_site_conditionals (all label slices for class -1, slice c alone otherwise), E_s = log R_{s,0} + ln2 (sum
+ * of the exponents), and log Z = E of the empty mask with class -1:
+ *   value   = -mean_s (E_s - log Z) = -mean_s log p(x_G,s [, c_s])        (it carries the w_k of the known sites)
+ *   g_s,i[a,d,c(,l')] = 2 / n_s,i  sum Lf_s,i[a,a'] S_s,i[d,d'] A_i[a',d',c'(,l')] R_s,i+1[c,c'],    n_s,i = <that contraction, A_i>
+ *   G_i     = (1/n) sum_s g_s,i - g_empty,i                                (the DESCENT direction: cores + lr G lowers the value)
+ * n_s,i is formed per site from the same rescaled environments, so that no exponent enters the gradient.  sum(G_i A_i) = 0 at every
+ * site.  Float64 throughout from the float32 cores, the sum over the samples of a tile inside the matrix cores' k-loop, the tiles
+ * added in ascending order, ONE rounding to float32 per element: two equal calls are bit-equal, and the result does not depend on
+ * the stack budget or the number of chunks (it may depend on the tile T, which the shape fixes: the largest of 16, 8, 4, 2, 1 at
+ * which both kernels fit 160 KB of LDS).  Per tile of a chunk the call needs T (N + 1) m^2 doubles of stack and one partial gradient
+ * of tnml_cores_size doubles; both count against tnml_set_sample_stack_bytes.
+ * grad_flat (layout of tnml_get_cores, capacity in floats) or NULL: the value alone, only the environments run.  logp_out [n] or
+ * NULL: E_s - log Z.  out4 = { value, log Z, samples with E_s = -inf or not finite, status bits }; bits: 1 a non-finite environment,
+ * 2 a per-site normaliser that is not positive and finite, 4 a gradient element beyond float32.
+ * The cost is O(n N m^3 D) float64 and (N + 1) m^2 doubles of stack a sample: fully observed, uniformly labelled batches should keep
+ * using tnml_nll_grad.  Nothing on the device changes but the call's own buffers and the scratch of tnml_sample_masked.
+ * Refused before anything is launched: the list of tnml_sample_masked (without its output and uniform rules), TNML_ERR_ARG for a NULL
+ * out4, a capacity below tnml_cores_size, a budget below one tile's need; TNML_ERR_SHAPE for a bond above 64, or LDS: the message
+ * names the bytes.  After the run: TNML_ERR_NONFINITE naming the count of bad samples (or log Z, or the status bits), with out4
+ * written and grad_flat not. */
+int tnml_nll_masked_grad(tnml_ctx *ctx, int n, int K, const double *phi, const double *w, const int32_t *classes, const uint8_t *mask,
+                         int mask_rows, const int32_t *known, float *grad_flat, size_t capacity, double *logp_out, double *out4);
+/* One optimiser step on that gradient: the optimiser of tnml_optim_config, its state rules and renorm as tnml_nll_step, the update
+ * kernel of tnml_gd_step.  values4 = out4 of the gradient BEFORE the step, its bits joined by 8 (a batch with a bad sample) and 16
+ * (the step was NOT applied).  THE GUARD: the call waits for the gradient once; a bad batch (a sample of zero weight, a status bit)
+ * returns TNML_ERR_NONFINITE before the update is enqueued, with cores, state and Adam's t untouched.  AFTER an applied step the
+ * context is as after tnml_gd_step: the stacks and f of the resident batch are stale until a tnml_forward.
+ * REFUSALS, all before anything is launched: those of tnml_nll_masked_grad; renorm outside {0, 1}; TNML_ERR_STATE for an optimiser
+ * state bound to other bonds or another l_pos. */
+int tnml_nll_masked_step(tnml_ctx *ctx, int n, int K, const double *phi, const double *w, const int32_t *classes, const uint8_t *mask,
+                         int mask_rows, const int32_t *known, float lr, float weight_dec, int renorm, double *values4);
+
 /* Host-side planning helper, exported so that CPU tests can check the bond bookkeeping without a
  * GPU: truncation rank kept by tensor_svd (Network_class.py:894-945) for a step on sites
  * (p, p+1).  Returns m >= 1, or TNML_ERR_SHAPE where the reference itself raises. */

@@ -47,6 +47,7 @@ SYMBOLS = [
     'tnml_get_bonds', 'tnml_log_norm_grad', 'tnml_nll_grad', 'tnml_nll_grad_indices', 'tnml_nll_eval', 'tnml_nll_eval_indices',
     'tnml_nll_step', 'tnml_nll_train_indices', 'tnml_set_nll_overlap',
     'tnml_nll_sweep', 'tnml_nll_sweep_indices', 'tnml_nll_sweep_debug',
+    'tnml_nll_masked_grad', 'tnml_nll_masked_step',
 ]
 NLL_SWEEP_DBG = {'B': 0, 'Gd': 1, 'Gz': 2, 'B_new': 3, 'sigma': 4}
 
@@ -174,6 +175,9 @@ def lib():
                                              f64p]
         L.tnml_nll_sweep_debug.argtypes = [vp, C.c_int, f64p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.tnml_set_nll_overlap.argtypes = [vp, C.c_int]
+        L.tnml_nll_masked_grad.argtypes = [vp, C.c_int, C.c_int, f64p, f64p, i32p, C.POINTER(C.c_uint8), C.c_int, i32p, f32p, C.c_size_t, f64p, f64p]
+        L.tnml_nll_masked_step.argtypes = [vp, C.c_int, C.c_int, f64p, f64p, i32p, C.POINTER(C.c_uint8), C.c_int, i32p, C.c_float, C.c_float, C.c_int,
+                                           f64p]
         _lib = L
     return _lib
 
@@ -852,6 +856,63 @@ class Context:
     def set_nll_overlap(self, on):
         """The norm walk of a likelihood step on a second stream beside the step's chunks (bit-equal results either way)."""
         _chk(lib().tnml_set_nll_overlap(self._h, int(on)))
+
+    # ---- likelihood training from incomplete data (DESIGN.md section 31)
+    def _masked_batch(self, n, phi, w, mask, known, classes):
+        """the arguments tnml_nll_masked_grad / _step share, checked and in the ABI's types (the arrays are returned to keep them alive)"""
+        phi = np.ascontiguousarray(phi, dtype=np.float64)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if phi.ndim != 2 or phi.shape[1] != self.D or w.shape != (phi.shape[0],):
+            raise TnmlError(-1, 'the grid has phi %s and w %s, not (K, %d) and (K,)' % (phi.shape, w.shape, self.D))
+        if mask is None:
+            raise TnmlError(-1, 'mask is None')
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if mask.shape not in ((self.N,), (n, self.N)):
+            raise TnmlError(-1, 'mask has shape %s, neither (%d,) nor (%d, %d)' % (mask.shape, self.N, n, self.N))
+        cp = kp = None
+        if classes is not None:
+            classes = np.ascontiguousarray(classes, dtype=np.int32)
+            if classes.shape != (n,):
+                raise TnmlError(-1, 'classes has shape %s, not (%d,)' % (classes.shape, n))
+            cp = _ptr(classes, C.c_int32)
+        if known is not None:
+            known = np.ascontiguousarray(known, dtype=np.int32)
+            if known.shape != (n, self.N):
+                raise TnmlError(-1, 'known has shape %s, not (%d, %d)' % (known.shape, n, self.N))
+            kp = _ptr(known, C.c_int32)
+        return (phi, w, mask, known, classes), (phi.shape[0], _ptr(phi, C.c_double), _ptr(w, C.c_double), cp, _ptr(mask, C.c_uint8),
+                                                1 if mask.ndim == 1 else n, kp)
+
+    def nll_masked_grad(self, n, phi, w, mask, known, classes=None, want=('G', 'logp')):
+        """-> (G, logp (n,), out4): the descent direction of -mean_s log p(known pixels of s [, class of s]) over all cores in the
+        canonical shapes, every sample with its own mask (mask (N,) or (n, N), known (n, N) levels read where it is set) and its own
+        class (classes (n,), -1: unknown and summed; None: all -1); logp[s] = log p(x_G,s [, c_s]); out4 = (the value -mean(logp),
+        log Z, samples of zero weight or a non-finite likelihood, status bits).  `want` without 'G': the value alone, only the
+        environments run.  A bad sample raises TnmlError(-7) whose .values holds out4.  Nothing on the device changes."""
+        n = int(n)
+        keep, (K, pp, wp, cp, mp, mask_rows, kp) = self._masked_batch(n, phi, w, mask, known, classes)
+        flat, fp, cap = None, None, 0
+        if 'G' in want:
+            sz = C.c_size_t()
+            _chk(lib().tnml_cores_size(self._h, C.byref(sz)))
+            flat = np.empty(sz.value, dtype=np.float32)
+            fp, cap = _ptr(flat, C.c_float), flat.size
+        logp = np.empty(max(n, 0), dtype=np.float64) if 'logp' in want else None
+        out = np.zeros(4, dtype=np.float64)
+        self._chk_values(lib().tnml_nll_masked_grad(self._h, n, K, pp, wp, cp, mp, mask_rows, kp, fp, cap,
+                                                    None if logp is None else _ptr(logp, C.c_double), _ptr(out, C.c_double)), out)
+        return (None if flat is None else self._cut(flat)), logp, out
+
+    def nll_masked_step(self, n, phi, w, mask, known, classes=None, lr=1e-3, weight_dec=0.0, renorm=True):
+        """One optimiser step (optim_config) on the gradient of nll_masked_grad -> float64 (4,): out4 of the batch BEFORE the step,
+        its bits joined by 8 (a bad sample) and 16 (not applied).  A bad batch raises TnmlError(-7) whose .values holds the array and
+        leaves cores and optimiser state untouched."""
+        n = int(n)
+        keep, (K, pp, wp, cp, mp, mask_rows, kp) = self._masked_batch(n, phi, w, mask, known, classes)
+        out = np.zeros(4, dtype=np.float64)
+        self._chk_values(lib().tnml_nll_masked_step(self._h, n, K, pp, wp, cp, mp, mask_rows, kp, float(lr), float(weight_dec), int(renorm),
+                                                    _ptr(out, C.c_double)), out)
+        return out
 
     # ---- gradient training over all cores
     def optim_config(self, kind='sgd', momentum=0.0, beta1=0.9, beta2=0.999, eps=1e-8, clip=True):

@@ -652,7 +652,7 @@ static void check_sample_masked(const SampleMaskedParams &p, dim3 g, dim3 b, siz
   }
   const size_t m2 = (size_t)mb * mb, rows = (size_t)p.n_tiles * p.T;
   if (p.lds_m != mb || mb > kSmpMaxBond || p.env_stride < m2) die("SampleMaskedParams: lds_m %d env_stride %zu for bond %d", p.lds_m, p.env_stride, mb);
-  const int want_T = g_site_cond_call ? site_cond_tile(mb, p.D, p.L, p.K) : sample_masked_tile(mb, p.D, p.L, p.K);
+  const int want_T = g_site_cond_call == 2 ? masked_grad_tile(mb, p.D, p.L, p.K) : g_site_cond_call ? site_cond_tile(mb, p.D, p.L, p.K) : sample_masked_tile(mb, p.D, p.L, p.K);
   if (p.T < 1 || p.T != want_T) die("SampleMaskedParams: tiles of %d rows, %d fit at bond %d", p.T, want_T, mb);
   if (!walk) g_last_env = p;
   need(p.S, (size_t)p.D * p.D * 8, "SampleMaskedParams.S");
@@ -697,7 +697,7 @@ static void check_sample_masked(const SampleMaskedParams &p, dim3 g, dim3 b, siz
 // the launch's rows and the outputs the call asked for with their extents; grid, block and LDS.
 static void check_site_cond(const SiteCondParams &p, dim3 g, dim3 b, size_t shm) {
   scan(&p, sizeof p, "SiteCondParams");
-  if (!g_site_cond_call) die("site_cond_kernel outside a tnml_site_conditionals call");
+  if (g_site_cond_call != 1) die("site_cond_kernel outside a tnml_site_conditionals call");
   const SampleMaskedParams &m = p.m, &e = g_last_env;
   if (m.T != e.T || m.n_tiles != e.n_tiles || m.lds_m != e.lds_m || m.n != e.n || m.tile_class != e.tile_class || m.tile_rows != e.tile_rows ||
       m.stack != e.stack || m.env_stride != e.env_stride || m.mask != e.mask || m.known != e.known || m.mask_rows != e.mask_rows || m.bond != e.bond ||
@@ -713,6 +713,53 @@ static void check_site_cond(const SiteCondParams &p, dim3 g, dim3 b, size_t shm)
   if (p.mode) need(p.mode, sites * 4, "SiteCondParams.mode");
   if (g.x != (unsigned)m.n_tiles || g.y != 1 || g.z != 1 || b.x != 512) die("site_cond_kernel: grid %u block %u for %d tiles", g.x, b.x, m.n_tiles);
   if (shm < site_cond_lds_bytes(m.lds_m, m.D, m.K, m.T)) die("site_cond_kernel: %zu bytes of LDS for bond %d, T %d", shm, m.lds_m, m.T);
+}
+
+// likelihood gradients from incomplete data (kernels_nll_masked.hip): masked_grad_kernel behind the environment launch of the same
+// chunk.  Its block m is that launch's, field for field; the offsets, the row weights, the left environments and the partial
+// gradients of the launch with their extents; grid, block and LDS.  A row with a sample carries 2 / n, a row without one 0 (padding) or
+// -2 (the normaliser: the first row of a tile of class -1); the normaliser rows since the last san_stub_masked_reset are counted.
+static long g_nmg_normalisers = 0;
+static void check_masked_grad(const MaskedGradParams &p, dim3 g, dim3 b, size_t shm) {
+  scan(&p, sizeof p, "MaskedGradParams");
+  if (g_site_cond_call != 2) die("masked_grad_kernel outside a tnml_nll_masked call");
+  const SampleMaskedParams &m = p.m, &e = g_last_env;
+  if (m.T != e.T || m.n_tiles != e.n_tiles || m.lds_m != e.lds_m || m.n != e.n || m.tile_class != e.tile_class || m.tile_rows != e.tile_rows ||
+      m.stack != e.stack || m.env_stride != e.env_stride || m.mask != e.mask || m.known != e.known || m.mask_rows != e.mask_rows || m.bond != e.bond ||
+      m.cores != e.cores || m.lab != e.lab || m.S != e.S || m.phi != e.phi || m.w != e.w || m.status != e.status)
+    die("masked_grad_kernel: its block is not the one of the environment launch before it (T %d against %d)", m.T, e.T);
+  const size_t rows = (size_t)m.n_tiles * m.T;
+  if (m.T != masked_grad_tile(m.lds_m, m.D, m.L, m.K) || m.lds_m > kNmgMaxBond) die("masked_grad_kernel: tiles of %d rows at bond %d", m.T, m.lds_m);
+  need(p.off, (size_t)m.N * 4, "MaskedGradParams.off");
+  size_t total = 0;
+  for (int i = 0; i < m.N; ++i) {
+    const int ml = i == 0 ? 1 : m.bond[i - 1], mr = i == m.N - 1 ? 1 : m.bond[i];
+    if ((size_t)p.off[i] != total) die("masked_grad_kernel: core %d at offset %d, expected %zu", i, p.off[i], total);
+    total += (size_t)ml * m.D * mr * (i == m.l_pos ? m.L : 1);
+  }
+  if (p.total != total) die("masked_grad_kernel: total %zu for cores of %zu floats", p.total, total);
+  need(p.wrow, rows * 8, "MaskedGradParams.wrow");
+  need(p.lf_next, rows * m.env_stride * 8, "MaskedGradParams.lf_next");
+  need(p.part, (size_t)m.n_tiles * total * 8, "MaskedGradParams.part");
+  need(p.status, 2 * 4, "MaskedGradParams.status");
+  for (size_t r = 0; r < rows; ++r) {
+    const int smp = m.tile_rows[r];
+    const double w = p.wrow[r];
+    if (smp >= 0 ? w != 2.0 / m.n : (w != 0.0 && !(w == -2.0 && r % m.T == 0 && m.tile_class[r / m.T] == -1)))
+      die("masked_grad_kernel: row %zu (sample %d) carries weight %g", r, smp, w);
+    if (w == -2.0) ++g_nmg_normalisers;
+  }
+  if (g.x != (unsigned)m.n_tiles || g.y != 1 || g.z != 1 || b.x != 512) die("masked_grad_kernel: grid %u block %u for %d tiles", g.x, b.x, m.n_tiles);
+  if (shm < masked_grad_lds_bytes(m.lds_m, m.D, m.K, m.T)) die("masked_grad_kernel: %zu bytes of LDS for bond %d, T %d", shm, m.lds_m, m.T);
+}
+static void check_masked_grad_reduce(const MaskedGradReduceParams &p, dim3 g, dim3 b) {
+  scan(&p, sizeof p, "MaskedGradReduceParams");
+  if (p.n_tiles < 1 || p.total < 1 || (p.first != 0 && p.first != 1) || (p.last != 0 && p.last != 1)) die("MaskedGradReduceParams: tiles %d total %zu", p.n_tiles, p.total);
+  need(p.part, (size_t)p.n_tiles * p.total * 8, "MaskedGradReduceParams.part");
+  need(p.acc, p.total * 8, "MaskedGradReduceParams.acc");
+  need(p.G, p.total * 4, "MaskedGradReduceParams.G");
+  need(p.status, 2 * 4, "MaskedGradReduceParams.status");
+  if (g.y != 1 || g.z != 1 || (size_t)g.x * b.x < p.total) die("masked_grad_reduce_kernel: grid %u x %u for %zu elements", g.x, b.x, p.total);
 }
 
 // gradient training (kernels_optim.hip).  loss_cot_kernel: f and cot at their own strides, the labels of the chunk, one thread per
@@ -843,6 +890,11 @@ static void tr_struct(const SiteCondParams &p) {
   tr_struct(p.m);
   P(values) P(lf_next) P(q) P(stats) P(mode)
 }
+static void tr_struct(const MaskedGradParams &p) {
+  tr_struct(p.m);
+  P(off) P(wrow) P(lf_next) P(part) I(total) P(status)
+}
+static void tr_struct(const MaskedGradReduceParams &p) { P(part) P(acc) P(G) I(total) I(n_tiles) I(first) I(last) P(status) }
 static void tr_struct(const LogNormParams &p) {
   I(N) I(D) I(L) I(l_pos) I(metric_sites) I(lds_m) I(mode) P(tab) P(cores) P(lab) I(core_stride) P(metric) P(envL) P(envR) P(expL) P(expR) I(env_stride)
   P(G) P(out) P(status)
@@ -895,6 +947,8 @@ static void tr_launch(const std::string &name, dim3 g, dim3 b, size_t shm, hipSt
     else if (is("AlgebraParams")) tr_struct(*(const AlgebraParams *)args[i]);
     else if (is("SampleParams")) tr_struct(*(const SampleParams *)args[i]);
     else if (is("SampleMaskedParams")) tr_struct(*(const SampleMaskedParams *)args[i]);
+    else if (is("MaskedGradReduceParams")) tr_struct(*(const MaskedGradReduceParams *)args[i]);
+    else if (is("MaskedGradParams")) tr_struct(*(const MaskedGradParams *)args[i]);
     else if (is("SiteCondParams")) tr_struct(*(const SiteCondParams *)args[i]);
     else if (is("PairParams")) tr_struct(*(const PairParams *)args[i]);
     else if (is("NllCotParams")) tr_struct(*(const NllCotParams *)args[i]);
@@ -990,6 +1044,10 @@ hipError_t hipLaunchKernel(const void *fn, dim3 g, dim3 b, void **args, size_t s
     check_sample(*(const SampleParams *)args[0], g, b, shm, has("sample_walk_kernel"));
   } else if (has("sample_env_masked_kernel") || has("sample_walk_masked_kernel")) {
     check_sample_masked(*(const SampleMaskedParams *)args[0], g, b, shm, has("sample_walk_masked_kernel"));
+  } else if (has("masked_grad_reduce_kernel")) {
+    check_masked_grad_reduce(*(const MaskedGradReduceParams *)args[0], g, b);
+  } else if (has("masked_grad_kernel")) {
+    check_masked_grad(*(const MaskedGradParams *)args[0], g, b, shm);
   } else if (has("site_cond_kernel")) {
     check_site_cond(*(const SiteCondParams *)args[0], g, b, shm);
   } else if (has("pair_close_kernel") || has("pair_walk_kernel") || has("pair_stats_kernel")) {
@@ -1240,8 +1298,11 @@ void san_stub_masked_check(int walk, int n, const int32_t *classes) {
   for (int s = 0; s < n; ++s)
     if (cls[s] != (classes ? classes[s] : -1)) die("tnml_sample_masked: sample %d of class %d is in %s", s, classes ? classes[s] : -1, cls[s] == INT_MIN ? "no tile" : "a tile of another class");
 }
-// the calls that follow are tnml_site_conditionals' (1) or the sampler's (0): which tile rule the environment launches are held to
+// the calls that follow are tnml_site_conditionals' (1), tnml_nll_masked_grad / _step's (2) or the sampler's (0): which tile rule the
+// environment launches are held to
 void san_stub_site_cond_call(int on) { g_site_cond_call = on; }
+// the normaliser rows (weight -2) of the masked_grad_kernel launches since the last call of this function
+long san_stub_nmg_normalisers(void) { const long k = g_nmg_normalisers; g_nmg_normalisers = 0; return k; }
 // the records of the last persistent launch as the "device" holds them (n steps; record n is the batch side's prologue)
 const void *san_stub_last_persist(int *n_steps) { *n_steps = g_last_persist_n; return g_last_persist; }
 }

@@ -806,7 +806,7 @@ static int grad_chunk_samples(const tnml_ctx *c, int setting) {
   return (int)std::max<size_t>(64, kIgStackBytes / per_sample / 64 * 64);
 }
 
-static int largest_bond(const tnml_ctx *c) {
+int tnml::largest_bond(const tnml_ctx *c) {
   int mb = 1;
   for (int v : c->bond) mb = std::max(mb, v);
   return mb;
@@ -1035,7 +1035,7 @@ extern "C" int tnml_set_core_grad_chunk(tnml_ctx *c, int samples) {
 // ---------------------------------------------------------------------------------------------
 // gradient training: optimiser steps over all cores from the core gradients (kernels_optim.hip)
 // ---------------------------------------------------------------------------------------------
-static bool opt_stateful(const tnml_ctx *c) { return c->opt.kind == TNML_OPT_ADAM || c->opt.momentum > 0.0; }
+bool tnml::opt_stateful(const tnml_ctx *c) { return c->opt.kind == TNML_OPT_ADAM || c->opt.momentum > 0.0; }
 static size_t opt_state_elems(const tnml_ctx *c) { return (size_t)c->N * c->core_stride + c->lab_elems; }     // cg_G's
 
 // zero vel / m / v (when they exist), t = 0, bound to the current bonds and l_pos
@@ -1069,7 +1069,7 @@ extern "C" int tnml_optim_reset(tnml_ctx *c) {
 }
 
 // State group, on the first step of a stateful optimiser: a failed allocation leaves it empty and the call repeatable
-static int opt_ensure_state(tnml_ctx *c) {
+int tnml::opt_ensure_state(tnml_ctx *c) {
   if (!opt_stateful(c) || c->opt_s0) return TNML_OK;
   HIP_TRY(hipStreamSynchronize(c->stream));
   int rc = make_group(c, "the optimiser state", {own_dev(c->opt_s0, opt_state_elems(c)), own_dev(c->opt_s1, opt_state_elems(c))});
@@ -1317,14 +1317,14 @@ static int smp_ensure(tnml_ctx *c, size_t n, size_t given, size_t u, size_t tile
 
 // The host front that tnml_sample and tnml_sample_masked (below) share: the refusals that read the same in both, each in the place
 // it has in the call's own order (`what` names the call), and what both upload alike.
-static int smp_check_sizes(const char *what, const double *phi, const double *w, int n, int K) {
+int tnml::smp_check_sizes(const char *what, const double *phi, const double *w, int n, int K) {
   if (!phi || !w) return fail(TNML_ERR_ARG, "%s: %s is NULL", what, phi ? "w" : "phi");
   if (n < 1) return fail(TNML_ERR_ARG, "%s: n = %d < 1", what, n);
   if (K < 2 || K > kSmpMaxK) return fail(TNML_ERR_ARG, "%s: K = %d outside [2, %d]", what, K, kSmpMaxK);
   return TNML_OK;
 }
 
-static int smp_check_grid(const char *what, int K, int D, const double *phi, const double *w) {
+int tnml::smp_check_grid(const char *what, int K, int D, const double *phi, const double *w) {
   for (int k = 0; k < K; ++k) {
     if (!(w[k] > 0.0) || !std::isfinite(w[k])) return fail(TNML_ERR_ARG, "%s: weight %d is %g (weights are positive and finite)", what, k, w[k]);
     for (int d = 0; d < D; ++d)
@@ -1333,7 +1333,7 @@ static int smp_check_grid(const char *what, int K, int D, const double *phi, con
   return TNML_OK;
 }
 
-static int smp_check_classes(const char *what, const int32_t *classes, int n, int L) {
+int tnml::smp_check_classes(const char *what, const int32_t *classes, int n, int L) {
   if (classes)
     for (int s = 0; s < n; ++s)
       if (classes[s] < -1 || classes[s] >= L) return fail(TNML_ERR_ARG, "%s: class %d of sample %d outside [-1, %d)", what, (int)classes[s], s, L);
@@ -1347,20 +1347,20 @@ static int smp_check_uniforms(const char *what, const double *u, int n, int N) {
   return TNML_OK;
 }
 
-static int smp_check_state(const tnml_ctx *c, const char *what) {
+int tnml::smp_check_state(const tnml_ctx *c, const char *what) {
   if (!c->cores_set) return fail(TNML_ERR_STATE, "cores were never set");
   if (c->comm) return fail(TNML_ERR_STATE, "%s runs on one GPU: this context has a communicator attached", what);
   return TNML_OK;
 }
 
 // the first N entries of a call's host tables: the bond to the right of every site, 1 behind the last
-static void smp_bond_table(const tnml_ctx *c, std::vector<int> &host) {
+void tnml::smp_bond_table(const tnml_ctx *c, std::vector<int> &host) {
   for (int i = 0; i < c->N - 1; ++i) host[i] = c->bond[i];
   host[c->N - 1] = 1;
 }
 
 // the grid's metric S = sum_k w_k phi_k phi_k^T, in this order
-static void smp_grid_metric(std::vector<double> &S, int K, int D, const double *phi, const double *w) {
+void tnml::smp_grid_metric(std::vector<double> &S, int K, int D, const double *phi, const double *w) {
   S.assign((size_t)D * D, 0.0);
   for (int k = 0; k < K; ++k)
     for (int d = 0; d < D; ++d)
@@ -1478,7 +1478,7 @@ extern "C" int tnml_sample(tnml_ctx *c, int n, int K, const double *phi, const d
 // the same given any set of known pixels (kernels_sample_masked.hip)
 // ---------------------------------------------------------------------------------------------
 // The group of the call, (re)sized when any member is too small: all of it or none
-static int smk_ensure(tnml_ctx *c, size_t tiles, size_t rows, size_t n, size_t mask, size_t u, size_t stack) {
+int tnml::smk_ensure(tnml_ctx *c, size_t tiles, size_t rows, size_t n, size_t mask, size_t u, size_t stack) {
   auto &g = c->smk;
   if (g.stack_cap > 0 && g.tiles_cap >= tiles && g.rows_cap >= rows && g.n_cap >= n && g.mask_cap >= mask && g.u_cap >= u && g.stack_cap >= stack)
     return TNML_OK;

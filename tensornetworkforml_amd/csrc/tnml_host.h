@@ -420,6 +420,18 @@ struct tnml_ctx {
     std::vector<NllSweepSite> sites_host;    // host copies for the call in flight (they outlive the asynchronous uploads)
     std::vector<double> metric_host;
   } nsw;
+  // likelihood gradients from incomplete data.  One group of its own, regrown when a call needs more of any
+  // member: the table of grad_table, the weight of every row of the call, the left environments behind the site a row of one chunk is
+  // on (lf_cap doubles), the partial gradients of one chunk's tiles (part_cap doubles), the float64 accumulator and the float32
+  // gradient (total_cap each), the status word.  The tables, the grid, the stack and E are the masked group's (smk), through smk_ensure.
+  struct {
+    int *tab = nullptr, *status = nullptr;
+    double *wrow = nullptr, *lf_next = nullptr, *part = nullptr, *acc = nullptr;
+    float *G = nullptr;
+    size_t rows_cap = 0, lf_cap = 0, part_cap = 0, total_cap = 0;
+    std::vector<int> tab_host;               // host copies for the call in flight (they outlive the asynchronous uploads)
+    std::vector<double> wrow_host;
+  } nmg;
   // multi-GPU
   ncclComm_t comm = nullptr;
   int rank = 0, nranks = 1;
@@ -493,6 +505,18 @@ int lnz_ensure(tnml_ctx *c, int mb, bool want_G);
 int lnz_upload(tnml_ctx *c, const std::vector<int> &tab_host, const double *S, int n_metric, bool wait);
 int lnz_launch_env(tnml_ctx *c, int n_metric, int mb, hipStream_t st);
 int nll_ensure(tnml_ctx *c, int n);
+// what the masked likelihood gradient (nll_masked_host.hip) borrows: the refusals and tables of the samplers' front, the masked
+// group, and the state rules of the optimiser
+int largest_bond(const tnml_ctx *c);
+int smp_check_sizes(const char *what, const double *phi, const double *w, int n, int K);
+int smp_check_grid(const char *what, int K, int D, const double *phi, const double *w);
+int smp_check_classes(const char *what, const int32_t *classes, int n, int L);
+int smp_check_state(const tnml_ctx *c, const char *what);
+void smp_bond_table(const tnml_ctx *c, std::vector<int> &host);
+void smp_grid_metric(std::vector<double> &S, int K, int D, const double *phi, const double *w);
+int smk_ensure(tnml_ctx *c, size_t tiles, size_t rows, size_t n, size_t mask, size_t u, size_t stack);
+bool opt_stateful(const tnml_ctx *c);
+int opt_ensure_state(tnml_ctx *c);
 int narrow_path(const tnml_ctx *c, int h, int g, int s, int L, int m);
 int run_narrow(tnml_ctx *c, NarrowParams &n, int path, bool skip_prep = false, hipEvent_t after_update = nullptr,
                const BigFront *front = nullptr, unsigned *sig_flag = nullptr, unsigned sig_val = 0);

@@ -556,6 +556,37 @@ int site_cond_tile(int mb, int D, int L, int K);
 // the environment launch and site_cond_kernel of one chunk; mb: largest bond.  false: refused (geometry / LDS)
 bool launch_site_cond(const SiteCondParams &p, int mb, hipStream_t st);
 
+// Likelihood gradients from incomplete data (kernels_nll_masked.hip): the environment launch above with the tile
+// of this call, then masked_grad_kernel on the same tiles, rows and stack, which leaves one partial gradient per tile, and per chunk
+// masked_grad_reduce_kernel, which adds the partials in ascending tile order.  The core is worked kNmgRows rows at a time; that
+// number and T fix the order of every sum.
+constexpr int kNmgMaxBond = kSmpMaxBond;
+constexpr int kNmgRows = 16;
+struct MaskedGradParams {
+  SampleMaskedParams m;    // the block of the environment launch: tables, grid, stack, E, status (u, levels, labels, logp0 unused)
+  const int *off;          // [N] the offset of core i in the flat layout of tnml_get_cores
+  const double *wrow;      // [n_tiles T] the weight of every row of the launch: 2 / n a sample, -2 the normaliser, 0 padding
+  double *lf_next;         // [n_tiles T][env_stride] the left environment behind the site a row is on, before its power of two
+  double *part;            // [n_tiles][total] the partial gradient of every tile of the launch
+  size_t total;            // floats of the flat layout
+  int *status;             // [0] bit 1 a non-finite left environment, bit 2 a per-site normaliser that is not positive and finite
+};
+struct MaskedGradReduceParams {
+  const double *part;      // [n_tiles][total]
+  double *acc;             // [total] the running sum over the tiles of the chunks so far
+  float *G;                // [total] written by the last chunk
+  size_t total;
+  int n_tiles, first, last;
+  int *status;             // [0] bit 4 an element beyond float32
+};
+size_t masked_grad_lds_bytes(int mb, int D, int K, int T);
+// the largest T of 16, 8, 4, 2, 1 at which the environment kernel and masked_grad_kernel both fit 160 KB of LDS (and which
+// sample_masked_tile allows, whose launch function is used); 0: none does
+int masked_grad_tile(int mb, int D, int L, int K);
+// the environment launch and masked_grad_kernel of one chunk; mb: largest bond.  false: refused (geometry / LDS)
+bool launch_masked_grad(const MaskedGradParams &p, int mb, hipStream_t st);
+bool launch_masked_grad_reduce(const MaskedGradReduceParams &p, hipStream_t st);
+
 // The gradient of the log-norm (kernels_nll.hip): one parameter block for the environment kernel (two
 // workgroups, one per direction) and the gradient kernel (grid (N, L)).  L_i 2^expL[i] and R_i 2^expR[i] are the environments.
 constexpr int kLnzMaxBond = 64;

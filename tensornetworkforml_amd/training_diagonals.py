@@ -18,6 +18,34 @@ import data_generator as gen   # noqa: E402
 import Network_class as tn     # noqa: E402
 
 
+def train_missing(net, data, label, train_idx, val_idx, args):
+    """Likelihood training from incomplete data: every batch loses a random fraction --missing of its pixels
+    and --unlabelled of its labels, and takes one Network.nll_step_masked step; after every epoch the validation accuracy of
+    classify_masked under the same occlusion.  -> (masked NLL (n_epochs, n_batches) before every step, validation accuracy)"""
+    rng = np.random.default_rng(0)
+    lev = np.rint(np.clip(data.reshape(len(data), -1), 0.0, 1.0) * 255.0).astype(np.int32)
+    label = np.asarray(label, dtype=np.int32)
+    net.configure_optimizer(args.optimizer)
+    hist, val_acc = [], []
+    for epoch in range(args.n_epochs):
+        row = []
+        for idx in train_idx:
+            idx = np.asarray(idx)
+            mask = rng.random((len(idx), net.N)) >= args.missing
+            y = np.where(rng.random(len(idx)) < args.unlabelled, -1, label[idx]).astype(np.int32)
+            row.append(net.nll_step_masked(lev[idx], mask, y, lr=args.lr, weight_dec=args.L2_decay, renorm=args.renorm)[0])
+        hist.append(row)
+        good = total = 0
+        for idx in val_idx:
+            idx = np.asarray(idx)
+            pred, _ = net.classify_masked(lev[idx], rng.random((len(idx), net.N)) >= args.missing)
+            good += int((pred == label[idx]).sum())
+            total += len(idx)
+        val_acc.append(good / max(total, 1))
+        print('Epoch %d/%d - masked NLL : %.4f - val accuracy under occlusion: %.4f' % (epoch, args.n_epochs, float(np.mean(row)), val_acc[-1]))
+    return np.array(hist), val_acc
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Train the Tensor Network to classify the dataset of diagonals')
     ap.add_argument('--n_samples', type=int, default=5000, help='Number of samples to generate')
@@ -54,6 +82,11 @@ def main(argv=None):
                     help='after training, cut every bond to M on its Schmidt decomposition (Network.compress; needs --resident)')
     ap.add_argument('--scaled-chains', dest='scaled_chains', action='store_true',
                     help='gradient training on range-safe chains (Network.scaled_chains; needs --resident --optimizer)')
+    ap.add_argument('--missing', type=float, default=None, metavar='F',
+                    help='likelihood training from incomplete data: hide a random fraction F of the pixels of every batch, summed out '
+                         'exactly (Network.nll_step_masked in a host loop; needs --objective nll; pixels are put on a grid of 256 levels)')
+    ap.add_argument('--unlabelled', type=float, default=0.0, metavar='F2',
+                    help='with --missing: hide the label of a random fraction F2 of the samples of every batch as well')
     ap.add_argument('--out', type=str, default='trained_diag_model.dat')
     args = ap.parse_args(argv)
     if args.compress is not None and not args.resident:
@@ -66,6 +99,12 @@ def main(argv=None):
         ap.error('--no-renorm needs --objective nll')
     if args.objective == 'nll' and args.optimizer is None:
         args.optimizer = 'sgd'
+    if args.missing is not None and (args.objective != 'nll' or args.method != 'gradient'):
+        ap.error('--missing needs --objective nll with --method gradient')
+    if args.missing is not None and not (0.0 <= args.missing < 1.0 and 0.0 <= args.unlabelled <= 1.0):
+        ap.error('--missing takes a fraction in [0, 1), --unlabelled one in [0, 1]')
+    if args.unlabelled and args.missing is None:
+        ap.error('--unlabelled needs --missing')
     if args.method == 'sweep' and args.objective != 'nll':
         ap.error('--method sweep needs --objective nll')
     if (args.max_bond is not None or args.threshold != 1.0) and args.method != 'sweep':
@@ -89,6 +128,13 @@ def main(argv=None):
                      act_fn=args.act_fn, loss_fn=args.loss_fn, trunc=args.trunc)
     if args.resident:
         _, train_idx, val_idx, _ = gen.prepare_device_dataset(net, data, label, 1, 0.2, train_batch, 128, 128, D=args.D)
+        if args.missing is not None:
+            hist, val_acc = train_missing(net, data, label, train_idx, val_idx, args)
+            with open(args.out, 'wb') as fh:
+                pickle.dump(net, fh)
+            print('masked NLL per epoch:', ['%.4f' % v for v in hist.mean(axis=1)])
+            print('validation accuracy of classify_masked per epoch:', ['%.4f' % v for v in val_acc])
+            return val_acc, hist
         if args.objective == 'nll':
             net.scaled_chains = args.scaled_chains
             val_nll, nll_hist = net.train_generative(train_idx, val_idx, lr=args.lr, n_epochs=args.n_epochs, weight_dec=args.L2_decay,

@@ -7,7 +7,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 ARCH=${ARCH:-gfx950}
 cd "$(dirname "$0")/../tensornetworkforml_amd/csrc"
 printf '%-44s %6s %6s %6s %11s %11s %9s %6s\n' kernel SGPRs VGPRs AGPRs SGPR-spill VGPR-spill scratch-B LDS-B
-for f in kernels_narrow kernels_wide kernels_big kernels_anyd kernels_inputgrad kernels_coregrad kernels_optim kernels_orth kernels_scaled kernels_algebra kernels_sample kernels_sample_masked kernels_nll kernels_site_cond kernels_pair kernels_nll_sweep; do
+for f in kernels_narrow kernels_wide kernels_big kernels_anyd kernels_inputgrad kernels_coregrad kernels_optim kernels_orth kernels_scaled kernels_algebra kernels_sample kernels_sample_masked kernels_nll kernels_site_cond kernels_pair kernels_nll_sweep kernels_nll_masked; do
   $HIPCC -O3 -std=c++17 -fPIC --offload-arch=$ARCH -I/opt/rocm/include --cuda-device-only -Rpass-analysis=kernel-resource-usage \
       -c $f.hip -o /dev/null 2>&1 | ${CXXFILT:-c++filt} |
   awk -v file=$f -v want="$*" '
